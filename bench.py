@@ -5,17 +5,27 @@ SegmentalKMeansWordseg, 10 000 utterances x 20 landmarks (n_slices_max = 6 -> 10
 spans each, 1.05 M embeddings), D = 100, K = 1000, synthetic unit-norm float32 embeddings
 (SURVEY.md 8(d)), batch-synchronous sweeps, sharded over N GPUs (strong scaling:
 the corpus is fixed, each rank owns 1/N of the utterances; one small RCCL all-gather per
-sweep).  `--windows` (default 9) back-to-back windows of exactly `--steps` sweeps are timed, each
-bracketed by barrier + synchronize; the line reports the median window and the spread.
+sweep).  A plain run times exactly `--steps` sweeps after `--warmup` untimed ones, in one window
+bracketed by barrier + synchronize, and prints the headline line; nothing else.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (the fp32 MFMA score
-kernel), its duration measured live with HIP events on the launch stream inside the timed
-region; `cpu_baseline` times the oracle's faithful single-core restatement of the reference
-on a bounded sample of the same corpus (rank 0, N = 1 only).
+Rank 0 prints ONE JSON line.  `--full` adds everything beyond the headline: `--windows` (default 9)
+back-to-back windows of `--steps` sweeps (the line reports the median window and the spread),
+`roofline` for the dominant kernel (the MFMA score kernel, its duration measured live with HIP
+events on the launch stream inside the timed region), the stage counts, the measured collective
+(N > 1), the sequential chain, the early sweeps and the mini-batch form, and `cpu_baseline`, which
+times the oracle's faithful single-core restatement of the reference on a bounded sample of the
+same corpus (rank 0, N = 1 only).
+
+`--dump-outputs DIR` writes, after the timed sweeps, what the timed path computed in its last sweep
+(what a caller reads back: boundaries, component assignments and statistics, the sweep's record
+values) as DIR/<name>.npy in float32 / float64, at most 64 MB in all.  The inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -32,6 +42,30 @@ import numpy as np  # noqa: E402
 METRIC = "Gibbs sweeps/sec (10k utts, D=100, K=1000) at 1/2/4/8 MI355X"
 PEAK_FP32_MATRIX_TFLOPS = 157.3     # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense
 PEAK_BF16_MATRIX_TFLOPS = 2516.6    # v_mfma_f32_32x32x16_bf16: 256 CUs x 4 SIMDs x 512 MAC/clk x 2 x 2.4 GHz ("~2.5 PF dense")
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as dirname/<name>.npy, float32 where the result is float32 (or boolean), float64
+    otherwise (integers included: exact below 2^53).  When they come to more than DUMP_BYTES_MAX, the smallest arrays
+    stay whole and the largest keep a fixed, seeded sample of their rows, listed in dirname/<name>.rows.npy, within an
+    equal share of what is left."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {name: np.asarray(a) for name, a in arrays.items()}
+    arrays = {name: a.astype(np.float32 if a.dtype in (np.float32, np.float16, np.bool_) else np.float64).reshape(a.shape or (1,))
+              for name, a in arrays.items()}
+    budget, left = DUMP_BYTES_MAX - 256 * len(arrays), len(arrays)         # (a .npy header is 128 bytes; two files per array)
+    for name in sorted(arrays, key=lambda n: arrays[n].nbytes):
+        a, share = arrays[name], budget // left
+        if a.nbytes > share:
+            n_keep = max(1, share // (a.nbytes // a.shape[0] + 8))         # sampled rows and their float64 row numbers
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], n_keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(dirname, name + ".rows.npy"), rows.astype(np.float64))
+            budget -= rows.nbytes
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        budget -= a.nbytes
+        left -= 1
 
 
 def cpu_blas_courtesy(corpus, n_utts_total, K, n_slices_max, budget_utts):
@@ -288,7 +322,7 @@ def main_fbgmm(args):
     barrier()
     seg._df.check_status()
     diag32 = (not bigram) and getattr(seg._get_sweeper(), "score_diag32", False)
-    if bigram or diag32:
+    if args.full and (bigram or diag32):
         _abi.check(_abi.lib().segk_profile_enable(_abi.ctx(), 1))
     win = []
     for _ in range(max(1, args.windows)):
@@ -304,6 +338,17 @@ def main_fbgmm(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         win = [float(v) for v in t.cpu()]
     elapsed = float(np.median(win))
+    if args.dump_outputs:
+        # what gibbs_sample() reads back after the sweep (every rank takes part: the reads are collectives when N > 1)
+        sw = seg._get_sweeper()
+        utt_logprob = sw.utt_values(seg._df.out_logprob)
+        seg.materialise()
+        lpz, lpx, n_comp, n_tok = (seg._df.record_metrics(urn=True, urn_a=seg.lm.a) if bigram else seg._df.record_metrics())
+        outputs = {"boundaries": seg.utterances.boundaries, "assignments": seg.acoustic_model.components.assignments,
+                   "utt_log_prob": utt_logprob, "log_marg": lpz + lpx, "log_prob_z": lpz, "log_prob_X_given_z": lpx,
+                   "components": n_comp, "n_tokens": n_tok}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
     if rank == 0:
         sw = seg._get_sweeper()
         cnt, tot, occ = sw.totals()
@@ -316,6 +361,7 @@ def main_fbgmm(args):
                                    "max": 1e3 * max(win) / args.steps},
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": ("f32 span scores and token likelihoods, f64 sampling" if diag32 else
+                      "fp16x2 span scores, f64 sampling" if bigram and getattr(sw, "score_f16", False) else
                       "f32 span scores, f64 sampling" if bigram else "f64"), "data": "synthetic",
             "config": {"workload": "%s batch-synchronous blocked Gibbs sweep, 8 blocks (BASELINE.json configs[%d])"
                                    % ("BigramAcousticWordseg" if bigram else "UnigramAcousticWordseg + FBGMM (diag)",
@@ -325,7 +371,7 @@ def main_fbgmm(args):
                        "parallelism": "utterance slices x%d, one all-gather of partial sums per Gibbs step" % world,
                        "components_after": occ, "tokens": int(tot)},
         }
-        if bigram:
+        if bigram and args.full:
             nmax = 256
             ms = (C.c_float * nmax)()
             rows = (C.c_int64 * nmax)()
@@ -362,7 +408,7 @@ def main_fbgmm(args):
                                        "frac": achieved / PEAK_FP32_MATRIX_TFLOPS, "traffic": None, "ms_per_launch": score_ms,
                                        "flops_per_launch": flops}
             _abi.check(_abi.lib().segk_profile_enable(_abi.ctx(), 0))
-        if diag32:
+        if diag32 and args.full:
             # dominant kernel: k_fbb_score_diag32, one launch per Gibbs step.  Algorithmic work = one Student-t term
             # log(1 + delta^2 q) per (row, slot, dimension): rows x K_max x D terms per launch; the roofline is what the
             # vector ALUs sustain on exactly that term with operands in registers (segk_calibrate_vlog, measured here)
@@ -390,7 +436,7 @@ def main_fbgmm(args):
                                    "traffic": None, "ms_per_launch": score_ms, "terms_per_launch": terms,
                                    "peak_source": "k_vlog_calibrate measured in this run: the kernel's inner term (v_sub, v_mul, v_fma, "
                                                   "v_log_f32, v_add) from registers on all %d CUs" % torch.cuda.get_device_properties(0).multi_processor_count}
-        if world == 1 and args.cpu_utts > 0:
+        if args.full and world == 1 and args.cpu_utts > 0:
             from oracle import np_oracle as no
             n_cpu = min(args.cpu_utts, 300 if bigram else 1000) // (10 if bigram else 1) or 1
             keys = sorted(corpus[0])[:n_cpu]
@@ -440,6 +486,11 @@ def main_sequential(args):
     rec = seg.segment(steps)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        c = seg.acoustic_model.components
+        outputs = {"boundaries": seg.utterances.boundaries, "assignments": c.assignments, "means": c.means, "counts": c.counts}
+        outputs.update({k: rec[k][-1] for k in ("sum_neg_sqrd_norm", "sum_neg_len_sqrd_norm", "components", "n_tokens")})
+        dump_outputs(args.dump_outputs, outputs)
     print(json.dumps({
         "metric": "Gibbs sweeps/sec (sequential reference chain, 10k utts, D=100, K=1000)",
         "value": steps / elapsed, "unit": "sweeps/s", "n_gpus": 1, "steps": steps, "warmup": warmup,
@@ -488,6 +539,10 @@ def main_fbgmm_sequential(args, bigram=False):
     rec = seg.gibbs_sample(args.steps)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        outputs = {"boundaries": seg.utterances.boundaries, "assignments": seg.acoustic_model.components.assignments}
+        outputs.update({k.replace("*", "_x_"): v[-1] for k, v in rec.items() if k != "sample_time"})
+        dump_outputs(args.dump_outputs, outputs)
     t_loop = float(np.mean(rec["sample_time"]))
     print(json.dumps({
         "metric": "Gibbs sweeps/sec (sequential reference chain, %s, 1k utts, D=39, K=100)"
@@ -519,15 +574,21 @@ def main():
     ap.add_argument("--K", type=int, default=1000)
     ap.add_argument("--landmarks", type=int, default=20)
     ap.add_argument("--n-slices-max", type=int, default=6)
-    ap.add_argument("--windows", type=int, default=9, help="timed windows of --steps sweeps each (at least; more are added "
-                    "until --min-seconds of timed sweeps have run); the median window is reported")
-    ap.add_argument("--min-seconds", type=float, default=2.0, help="lower bound of the total timed region")
-    ap.add_argument("--no-seq-chain", action="store_true", help="skip the sequential_chain extra key (N = 1)")
-    ap.add_argument("--no-early", action="store_true", help="skip the early_sweeps and minibatch extra keys (N = 1)")
-    ap.add_argument("--cpu-utts", type=int, default=2000, help="utterances timed for cpu_baseline (0 = skip)")
-    ap.add_argument("--no-events", action="store_true", help="do not bracket the score kernel with events")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline: several timed windows, "
+                    "roofline, stage counts, the measured collective, the sequential chain, early sweeps, mini-batch form, "
+                    "cpu_baseline (a plain run times exactly --steps sweeps and prints the headline line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed sweeps, write what the last one "
+                    "computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--windows", type=int, default=None, help="timed windows of --steps sweeps each (at least; more are added "
+                    "until --min-seconds of timed sweeps have run); the median window is reported (default 9 with --full, else 1)")
+    ap.add_argument("--min-seconds", type=float, default=None,
+                    help="lower bound of the total timed region (default 2.0 with --full, else 0)")
+    ap.add_argument("--no-seq-chain", action="store_true", help="skip the sequential_chain extra key (--full, N = 1)")
+    ap.add_argument("--no-early", action="store_true", help="skip the early_sweeps and minibatch extra keys (--full, N = 1)")
+    ap.add_argument("--cpu-utts", type=int, default=2000, help="utterances timed for cpu_baseline (--full; 0 = skip)")
+    ap.add_argument("--no-events", action="store_true", help="do not bracket the score kernel with events (--full)")
     ap.add_argument("--event-period", type=int, default=8,
-                    help="bracket the score kernel of every Nth sweep of the timed region with HIP events (roofline.achieved)")
+                    help="bracket the score kernel of every Nth sweep of the timed region with HIP events (--full: roofline.achieved)")
     ap.add_argument("--workload", default="kmeans_c3", choices=["kmeans_c3", "fbgmm_diag_c2", "bigram_c5", "kmeans_c3_sequential", "fbgmm_c2_sequential",
                              "bigram_c2_sequential"],
                     help="kmeans_c3 (default) is the headline of BASELINE.json (configs[2]); fbgmm_diag_c2 = configs[1] "
@@ -543,6 +604,10 @@ def main():
         args.steps = 3 if seq else 50
     if args.warmup is None:
         args.warmup = 1 if seq else 5
+    if args.windows is None:
+        args.windows = 9 if args.full else 1
+    if args.min_seconds is None:
+        args.min_seconds = 2.0 if args.full else 0.0
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not seq:
         self_launch(args.gpus)                           # does not return
     if args.workload in ("fbgmm_c2_sequential", "bigram_c2_sequential"):
@@ -595,13 +660,16 @@ def main():
     import ctypes as C
     from segmentalist_amd import _abi
     use_ev = not args.no_events
+    # --full: every `--event-period`-th sweep of the timed region has its score kernel bracketed by events (an event record
+    # between two kernels costs the stream ~3 us of bubble: around every launch that was 6.5 us, 1.2 %, of the sweep it
+    # measures).  A plain run brackets the first timed sweep's only: no figure is read from it, but the library notes which
+    # score kernel ran, and `dtype` names it.
+    ev_period = max(1, args.event_period) if args.full else 1 << 30
     # a hipGraph capture cannot contain the event records: with SEGK_SWEEP_GRAPH=1 the timed windows replay the graph
-    # and the score kernel is timed afterwards over `steps` further sweeps launched plainly
+    # and the score kernel is timed afterwards over further sweeps launched plainly (`steps` of them; one in a plain run)
     ev_after = use_ev and sweeper.use_graph
     if use_ev and not ev_after:
-        # every `--event-period`-th sweep of the timed region has its score kernel bracketed by events (an event record between
-        # two kernels costs the stream ~3 us of bubble: around every launch that was 6.5 us, 1.2 %, of the sweep it measures)
-        _abi.check(_abi.lib().segk_profile_enable(_abi.ctx(), max(1, args.event_period)))
+        _abi.check(_abi.lib().segk_profile_enable(_abi.ctx(), ev_period))
     # `windows` back-to-back timed windows of EXACTLY `steps` sweeps each, every one bracketed by barrier +
     # synchronize on both sides and reduced with MAX over the ranks; the line reports the MEDIAN window (a 13 ms
     # window moves by percent with one clock ramp; the spread is reported beside it)
@@ -629,34 +697,64 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         win = [float(v) for v in t.cpu()]
     elapsed = float(np.median(win))
+    if args.dump_outputs:
+        # what a caller reads back after the last timed sweep: segment()'s record of it (one rank: from the token lists) and
+        # the state (every rank takes part: with N > 1 the reads are collectives)
+        c = seg.acoustic_model.components
+        if world == 1:
+            rec = seg._dk.batch_record(sweeper.part.utt_lo, sweeper.part.utt_hi)
+            rec = {"sum_neg_len_sqrd_norm": rec[0], "components": rec[1], "n_tokens": rec[2], "sum_neg_sqrd_norm": rec[3]}
+        else:
+            rec = {"sum_neg_len_sqrd_norm": float(seg._dk.out_scalars[0].item())}
+        outputs = {"boundaries": seg.utterances.boundaries, "assignments": c.assignments, "means": c.means, "counts": c.counts}
+        outputs.update(rec)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
     if ev_after:
         sweeper.use_graph = False
         _abi.check(_abi.lib().segk_profile_enable(_abi.ctx(), 1))
-        for _ in range(args.steps):
+        for _ in range(args.steps if args.full else 1):
             seg.batch_sweep_async()
         barrier()
         sweeper.use_graph = True
 
-    score_ms, score_rows = None, rows_local
+    score_ms, score_rows, kind, launches = None, rows_local, -1, 1
     if use_ev:
-        nmax = min(args.steps * len(win), 256)
-        ms = (C.c_float * nmax)()
-        rows = (C.c_int64 * nmax)()
-        got = _abi.lib().segk_profile_read(_abi.ctx(), ms, rows, nmax)
-        if got > 0:
-            score_ms = float(np.mean(ms[:got]))
-            score_rows = int(rows[got - 1])
+        if args.full:
+            nmax = min(args.steps * len(win), 256)
+            ms = (C.c_float * nmax)()
+            rows = (C.c_int64 * nmax)()
+            got = _abi.lib().segk_profile_read(_abi.ctx(), ms, rows, nmax)
+            if got > 0:
+                score_ms = float(np.mean(ms[:got]))
+                score_rows = int(rows[got - 1])
+        kind = int(_abi.lib().segk_profile_last_kind(_abi.ctx()))
+        launches = int(_abi.lib().segk_profile_last_launches(_abi.ctx()))
         _abi.check(_abi.lib().segk_profile_enable(_abi.ctx(), 0))
+    b3 = getattr(seg._corpus, "Xb3", None) is not None and os.environ.get("SEGK_SCORE_B3", "2") != "0"
+    pieces = int(seg._corpus.c.sp_pieces) if b3 else 0
+    if kind < 0:
+        dtype = "f32"                                    # (no score launch was bracketed: --no-events)
+    elif b3 and kind == 5:
+        dtype = "fp16 one-product filter + fp16x2 second stage, float32 reference arithmetic for the results"
+    elif b3 and kind == 1:
+        dtype = "fp16 pre-filter + fp16x2"
+    elif b3:
+        dtype = "fp16x2" if pieces == 2 else "bf16x3"
+    else:
+        dtype = "f32"
 
     # rows the hinted exact stage passed on to the second stage / rows of the full scan, last sweep (diagnostic)
-    sc = (C.c_int32 * 2)()
-    _abi.check(_abi.lib().segk_kmeans_stage_counts(_abi.ctx(), C.byref(seg._dk.cand), sc, _abi.stream()))
-    stage_counts = {"second_stage_rows": int(sc[0]), "full_scan_rows": int(sc[1]), "rows": int(rows_local)}
+    stage_counts = None
+    if args.full:
+        sc = (C.c_int32 * 2)()
+        _abi.check(_abi.lib().segk_kmeans_stage_counts(_abi.ctx(), C.byref(seg._dk.cand), sc, _abi.stream()))
+        stage_counts = {"second_stage_rows": int(sc[0]), "full_scan_rows": int(sc[1]), "rows": int(rows_local)}
 
     # N > 1: the cost of the per-sweep collective, measured outside the timed windows -- `steps` further sweeps with the
     # all-gather bracketed by stream synchronisation on every rank (comm.TorchComm.timed)
     gather_info = None
-    if world > 1:
+    if args.full and world > 1:
         comm = sweeper.comm
         comm.timed, comm.gather_us, comm.gather_calls = True, 0.0, 0
         for _ in range(args.steps):
@@ -675,7 +773,7 @@ def main():
     # N = 1: the reference's own chain (sync='sequential', the API default; bit-identical to the reference) on the same
     # corpus, outside the timed region: one warm sweep, two timed by the chain's own record['sample_time'] bracket
     seq_chain = None
-    if world == 1 and rank == 0 and not args.no_seq_chain:
+    if args.full and world == 1 and rank == 0 and not args.no_seq_chain:
         try:
             random.seed(0)
             np.random.seed(0)
@@ -694,7 +792,7 @@ def main():
 
     # N = 1: sweeps 1-10 of a fresh chain on both score paths, and the mini-batch form beside `value` (outside the timed region)
     early, mb = None, None
-    if world == 1 and rank == 0 and not args.no_early:
+    if args.full and world == 1 and rank == 0 and not args.no_early:
         try:
             early = early_sweeps(kaw, corpus, args)
         except Exception as e:                           # the extra keys must never cost the line
@@ -722,7 +820,7 @@ def main():
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": None,
-            "dtype": "f32",
+            "dtype": dtype,
             "data": "synthetic",
             "config": {
                 "workload": "SegmentalKMeansWordseg batch-synchronous sweep (BASELINE.json configs[2])",
@@ -752,9 +850,6 @@ def main():
                         (args.utts, args.landmarks, args.n_slices_max, args.dim, args.K, world):
                     traffic = tj["traffic_bytes_per_launch"]
             achieved = flops_per_launch / (score_ms * 1e-3) / 1e12
-            b3 = getattr(seg._corpus, "Xb3", None) is not None and os.environ.get("SEGK_SCORE_B3", "2") != "0"
-            kind = int(_abi.lib().segk_profile_last_kind(_abi.ctx())) if use_ev else -1
-            launches = int(_abi.lib().segk_profile_last_launches(_abi.ctx())) if use_ev else 1
             if b3 and kind == 5:
                 # segk_kmeans_score_hinted (every sweep but the first): k_kmeans_top2_rs scores every row against every
                 # component with ONE v_mfma_f32_32x32x16_f16 product per 16 dimensions and keeps the two largest values per
@@ -771,7 +866,6 @@ def main():
                     if (wl["utterances"], wl["landmarks_per_utt"], wl["n_slices_max"], wl["D"], wl["K"], wl["n_gpus"]) == \
                             (args.utts, args.landmarks, args.n_slices_max, args.dim, args.K, world):
                         traffic = tj["traffic_bytes_per_launch"]
-                out["dtype"] = "fp16 one-product filter + fp16x2 second stage, float32 reference arithmetic for the results"
                 out["roofline"] = {
                     "bound": "mfma",
                     "kernel": "k_kmeans_top2_rs<%d> (all %d rows of the rank x all %d component slots; one fp16 product on the 16-bit "
@@ -808,7 +902,6 @@ def main():
                     if (wl["utterances"], wl["landmarks_per_utt"], wl["n_slices_max"], wl["D"], wl["K"], wl["n_gpus"]) == \
                             (args.utts, args.landmarks, args.n_slices_max, args.dim, args.K, world):
                         traffic = tj["traffic_bytes_per_launch"]
-                out["dtype"] = "fp16 pre-filter + fp16x2"
                 out["roofline"] = {
                     "bound": "mfma",
                     "kernel": "k_kmeans_score_h1<%d, 4> (main launch: %d of %d rows; one-product fp16 pre-filter on the 16-bit "
@@ -829,11 +922,9 @@ def main():
                 # of the dtype the matrix pipe computes in); the executed_* keys count what the pipe really
                 # does: 3 (6) products x (K padded to 32) x (D padded to 16).
                 kp, kpad = (args.dim + 15) // 16 * 16, (args.K + 31) // 32 * 32
-                pieces = int(seg._corpus.c.sp_pieces)
                 n_prod = 3 if pieces == 2 else 6
                 executed = n_prod * 2.0 * score_rows * kpad * kp
                 ex_tf = executed / (score_ms * 1e-3) / 1e12
-                out["dtype"] = "fp16x2" if pieces == 2 else "bf16x3"
                 out["roofline"] = {
                     "bound": "mfma",
                     "kernel": "k_kmeans_score_sp<%d, 4, %d> (main launch: %d of %d rows; float32 contraction as %s "
@@ -855,7 +946,8 @@ def main():
                     "traffic": traffic, "ms_per_launch": score_ms,
                     "flops_per_launch": flops_per_launch,
                 }
-        out["stage_counts"] = stage_counts
+        if stage_counts is not None:
+            out["stage_counts"] = stage_counts
         if gather_info is not None:
             out["config"]["collective_measured"] = gather_info
         if seq_chain is not None:
@@ -869,7 +961,7 @@ def main():
                                   "note": "`value` is n_batches = 1 (statistics frozen for a whole sweep); n_batches = 8 refreshes them "
                                           "eight times per sweep (closer to the reference's per-utterance refresh: more components "
                                           "survive) at the cost of eight statistics passes per sweep"}
-        if world == 1 and args.cpu_utts > 0:
+        if args.full and world == 1 and args.cpu_utts > 0:
             out["cpu_baseline"] = cpu_baseline(corpus, args.utts, args.K, args.n_slices_max, args.cpu_utts)
         print(json.dumps(out))
     if world > 1:

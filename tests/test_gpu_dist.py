@@ -119,7 +119,7 @@ def test_bench_self_launches_its_ranks_and_reports_the_measured_collective(tmp_p
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--windows", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--windows", "1",
            "--min-seconds", "0", "--cpu-utts", "0", "--utts", "400", "--K", "64", "--dim", "16"]
     res = subprocess.run(cmd, check=True, env=env, timeout=600, cwd=ROOT, stdout=subprocess.PIPE, text=True)
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

@@ -285,3 +285,25 @@ def test_parallel_forms_of_the_finalize_kernels_serial_loops_equal_the_serial_lo
             got.extend(np.minimum(kr, K2 + below).tolist())
             K2 += int(mask.sum())
         assert got == want and K2 == K, trial
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_the_cap(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: one DIR/<name>.npy per output, float32 for float32 / boolean results and float64 for
+    everything else (integers exactly); an output over its share of the cap keeps the same seeded sample of rows every run,
+    with the rows it kept beside it, and the files stay within the cap."""
+    import os
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 1 << 16)
+    big = np.arange(40000, dtype=np.int64).reshape(20000, 2)
+    outs = {"means": np.ones((3, 4), np.float32), "boundaries": np.array([[True, False]]), "counts": np.arange(5),
+            "total": 1.5, "big": big}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outs)
+    a = tmp_path / "a"
+    assert np.load(a / "means.npy").dtype == np.float32 and np.load(a / "boundaries.npy").dtype == np.float32
+    assert np.load(a / "counts.npy").dtype == np.float64 and np.array_equal(np.load(a / "counts.npy"), np.arange(5))
+    assert np.load(a / "total.npy").tolist() == [1.5]
+    rows = np.load(a / "big.rows.npy")
+    assert np.array_equal(np.load(a / "big.npy"), big[rows.astype(np.int64)].astype(np.float64))
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "big.rows.npy"))
+    assert sum(os.path.getsize(str(p)) for p in a.iterdir()) <= 1 << 16

@@ -3,7 +3,7 @@
 # 16 return behind the row staging, 32 return at once (the empty launch)
 cd $GRAFT_REPO_ROOT
 for dbg in 0 1 2 3 11 19 32; do
-    SEGK_D32_DBG=$dbg timeout -k 10 200 python bench.py --workload fbgmm_diag_c2 --steps 20 --warmup 3 --cpu-utts 0 2>/dev/null | python -c "
+    SEGK_D32_DBG=$dbg timeout -k 10 200 python bench.py --full --workload fbgmm_diag_c2 --steps 20 --warmup 3 --cpu-utts 0 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print('dbg=$dbg ms_per_launch %.4f  ms_per_step %.4f' % (d['roofline']['ms_per_launch'], d['ms_per_step']))"
 done
