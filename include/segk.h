@@ -65,8 +65,8 @@ int32_t segk_abi_version(void);
  * stream a few microseconds of bubble: bench.py samples every 8th sweep of its timed region).                            */
 int32_t segk_profile_enable(segk_ctx *ctx, int32_t on);
 int32_t segk_profile_read(segk_ctx *ctx, float *ms_out, int64_t *rows_out, int32_t max);
-/* Which kernel the most recent recorded launch was: 0 the fp32-MFMA filter, 2 / 3 the split-precision
- * filter (fp16x2 / bf16x3), 1 the one-product fp16 pre-filter (k_kmeans_score_h1: rows above ~260 k,
+/* Which kernel the most recent recorded launch was: 0 the fp32-MFMA filter, 2 the split-precision
+ * filter (fp16x2), 1 the one-product fp16 pre-filter (k_kmeans_score_h1: rows above ~260 k,
  * D % 4 == 0), 4 the log-sum-exp kernels of the FBGMM batch sampler, 5 the range-stationary one-product
  * top-2 kernel of segk_kmeans_score_hinted (k_kmeans_top2_rs); -1 none recorded.                      */
 int32_t segk_profile_last_kind(segk_ctx *ctx);
@@ -107,7 +107,7 @@ typedef struct segk_corpus {
     const void *Xb3;         /* [dev] optional (float32 data, 8 <= D <= 128): the rows split into 16-bit pieces
                                 (segk_corpus_b3_bytes bytes, written by segk_corpus_prepare_b3); enables the
                                 split-precision k-means filter on the 16-bit matrix pipe (NULL: fp32 MFMA)  */
-    int32_t sp_pieces;       /* 2 = fp16x2, 3 = bf16x3: what Xb3 holds                        */
+    int32_t sp_pieces;       /* 2 = fp16x2: what Xb3 holds (any other value: Xb3 is not used) */
     int32_t band_W;          /* window of the banded span tables below (0: none)              */
     /* optional banded image of vec_ids / durations (utterances.py:91-105 keeps the triangular tables; the
      * per-utterance kernels only ever read the band t - s <= n_slices_max): entry (t, w), t = 1..N_max the span's
@@ -125,8 +125,8 @@ typedef struct segk_corpus {
  * passes a separate [n_emb, ld32] float buffer, written here) and xnorm. */
 int32_t segk_corpus_prepare(segk_ctx *ctx, const segk_corpus *c, float *X32_out, float *xnorm_out,
                             void *stream);
-/* Xb3_out [dev] segk_corpus_b3_bytes(n_emb, D) bytes (the size of three piece planes whatever `pieces` is).
- * pieces = 3: x = x1 + x2 + x3 exactly in bf16; pieces = 2: 2^a x = x1 + 2^-11 x2 (+ two dropped bits) in
+/* Xb3_out [dev] segk_corpus_b3_bytes(n_emb, D) bytes (the size of three piece planes).  pieces must be 2
+ * (anything else: SEGK_ERR_ARG): 2^a x = x1 + 2^-11 x2 (+ two dropped bits) in
  * fp16, a chosen from max |x|, followed -- in the room of the third plane -- by float [n_emb]
  * |x - x1| per row, which the one-product pre-filter's margin uses, and float [n_emb] -|x|^2 in the reference's
  * float32 summation order, which segk_kmeans_score_hinted uses.                                          */
@@ -149,7 +149,7 @@ typedef struct segk_kmeans {
     /* derived operands of the MFMA score kernel, maintained by the library: */
     float *tiles;              /* [dev] segk_kmeans_tiles_floats(K_max, D) floats               */
     double *mnorm_max;         /* [dev] [1] max_k ||means[k]||_2^2 (kept with atomicMax on the bits) */
-    float *tiles_b3;           /* [dev] optional: segk_kmeans_tiles_b3_floats(K_max, D) floats, the bf16x3
+    float *tiles_b3;           /* [dev] optional: segk_kmeans_tiles_b3_floats(K_max, D) floats, the fp16x2
                                   operand image of the means (maintained beside `tiles` when non-NULL) */
 } segk_kmeans;
 

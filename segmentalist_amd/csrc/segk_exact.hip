@@ -628,7 +628,7 @@ int segk_resolve_on(segk_ctx *ctx, const segk_corpus *c, const segk_kmeans *m, c
                                            *c, *m, ids, row0, n, *cand););
     const int nt = 256;
     // components in LDS, a chunk of the queue per workgroup (SEGK_BRUTE_LS=0: one workgroup per four rows)
-    if (fused && !ctx->capturing && !(getenv("SEGK_BRUTE_LS") && atoi(getenv("SEGK_BRUTE_LS")) == 0)) {
+    if (fused && !ctx->capturing && segk_env_int("SEGK_BRUTE_LS", 1) != 0) {
         if (ctx->brute_ws_cap < n) {
             SEGK_CHECK_HIP(hipStreamSynchronize(st));
             if (ctx->brute_ws) (void)hipFree(ctx->brute_ws);

@@ -1477,13 +1477,12 @@ __global__ __launch_bounds__(512) void k_fbb_assign(segk_corpus c, segk_fbgmm f,
 // The same with a language model and the token likelihoods from the matrix-core contraction: ONE WAVE per utterance.
 // The draws of an utterance are a chain (each needs the slot of the token before), and the block-wide form above
 // pays seven workgroup barriers per token for it; a wave needs none, and four times as many utterances are in flight.
-// Per token the same expressions in the same order; the sums keep the association of the block-wide form at 256 threads
-// (virtual thread v = 64 cw + lane sums the slots v, v + 256, ...; a butterfly per cw; the four results added in order),
-// so the probabilities and the draws are the same bits.
+// Per token the same likelihood and language-model terms; the softmax on the hardware float32 logarithm and exponential
+// (below), so the probabilities differ from the block-wide form's by ~3e-6 relative.
 // ---------------------------------------------------------------------------------------
 // PROBE: the variant the library launches while segk_fbb_set_probe is in force -- the same statements plus the stores of
 // the token likelihoods (a test of a null pointer per slot inside the token loop cost the production kernel ~9 %)
-template <int F32, bool PROBE = false>
+template <bool PROBE = false>
 __global__ __launch_bounds__(256) void k_fbb_assign_lm_wave(segk_corpus c, segk_fbgmm f, segk_fbatch bt, FbbMap map, int b, uint64_t sweep,
                                                             double prior_alpha, double anneal_temp, const int32_t *new_tok,
                                                             const int32_t *n_new, const float *llmat, int64_t ll_ld, int n_items,
@@ -1499,7 +1498,7 @@ __global__ __launch_bounds__(256) void k_fbb_assign_lm_wave(segk_corpus c, segk_
     // (the packed form below wants the other direction, slot of column c, in the same place)
     int *cm = (int *)((double *)smem + 4 * (int64_t)KM);   // [K_max + 1]
     constexpr int KPL = 16;
-    const bool packed = F32 && KM <= 64 * KPL;
+    const bool packed = KM <= 64 * KPL;
     {
         const int32_t *g = fbb_cmap(&bt, KM);
         const int pcol = g[KM];
@@ -1524,238 +1523,177 @@ __global__ __launch_bounds__(256) void k_fbb_assign_lm_wave(segk_corpus c, segk_
     const double tot = bt.scal[0];
     const double norm = f.lms * log(tot + prior_alpha);
     const double n_empty = (double)KM - bt.scal[1];
-    auto sum_exp = [&](double shift) -> double {           // sum_k exp(z[k] - shift) in the order of block_sum at 256 threads
-        double acc = 0.0;
-        for (int cw = 0; cw < 4 && cw * 64 < KM; cw++) {
-            double sv = 0.0;
-            for (int k = cw * 64 + lane; k < KM; k += 256) sv += exp(z[k] - shift);
-            sv = fb_wave_sum(sv);
-            acc = cw == 0 ? sv : acc + sv;
-        }
-        return acc;
-    };
     int j_prev = -1;
-    if (F32) {
-        // The matrix-core modes (`score_precision` f32 / f16: log-likelihoods within 1e-4 relative) take the token
-        // likelihoods as float32 already; here the softmax follows: K_max hardware logarithms and 2 K_max hardware
-        // exponentials per token (v_log_f32 / v_exp_f32 on differences that were formed in fp64) instead of 3 K_max fp64
-        // software ones -- the step was bound by them (290 us per Gibbs step of bigram_c5).  Probabilities carry ~3e-6
-        // relative error; a draw changes when the uniform falls that close to a cumulative boundary.
-        const float LOG2E = 1.4426950408889634f;
-        const double le = log(n_empty), ltot = log(tot + f.lm_a), inv_tot = 1. / (tot + f.lm_a), aK = f.lm_a / (double)KM, bK = f.lm_b / (double)KM;
-        if (packed) {
-            // The softmax over the OCCUPIED slots only (419 of 1 000 at configs[4]): the empty ones share one logit -- no
-            // tokens, no bigram counts, the pseudo-component's likelihood -- which is evaluated once and enters the sum
-            // n_empty times.  Lane l holds the columns l, l + 64, ... of the packed matrix (up to 16; what does not change
-            // from token to token stays in registers for the utterance, and a token's loads are all issued before the
-            // first is used).  The draw walks the slots in slot order as utils.draw does: the columns' probabilities go to
-            // LDS, lane l sums the chunk [l per, (l + 1) per) of them plus the empty slots that lie between its first
-            // column's slot and the next chunk's, a scan over the lanes finds the chunk and one walk over it the slot.
-            const int *inv = cm;
-            const int n_occ = fbb_cmap(&bt, KM)[KM];
-            const int jmax = (n_occ + 63) >> 6, per = jmax > 0 ? jmax : 1;
-            const bool has_e = n_empty > 0.0;
-            // (per column: count + a/K for the prior's argument -- which goes through v_log_f32 and is formed in float32 --
-            // and the constant of the likelihood; float32 like the matrix's values they are added to)
-            float naK[KPL], c2[KPL];
+    // The matrix-core modes (`score_precision` f32 / f16: log-likelihoods within 1e-4 relative) take the token
+    // likelihoods as float32 already; here the softmax follows: K_max hardware logarithms and 2 K_max hardware
+    // exponentials per token (v_log_f32 / v_exp_f32 on differences that were formed in fp64) instead of 3 K_max fp64
+    // software ones -- the step was bound by them (290 us per Gibbs step of bigram_c5).  Probabilities carry ~3e-6
+    // relative error; a draw changes when the uniform falls that close to a cumulative boundary.
+    const float LOG2E = 1.4426950408889634f;
+    const double le = log(n_empty), ltot = log(tot + f.lm_a), inv_tot = 1. / (tot + f.lm_a), aK = f.lm_a / (double)KM, bK = f.lm_b / (double)KM;
+    if (packed) {
+        // The softmax over the OCCUPIED slots only (419 of 1 000 at configs[4]): the empty ones share one logit -- no
+        // tokens, no bigram counts, the pseudo-component's likelihood -- which is evaluated once and enters the sum
+        // n_empty times.  Lane l holds the columns l, l + 64, ... of the packed matrix (up to 16; what does not change
+        // from token to token stays in registers for the utterance, and a token's loads are all issued before the
+        // first is used).  The draw walks the slots in slot order as utils.draw does: the columns' probabilities go to
+        // LDS, lane l sums the chunk [l per, (l + 1) per) of them plus the empty slots that lie between its first
+        // column's slot and the next chunk's, a scan over the lanes finds the chunk and one walk over it the slot.
+        const int *inv = cm;
+        const int n_occ = fbb_cmap(&bt, KM)[KM];
+        const int jmax = (n_occ + 63) >> 6, per = jmax > 0 ? jmax : 1;
+        const bool has_e = n_empty > 0.0;
+        // (per column: count + a/K for the prior's argument -- which goes through v_log_f32 and is formed in float32 --
+        // and the constant of the likelihood; float32 like the matrix's values they are added to)
+        float naK[KPL], c2[KPL];
 #pragma unroll
-            for (int j = 0; j < KPL; j++) {
-                naK[j] = 1.f;
-                c2[j] = 0.f;
-                if (j < jmax) {
-                    const int q = lane + 64 * j, k = q < n_occ ? inv[q] : inv[0];
-                    naK[j] = (float)(bt.cnt[k] + aK);
-                    c2[j] = (float)(norm - (bt.zconst[k] - bt.lconst[k]));
-                }
+        for (int j = 0; j < KPL; j++) {
+            naK[j] = 1.f;
+            c2[j] = 0.f;
+            if (j < jmax) {
+                const int q = lane + 64 * j, k = q < n_occ ? inv[q] : inv[0];
+                naK[j] = (float)(bt.cnt[k] + aK);
+                c2[j] = (float)(norm - (bt.zconst[k] - bt.lconst[k]));
             }
-            const float lam_it = (float)(f.lm_lambda * inv_tot), bKf = (float)bK, lmsf = (float)f.lms, LN2f = 0.6931471805599453f;
-            const int *bg32 = (const int *)f.lm_bigram;                         // (counts: the low words)
-            const int lo = lane * per < n_occ ? lane * per : n_occ, hi = lo + per < n_occ ? lo + per : n_occ;
-            const int b_lo = lane == 0 ? 0 : (lo < n_occ ? inv[lo] : KM);       // first slot of this lane's chunk
-            const int b_hi = hi < n_occ ? inv[hi] : KM;                         // ... of the next one's
-            const double n_gap = (double)((b_hi - b_lo) - (hi - lo));           // empty slots inside
-            for (int t = 0; t < nn; t++) {
-                const int64_t e = new_tok[(int64_t)utt * c.N_max + t];
-                const float *mrow = llmat + ((int64_t)item * c.N_max + t) * ll_ld;
-                const double inv_prev = j_prev >= 0 ? (1. - f.lm_lambda) / (bt.cnt[j_prev] + f.lm_b) : 0.0;
-                const float mre = mrow[n_occ];
-                const float inv_prevf = (float)inv_prev;
-                float mr[KPL];
-                int bg[KPL];
-#pragma unroll
-                for (int j = 0; j < KPL; j++) {
-                    mr[j] = 0.f;
-                    bg[j] = 0;
-                    if (j < jmax) {
-                        const int q = lane + 64 * j;
-                        mr[j] = mrow[q < n_occ ? q : n_occ];
-                        bg[j] = j_prev >= 0 ? bg32[2 * ((int64_t)j_prev * KM + inv[q < n_occ ? q : 0])] : 0;
-                    }
-                }
-                const double empty_ll = (double)mre * LN2 - zc_empty - le + norm;
-                double ze = NEG_INF_D;
-                if (has_e) {
-                    double pz;
-                    if (j_prev < 0) pz = ((double)(__builtin_amdgcn_logf((float)aK) * 0.6931471805599453f) - ltot) * f.lms;
-                    else pz = (double)(__builtin_amdgcn_logf((float)aK * lam_it + bKf * inv_prevf) * LN2f * lmsf);
-                    ze = pz + empty_ll;
-                }
-                if constexpr (PROBE) {
-                    const int32_t *g = fbb_cmap(&bt, KM);
-                    for (int k = lane; k < KM; k += 64)
-                        if (g[k] < 0) probe_ll[((int64_t)utt * c.N_max + t) * probe_ld + k] = empty_ll;
-                }
-                double zv[KPL], mx = ze;
-#pragma unroll
-                for (int j = 0; j < KPL; j++) {
-                    zv[j] = NEG_INF_D;
-                    if (j < jmax) {
-                        const double llv = (double)mr[j] * LN2 + (double)c2[j];
-                        const bool ok = lane + 64 * j < n_occ;
-                        if constexpr (PROBE)
-                            if (ok) probe_ll[((int64_t)utt * c.N_max + t) * probe_ld + inv[lane + 64 * j]] = llv;
-                        double pz;
-                        if (j_prev < 0) pz = ((double)(__builtin_amdgcn_logf(naK[j]) * LN2f) - ltot) * f.lms;
-                        else pz = (double)(__builtin_amdgcn_logf(naK[j] * lam_it + ((float)bg[j] + bKf) * inv_prevf) * LN2f * lmsf);
-                        zv[j] = ok ? pz + llv : NEG_INF_D;
-                        mx = zv[j] > mx ? zv[j] : mx;
-                    }
-                }
-                mx = fb_wave_max(mx, false);
-                // (the sum of the exponentials in float32 like its terms, the logarithm by v_log_f32: the differences were formed in
-                // fp64, what is summed lies in [0, 1])
-                auto sum_reg = [&](double shift) -> double {
-                    float sv = 0.f;
-#pragma unroll
-                    for (int j = 0; j < KPL; j++)
-                        if (j < jmax) sv += __builtin_amdgcn_exp2f((float)(zv[j] - shift) * LOG2E);      // 2^-inf = 0 behind the last column
-                    sv = fb_wave_sum_f32(sv);
-                    if (has_e) sv += (float)n_empty * __builtin_amdgcn_exp2f((float)(ze - shift) * LOG2E);
-                    return (double)sv;
-                };
-                double lse = fb_log_fast(sum_reg(mx)) + mx;
-                if (anneal_temp != 1.0) {                               // fbgmm.py:446-449
-                    double mx2 = NEG_INF_D;
-                    if (has_e) {
-                        ze = (1. / anneal_temp) * (ze - lse);
-                        mx2 = ze;
-                    }
-#pragma unroll
-                    for (int j = 0; j < KPL; j++)
-                        if (j < jmax) {
-                            zv[j] = (1. / anneal_temp) * (zv[j] - lse);
-                            mx2 = zv[j] > mx2 ? zv[j] : mx2;
-                        }
-                    mx2 = fb_wave_max(mx2, false);
-                    lse = fb_log_fast(sum_reg(mx2)) + mx2;
-                }
-#pragma unroll
-                for (int j = 0; j < KPL; j++)
-                    if (j < jmax && lane + 64 * j < n_occ) z[lane + 64 * j] = (double)__builtin_amdgcn_exp2f((float)(zv[j] - lse) * LOG2E);
-                const double p_e = has_e ? (double)__builtin_amdgcn_exp2f((float)(ze - lse) * LOG2E) : 0.0;
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                // ---- the draw
-                double sl = 0.0;
-                for (int q = lo; q < hi; q++) sl += z[q];
-                sl += n_gap * p_e;
-                const double incl = fb_wave_scan(sl);
-                const double u = segk_u01(bt.seed, sweep, (uint64_t)utt, (uint64_t)(c.N_max + t));
-                const unsigned long long below = __ballot(u < incl);
-                int kd = KM - 1;
-                if (below) {
-                    const int run = __ffsll((long long)below) - 1;
-                    double r = u - (fb_readlane(incl, run) - fb_readlane(sl, run));
-                    const int rlo = run * per < n_occ ? run * per : n_occ, rhi = rlo + per < n_occ ? rlo + per : n_occ;
-                    int pos = __builtin_amdgcn_readlane(b_lo, run);
-                    const int end = __builtin_amdgcn_readlane(b_hi, run);
-                    bool found = false;
-                    for (int q = rlo; q < rhi && !found; q++) {
-                        const int k = inv[q];
-                        const int gap = k - pos;
-                        if (gap > 0) {
-                            const double m = (double)gap * p_e;
-                            if (r < m) {
-                                int o = (int)(r / p_e);
-                                o = o < 0 ? 0 : (o > gap - 1 ? gap - 1 : o);
-                                kd = pos + o;
-                                found = true;
-                                break;
-                            }
-                            r -= m;
-                        }
-                        const double pq = z[q];
-                        if (r < pq) {
-                            kd = k;
-                            found = true;
-                            break;
-                        }
-                        r -= pq;
-                        pos = k + 1;
-                    }
-                    if (!found) {
-                        const int gap = end - pos;
-                        if (gap > 0 && p_e > 0.0) {
-                            int o = (int)(r / p_e);
-                            o = o < 0 ? 0 : (o > gap - 1 ? gap - 1 : o);
-                            kd = pos + o;
-                        } else {
-                            kd = pos > 0 ? pos - 1 : 0;
-                        }
-                    }
-                }
-                if (lane == 0) bt.slot[e] = kd;
-                j_prev = kd;
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            }
-            return;
         }
+        const float lam_it = (float)(f.lm_lambda * inv_tot), bKf = (float)bK, lmsf = (float)f.lms, LN2f = 0.6931471805599453f;
+        const int *bg32 = (const int *)f.lm_bigram;                         // (counts: the low words)
+        const int lo = lane * per < n_occ ? lane * per : n_occ, hi = lo + per < n_occ ? lo + per : n_occ;
+        const int b_lo = lane == 0 ? 0 : (lo < n_occ ? inv[lo] : KM);       // first slot of this lane's chunk
+        const int b_hi = hi < n_occ ? inv[hi] : KM;                         // ... of the next one's
+        const double n_gap = (double)((b_hi - b_lo) - (hi - lo));           // empty slots inside
         for (int t = 0; t < nn; t++) {
             const int64_t e = new_tok[(int64_t)utt * c.N_max + t];
             const float *mrow = llmat + ((int64_t)item * c.N_max + t) * ll_ld;
             const double inv_prev = j_prev >= 0 ? (1. - f.lm_lambda) / (bt.cnt[j_prev] + f.lm_b) : 0.0;
-            const double empty_ll = (double)mrow[cm[KM]] * LN2 - zc_empty - le + norm;
-            double mx = NEG_INF_D;
-            for (int k = lane; k < KM; k += 64) {
-                const double n = bt.cnt[k];
-                const double llv = n > 0.0 ? (double)mrow[cm[k]] * LN2 - (bt.zconst[k] - bt.lconst[k]) + norm : empty_ll;
-                if constexpr (PROBE) probe_ll[((int64_t)utt * c.N_max + t) * probe_ld + k] = llv;
-                double pz;
-                if (j_prev < 0) pz = ((double)(__builtin_amdgcn_logf((float)(n + aK)) * 0.6931471805599453f) - ltot) * f.lms;      // bigram_lms.py:64-69
-                else {                                                                                                          // bigram_lms.py:84-91
-                    const double pi = (n + aK) * inv_tot;
-                    const double pij = ((double)f.lm_bigram[(int64_t)j_prev * KM + k] + bK) * inv_prev;
-                    pz = (double)(__builtin_amdgcn_logf((float)(f.lm_lambda * pi + pij)) * 0.6931471805599453f) * f.lms;
+            const float mre = mrow[n_occ];
+            const float inv_prevf = (float)inv_prev;
+            float mr[KPL];
+            int bg[KPL];
+#pragma unroll
+            for (int j = 0; j < KPL; j++) {
+                mr[j] = 0.f;
+                bg[j] = 0;
+                if (j < jmax) {
+                    const int q = lane + 64 * j;
+                    mr[j] = mrow[q < n_occ ? q : n_occ];
+                    bg[j] = j_prev >= 0 ? bg32[2 * ((int64_t)j_prev * KM + inv[q < n_occ ? q : 0])] : 0;
                 }
-                const double v = pz + llv;
-                z[k] = v;
-                mx = v > mx ? v : mx;
+            }
+            const double empty_ll = (double)mre * LN2 - zc_empty - le + norm;
+            double ze = NEG_INF_D;
+            if (has_e) {
+                double pz;
+                if (j_prev < 0) pz = ((double)(__builtin_amdgcn_logf((float)aK) * 0.6931471805599453f) - ltot) * f.lms;
+                else pz = (double)(__builtin_amdgcn_logf((float)aK * lam_it + bKf * inv_prevf) * LN2f * lmsf);
+                ze = pz + empty_ll;
+            }
+            if constexpr (PROBE) {
+                const int32_t *g = fbb_cmap(&bt, KM);
+                for (int k = lane; k < KM; k += 64)
+                    if (g[k] < 0) probe_ll[((int64_t)utt * c.N_max + t) * probe_ld + k] = empty_ll;
+            }
+            double zv[KPL], mx = ze;
+#pragma unroll
+            for (int j = 0; j < KPL; j++) {
+                zv[j] = NEG_INF_D;
+                if (j < jmax) {
+                    const double llv = (double)mr[j] * LN2 + (double)c2[j];
+                    const bool ok = lane + 64 * j < n_occ;
+                    if constexpr (PROBE)
+                        if (ok) probe_ll[((int64_t)utt * c.N_max + t) * probe_ld + inv[lane + 64 * j]] = llv;
+                    double pz;
+                    if (j_prev < 0) pz = ((double)(__builtin_amdgcn_logf(naK[j]) * LN2f) - ltot) * f.lms;
+                    else pz = (double)(__builtin_amdgcn_logf(naK[j] * lam_it + ((float)bg[j] + bKf) * inv_prevf) * LN2f * lmsf);
+                    zv[j] = ok ? pz + llv : NEG_INF_D;
+                    mx = zv[j] > mx ? zv[j] : mx;
+                }
             }
             mx = fb_wave_max(mx, false);
-            auto sum_exp32 = [&](double shift) -> double {
-                double sv = 0.0;
-                for (int k = lane; k < KM; k += 64) sv += (double)__builtin_amdgcn_exp2f((float)(z[k] - shift) * LOG2E);
-                sv = fb_wave_sum(sv);
-                return sv;
+            // (the sum of the exponentials in float32 like its terms, the logarithm by v_log_f32: the differences were formed in
+            // fp64, what is summed lies in [0, 1])
+            auto sum_reg = [&](double shift) -> double {
+                float sv = 0.f;
+#pragma unroll
+                for (int j = 0; j < KPL; j++)
+                    if (j < jmax) sv += __builtin_amdgcn_exp2f((float)(zv[j] - shift) * LOG2E);      // 2^-inf = 0 behind the last column
+                sv = fb_wave_sum_f32(sv);
+                if (has_e) sv += (float)n_empty * __builtin_amdgcn_exp2f((float)(ze - shift) * LOG2E);
+                return (double)sv;
             };
-            double lse = log(sum_exp32(mx)) + mx;
+            double lse = fb_log_fast(sum_reg(mx)) + mx;
             if (anneal_temp != 1.0) {                               // fbgmm.py:446-449
                 double mx2 = NEG_INF_D;
-                for (int k = lane; k < KM; k += 64) {
-                    const double v = (1. / anneal_temp) * (z[k] - lse);
-                    z[k] = v;
-                    mx2 = v > mx2 ? v : mx2;
+                if (has_e) {
+                    ze = (1. / anneal_temp) * (ze - lse);
+                    mx2 = ze;
                 }
+#pragma unroll
+                for (int j = 0; j < KPL; j++)
+                    if (j < jmax) {
+                        zv[j] = (1. / anneal_temp) * (zv[j] - lse);
+                        mx2 = zv[j] > mx2 ? zv[j] : mx2;
+                    }
                 mx2 = fb_wave_max(mx2, false);
-                lse = log(sum_exp32(mx2)) + mx2;
+                lse = fb_log_fast(sum_reg(mx2)) + mx2;
             }
-            for (int k = lane; k < KM; k += 64) z[k] = (double)__builtin_amdgcn_exp2f((float)(z[k] - lse) * LOG2E);
+#pragma unroll
+            for (int j = 0; j < KPL; j++)
+                if (j < jmax && lane + 64 * j < n_occ) z[lane + 64 * j] = (double)__builtin_amdgcn_exp2f((float)(zv[j] - lse) * LOG2E);
+            const double p_e = has_e ? (double)__builtin_amdgcn_exp2f((float)(ze - lse) * LOG2E) : 0.0;
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            const int kd = fb_draw_chunked(z, KM, segk_u01(bt.seed, sweep, (uint64_t)utt, (uint64_t)(c.N_max + t)), lane);
+            // ---- the draw
+            double sl = 0.0;
+            for (int q = lo; q < hi; q++) sl += z[q];
+            sl += n_gap * p_e;
+            const double incl = fb_wave_scan(sl);
+            const double u = segk_u01(bt.seed, sweep, (uint64_t)utt, (uint64_t)(c.N_max + t));
+            const unsigned long long below = __ballot(u < incl);
+            int kd = KM - 1;
+            if (below) {
+                const int run = __ffsll((long long)below) - 1;
+                double r = u - (fb_readlane(incl, run) - fb_readlane(sl, run));
+                const int rlo = run * per < n_occ ? run * per : n_occ, rhi = rlo + per < n_occ ? rlo + per : n_occ;
+                int pos = __builtin_amdgcn_readlane(b_lo, run);
+                const int end = __builtin_amdgcn_readlane(b_hi, run);
+                bool found = false;
+                for (int q = rlo; q < rhi && !found; q++) {
+                    const int k = inv[q];
+                    const int gap = k - pos;
+                    if (gap > 0) {
+                        const double m = (double)gap * p_e;
+                        if (r < m) {
+                            int o = (int)(r / p_e);
+                            o = o < 0 ? 0 : (o > gap - 1 ? gap - 1 : o);
+                            kd = pos + o;
+                            found = true;
+                            break;
+                        }
+                        r -= m;
+                    }
+                    const double pq = z[q];
+                    if (r < pq) {
+                        kd = k;
+                        found = true;
+                        break;
+                    }
+                    r -= pq;
+                    pos = k + 1;
+                }
+                if (!found) {
+                    const int gap = end - pos;
+                    if (gap > 0 && p_e > 0.0) {
+                        int o = (int)(r / p_e);
+                        o = o < 0 ? 0 : (o > gap - 1 ? gap - 1 : o);
+                        kd = pos + o;
+                    } else {
+                        kd = pos > 0 ? pos - 1 : 0;
+                    }
+                }
+            }
             if (lane == 0) bt.slot[e] = kd;
-            j_prev = __shfl(kd, 0);
+            j_prev = kd;
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
         }
@@ -1764,26 +1702,32 @@ __global__ __launch_bounds__(256) void k_fbb_assign_lm_wave(segk_corpus c, segk_
     for (int t = 0; t < nn; t++) {
         const int64_t e = new_tok[(int64_t)utt * c.N_max + t];
         const float *mrow = llmat + ((int64_t)item * c.N_max + t) * ll_ld;
+        const double inv_prev = j_prev >= 0 ? (1. - f.lm_lambda) / (bt.cnt[j_prev] + f.lm_b) : 0.0;
+        const double empty_ll = (double)mrow[cm[KM]] * LN2 - zc_empty - le + norm;
         double mx = NEG_INF_D;
         for (int k = lane; k < KM; k += 64) {
             const double n = bt.cnt[k];
-            const double llv = n > 0.0 ? (double)mrow[cm[k]] * LN2 - (bt.zconst[k] - bt.lconst[k]) + norm
-                                       : (double)mrow[cm[KM]] * LN2 - zc_empty - log(n_empty) + norm;
+            const double llv = n > 0.0 ? (double)mrow[cm[k]] * LN2 - (bt.zconst[k] - bt.lconst[k]) + norm : empty_ll;
             if constexpr (PROBE) probe_ll[((int64_t)utt * c.N_max + t) * probe_ld + k] = llv;
             double pz;
-            if (j_prev < 0) pz = (log(n + f.lm_a / (double)KM) - log(tot + f.lm_a)) * f.lms;                       // bigram_lms.py:64-69
-            else {                                                                                              // bigram_lms.py:84-91
-                const double pi = (n + f.lm_a / (double)KM) / (tot + f.lm_a);
-                const double pij = (1. - f.lm_lambda) * ((double)f.lm_bigram[(int64_t)j_prev * KM + k] + f.lm_b / (double)KM)
-                                   / (bt.cnt[j_prev] + f.lm_b);
-                pz = log(f.lm_lambda * pi + pij) * f.lms;
+            if (j_prev < 0) pz = ((double)(__builtin_amdgcn_logf((float)(n + aK)) * 0.6931471805599453f) - ltot) * f.lms;      // bigram_lms.py:64-69
+            else {                                                                                                          // bigram_lms.py:84-91
+                const double pi = (n + aK) * inv_tot;
+                const double pij = ((double)f.lm_bigram[(int64_t)j_prev * KM + k] + bK) * inv_prev;
+                pz = (double)(__builtin_amdgcn_logf((float)(f.lm_lambda * pi + pij)) * 0.6931471805599453f) * f.lms;
             }
             const double v = pz + llv;
             z[k] = v;
             mx = v > mx ? v : mx;
         }
         mx = fb_wave_max(mx, false);
-        double lse = log(sum_exp(mx)) + mx;
+        auto sum_exp32 = [&](double shift) -> double {
+            double sv = 0.0;
+            for (int k = lane; k < KM; k += 64) sv += (double)__builtin_amdgcn_exp2f((float)(z[k] - shift) * LOG2E);
+            sv = fb_wave_sum(sv);
+            return sv;
+        };
+        double lse = log(sum_exp32(mx)) + mx;
         if (anneal_temp != 1.0) {                               // fbgmm.py:446-449
             double mx2 = NEG_INF_D;
             for (int k = lane; k < KM; k += 64) {
@@ -1792,9 +1736,9 @@ __global__ __launch_bounds__(256) void k_fbb_assign_lm_wave(segk_corpus c, segk_
                 mx2 = v > mx2 ? v : mx2;
             }
             mx2 = fb_wave_max(mx2, false);
-            lse = log(sum_exp(mx2)) + mx2;
+            lse = log(sum_exp32(mx2)) + mx2;
         }
-        for (int k = lane; k < KM; k += 64) z[k] = exp(z[k] - lse);
+        for (int k = lane; k < KM; k += 64) z[k] = (double)__builtin_amdgcn_exp2f((float)(z[k] - lse) * LOG2E);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
         const int kd = fb_draw_chunked(z, KM, segk_u01(bt.seed, sweep, (uint64_t)utt, (uint64_t)(c.N_max + t)), lane);
@@ -1979,7 +1923,7 @@ __global__ void k_fbb_tiles32(segk_fbgmm f, segk_fbatch bt, int D, double prior_
 // fp16x2 form: the same per-slot rows and constants as k_fbb_tiles32, written as a plain float32 matrix
 // [(K_max + 1), 2D] (interleaved [-pp/2, pp*mu] * log2 e) plus constants; consts16[K_max + 1] collects the
 // largest squared row norm (the exponent of the fp16 scaling follows it).  segk_sp_prepare_tiles turns
-// them into the operand image of k_kmeans_score_sp<.., 2, 1>.
+// them into the operand image of k_kmeans_score_sp<.., 1>.
 // Columns of the fp16x2 operand image: the occupied slots in slot order, then the pseudo-component of the empty ones; everything
 // behind is "absent".  (At configs[4] 419 of 1 000 slots are occupied in the settled chain: 14 tiles of components instead of 32
 // for the span scores and the token likelihoods -- an empty slot's score is the pseudo-component's, multiplying its tile was
@@ -2120,9 +2064,8 @@ int32_t segk_fbb_partials(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm 
     const int64_t waves = (int64_t)s_n * f->K_max;
     // many slots: bucket the tokens by slot first (k_fbb_sort), then every slot sums its own list; SEGK_FBB_SORT=0: the
     // one-step kernel.  LDS of the sort: 16 waves x K_max counters.
-    const char *se = getenv("SEGK_FBB_SORT");
     const size_t lds_sort = ((size_t)FBS_WAVES * f->K_max + FBS_WAVES + 1) * sizeof(int32_t);
-    if (ctx && f->K_max >= 256 && f->K_max <= 1024 && lds_sort <= 150 * 1024 && !(se && atoi(se) == 0)) {
+    if (ctx && f->K_max >= 256 && f->K_max <= 1024 && lds_sort <= 150 * 1024 && segk_env_int("SEGK_FBB_SORT", 1) != 0) {
         const int64_t stride = (int64_t)c->n_utt * c->N_max;             // more than any (slice, block) can hold
         const size_t need = ((size_t)s_n * stride + (size_t)s_n * (f->K_max + 1)) * sizeof(int32_t);
         if (ctx->fbs_bytes < need) {
@@ -2385,26 +2328,18 @@ static int32_t fbb_assign_impl(segk_ctx *ctx, const segk_corpus *c, const segk_f
     const size_t lds = fixed_b + (size_t)rcap * f->K_max * sizeof(double);
     SEGK_REQUIRE(lds <= 160 * 1024, "K_max too large for the LDS logits buffer");
     // language model + matrix-core likelihoods: one wave per utterance (SEGK_FBB_ASSIGN_WAVE=0: the block-wide form)
-    const char *awe = getenv("SEGK_FBB_ASSIGN_WAVE");
-    if (f->lm_unigram && ll_mat && dbg == 0 && !(awe && atoi(awe) == 0) && 4 * (size_t)f->K_max * sizeof(double) <= 146 * 1024) {
+    if (f->lm_unigram && ll_mat && dbg == 0 && segk_env_int("SEGK_FBB_ASSIGN_WAVE", 1) != 0 && 4 * (size_t)f->K_max * sizeof(double) <= 146 * 1024) {
         const size_t ldsw = 4 * (size_t)f->K_max * sizeof(double) + sizeof(int) * (size_t)(f->K_max + 2);
         const int n_items = m.off[s_n];
-        // SEGK_FBB_ASSIGN_WAVE=2: the softmax with the fp64 library functions (the bits of the block-wide form)
-        const bool lib64 = awe && atoi(awe) == 2;
-#define SEGK_LM_WAVE(FF, PP)                                                                                                    \
+#define SEGK_LM_WAVE(PP)                                                                                                        \
     do {                                                                                                                        \
         if (ldsw > 48 * 1024)                                                                                                   \
-            SEGK_CHECK_HIP(hipFuncSetAttribute((const void *)k_fbb_assign_lm_wave<FF, PP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw)); \
-        hipLaunchKernelGGL((k_fbb_assign_lm_wave<FF, PP>), dim3((n_items + 3) / 4), dim3(256), ldsw, (hipStream_t)stream, *c, *f, *bt, m, b, \
+            SEGK_CHECK_HIP(hipFuncSetAttribute((const void *)k_fbb_assign_lm_wave<PP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw)); \
+        hipLaunchKernelGGL((k_fbb_assign_lm_wave<PP>), dim3((n_items + 3) / 4), dim3(256), ldsw, (hipStream_t)stream, *c, *f, *bt, m, b, \
                            sweep, alpha, anneal_temp, new_tok, n_new, ll_mat, ll_ld, n_items, ctx->probe_ll, ctx->probe_ll_ld);  \
     } while (0)
-        if (ctx->probe_ll) {
-            if (lib64) SEGK_LM_WAVE(0, true);
-            else SEGK_LM_WAVE(1, true);
-        } else {
-            if (lib64) SEGK_LM_WAVE(0, false);
-            else SEGK_LM_WAVE(1, false);
-        }
+        if (ctx->probe_ll) SEGK_LM_WAVE(true);
+        else SEGK_LM_WAVE(false);
 #undef SEGK_LM_WAVE
         SEGK_LAUNCH_CHECK();
         return SEGK_OK;
@@ -2462,8 +2397,7 @@ int32_t segk_fbb_step_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_fbg
     SEGK_REQUIRE(f->cov_type == 1, "the fused float32 Gibbs step is the diagonal (Student-t) one");
     SEGK_REQUIRE(n_slices_min == 0 || n_slices_min == 1, "n_slices_min must be 0 or 1");
     SEGK_REQUIRE(score && boundaries && new_tok && n_new && out_logprob && status, "step operands");
-    const char *env = getenv("SEGK_FBB_FUSED");
-    if (env && atoi(env) == 0) { segk_set_error("segk_fbb_step_diag32: disabled (SEGK_FBB_FUSED=0)"); return SEGK_ERR_UNSUPPORTED; }
+    if (segk_env_int("SEGK_FBB_FUSED", 1) == 0) { segk_set_error("segk_fbb_step_diag32: disabled (SEGK_FBB_FUSED=0)"); return SEGK_ERR_UNSUPPORTED; }
     if (f->lm_unigram || !bt->prior_rows || f->K_max > 256 || c->D > 256) {
         segk_set_error("segk_fbb_step_diag32: needs prior_rows, no language model, K_max <= 256, D <= 256");
         return SEGK_ERR_UNSUPPORTED;

@@ -1383,8 +1383,7 @@ int32_t segk_fbgmm_sequential_sweep(segk_ctx *ctx, const segk_corpus *c, segk_fb
     SEGK_REQUIRE(n_slices_min == 0 || n_slices_min == 1, "n_slices_min must be 0 or 1");
     SEGK_REQUIRE(viterbi == 0 || viterbi == 1, "viterbi");
     if (n_order == 0) return SEGK_OK;
-    const char *env = getenv("SEGK_FB_CHAIN");
-    if (env && atoi(env) == 0) { segk_set_error("segk_fbgmm_sequential_sweep: disabled (SEGK_FB_CHAIN=0)"); return SEGK_ERR_UNSUPPORTED; }
+    if (segk_env_int("SEGK_FB_CHAIN", 1) == 0) { segk_set_error("segk_fbgmm_sequential_sweep: disabled (SEGK_FB_CHAIN=0)"); return SEGK_ERR_UNSUPPORTED; }
     if (c->N_max > 64 || ctx->capturing) {
         segk_set_error("segk_fbgmm_sequential_sweep: at most 64 landmarks, not under stream capture");
         return SEGK_ERR_UNSUPPORTED;
@@ -1436,8 +1435,7 @@ int32_t segk_fbgmm_sequential_sweep(segk_ctx *ctx, const segk_corpus *c, segk_fb
     // span indices and the components' flags -- when they fit beside the model (SEGK_FB_CHAIN_TERMS=0: evaluate every
     // component per segment as before; the same results)
     const size_t lds_terms = (size_t)((size_t)NM * KM) * sizeof(double) + (size_t)NM * sizeof(int32_t) + (((size_t)KM + 15) & ~(size_t)15) + 16;
-    const char *et = getenv("SEGK_FB_CHAIN_TERMS");
-    const bool terms = lds + lds_terms <= 150 * 1024 && !(et && atoi(et) == 0);
+    const bool terms = lds + lds_terms <= 150 * 1024 && segk_env_int("SEGK_FB_CHAIN_TERMS", 1) != 0;
     // control words + the order, owned by the context
     const size_t ctl_bytes = 32 * (1 + CH_FLAGS) * sizeof(int32_t), need = ctl_bytes + (size_t)n_order * sizeof(int32_t);
     if (ctx->fbchain_bytes < need) {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "../../include/segk.h"
@@ -108,12 +109,18 @@ static inline bool segk_prof_now(segk_ctx *ctx)
 
 void segk_set_error(const char *fmt, ...);
 
+// A launch-plan switch (SEGK_SCORE_HINT, SEGK_SCORE_PRE, SEGK_SCORE_B3, ...: they choose between paths with identical
+// results), read at every call so that one context can be switched between calls: atoi of the variable, `dflt` when unset.
+static inline int segk_env_int(const char *name, int dflt)
+{
+    const char *e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
 // Development switches that ALTER RESULTS (timing ablations, debug modes) or hand raw pointers to kernels exist only in builds
-// with -DSEGK_DEV: the shipped library cannot be told through the environment to compute wrong answers.  (The launch-plan
-// switches that remain -- SEGK_SCORE_HINT, SEGK_SCORE_PRE, SEGK_SCORE_B3, ... -- choose between paths with identical results.)
+// with -DSEGK_DEV: the shipped library cannot be told through the environment to compute wrong answers.
 #ifdef SEGK_DEV
-#include <stdlib.h>
-static inline int segk_dev_env(const char *name) { const char *e = getenv(name); return e ? atoi(e) : 0; }
+static inline int segk_dev_env(const char *name) { return segk_env_int(name, 0); }
 #else
 static inline int segk_dev_env(const char *) { return 0; }
 #endif
@@ -186,16 +193,15 @@ static inline __host__ __device__ int segk_n_tiles(int K_max) { return (K_max + 
 
 // ---------------------------------------------------------------------------------------
 // Operand images of the split-precision k-means filter (float32 data, 8 <= D <= 128; segk_score_sp.hip, segk_score_h1.hip).
-// P = 3: three bf16 pieces, x = x1 + x2 + x3 exactly.  P = 2: two fp16 pieces of 2^a x (power-of-two
-// scaling), the second one carried at 2^11 times its weight.
+// fp16x2: two fp16 pieces (P = 2) of 2^a x (power-of-two scaling), the second one carried at 2^11 times its weight.
 //   rows   [SEGK_SP_HEADER bytes: int32 {P, exponent a, bits of max |x_d|, 0}, int64 n_emb * KP] then P planes
 //          [n_emb][KP] of 16-bit pieces (piece p of every row together), KP = D rounded up to 16 (zero padded,
-//          dimensions permuted by segk_b3_dim); for P = 2 the float [n_emb] residual norms follow the planes
+//          dimensions permuted by segk_b3_dim); the float [n_emb] residual norms follow the planes
 //   tiles  [1024 floats header: int32 exponent b at [0]; float E_m at [1]; [2], [3]: the batch finalize's residual
 //          maximum and the exponent it built its rows with (k_batch_post reads them)] then per tile of 32 components:
 //          16-bit [s][p][lane 64][8], s < KS = KP/16 (k-step), p < P (piece): piece p of
 //          2^b M[32*tile + (lane & 31)][segk_b3_dim(16 s + 8 (lane >> 5) + i)], i < 8 -- the A operand of
-//          v_mfma_f32_32x32x16_{f16,bf16} as one 16-byte load per lane; followed, at float offset KS*P*256,
+//          v_mfma_f32_32x32x16_f16 as one 16-byte load per lane; followed, at float offset KS*P*256,
 //          by 32 floats -2^(a+b) |m|^2/2 (-3e38 beyond K_max); padded to a multiple of 1024 floats.
 // ---------------------------------------------------------------------------------------
 #define SEGK_SP_HEADER 64
@@ -210,6 +216,7 @@ static inline __host__ __device__ int segk_b3_dim(int pos)       // position in 
     return (pos & ~15) + 8 * (i >> 2) + 4 * h + (i & 3);
 }
 static inline __host__ __device__ int segk_b3_kp(int D) { return (D + 15) & ~15; }
+// floats per tile of P pieces (the image holds 2; segk_kmeans_tiles_b3_floats keeps the ABI's room for 3)
 static inline __host__ __device__ int segk_sp_tile_stride(int D, int P)
 {
     return ((segk_b3_kp(D) / 16) * P * 256 + 32 + 1023) / 1024 * 1024;

@@ -14,7 +14,7 @@ int32_t segk_kmeans_clear_queue(segk_ctx *ctx, const segk_cand *cand, void *stre
 }
 
 // launch arguments of the filter stage for rows ids[0..n) / row0..row0+n-1 (the split-precision members are filled when
-// the fp16x2 / bf16x3 images are in use: segk_use_b3)
+// the fp16x2 images are in use: segk_use_b3)
 static ScoreArgs make_score_args(const segk_corpus *c, const segk_kmeans *m, const int32_t *ids, int64_t row0, int64_t n,
                                  const segk_cand *cand, bool b3)
 {
@@ -31,7 +31,7 @@ static ScoreArgs make_score_args(const segk_corpus *c, const segk_kmeans *m, con
         A.xrows32 = c->X32;
         A.X32 = (const float *)c->Xb3;
         A.tiles = m->tiles_b3;
-        A.tile_stride = segk_sp_tile_stride(c->D, c->sp_pieces);
+        A.tile_stride = segk_sp_tile_stride(c->D, 2);
         A.means32 = (const float *)m->means;
         A.fuse_exact = (c->D % 4 == 0) ? 1 : 0;
         A.K_max = m->K_max;
@@ -59,17 +59,16 @@ int32_t segk_kmeans_filter(segk_ctx *ctx, const segk_corpus *c, const segk_kmean
         // -- pay once the split-precision kernel alone would need more than four rounds of the chip
         // (estimated break-even near 130 k rows; 1 M rows: 0.58 ms against 0.77 ms).
         // SEGK_SCORE_PRE=0 disables it, =1 forces it at every size (tests).
-        const char *pre_env = getenv("SEGK_SCORE_PRE");
-        const int pre_mode = pre_env ? atoi(pre_env) : -1;
+        const int pre_mode = segk_env_int("SEGK_SCORE_PRE", -1);
         // (round 2: from 384 rows per CU on -- 98 304 -- with the second stage split over component ranges for small
         // queues: a 1 250-utterance shard 5 636 against 5 329 sweeps/s, 2 500 utterances 4 493 against 4 278; at 625
         // utterances the split-precision kernel alone still wins, 7 154 against 6 273)
         const bool small_table = m->K_max < (1 << 24) && (int64_t)m->K_max * c->D * 4 < ((int64_t)1 << 32);      // the exact stage's 32-bit offsets
-        if (c->sp_pieces == 2 && A.fuse_exact && small_table && pre_mode != 0 && (pre_mode == 1 || n > 384 * (int64_t)ctx->n_cu) &&
+        if (A.fuse_exact && small_table && pre_mode != 0 && (pre_mode == 1 || n > 384 * (int64_t)ctx->n_cu) &&
             n < (int64_t)1 << 30)
             return segk_dispatch_score_pre(ctx, A, segk_b3_kp(c->D) / 16, st);
         segk_flush_deferred_zero(ctx, st);
-        return segk_dispatch_score_sp(ctx, A, segk_b3_kp(c->D) / 16, c->sp_pieces, st);
+        return segk_dispatch_score_sp(ctx, A, segk_b3_kp(c->D) / 16, st);
     }
     const ScoreArgs A = make_score_args(c, m, ids, row0, n, cand, false);
     segk_flush_deferred_zero(ctx, st);
@@ -80,10 +79,9 @@ int32_t segk_kmeans_filter(segk_ctx *ctx, const segk_corpus *c, const segk_kmean
 // fill the chip (the threshold of the pre-filter path), SEGK_SCORE_HINT not 0 (=1: at every size, tests)
 static bool hinted_path_applies(const segk_ctx *ctx, const segk_corpus *c, const segk_kmeans *m, int64_t n)
 {
-    const char *he = getenv("SEGK_SCORE_HINT");
-    const int mode = he ? atoi(he) : -1;
+    const int mode = segk_env_int("SEGK_SCORE_HINT", -1);
     if (mode == 0 || ctx->capturing) return false;
-    if (!segk_use_b3(c, m) || c->sp_pieces != 2 || c->D % 4 != 0) return false;
+    if (!segk_use_b3(c, m) || c->D % 4 != 0) return false;
     if (n >= (int64_t)1 << 30) return false;
     // K1 keeps at most four LDS ranges of tile images
     {
@@ -164,8 +162,7 @@ int32_t segk_kmeans_sequential_sweep(segk_ctx *ctx, const segk_corpus *c, segk_k
     }
     // the whole sweep in one persistent kernel (segk_seq_chain.hip) where the configuration allows; SEGK_SEQ_CHAIN=0: three
     // launches per utterance
-    const char *che = getenv("SEGK_SEQ_CHAIN");
-    if (!(che && atoi(che) == 0) && !repeats && !ctx->capturing && (n_slices_min == 0 || n_slices_min == 1)) {
+    if (segk_env_int("SEGK_SEQ_CHAIN", 1) != 0 && !repeats && !ctx->capturing && (n_slices_min == 0 || n_slices_min == 1)) {
         rc = segk_launch_seq_chain(ctx, c, m, order, n_order, n_slices_max, wip, boundaries, old_tok, new_tok, new_k, n_old, n_new,
                                    n_flag, out_total, status, st);
         if (rc == SEGK_OK) return segk_kmeans_prepare(ctx, c, m, stream);

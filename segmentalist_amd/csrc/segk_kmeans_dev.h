@@ -368,27 +368,21 @@ static inline void segk_tstamp_bind()
 static inline void segk_tstamp_bind() {}
 #endif
 
-template <int P> struct SegkPiece;
-template <> struct SegkPiece<3> {
-    typedef __bf16 T;
-    typedef __bf16 V8 __attribute__((ext_vector_type(8)));
-};
-template <> struct SegkPiece<2> {
+// the split image's 16-bit piece (fp16x2: two of them per value)
+struct SegkPiece {
     typedef _Float16 T;
     typedef _Float16 V8 __attribute__((ext_vector_type(8)));
 };
-template <int P>
-__device__ __forceinline__ f32x16 mfma_piece(typename SegkPiece<P>::V8 a, typename SegkPiece<P>::V8 b, f32x16 c)
+__device__ __forceinline__ f32x16 mfma_piece(SegkPiece::V8 a, SegkPiece::V8 b, f32x16 c)
 {
-    if constexpr (P == 3) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
 
-__device__ __forceinline__ float filter_tau_sp(float xn, float M, int D, int pieces)
+__device__ __forceinline__ float filter_tau_sp(float xn, float M, int D)
 {
     const float u = 5.9604645e-8f;
     const int KP = (D + 15) & ~15;
-    float e1 = (1.02f * (float)(KP + 16) + (pieces == 2 ? 16.f : 0.f)) * u * (xn * M + 0.5f * M * M);
+    float e1 = (1.02f * (float)(KP + 16) + 16.f) * u * (xn * M + 0.5f * M * M);
     int levels = 0;
     for (int n = D; n > 128; n = (n + 1) / 2) levels++;
     int deff = D < 128 ? D : 128;
@@ -398,28 +392,17 @@ __device__ __forceinline__ float filter_tau_sp(float xn, float M, int D, int pie
     return 1.25f * (2.0f * e1 + e2) + 1e-30f;
 }
 
-// pieces of one value (already scaled by its power of two for P = 2)
-template <int P>
-__device__ __forceinline__ void split_sp(float x, typename SegkPiece<P>::T *pc)
+// the two pieces of one value (already scaled by its power of two)
+__device__ __forceinline__ void split_sp(float x, SegkPiece::T *pc)
 {
-    typedef typename SegkPiece<P>::T T;
-    if constexpr (P == 3) {
-        const T a = (T)x;
-        const float r1 = x - (float)a;
-        const T b = (T)r1;
-        const float r2 = r1 - (float)b;
-        pc[0] = a;
-        pc[1] = b;
-        pc[2] = (T)r2;
-    } else {
-        const T a = (T)x;
-        const float r1 = x - (float)a;                   // exact
-        pc[0] = a;
-        pc[1] = (T)(r1 * 2048.f);                        // 2^11 r1: exact scaling, then 11 of its <= 13 bits
-    }
+    typedef SegkPiece::T T;
+    const T a = (T)x;
+    const float r1 = x - (float)a;                   // exact
+    pc[0] = a;
+    pc[1] = (T)(r1 * 2048.f);                        // 2^11 r1: exact scaling, then 11 of its <= 13 bits
 }
 
-// exponent e such that 2^e * vmax lies in [2^12, 2^13); 0 for vmax = 0 / P = 3
+// exponent e such that 2^e * vmax lies in [2^12, 2^13); 0 for vmax = 0
 __device__ __forceinline__ int sp_exponent(float vmax)
 {
     if (!(vmax > 0.f)) return 0;
@@ -513,7 +496,7 @@ __device__ __forceinline__ float filter_tau_h1(float xn, float M, int D, float e
     // than the a-priori 1.01 * 2^-10 |x| M
     const float meas = (xn + ex) * Em + ex * M;
     const float apriori = 1.01f * 9.765625e-4f * xn * M;
-    return filter_tau_sp(xn, M, D, 2) + 2.5f * 1.00001f * fminf(meas, apriori);
+    return filter_tau_sp(xn, M, D) + 2.5f * 1.00001f * fminf(meas, apriori);
 }
 
 // A handful of left-over rows (fewer than SEGK_TAIL_QUEUE): not worth three more launches -- they
@@ -565,9 +548,8 @@ static inline int check_corpus(const segk_corpus *c)
 
 static inline bool segk_use_b3(const segk_corpus *c, const segk_kmeans *m)
 {
-    const char *e = getenv("SEGK_SCORE_B3");
-    if (e && atoi(e) == 0) return false;
-    return c->Xb3 && (c->sp_pieces == 2 || c->sp_pieces == 3) && m->tiles_b3 && c->x_dtype == SEGK_F32 && c->D >= 8 &&
+    if (segk_env_int("SEGK_SCORE_B3", 2) == 0) return false;
+    return c->Xb3 && c->sp_pieces == 2 && m->tiles_b3 && c->x_dtype == SEGK_F32 && c->D >= 8 &&
            c->D <= 128;
 }
 
@@ -643,15 +625,15 @@ __device__ __forceinline__ void dev_prepare_tile(const XT *means, int K_max, int
 // tiles image: [header 1024 floats: int32 exponent b at [0]] then per tile [s][p][lane][8] pieces + 32 constants
 // consts == NULL: the k-means constants -|m|^2/2; otherwise consts[k] (< -1e37: component absent) -- the
 // log-sum-exp use of the kernel (segk_fbbatch.hip), whose rows are not means.
-template <int P>
 __device__ __forceinline__ void dev_prepare_sp_tile(const float *means, int K_max, int D, float *tiles, const double *mnorm2,
                                                     const unsigned char *ximg, const double *consts, const int tile)
 {
-    typedef typename SegkPiece<P>::T T;
+    typedef SegkPiece::T T;
+    constexpr int P = 2;                                             // pieces
     const int KS = segk_b3_kp(D) / 16;
     const int stride = segk_sp_tile_stride(D, P);
     // max |m_d| <= sqrt(max |m|^2): every block derives the same exponent
-    const int eb = P == 2 ? sp_exponent((float)(sqrt(*mnorm2) * (1.0 + 1e-6))) : 0;
+    const int eb = sp_exponent((float)(sqrt(*mnorm2) * (1.0 + 1e-6)));
     const int ea = ((const int *)ximg)[1];
     if (tile == 0 && threadIdx.x == 0) ((int *)tiles)[0] = eb;
     float *Tt = tiles + 1024 + (int64_t)tile * stride;
@@ -683,19 +665,18 @@ __device__ __forceinline__ void dev_prepare_sp_tile(const float *means, int K_ma
                 const float mv = elem(ci, d);
                 double v = (double)mv;
                 s += v * v;
-                if (P == 2) rs += sp_resid2(ldexpf(mv, eb));
+                rs += sp_resid2(ldexpf(mv, eb));
             }
         s += __shfl_xor(s, 1);
         s += __shfl_xor(s, 2);
         s += __shfl_xor(s, 4);
         if (sub == 0) nrm[ci] = s;
-        if (P == 2) {                     // E_m = max_k |m_k - m1_k|: tiles header [1], zeroed by k_kmeans_prepare just before
-            rs += __shfl_xor(rs, 1);
-            rs += __shfl_xor(rs, 2);
-            rs += __shfl_xor(rs, 4);
-            const float em = (float)(ldexp(sqrt(rs), -eb) * (1.0 + 1e-6));
-            if (sub == 0 && comp < K_max) atomicMax((unsigned int *)tiles + 1, __float_as_uint(em));
-        }
+        // E_m = max_k |m_k - m1_k|: tiles header [1], zeroed by k_kmeans_prepare just before
+        rs += __shfl_xor(rs, 1);
+        rs += __shfl_xor(rs, 2);
+        rs += __shfl_xor(rs, 4);
+        const float em = (float)(ldexp(sqrt(rs), -eb) * (1.0 + 1e-6));
+        if (sub == 0 && comp < K_max) atomicMax((unsigned int *)tiles + 1, __float_as_uint(em));
     }
     __syncthreads();
     SEGK_TSTAMP(4, 6);
@@ -704,18 +685,18 @@ __device__ __forceinline__ void dev_prepare_sp_tile(const float *means, int K_ma
         const int sidx = pr >> 6, lane = pr & 63;
         const int ci = lane & 31;
         const bool live = tile * 32 + ci < K_max;
-        typename SegkPiece<P>::V8 out[P];
+        SegkPiece::V8 out[P];
 #pragma unroll
         for (int i = 0; i < 8; i++) {
             const int d = segk_b3_dim(16 * sidx + 8 * (lane >> 5) + i);
             const float v = (live && d < D) ? ldexpf(elem(ci, d), eb) : 0.f;
             T pc[P];
-            split_sp<P>(v, pc);
+            split_sp(v, pc);
 #pragma unroll
             for (int q = 0; q < P; q++) out[q][i] = pc[q];
         }
 #pragma unroll
-        for (int q = 0; q < P; q++) *reinterpret_cast<typename SegkPiece<P>::V8 *>(Tb + ((sidx * P + q) * 64 + lane) * 8) = out[q];
+        for (int q = 0; q < P; q++) *reinterpret_cast<SegkPiece::V8 *>(Tb + ((sidx * P + q) * 64 + lane) * 8) = out[q];
     }
     for (int idx = threadIdx.x; idx < stride - KS * P * 256; idx += blockDim.x) {
         float v = 0.f;
@@ -778,8 +759,8 @@ static inline void segk_flush_deferred_zero(segk_ctx *ctx, hipStream_t st)
 int segk_kmeans_prepare_impl(segk_ctx *ctx, const segk_corpus *c, segk_kmeans *m, void *stream, bool mnorm_zeroed);
 // segk_score_f32.hip: the fp32-MFMA filter (float64 data, D outside 8..128, SEGK_SCORE_B3=0)
 int segk_dispatch_score_f32(segk_ctx *ctx, const segk_corpus *c, const segk_kmeans *m, const ScoreArgs &A, hipStream_t st);
-// segk_score_sp.hip: the split-precision filter (pieces = 2 fp16x2, 3 bf16x3) and the pre-filter's second stage
-int segk_dispatch_score_sp(segk_ctx *ctx, const ScoreArgs &A, int ks, int pieces, hipStream_t st);
+// segk_score_sp.hip: the split-precision filter (fp16x2) and the pre-filter's second stage
+int segk_dispatch_score_sp(segk_ctx *ctx, const ScoreArgs &A, int ks, hipStream_t st);
 int segk_launch_sp_second(segk_ctx *ctx, const ScoreArgs &B, int ks, hipStream_t st);
 int segk_launch_clean(const segk_corpus *c, segk_kmeans *m, int32_t *status, hipStream_t st, int32_t *relog = nullptr);
 int segk_launch_seq_chain(segk_ctx *ctx, const segk_corpus *c, segk_kmeans *m, const int32_t *order, int n_order, int n_slices_max,

@@ -52,13 +52,13 @@ __global__ void k_corpus_maxabs(const float *X, int64_t ldx, int64_t n_emb, int 
     }
 }
 
-template <int P>
 __global__ void k_corpus_split_sp(const float *X, int64_t ldx, int64_t n_emb, int D, unsigned char *img)
 {
-    typedef typename SegkPiece<P>::T T;
+    typedef SegkPiece::T T;
+    constexpr int P = 2;                                             // pieces
     const int KP = segk_b3_kp(D);
     int *hdr = (int *)img;
-    const int ea = P == 2 ? sp_exponent(__uint_as_float(((unsigned int *)img)[2])) : 0;
+    const int ea = sp_exponent(__uint_as_float(((unsigned int *)img)[2]));
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx == 0) { hdr[0] = P; hdr[1] = ea; *reinterpret_cast<int64_t *>(img + 16) = n_emb * KP; }
     if (idx >= n_emb * KP) return;
@@ -66,7 +66,7 @@ __global__ void k_corpus_split_sp(const float *X, int64_t ldx, int64_t n_emb, in
     const int pos = (int)(idx - e * KP), d = segk_b3_dim(pos);
     const float x = d < D ? ldexpf(X[e * ldx + d], ea) : 0.f;
     T pc[P];
-    split_sp<P>(x, pc);
+    split_sp(x, pc);
     // one PLANE per piece ([P][n_emb][KP]): the one-product pre-filter streams the leading pieces alone, 2 KP contiguous
     // bytes per row (interleaved, its 224 bytes shared 128-byte lines with the second piece: 369 MB fetched for 235)
     T *row = (T *)(img + SEGK_SP_HEADER) + e * KP;
@@ -98,11 +98,10 @@ __global__ void k_corpus_resid_sp(const float *X, int64_t ldx, int64_t n_emb, in
     nxx[e] = neg_sqd_exact<float>(ZeroRow{}, X + e * ldx, D);
 }
 
-template <int P>
 __global__ void k_kmeans_prepare_sp(const float *means, int K_max, int D, float *tiles, const double *mnorm2,
                                     const unsigned char *ximg, const double *consts)
 {
-    dev_prepare_sp_tile<P>(means, K_max, D, tiles, mnorm2, ximg, consts, (int)blockIdx.x);
+    dev_prepare_sp_tile(means, K_max, D, tiles, mnorm2, ximg, consts, (int)blockIdx.x);
 }
 
 // ---- split-precision images of arbitrary float32 matrices (internal; used by segk_fbbatch.hip) ----
@@ -114,7 +113,7 @@ int segk_sp_prepare_rows(const float *Y, int64_t ldy, int64_t n, int D2, void *i
     const int64_t blocks = (nx + 255) / 256;
     hipLaunchKernelGGL(k_corpus_maxabs, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, Y, ldy, n, D2,
                        (unsigned int *)img);
-    hipLaunchKernelGGL(k_corpus_split_sp<2>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, Y, ldy, n, D2,
+    hipLaunchKernelGGL(k_corpus_split_sp, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, Y, ldy, n, D2,
                        (unsigned char *)img);
     SEGK_LAUNCH_CHECK();
     return SEGK_OK;
@@ -123,7 +122,7 @@ int segk_sp_prepare_rows(const float *Y, int64_t ldy, int64_t n, int D2, void *i
 int segk_sp_prepare_tiles(const float *rows, const double *consts, const double *rowmax2, int K, int D2, float *tiles_sp,
                           const void *ximg, void *stream)
 {
-    hipLaunchKernelGGL(k_kmeans_prepare_sp<2>, dim3(segk_n_tiles(K)), dim3(256), 0, (hipStream_t)stream, rows, K, D2, tiles_sp,
+    hipLaunchKernelGGL(k_kmeans_prepare_sp, dim3(segk_n_tiles(K)), dim3(256), 0, (hipStream_t)stream, rows, K, D2, tiles_sp,
                        rowmax2, (const unsigned char *)ximg, consts);
     SEGK_LAUNCH_CHECK();
     return SEGK_OK;
@@ -235,14 +234,9 @@ int segk_kmeans_prepare_impl(segk_ctx *ctx, const segk_corpus *c, segk_kmeans *m
                                        (const XT *)m->means, m->K_max, c->D, m->tiles,
                                        (unsigned long long *)m->mnorm_max, m->tiles_b3 ? (unsigned int *)m->tiles_b3 + 1 : nullptr,
                                        row_hash););
-    if (m->tiles_b3 && c->Xb3 && c->x_dtype == SEGK_F32 && c->D >= 8 && c->D <= 128) {
-        if (c->sp_pieces == 2)
-            hipLaunchKernelGGL(k_kmeans_prepare_sp<2>, dim3(segk_n_tiles(m->K_max)), dim3(256), 0, st, (const float *)m->means,
-                               m->K_max, c->D, m->tiles_b3, m->mnorm_max, (const unsigned char *)c->Xb3, (const double *)nullptr);
-        else if (c->sp_pieces == 3)
-            hipLaunchKernelGGL(k_kmeans_prepare_sp<3>, dim3(segk_n_tiles(m->K_max)), dim3(256), 0, st, (const float *)m->means,
-                               m->K_max, c->D, m->tiles_b3, m->mnorm_max, (const unsigned char *)c->Xb3, (const double *)nullptr);
-    }
+    if (m->tiles_b3 && c->Xb3 && c->sp_pieces == 2 && c->x_dtype == SEGK_F32 && c->D >= 8 && c->D <= 128)
+        hipLaunchKernelGGL(k_kmeans_prepare_sp, dim3(segk_n_tiles(m->K_max)), dim3(256), 0, st, (const float *)m->means,
+                           m->K_max, c->D, m->tiles_b3, m->mnorm_max, (const unsigned char *)c->Xb3, (const double *)nullptr);
     SEGK_LAUNCH_CHECK();
     return SEGK_OK;
 }
@@ -257,24 +251,24 @@ int32_t segk_kmeans_mark_duplicates(segk_ctx *ctx, const segk_corpus *c, const s
     // needs the row hashes of the segk_kmeans_prepare that built these images (same context, same means buffer)
     if (!ctx || m->K_max > 2048 || !ctx->row_hash || ctx->row_hash_means != m->means) return SEGK_OK;
     hipStream_t st = (hipStream_t)stream;
-    const bool sp = m->tiles_b3 && c->Xb3 && c->x_dtype == SEGK_F32 && c->D >= 8 && c->D <= 128 && (c->sp_pieces == 2 || c->sp_pieces == 3);
+    const bool sp = m->tiles_b3 && c->Xb3 && c->x_dtype == SEGK_F32 && c->D >= 8 && c->D <= 128 && c->sp_pieces == 2;
     const int kp = segk_b3_kp(c->D);
     DISPATCH_XT(c, hipLaunchKernelGGL(k_kmeans_mark_dups<XT>, dim3(1), dim3(1024), 0, st,
                                        (const XT *)m->means, m->K_max, c->D, m->tiles, segk_tile_stride(c->D), segk_gmax(c->D),
-                                       sp ? m->tiles_b3 : (float *)nullptr, sp ? segk_sp_tile_stride(c->D, c->sp_pieces) : 0,
-                                       sp ? (kp / 16) * c->sp_pieces * 256 : 0, n_marked, ctx->row_hash););
+                                       sp ? m->tiles_b3 : (float *)nullptr, sp ? segk_sp_tile_stride(c->D, 2) : 0,
+                                       sp ? (kp / 16) * 2 * 256 : 0, n_marked, ctx->row_hash););
     SEGK_LAUNCH_CHECK();
     return SEGK_OK;
 }
 
 int64_t segk_kmeans_tiles_b3_floats(int32_t K_max, int32_t D)
 {
-    return 1024 + (int64_t)segk_n_tiles(K_max) * segk_sp_tile_stride(D, 3);     // sized for either piece count
+    return 1024 + (int64_t)segk_n_tiles(K_max) * segk_sp_tile_stride(D, 3);     // room for three pieces (ABI)
 }
 
 int64_t segk_corpus_b3_bytes(int64_t n_emb, int32_t D)
 {
-    return SEGK_SP_HEADER + n_emb * 3 * (int64_t)segk_b3_kp(D) * 2;             // sized for either piece count
+    return SEGK_SP_HEADER + n_emb * 3 * (int64_t)segk_b3_kp(D) * 2;             // room for three planes (ABI)
 }
 
 int32_t segk_corpus_prepare_b3(segk_ctx *ctx, const segk_corpus *c, void *Xb3_out, int32_t pieces, void *stream)
@@ -283,24 +277,19 @@ int32_t segk_corpus_prepare_b3(segk_ctx *ctx, const segk_corpus *c, void *Xb3_ou
     int rc = check_corpus(c);
     if (rc) return rc;
     SEGK_REQUIRE(Xb3_out != nullptr, "Xb3_out is NULL");
-    SEGK_REQUIRE(pieces == 2 || pieces == 3, "pieces must be 2 (fp16x2) or 3 (bf16x3)");
+    SEGK_REQUIRE(pieces == 2, "pieces must be 2 (fp16x2)");
     SEGK_REQUIRE(c->x_dtype == SEGK_F32 && c->D >= 8 && c->D <= 128, "the split images exist for float32 data with 8 <= D <= 128");
     hipStream_t st = (hipStream_t)stream;
     SEGK_CHECK_HIP(hipMemsetAsync(Xb3_out, 0, SEGK_SP_HEADER, st));
     const int64_t tot = c->n_emb * segk_b3_kp(c->D);
-    if (pieces == 2) {
-        const int64_t nx = c->n_emb * c->D;
-        const int64_t blocks = (nx + 255) / 256;
-        hipLaunchKernelGGL(k_corpus_maxabs, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, (const float *)c->X,
-                           c->ldx, c->n_emb, c->D, (unsigned int *)Xb3_out);
-        hipLaunchKernelGGL(k_corpus_split_sp<2>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const float *)c->X,
-                           c->ldx, c->n_emb, c->D, (unsigned char *)Xb3_out);
-        hipLaunchKernelGGL(k_corpus_resid_sp, dim3((unsigned)((c->n_emb + 255) / 256)), dim3(256), 0, st, (const float *)c->X,
-                           c->ldx, c->n_emb, c->D, (unsigned char *)Xb3_out);
-    } else {
-        hipLaunchKernelGGL(k_corpus_split_sp<3>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const float *)c->X,
-                           c->ldx, c->n_emb, c->D, (unsigned char *)Xb3_out);
-    }
+    const int64_t nx = c->n_emb * c->D;
+    const int64_t blocks = (nx + 255) / 256;
+    hipLaunchKernelGGL(k_corpus_maxabs, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, (const float *)c->X,
+                       c->ldx, c->n_emb, c->D, (unsigned int *)Xb3_out);
+    hipLaunchKernelGGL(k_corpus_split_sp, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const float *)c->X,
+                       c->ldx, c->n_emb, c->D, (unsigned char *)Xb3_out);
+    hipLaunchKernelGGL(k_corpus_resid_sp, dim3((unsigned)((c->n_emb + 255) / 256)), dim3(256), 0, st, (const float *)c->X,
+                       c->ldx, c->n_emb, c->D, (unsigned char *)Xb3_out);
     SEGK_LAUNCH_CHECK();
     return SEGK_OK;
 }

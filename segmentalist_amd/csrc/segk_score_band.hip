@@ -69,7 +69,7 @@ template <int KS>
 __global__ __launch_bounds__(256, 2) void k_kmeans_band_rs(BandArgs B)
 {
     typedef _Float16 T;
-    typedef SegkPiece<2>::V8 V8;
+    typedef SegkPiece::V8 V8;
     constexpr int P = 2, KP = KS * 16, NW = 4, NBLK = 2, TPR = SEGK_BAND_TPR;
     constexpr int STRIDE = (KS * P * 256 + 32 + 1023) / 1024 * 1024;      // floats per tile of the global image
     constexpr int TL = KS * 256 + 32;                                     // floats per tile in LDS: KS piece-0 blocks + constants

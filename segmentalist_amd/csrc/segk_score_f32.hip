@@ -362,8 +362,8 @@ static int launch_score(segk_ctx *ctx, const segk_corpus *c, const segk_kmeans *
         if (n_split > A.n_tiles) n_split = A.n_tiles;
         if ((int64_t)n_split * tail_chunks * rows_per_wg > SEGK_WS_ENTRIES) n_split = (int)(SEGK_WS_ENTRIES / (tail_chunks * rows_per_wg));
     }
-    const char *no_split = getenv("SEGK_SCORE_NOSPLIT");
-    if (n_split < 2 || (no_split && atoi(no_split))) {          // the tail fills at least half a round: no split
+    const int no_split = segk_env_int("SEGK_SCORE_NOSPLIT", 0);
+    if (n_split < 2 || no_split) {          // the tail fills at least half a round: no split
         main_chunks = chunks;
         tail_chunks = 0;
     }
@@ -382,7 +382,7 @@ static int launch_score(segk_ctx *ctx, const segk_corpus *c, const segk_kmeans *
             ctx->prof_n++;
         }
     }
-    if (tail_chunks > 0 && A.n - n_main < SEGK_TAIL_QUEUE && A.fuse_exact && !(no_split && atoi(no_split) == 2)) {
+    if (tail_chunks > 0 && A.n - n_main < SEGK_TAIL_QUEUE && A.fuse_exact && no_split != 2) {
         ScoreArgs T = A;
         T.n = A.n - n_main;
         T.row0 = A.row0 + n_main;

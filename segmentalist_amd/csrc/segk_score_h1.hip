@@ -27,14 +27,14 @@
 // Reads the two-piece images (segk_internal.h): piece 0 of the rows, the piece-0 blocks and the
 // constants of the tile image -- each a 1 KiB LDS-DMA piece.
 // ======================================================================================
-// ABL: timing-only ablations for development (SEGK_H1_ABL; results are wrong): 1 no top-2 drain (one running maximum per
+// ABL: timing-only ablations for development (SEGK_H1_ABL, -DSEGK_DEV builds only; results are wrong): 1 no top-2 drain (one running maximum per
 // block), 2 drain without the pair index, 3 drain without the MFMAs
 template <int KS, int NBLK, int ABL = 0>
 __global__ __launch_bounds__(256, 2) void k_kmeans_score_h1(ScoreArgs A)
 {
     static_assert(NBLK == 2 || NBLK == 4, "an even number of row blocks per wave (static accumulator parity)");
     typedef _Float16 T;
-    typedef SegkPiece<2>::V8 V8;
+    typedef SegkPiece::V8 V8;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int32_t *__restrict__ ids = A.ids;
     const int64_t row0 = A.row0, n = A.n;
@@ -693,11 +693,14 @@ static int launch_score_pre(segk_ctx *ctx, ScoreArgs A, hipStream_t st)
     if (n4 > 0) {
         ScoreArgs M = A;
         M.n = n4;
+#ifdef SEGK_DEV
         const int ab = segk_dev_env("SEGK_H1_ABL");                  // development (-DSEGK_DEV builds), timing only
         if (ab == 1) hipLaunchKernelGGL((k_kmeans_score_h1<KS, 4, 1>), dim3((unsigned)(n4 / 512)), dim3(256), lds, st, M);
         else if (ab == 2) hipLaunchKernelGGL((k_kmeans_score_h1<KS, 4, 2>), dim3((unsigned)(n4 / 512)), dim3(256), lds, st, M);
         else if (ab == 3) hipLaunchKernelGGL((k_kmeans_score_h1<KS, 4, 3>), dim3((unsigned)(n4 / 512)), dim3(256), lds, st, M);
-        else hipLaunchKernelGGL((k_kmeans_score_h1<KS, 4>), dim3((unsigned)(n4 / 512)), dim3(256), lds, st, M);
+        else
+#endif
+        hipLaunchKernelGGL((k_kmeans_score_h1<KS, 4>), dim3((unsigned)(n4 / 512)), dim3(256), lds, st, M);
         if (int rc = prof_end(n4, 1)) return rc;
     }
     if (rem > 0 && !rem_queued) {

@@ -213,7 +213,7 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
 {
     static_assert(NW == 4, "four matrix waves (one per SIMD, rows prefetched) + four hint waves per workgroup");
     typedef _Float16 T;
-    typedef SegkPiece<2>::V8 V8;
+    typedef SegkPiece::V8 V8;
     // (only 256 of a lone wave's 512 registers are addressable by vector instructions, the rest is the accumulator file: a
     // second 4-block row set lands there and is copied back and forth -- 5 000 v_accvgpr moves.  So: two blocks per group with
     // prefetch for NW = 4, four without for NW = 8)
@@ -835,7 +835,7 @@ static int launch_score_hint(segk_ctx *ctx, ScoreArgs A, const int32_t *remap, i
         SEGK_CHECK_HIP(hipStreamSynchronize(st));                            // (`init` lives on this stack frame)
         ctx->hint_fb_launch = 0;
     }
-    const bool fb_off = getenv("SEGK_HINT_BALANCE") && atoi(getenv("SEGK_HINT_BALANCE")) == 0;
+    const bool fb_off = segk_env_int("SEGK_HINT_BALANCE", 1) == 0;
     float *fb_w = (float *)ctx->hint_fb;
     // (only where a wave has a few dozen groups to shift: at shard sizes -- 4 to 8 groups of 5 us per wave -- shares other
     // than equal ones only make the last round ragged: 1 250 utterances 5 960 against 6 215 sweeps/s, 2 500: 4 878 against 4 948)

@@ -1,31 +1,27 @@
-// segk_score_sp.hip -- A1 filter on the 16-bit matrix pipe: fp16x2 / bf16x3 splits, log-sum-exp and matrix-output modes
+// segk_score_sp.hip -- A1 filter on the 16-bit matrix pipe: fp16x2 split, log-sum-exp and matrix-output modes
 // (one of the translation units of the k-means path; shared helpers: segk_kmeans_dev.h)
 #include "segk_kmeans_dev.h"
 
 // ======================================================================================
 // Split-precision filter (float32 data, 8 <= D <= 128).  f[k] = x.m_k - |m_k|^2/2 as above, but the
-// contraction runs on the 16-bit matrix pipe (v_mfma_f32_32x32x16_{f16,bf16}: 16x the MAC rate of
-// 32x32x2_f32) on exact or almost exact splits of the float32 operands.  Products of two 16-bit
+// contraction runs on the 16-bit matrix pipe (v_mfma_f32_32x32x16_f16: 16x the MAC rate of
+// 32x32x2_f32) on almost exact splits of the float32 operands.  Products of two 16-bit
 // pieces are exact in float32.
 //
-//   P = 3, bf16x3:  x = x1 + x2 + x3 exactly (8 significand bits each).  Kept: m1.x1 in its own
-//       chain (seeded with -|m|^2/2; KP/16 MFMAs, KP roundings at worst), the five products of level
-//       2^-8 and 2^-16 in a second chain whose rounding error is negligible; dropped: the three of
-//       level <= 2^-24, bounded by 2u |x| M.  Six MFMAs per k-step.
-//   P = 2, fp16x2 (default):  x' = 2^a x, m' = 2^b m with powers of two chosen so that the largest
+//   fp16x2 (P = 2 pieces):  x' = 2^a x, m' = 2^b m with powers of two chosen so that the largest
 //       element sits in [2^12, 2^13) (exact scaling, well inside fp16's range; the means' exponent
 //       follows max|m| at every prepare).  x' = x1 + 2^-11 x2 + r with x1 = fp16(x'),
 //       x2 = fp16(2^11 (x' - x1)), |r| <= 2^-22 |x'| (two of the 24 significand bits are dropped).
 //       Kept: m1.x1 (main chain) and m1.x2 + m2.x1 (second chain, carried at 2^11 times its weight so
 //       that the small pieces stay normal numbers; multiplied by 2^-11 when read); dropped: m2.x2 and
-//       the r terms, bounded by 9u |x| M.  Three MFMAs per k-step -- half the matrix work of bf16x3.
+//       the r terms, bounded by 9u |x| M.  Three MFMAs per k-step.
 //       Scaled elements below 2^-14 (2^-26 of the largest one) are subnormal in fp16; even if the pipe
 //       flushed them all to zero the error would be at most 2^-14 (sum_d |m'_d| + sum_d |x'_d|) <=
 //       2^-14 sqrt(D) (M' + |x'|), i.e. (sqrt(D)/2) u |x| M relative to |x'| M' >= 2^12 max(|x'|, M'):
-//       5.7u for D = 128.  Budget for P = 2: 9u + 5.7u -> 16u.
+//       5.7u for D = 128.  Budget: 9u + 5.7u -> 16u.
 //
 // The margin below which two filter values cannot be ordered (filter_tau_sp):
-//     E1' = (1.02 (KP + 16) + 16 [P = 2]) u (|x| M + M^2/2)      (fp32 chain: (D4 + 3) u (...))
+//     E1' = (1.02 (KP + 16) + 16) u (|x| M + M^2/2)      (fp32 chain: (D4 + 3) u (...))
 // with E2 (the reference's own rounding) unchanged -- the filter stays only a filter, every decision
 // it cannot make with certainty goes to the exact stage.  tests/test_gpu_kmeans.py checks that the
 // observed error stays under a quarter of E1'.
@@ -42,11 +38,12 @@
 #define SEGK_LSE_WAVES 4
 #endif
 #define SEGK_LSE_CHUNK 2            /* tiles per chunk of the log-sum-exp mode's association (see SEGK_LSE_CLOSE) */
-template <int KS, int WAVES, int P, int MODE = 0, int SPLIT = 0>
+template <int KS, int WAVES, int MODE = 0, int SPLIT = 0>
 __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 1 : 2) void k_kmeans_score_sp(ScoreArgs A)
 {
-    typedef typename SegkPiece<P>::T T;
-    typedef typename SegkPiece<P>::V8 V8;
+    typedef SegkPiece::T T;
+    typedef SegkPiece::V8 V8;
+    constexpr int P = 2;                  // pieces
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int32_t *__restrict__ ids = A.ids;
     const int64_t row0 = A.row0;
@@ -79,10 +76,10 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 1 : 2) void k_kmeans_score
     const int D = A.D;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 31, h = lane >> 5;
-    // scaled domain: accumulators hold 2^(a+b) f (P = 2), unscaled again before anything leaves the kernel
+    // scaled domain: accumulators hold 2^(a+b) f, unscaled again before anything leaves the kernel
     const int e_ab = ((const int *)A.X32)[1] + ((const int *)A.tiles)[0];
     const float unscale = ldexpf(1.f, -e_ab);
-    constexpr float LS = P == 2 ? 1.f / 2048.f : 1.f;
+    constexpr float LS = 1.f / 2048.f;    // weight of the second chain
 
     for (int64_t rblock = rb_first; rblock * WAVES * 32 < n; rblock += rb_stride) {
     V8 xb[P][KS];
@@ -220,14 +217,9 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 1 : 2) void k_kmeans_score
                 _Pragma("unroll") for (int p = 0; p < P; p++)                                         \
                     nx[p] = *reinterpret_cast<const V8 *>(Tb + (((s + 1) * P + p) * 64 + lane) * 8);  \
             }                                                                                         \
-            NEWM = mfma_piece<P>(a[0], xb[0][s], NEWM);                                               \
-            NEWL = mfma_piece<P>(a[0], xb[1][s], NEWL);                                               \
-            NEWL = mfma_piece<P>(a[1], xb[0][s], NEWL);                                               \
-            if constexpr (P == 3) {                                                                   \
-                NEWL = mfma_piece<P>(a[1], xb[1][s], NEWL);                                           \
-                NEWL = mfma_piece<P>(a[0], xb[P - 1][s], NEWL);                                       \
-                NEWL = mfma_piece<P>(a[P - 1], xb[0][s], NEWL);                                       \
-            }                                                                                         \
+            NEWM = mfma_piece(a[0], xb[0][s], NEWM);                                                  \
+            NEWL = mfma_piece(a[0], xb[1][s], NEWL);                                                  \
+            NEWL = mfma_piece(a[1], xb[0][s], NEWL);                                                  \
             _Pragma("unroll") for (int q = 0; q < VPS; q++)                                           \
                 if (s * VPS + q < 16) SEGK_DRAIN(OLDM, OLDL, s * VPS + q);                            \
         }                                                                                             \
@@ -354,7 +346,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 1 : 2) void k_kmeans_score
         A.cand.f[2 * (int64_t)rowid + 1] = top2;
         A.cand.s[rowid] = (double)sexact;                          // NaN when not fused: k_kmeans_exact_fill
         const float M = (float)(sqrt(*A.mnorm2) * (1.0 + 1e-6)) + 1e-30f;
-        const float tau = filter_tau_sp(A.xnorm[rowid], M, D, P);
+        const float tau = filter_tau_sp(A.xnorm[rowid], M, D);
         if (!(top1 - top2 > tau)) {
             int q = atomicAdd(A.cand.count, 1);
             if (q < A.amb_cap) A.cand.queue[q] = rowid;
@@ -366,13 +358,13 @@ __global__ __launch_bounds__(64 * WAVES, WAVES >= 8 ? 1 : 2) void k_kmeans_score
 
 // split-precision filter: whole rounds (and any larger remainder) to k_kmeans_score_sp, a remainder of
 // fewer than SEGK_TAIL_QUEUE rows to the ambiguity queue.
-template <int KS, int P>
+template <int KS>
 static int launch_score_sp(segk_ctx *ctx, ScoreArgs A, hipStream_t st)
 {
-    constexpr int STRIDE = (KS * P * 256 + 32 + 1023) / 1024 * 1024;
+    constexpr int STRIDE = (KS * 2 * 256 + 32 + 1023) / 1024 * 1024;
     const size_t lds = 2 * (size_t)STRIDE * sizeof(float);
     int wg_per_cu = 1;
-    SEGK_CHECK_HIP(segk_occupancy((const void *)k_kmeans_score_sp<KS, 4, P>, 256, lds, &wg_per_cu));
+    SEGK_CHECK_HIP(segk_occupancy((const void *)k_kmeans_score_sp<KS, 4>, 256, lds, &wg_per_cu));
     const int64_t slots = (int64_t)wg_per_cu * ctx->n_cu;
     const int64_t chunks = (A.n + 127) / 128;
     int64_t main_chunks = (chunks / slots) * slots;
@@ -387,11 +379,11 @@ static int launch_score_sp(segk_ctx *ctx, ScoreArgs A, hipStream_t st)
         const bool prof = segk_prof_now(ctx);
         const int slot = ctx->prof_n % SEGK_PROF_SLOTS;
         if (prof) SEGK_CHECK_HIP(hipEventRecord(ctx->prof_ev[slot][0], st));
-        hipLaunchKernelGGL((k_kmeans_score_sp<KS, 4, P>), dim3((unsigned)main_chunks), dim3(256), lds, st, M);
+        hipLaunchKernelGGL((k_kmeans_score_sp<KS, 4>), dim3((unsigned)main_chunks), dim3(256), lds, st, M);
         if (prof) {
             SEGK_CHECK_HIP(hipEventRecord(ctx->prof_ev[slot][1], st));
             ctx->prof_rows[slot] = n_main;
-            ctx->prof_kind = P;
+            ctx->prof_kind = 2;
             ctx->prof_n++;
         }
     }
@@ -406,18 +398,17 @@ static int launch_score_sp(segk_ctx *ctx, ScoreArgs A, hipStream_t st)
     return SEGK_OK;
 }
 
-template <int P>
-static int dispatch_score_sp(segk_ctx *ctx, const ScoreArgs &A, int ks, hipStream_t st)
+int segk_dispatch_score_sp(segk_ctx *ctx, const ScoreArgs &A, int ks, hipStream_t st)
 {
     switch (ks) {
-        case 1: return launch_score_sp<1, P>(ctx, A, st);
-        case 2: return launch_score_sp<2, P>(ctx, A, st);
-        case 3: return launch_score_sp<3, P>(ctx, A, st);
-        case 4: return launch_score_sp<4, P>(ctx, A, st);
-        case 5: return launch_score_sp<5, P>(ctx, A, st);
-        case 6: return launch_score_sp<6, P>(ctx, A, st);
-        case 7: return launch_score_sp<7, P>(ctx, A, st);
-        case 8: return launch_score_sp<8, P>(ctx, A, st);
+        case 1: return launch_score_sp<1>(ctx, A, st);
+        case 2: return launch_score_sp<2>(ctx, A, st);
+        case 3: return launch_score_sp<3>(ctx, A, st);
+        case 4: return launch_score_sp<4>(ctx, A, st);
+        case 5: return launch_score_sp<5>(ctx, A, st);
+        case 6: return launch_score_sp<6>(ctx, A, st);
+        case 7: return launch_score_sp<7>(ctx, A, st);
+        case 8: return launch_score_sp<8>(ctx, A, st);
         default: break;
     }
     segk_set_error("split-precision filter: D out of range");
@@ -434,8 +425,8 @@ static int launch_score_lse_sp(segk_ctx *ctx, const ScoreArgs &A, hipStream_t st
     // (SQ_WAIT_INST_ANY 44 % of the wave cycles, SQ_WAIT_INST_LDS 3 %, matrix pipe 41 % busy), not for the tiles
     constexpr int LSE_W = SEGK_LSE_WAVES;
     constexpr int RB = 32 * LSE_W;
-    SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_kmeans_score_sp<KS, LSE_W, 2, 1>, lds));
-    SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_kmeans_score_sp<KS, LSE_W, 2, 1, 1>, lds));
+    SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_kmeans_score_sp<KS, LSE_W, 1>, lds));
+    SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_kmeans_score_sp<KS, LSE_W, 1, 1>, lds));
     const int64_t chunks = (A.n + RB - 1) / RB;
     const bool prof = ctx && segk_prof_now(ctx);
     const int slot = prof ? ctx->prof_n % SEGK_PROF_SLOTS : 0;
@@ -446,12 +437,11 @@ static int launch_score_lse_sp(segk_ctx *ctx, const ScoreArgs &A, hipStream_t st
     int64_t rem = 0;
     if (ctx && ctx->n_cu > 0) {
         int wg_per_cu = 1;
-        SEGK_CHECK_HIP(segk_occupancy((const void *)k_kmeans_score_sp<KS, LSE_W, 2, 1>, 64 * LSE_W, lds, &wg_per_cu));
+        SEGK_CHECK_HIP(segk_occupancy((const void *)k_kmeans_score_sp<KS, LSE_W, 1>, 64 * LSE_W, lds, &wg_per_cu));
         const int64_t slots = (int64_t)wg_per_cu * ctx->n_cu;
         const int64_t whole = (chunks / slots) * slots;
         if (whole > 0 && chunks - whole > 0 && chunks - whole <= slots / 8 && !ctx->capturing) rem = chunks - whole;
-        const char *e = getenv("SEGK_LSE_SPLIT");               // 0: every row block by a workgroup of its own (same bits, the tests compare)
-        if (e && atoi(e) == 0) rem = 0;
+        if (segk_env_int("SEGK_LSE_SPLIT", 1) == 0) rem = 0;    // 0: every row block by a workgroup of its own (same bits, the tests compare)
     }
     // (the partials' buffer is the second stage's, in its units: 8 x 128 x 4 floats and one ticket per block of 128 rows)
     const int64_t units = rem * (RB / 128);
@@ -476,12 +466,12 @@ static int launch_score_lse_sp(segk_ctx *ctx, const ScoreArgs &A, hipStream_t st
         S.n_chunks = (A.n_tiles + SEGK_LSE_CHUNK - 1) / SEGK_LSE_CHUNK;         // 16 at most (32 tiles): 32 floats per row of part_f
         S.part_f = ctx->sp2_part;
         S.part_k = ctx->sp2_ticket;
-        hipLaunchKernelGGL((k_kmeans_score_sp<KS, LSE_W, 2, 1, 1>), dim3((unsigned)(rem * S.n_chunks)), dim3(64 * LSE_W), lds, st, S);
+        hipLaunchKernelGGL((k_kmeans_score_sp<KS, LSE_W, 1, 1>), dim3((unsigned)(rem * S.n_chunks)), dim3(64 * LSE_W), lds, st, S);
         ScoreArgs M = A;
         M.n = n_main;
-        hipLaunchKernelGGL((k_kmeans_score_sp<KS, LSE_W, 2, 1>), dim3((unsigned)(chunks - rem)), dim3(64 * LSE_W), lds, st, M);
+        hipLaunchKernelGGL((k_kmeans_score_sp<KS, LSE_W, 1>), dim3((unsigned)(chunks - rem)), dim3(64 * LSE_W), lds, st, M);
     } else
-    hipLaunchKernelGGL((k_kmeans_score_sp<KS, LSE_W, 2, 1>), dim3((unsigned)chunks), dim3(64 * LSE_W), lds, st, A);
+    hipLaunchKernelGGL((k_kmeans_score_sp<KS, LSE_W, 1>), dim3((unsigned)chunks), dim3(64 * LSE_W), lds, st, A);
     if (prof) {
         SEGK_CHECK_HIP(hipEventRecord(ctx->prof_ev[slot][1], st));
         ctx->prof_rows[slot] = A.n;
@@ -497,7 +487,7 @@ static int launch_score_mat_sp(const ScoreArgs &A, hipStream_t st, int tiles_hin
 {
     constexpr int STRIDE = (KS * 2 * 256 + 32 + 1023) / 1024 * 1024;
     const size_t lds = 2 * (size_t)STRIDE * sizeof(float);
-    SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_kmeans_score_sp<KS, 4, 2, 2>, lds));
+    SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_kmeans_score_sp<KS, 4, 2>, lds));
     // few rows (the new tokens of one Gibbs block: ~10 k): the tiles of a row block over several workgroups -- every
     // workgroup writes its own columns of the matrix, nothing to merge (78 workgroups walking 32 tiles each: 54 us)
     const int64_t blocks = (A.n + 127) / 128;
@@ -509,15 +499,15 @@ static int launch_score_mat_sp(const ScoreArgs &A, hipStream_t st, int tiles_hin
     const int t_used = tiles_hint > 0 && tiles_hint < A.n_tiles ? tiles_hint : A.n_tiles;
     if (n_split > t_used) n_split = t_used;
     if (n_split >= 2) {
-        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_kmeans_score_sp<KS, 4, 2, 2, 1>, lds));
+        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_kmeans_score_sp<KS, 4, 2, 1>, lds));
         ScoreArgs S = A;
         S.tiles_per_split = (t_used + n_split - 1) / n_split;
         S.n_chunks = (A.n_tiles + S.tiles_per_split - 1) / S.tiles_per_split;
-        hipLaunchKernelGGL((k_kmeans_score_sp<KS, 4, 2, 2, 1>), dim3((unsigned)(blocks * S.n_chunks)), dim3(256), lds, st, S);
+        hipLaunchKernelGGL((k_kmeans_score_sp<KS, 4, 2, 1>), dim3((unsigned)(blocks * S.n_chunks)), dim3(256), lds, st, S);
         SEGK_LAUNCH_CHECK();
         return SEGK_OK;
     }
-    hipLaunchKernelGGL((k_kmeans_score_sp<KS, 4, 2, 2>), dim3((unsigned)blocks), dim3(256), lds, st, A);
+    hipLaunchKernelGGL((k_kmeans_score_sp<KS, 4, 2>), dim3((unsigned)blocks), dim3(256), lds, st, A);
     SEGK_LAUNCH_CHECK();
     return SEGK_OK;
 }
@@ -573,11 +563,6 @@ int segk_launch_score_lse_sp(segk_ctx *ctx, const void *ximg, int D2, const int3
     return SEGK_ERR_UNSUPPORTED;
 }
 
-int segk_dispatch_score_sp(segk_ctx *ctx, const ScoreArgs &A, int ks, int pieces, hipStream_t st)
-{
-    return pieces == 2 ? dispatch_score_sp<2>(ctx, A, ks, st) : dispatch_score_sp<3>(ctx, A, ks, st);
-}
-
 // second stage of the one-product pre-filter (segk_score_h1.hip): all three fp16x2 products for the rows it
 // queued; B.n_dev holds the row count on the device, the launch covers B.n rows
 template <int KS>
@@ -585,8 +570,8 @@ static int launch_sp_second(segk_ctx *ctx, const ScoreArgs &B, hipStream_t st)
 {
     constexpr int STRIDE = (KS * 2 * 256 + 32 + 1023) / 1024 * 1024;
     const size_t lds2 = 2 * (size_t)STRIDE * sizeof(float);
-    SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_kmeans_score_sp<KS, 4, 2>, lds2));
-    SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_kmeans_score_sp<KS, 4, 2, 0, 1>, lds2));
+    SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_kmeans_score_sp<KS, 4>, lds2));
+    SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_kmeans_score_sp<KS, 4, 0, 1>, lds2));
     // ranges of component tiles per row block (1: the plain kernel), by the size of the launch: a workgroup walks the 32 tiles
     // of its row block in ~55 us however few blocks there are, so that short queues (a multi-GPU shard) gain from the split
     // although the stage is matrix-bound on the whole corpus (1.05 M rows: 1 588 unsplit against 1 500 split); two workgroups
@@ -600,7 +585,7 @@ static int launch_sp_second(segk_ctx *ctx, const ScoreArgs &B, hipStream_t st)
     if (grid > blocks) grid = blocks;
     if (grid < 1) grid = 1;
     if (n_split <= 1 || ctx->capturing) {
-        hipLaunchKernelGGL((k_kmeans_score_sp<KS, 4, 2>), dim3((unsigned)grid), dim3(256), lds2, st, B);
+        hipLaunchKernelGGL((k_kmeans_score_sp<KS, 4>), dim3((unsigned)grid), dim3(256), lds2, st, B);
         SEGK_LAUNCH_CHECK();
         return SEGK_OK;
     }
@@ -618,7 +603,7 @@ static int launch_sp_second(segk_ctx *ctx, const ScoreArgs &B, hipStream_t st)
     S.n_chunks = (B.n_tiles + S.tiles_per_split - 1) / S.tiles_per_split;
     S.part_f = ctx->sp2_part;
     S.part_k = ctx->sp2_ticket;
-    hipLaunchKernelGGL((k_kmeans_score_sp<KS, 4, 2, 0, 1>), dim3((unsigned)(grid * S.n_chunks)), dim3(256), lds2, st, S);
+    hipLaunchKernelGGL((k_kmeans_score_sp<KS, 4, 0, 1>), dim3((unsigned)(grid * S.n_chunks)), dim3(256), lds2, st, S);
     SEGK_LAUNCH_CHECK();
     return SEGK_OK;
 }

@@ -12,23 +12,8 @@
 // The window-of-eight segmenter of ONE utterance by a whole wave, on wave-private LDS arrays (k_kmeans_segment_w8 and the
 // persistent sequential chain, segk_seq_chain.hip): A8 forward and backward, the new tokens and their components --
 // seg_w8_uniform below.  (Round 2's form, seg_w8_wave, spread a step's eight candidates over eight lanes: one add, a three-step
-// DPP maximum, a DPP shift of the gammas -- 230 clocks per step for a lone wave, 180 per backward token; k_kmeans_segment_oct
-// still advances eight utterances that way in one wave.  A one-lane form before it: 14 us per utterance.)
-// The DPP helpers:
-template <int CTRL>
-__device__ __forceinline__ double seg_dpp_f64(double v)
-{
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    const int lo2 = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xF, 0xF, false);
-    const int hi2 = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xF, 0xF, false);
-    return __hiloint2double(hi2, lo2);
-}
-template <int CTRL>
-__device__ __forceinline__ int seg_dpp_i32(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xF, 0xF, false); }
-#define SEG_DPP_XOR1 0xB1          /* quad_perm [1,0,3,2] */
-#define SEG_DPP_XOR2 0x4E          /* quad_perm [2,3,0,1] */
-#define SEG_DPP_HMIRROR 0x141      /* row_half_mirror: lane i <-> 7 - i inside every group of eight */
-#define SEG_DPP_SHR1 0x111         /* row_shr:1: lane i reads lane i - 1 (lane 0 of a row keeps its own) */
+// DPP maximum, a DPP shift of the gammas -- 230 clocks per step for a lone wave, 180 per backward token.  A one-lane form
+// before it: 14 us per utterance.)
 
 // the tokens of a boundary mask, by a whole wave: the lane of a set bit j looks up its own span [jp, j + 1) (band entry, or the
 // triangular table for a span longer than the window); spans without an embedding are skipped.  Returns their number.
@@ -48,8 +33,8 @@ __device__ __forceinline__ int seg_old_tokens_wave(const int32_t *bid, const int
     return __popcll(keep);
 }
 
-// ---- the same once more, for a wave that has nothing else to do (the persistent sequential chain: one utterance at a time, its
-// latency IS the throughput).  A lone wave issues a dependent instruction every 8-16 clocks: the DPP form above (three
+// ---- seg_w8_uniform, written for a wave that has nothing else to do (the persistent sequential chain: one utterance at a time, its
+// latency IS the throughput).  A lone wave issues a dependent instruction every 8-16 clocks: the DPP form (three
 // cross-lane stages per step) measured 230 clocks a step and 180 a backward token -- 4.7 us per utterance inside the chain.
 // Here the forward recurrence is UNIFORM: every lane keeps the last eight gammas in registers and computes all the
 // candidates of a step itself -- WW independent adds and a tree of maxima, no cross-lane traffic; the candidates come from

@@ -1572,8 +1572,8 @@ __global__ __launch_bounds__(256) void k_batch_finalize(
         }
     }
     if (sp_spec) {
-        typedef SegkPiece<2>::T T16;
-        typedef SegkPiece<2>::V8 V8;
+        typedef SegkPiece::T T16;
+        typedef SegkPiece::V8 V8;
         T16 *Tb = (T16 *)Tsp;
         for (int it = tid; it < FIN_ROWS * KSsp * 2; it += nt) {
             const int r = it / (KSsp * 2), rem = it - r * (KSsp * 2), sidx = rem >> 1, h = rem & 1;
@@ -1586,7 +1586,7 @@ __global__ __launch_bounds__(256) void k_batch_finalize(
                 const int d = segk_b3_dim(16 * sidx + 8 * h + i);
                 const float v = d < D ? ldexpf((float)mrow[r * D + d], eb_prev) : 0.f;
                 T16 pc[2];
-                split_sp<2>(v, pc);
+                split_sp(v, pc);
                 out[0][i] = pc[0];
                 out[1][i] = pc[1];
             }
@@ -1601,11 +1601,11 @@ __global__ __launch_bounds__(256) void k_batch_finalize(
     SEGK_TSTAMP(3, 6);
 }
 
-// final labels of the local tokens + (tile workgroups) split-precision image and duplicate marking
-template <typename XT, int P>
+// final labels of the local tokens + (tile workgroups) split-precision image (SP) and duplicate marking
+template <typename XT, bool SP>
 __global__ __launch_bounds__(256) void k_batch_post(segk_corpus c, segk_kmeans m, int lo, int hi, int32_t *new_k, const int32_t *remap,
                                                     int n_tiles, int stride32, int G, float *tiles_sp, int stride_sp, int sp_const_off,
-                                                    const unsigned long long *row_hash, int sp_spec)
+                                                    const unsigned long long *row_hash)
 {
     if ((int)blockIdx.x >= n_tiles) {
         const int64_t idx = (int64_t)(blockIdx.x - n_tiles) * blockDim.x + threadIdx.x;
@@ -1619,19 +1619,16 @@ __global__ __launch_bounds__(256) void k_batch_post(segk_corpus c, segk_kmeans m
     }
     const int tile = blockIdx.x;
     SEGK_TSTAMP(4, 0);
-    if constexpr (P != 0) {
+    if constexpr (SP) {
         if (tiles_sp) {
-            // P = 2: the finalize kernel has written the image with the exponent of the previous one (its sp_spec path); when
+            // the finalize kernel has written the image with the exponent of the previous one (its sp_spec path); when
             // the exponent of the new means is the same there is nothing to build (workgroup-uniform)
-            bool built = false;
-            if (P == 2 && sp_spec) {
-                const int eb_new = sp_exponent((float)(sqrt(*m.mnorm_max) * (1.0 + 1e-6)));
-                built = eb_new == ((const int *)tiles_sp)[3];           // (word 3: no workgroup of this kernel writes it)
-            }
+            const int eb_new = sp_exponent((float)(sqrt(*m.mnorm_max) * (1.0 + 1e-6)));
+            const bool built = eb_new == ((const int *)tiles_sp)[3];    // (word 3: no workgroup of this kernel writes it)
             if (!built)
-                dev_prepare_sp_tile<P>((const float *)m.means, m.K_max, c.D, tiles_sp, m.mnorm_max, (const unsigned char *)c.Xb3,
-                                       (const double *)nullptr, tile);
-            if (P == 2 && sp_spec && tile == 0 && threadIdx.x == 0) {
+                dev_prepare_sp_tile((const float *)m.means, m.K_max, c.D, tiles_sp, m.mnorm_max, (const unsigned char *)c.Xb3,
+                                    (const double *)nullptr, tile);
+            if (tile == 0 && threadIdx.x == 0) {
                 if (built) ((unsigned int *)tiles_sp)[1] = ((const unsigned int *)tiles_sp)[2];      // E_m of the rows
                 ((unsigned int *)tiles_sp)[2] = 0u;
             }
@@ -1834,8 +1831,7 @@ int segk_launch_update_utt(const segk_corpus *c, segk_kmeans *m, int utt, const 
                            const int32_t *new_k, const int32_t *n_old, const int32_t *n_new, int32_t *status, hipStream_t st)
 {
     // the LDS-staged form for utterances of at most 64 landmarks (SEGK_SEQ_UPDATE=0: the item-by-item kernel)
-    const char *e = getenv("SEGK_SEQ_UPDATE");
-    if (c->N_max <= 32 && !(e && atoi(e) == 0)) {
+    if (c->N_max <= 32 && segk_env_int("SEGK_SEQ_UPDATE", 1) != 0) {
         const size_t esz = c->x_dtype == SEGK_F32 ? 4 : 8;
         const size_t lds = (size_t)2 * c->N_max * c->D * (8 + 2 * esz);
         if (lds <= 150 * 1024) {
@@ -1987,12 +1983,11 @@ int32_t segk_kmeans_batch_finalize(segk_ctx *ctx, const segk_corpus *c, segk_kme
     hipStream_t st = (hipStream_t)stream;
     // value hashes of the rows, for the duplicate marking (context-owned, K_max <= 2048 only; SEGK_MARK_DUPS=0: leave
     // the duplicates in the filters' images)
-    const char *md = getenv("SEGK_MARK_DUPS");
     unsigned long long *row_hash = nullptr;
     if (ctx && m->K_max <= 2048) {
         if (!ctx->row_hash) SEGK_CHECK_HIP(hipMalloc((void **)&ctx->row_hash, 2048 * sizeof(unsigned long long)));
         ctx->row_hash_means = m->means;
-        if (!(md && atoi(md) == 0)) row_hash = ctx->row_hash;
+        if (segk_env_int("SEGK_MARK_DUPS", 1) != 0) row_hash = ctx->row_hash;
     }
     // overflow arrays of the clamp replay: the flagged tokens of a sweep beyond the SEGK_FLAG_LDS the kernel keeps in LDS
     // (a first sweep with K << K_max: the inactive rows are data points, every token near one founds a component)
@@ -2014,8 +2009,7 @@ int32_t segk_kmeans_batch_finalize(segk_ctx *ctx, const segk_corpus *c, segk_kme
         ovf = ctx->flag_ovf;
         ovf_cap = (int)ctx->flag_ovf_cap;
     }
-    const bool sp = m->tiles_b3 && c->Xb3 && c->x_dtype == SEGK_F32 && c->D >= 8 && c->D <= 128 && (c->sp_pieces == 2 || c->sp_pieces == 3);
-    const int sp_spec = sp && c->sp_pieces == 2 ? 1 : 0;      // fp16x2 image by the finalize kernel, checked by the post kernel
+    const bool sp = m->tiles_b3 && c->Xb3 && c->x_dtype == SEGK_F32 && c->D >= 8 && c->D <= 128 && c->sp_pieces == 2;
     const int n_tiles = segk_n_tiles(m->K_max);
     const size_t lds = (((size_t)m->K_max * 8 + ((size_t)m->K_max / 32 + 2) * 4 + 15) & ~(size_t)15) + (size_t)FIN_ROWS * c->D * sizeof(double);
     DISPATCH_XT(c, {
@@ -2024,23 +2018,20 @@ int32_t segk_kmeans_batch_finalize(segk_ctx *ctx, const segk_corpus *c, segk_kme
         hipLaunchKernelGGL(k_batch_finalize<XT>, dim3((m->K_max + FIN_ROWS - 1) / FIN_ROWS + 1), dim3(256), lds, st, *c, *m, records,
                            n_blocks_total, n_blocks_per_rank, rank_stride, flag_cap, my_rank, new_k, remap_scratch, out_scalars,
                            status, ctx && m->K_max <= 2048 ? ctx->row_hash : (unsigned long long *)nullptr,
-                           sp ? (unsigned int *)m->tiles_b3 + 1 : (unsigned int *)nullptr, ovf, ovf_cap, sp_spec,
+                           sp ? (unsigned int *)m->tiles_b3 + 1 : (unsigned int *)nullptr, ovf, ovf_cap, sp ? 1 : 0,
                            flag_rows ? segk_flag_row_words(flag_cap, c->D, c->x_dtype == SEGK_F32 ? 4 : 8) : (int64_t)0);
     });
     const int64_t nslot = (int64_t)(utt_hi - utt_lo) * c->N_max;
     const unsigned grid = (unsigned)(n_tiles + (nslot + 255) / 256);
     const int kp = segk_b3_kp(c->D);
     const int stride32 = segk_tile_stride(c->D), G = segk_gmax(c->D);
-    const int stride_sp = sp ? segk_sp_tile_stride(c->D, c->sp_pieces) : 0, sp_off = sp ? (kp / 16) * c->sp_pieces * 256 : 0;
-    if (sp && c->sp_pieces == 2)
-        hipLaunchKernelGGL((k_batch_post<float, 2>), dim3(grid), dim3(256), 0, st, *c, *m, utt_lo, utt_hi, new_k, remap_scratch,
-                           n_tiles, stride32, G, m->tiles_b3, stride_sp, sp_off, row_hash, sp_spec);
-    else if (sp)
-        hipLaunchKernelGGL((k_batch_post<float, 3>), dim3(grid), dim3(256), 0, st, *c, *m, utt_lo, utt_hi, new_k, remap_scratch,
-                           n_tiles, stride32, G, m->tiles_b3, stride_sp, sp_off, row_hash, 0);
+    const int stride_sp = sp ? segk_sp_tile_stride(c->D, 2) : 0, sp_off = sp ? (kp / 16) * 2 * 256 : 0;
+    if (sp)
+        hipLaunchKernelGGL((k_batch_post<float, true>), dim3(grid), dim3(256), 0, st, *c, *m, utt_lo, utt_hi, new_k, remap_scratch,
+                           n_tiles, stride32, G, m->tiles_b3, stride_sp, sp_off, row_hash);
     else
-        DISPATCH_XT(c, hipLaunchKernelGGL((k_batch_post<XT, 0>), dim3(grid), dim3(256), 0, st, *c, *m, utt_lo, utt_hi, new_k,
-                                           remap_scratch, n_tiles, stride32, G, (float *)nullptr, 0, 0, row_hash, 0););
+        DISPATCH_XT(c, hipLaunchKernelGGL((k_batch_post<XT, false>), dim3(grid), dim3(256), 0, st, *c, *m, utt_lo, utt_hi, new_k,
+                                           remap_scratch, n_tiles, stride32, G, (float *)nullptr, 0, 0, row_hash););
     SEGK_LAUNCH_CHECK();
     return SEGK_OK;
 }

@@ -105,7 +105,7 @@ class DeviceCorpus(object):
             bi, bd = band
             assert bi.shape == bd.shape == (self.n_utt, self.N_max, bi.shape[2])
             self.band_ids, self.band_dur, self.band_W = to_dev(bi, np.int32), to_dev(bd, np.float64), int(bi.shape[2])
-        # bf16x3 image of the rows for the k-means filter (float32 data, 8 <= D <= 128); built on demand
+        # fp16x2 image of the rows for the k-means filter (float32 data, 8 <= D <= 128); built on demand
         self.Xb3 = None
         self.c = _abi.Corpus(
             X=self.X.data_ptr(), X32=self.X32.data_ptr(), x_dtype=self.x_dtype, D=self.D,
@@ -120,11 +120,11 @@ class DeviceCorpus(object):
                                              _abi.stream()))
 
     def ensure_b3(self):
-        """The rows split into 16-bit pieces (segk_corpus_prepare_b3) for the split-precision k-means
-        filter: fp16x2 by default, bf16x3 with SEGK_SCORE_B3=3, none (fp32 MFMA filter) with 0."""
+        """The rows split into two fp16 pieces (segk_corpus_prepare_b3) for the split-precision k-means
+        filter: SEGK_SCORE_B3=2 (default) builds them; 0 (or any other value) keeps the fp32 MFMA filter."""
         import os
         pieces = int(os.environ.get("SEGK_SCORE_B3", "2") or 2)
-        if pieces not in (2, 3):
+        if pieces != 2:
             return False
         if self.Xb3 is None and self.x_dtype == SEGK_F32 and 8 <= self.D <= 128:
             torch = _torch()

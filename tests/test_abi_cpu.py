@@ -95,6 +95,19 @@ def test_host_shims_match_oracle(built, golden):
     assert cu.sum_square_a_times_b(y, y) == 3.0 ** 3 + 0.5 ** 3 + 2.0 ** 3
 
 
+def test_split_image_refuses_any_piece_count_but_two(built):
+    """segk_corpus_prepare_b3 builds the fp16x2 image only: pieces = 3 (the retired bf16x3 split) is an argument error, and
+    so is D = 4 with pieces = 2 as before -- both refused on the host, before anything touches a device."""
+    L = built.lib()
+    X = np.zeros((4, 16), np.float32)
+    dummy = ctypes.create_string_buffer(64)
+    for D, pieces, msg in ((16, 3, b"pieces"), (4, 2, b"8 <= D <= 128")):
+        c = built.Corpus(X=X.ctypes.data, X32=X.ctypes.data, x_dtype=built.SEGK_F32, D=D, n_emb=4, ldx=16, ld32=16)
+        rc = L.segk_corpus_prepare_b3(None, ctypes.byref(c), ctypes.addressof(dummy), pieces, None)
+        assert rc == -1, (D, pieces, rc)          # SEGK_ERR_ARG
+        assert msg in L.segk_last_error(), L.segk_last_error()
+
+
 def test_no_cpu_fallback(built):
     import torch
     if torch.cuda.is_available():

@@ -52,7 +52,7 @@ def headline(gpu, monkeypatch_module):
     """The headline segmenter after two batch sweeps (default environment)."""
     from segmentalist_amd import kmeans_acoustic_wordseg as kaw
     from segmentalist_amd.synth import make_corpus
-    for v in ("SEGK_SCORE_PRE", "SEGK_SCORE_B3", "SEGK_SCORE_HINT", "SEGK_MARK_DUPS", "SEGK_SEGMENT_OCT", "SEGK_SWEEP_GRAPH", "SEGK_BRUTE_LS"):
+    for v in ("SEGK_SCORE_PRE", "SEGK_SCORE_B3", "SEGK_SCORE_HINT", "SEGK_MARK_DUPS", "SEGK_SWEEP_GRAPH", "SEGK_BRUTE_LS"):
         monkeypatch_module.delenv(v, raising=False)
     corpus = make_corpus(N_UTT, D, K, seed=0, N=N_LM, n_slices_max=NMAX)
     random.seed(0)

@@ -61,7 +61,8 @@ def test_a1_scores_bit_exact_vs_reference(gpu, golden, case):
                                           (200, 64, 600, "float32"), (300, 40, 300, "float32")])
 @pytest.mark.parametrize("b3", ["2", "3", "0"], ids=["fp16x2", "bf16x3", "fp32mfma"])
 def test_a1_max_argmax_vs_oracle_random(gpu, monkeypatch, D, K, n, dtype, b3):
-    """Both filters (SEGK_SCORE_B3=0 forces the fp32-MFMA one where the bf16x3 one would be chosen)."""
+    """Both filters (SEGK_SCORE_B3=0 forces the fp32-MFMA one where the fp16x2 one would be chosen).  SEGK_SCORE_B3=3 asks
+    for the retired bf16x3 split: no split image is built, and the fp32-MFMA filter gives the same decisions."""
     from oracle import c_oracle as co
     monkeypatch.setenv("SEGK_SCORE_B3", b3)
     rs = np.random.RandomState(D * 1000 + K)
@@ -76,6 +77,8 @@ def test_a1_max_argmax_vs_oracle_random(gpu, monkeypatch, D, K, n, dtype, b3):
     means[K // 2] = means[1]          # exact duplicate of row 1 ...
     X[5] = means[1]                   # ... and a data point sitting on it: an exact tie, lowest index wins
     c = _components(X, means)
+    if b3 != "2":
+        assert c.dev.corpus.Xb3 is None
     mx, am, nbrute = c.dev.exact_max(np.arange(n))
     want_mx, want_am = co.kmeans_max_argmax(means, X)
     assert np.array_equal(am, want_am)
@@ -600,7 +603,7 @@ def test_batch_sweep_headline_shape_properties(gpu):
 
 
 @pytest.mark.parametrize("D,K,scale", [(100, 1000, 1.0), (128, 513, 1.0), (40, 257, 30.0), (16, 64, 1e-3)])
-@pytest.mark.parametrize("pieces", ["2", "3"], ids=["fp16x2", "bf16x3"])
+@pytest.mark.parametrize("pieces", ["2"], ids=["fp16x2"])
 def test_split_precision_filter_error_is_far_inside_the_proven_bound(gpu, monkeypatch, D, K, scale, pieces):
     """The split-precision filter's values against float64: the observed error must sit well inside
     E1' (the bound assumes one rounding of size u per accumulated product and the stated split
@@ -624,7 +627,7 @@ def test_split_precision_filter_error_is_far_inside_the_proven_bound(gpu, monkey
     KP = (D + 15) // 16 * 16
     xn = np.linalg.norm(X64, axis=1)
     Mmax = np.sqrt((M64 ** 2).sum(1).max())
-    e1 = (1.02 * (KP + 16) + (16 if pieces == "2" else 0)) * u * (xn * Mmax + 0.5 * Mmax ** 2)
+    e1 = (1.02 * (KP + 16) + 16) * u * (xn * Mmax + 0.5 * Mmax ** 2)
     ratio = np.abs(cf[:, 0] - f1) / e1
     assert ratio.max() < 0.25, ratio.max()
     # and the decisions are the reference's: exact argmax / max after the exact stage
@@ -634,7 +637,7 @@ def test_split_precision_filter_error_is_far_inside_the_proven_bound(gpu, monkey
     assert np.array_equal(am, want_am) and np.array_equal(mx, want_mx)
 
 
-@pytest.mark.parametrize("pieces", ["2", "3"], ids=["fp16x2", "bf16x3"])
+@pytest.mark.parametrize("pieces", ["2"], ids=["fp16x2"])
 def test_split_precision_filter_wide_dynamic_range(gpu, monkeypatch, pieces):
     """Rows and means whose elements span nine decades (most of them subnormal or flushed in fp16 after
     the power-of-two scaling), a corpus-wide scale far from 1, duplicated means: the decisions after the
@@ -662,7 +665,7 @@ def test_split_precision_filter_wide_dynamic_range(gpu, monkeypatch, pieces):
         u = 2.0 ** -24
         xn = np.linalg.norm(X64, axis=1)
         Mmax = np.sqrt((M64 ** 2).sum(1).max())
-        e1 = (1.02 * (64 + 16) + (16 if pieces == "2" else 0)) * u * (xn * Mmax + 0.5 * Mmax ** 2)
+        e1 = (1.02 * (64 + 16) + 16) * u * (xn * Mmax + 0.5 * Mmax ** 2)
         sel = np.isfinite(cf[:, 0])
         assert (np.abs(cf[sel, 0] - f1[sel]) / e1[sel]).max() < 0.5
 
@@ -913,19 +916,18 @@ def test_sequential_sweep_with_a_repeated_utterance(gpu, monkeypatch):
 @pytest.mark.parametrize("n_utt,D,K,N,nmax,ragged", [(400, 16, 40, 20, 6, False), (300, 8, 25, 0, 8, True), (200, 12, 30, 0, 3, True),
                                                      (150, 8, 20, 44, 8, False), (120, 8, 20, 64, 5, False)])
 def test_segment_kernels_agree(gpu, monkeypatch, n_utt, D, K, N, nmax, ragged):
-    """The per-utterance DP by the whole wave (seg_w8_wave: eight lanes per step, DPP maxima, token lists from ballots; the
-    default below 4 096 utterances), with eight utterances per wave (k_kmeans_segment_oct, the default above; forced here with
-    SEGK_SEGMENT_OCT=1) and the generic kernel (SEGK_SEGMENT_GENERIC=1): identical boundaries, labels and statistics after
-    three batch sweeps -- uniform utterances, ragged ones shorter than the window, a window of eight, 44 and 64 landmarks
-    (boundary masks beyond 32 bits, several steps of eight bits in the token lists)."""
+    """The per-utterance DP by one wave per utterance (k_kmeans_segment_w8, the default) and by the generic kernel
+    (SEGK_SEGMENT_GENERIC=1): identical boundaries, labels and statistics after three batch sweeps -- uniform utterances,
+    ragged ones shorter than the window, a window of eight, 44 and 64 landmarks (boundary masks beyond 32 bits, several
+    steps of eight bits in the token lists)."""
     from segmentalist_amd import kmeans_acoustic_wordseg as kaw
     corpus = cases.chain_corpus(n_utt, D, K, 31 * n_utt + D, ragged, N, nmax, "float32")
     out = []
-    for env in ({"SEGK_SEGMENT_OCT": "0"}, {"SEGK_SEGMENT_OCT": "1"}, {"SEGK_SEGMENT_GENERIC": "1"}):
-        for k in ("SEGK_SEGMENT_OCT", "SEGK_SEGMENT_GENERIC"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
+    for generic in (False, True):
+        if generic:
+            monkeypatch.setenv("SEGK_SEGMENT_GENERIC", "1")
+        else:
+            monkeypatch.delenv("SEGK_SEGMENT_GENERIC", raising=False)
         random.seed(9)
         np.random.seed(9)
         seg = kaw.SegmentalKMeansWordseg(K, *corpus, n_slices_min=0, n_slices_max=nmax, p_boundary_init=0.5,
