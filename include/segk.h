@@ -53,8 +53,9 @@ const char *segk_last_error(void);
  *   7 round 4: segk_fbatch.consts16 holds 2 (K_max + 2) + 32 doubles (the column maps of the packed operand image behind the
  *              constants) and the token-likelihood matrix has the image's columns; the FBGMM / bigram kernels read
  *              segk_corpus.band_ids / band_dur (a COMPLETE band only); segk_fbgmm_sequential_sweep with a language model
- *   8 round 4: segk_fbb_step_diag32                                                                                           */
-#define SEGK_ABI_VERSION 8
+ *   8 round 4: segk_fbb_step_diag32
+ *   9 segk_fbatch.centre (the reduced-precision FBGMM kernels work in coordinates centred on it), segk_fbatch.tab32         */
+#define SEGK_ABI_VERSION 9
 int32_t segk_abi_version(void);
 
 /* Timing of the MAIN launch of the MFMA score kernel (k_kmeans_score<..., 0>) with HIP events
@@ -588,6 +589,15 @@ typedef struct {
      * the score and assignment kernels of every Gibbs step need not evaluate its D logarithms per row again
      * (segk_fbb_prior_rows once; NULL: evaluated in the kernels; the values are the same either way)                           */
     const double *prior_rows;     /* [dev] [n_emb] or NULL                                         */
+    /* optional: a per-dimension vector c that the reduced-precision kernels subtract from the rows and from the slot means (and
+     * the prior mean) in fp64 before rounding them -- the operands of segk_fbb_make_y / segk_fbb_prepare's operand images and
+     * the float32 terms of segk_fbb_score_diag32 / _assign_diag32 / _step_diag32.  Exact in real arithmetic (the densities are
+     * functions of x - mu); it keeps the rounding at the data's spread instead of its distance from the origin.  Must stay
+     * the same for the sampler's lifetime (segk_fbb_make_y reads it once) and on every rank.  NULL: c = 0.                    */
+    const double *centre;         /* [dev] [D] or NULL                                             */
+    /* optional: [dev] [2, D, K_max] floats, written by segk_fbb_prepare when non-NULL: float(mean - centre) and float(q) of
+     * every slot, the tables the diagonal float32 kernels stage (each of their workgroups converted the fp64 ones itself)  */
+    float *tab32;
 } segk_fbatch;
 
 /* token lists of all utterances from the boundaries: new_tok [n_utt, N_max], n_new [n_utt]     */

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("SEGK_LIB_PATH") or os.path.join(_HERE, "libsegk.so") 
 
 SEGK_F32, SEGK_F64 = 0, 1
 SEGK_ERR_UNSUPPORTED = -4          # include/segk.h
-ABI_VERSION = 8          # SEGK_ABI_VERSION of include/segk.h this binding was written against
+ABI_VERSION = 9          # SEGK_ABI_VERSION of include/segk.h this binding was written against
 
 
 class SegkError(RuntimeError):
@@ -47,7 +47,7 @@ class FbatchDev(C.Structure):
         ("half", C.c_void_p), ("scal", C.c_void_p), ("slot", C.c_void_p), ("lm_tok", C.c_void_p),
         ("seed", C.c_uint64), ("y", C.c_void_p), ("ldy", C.c_int64), ("tiles32", C.c_void_p),
         ("y16", C.c_void_p), ("tiles16", C.c_void_p), ("rows32", C.c_void_p), ("consts16", C.c_void_p),
-        ("prior_rows", C.c_void_p),
+        ("prior_rows", C.c_void_p), ("centre", C.c_void_p), ("tab32", C.c_void_p),
     ]
 
 

@@ -324,6 +324,10 @@ static __device__ __forceinline__ double fbb_tree(double *p, int n, int stride)
     return p[0];
 }
 
+// dimension d of the vector the float32 kernels subtract from both x and the slot means before rounding them
+// (segk_fbatch.centre; 0 without one): mu - x is then formed from operands of the data's spread, not of its offset
+__device__ inline double fbb_centre(const segk_fbatch &bt, int d) { return bt.centre ? bt.centre[d] : 0.0; }
+
 // ---------------------------------------------------------------------------------------
 // statistics without block b (b = -1: all) and the per-slot predictive parameters.
 // One workgroup of three waves per slot: wave 0 sums the counts, wave 1 the sums, wave 2 the sums of squares (their loads
@@ -406,6 +410,10 @@ __global__ __launch_bounds__(192) void k_fbb_prepare(segk_fbgmm f, segk_fbatch b
                 }
                 bt.mean_t[(int64_t)d * KM + k] = mean;
                 bt.q_t[(int64_t)d * KM + k] = q;
+                if (bt.tab32) {                 // the float32 kernels' operands, once per step instead of once per workgroup
+                    bt.tab32[(int64_t)d * KM + k] = (float)(mean - fbb_centre(bt, d));
+                    bt.tab32[(int64_t)D * KM + (int64_t)d * KM + k] = (float)q;
+                }
                 lsum += lt;
             }
         }
@@ -509,41 +517,46 @@ static __device__ __forceinline__ void fbb_accumulate_rows32(const segk_fbatch &
     // same order
     for (; d + 16 <= D; d += 16) {
         float m[16], q[16];
+        double cj[16];
 #pragma unroll
         for (int j = 0; j < 16; j++) {
-            m[j] = (float)bt.mean_t[(int64_t)(d + j) * KM + k];
+            cj[j] = fbb_centre(bt, d + j);
+            m[j] = (float)(bt.mean_t[(int64_t)(d + j) * KM + k] - cj[j]);
             q[j] = (float)bt.q_t[(int64_t)(d + j) * KM + k];
         }
 #pragma unroll
         for (int j = 0; j < 16; j++) {
 #pragma unroll
             for (int r = 0; r < NR; r++) {
-                const float delta = m[j] - (float)xs[r * D + d + j];
+                const float delta = m[j] - (float)(xs[r * D + d + j] - cj[j]);
                 acc[r] += __builtin_amdgcn_logf(1.f + (delta * delta) * q[j]);
             }
         }
     }
     for (; d + 4 <= D; d += 4) {
         float m[4], q[4];
+        double cj[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            m[j] = (float)bt.mean_t[(int64_t)(d + j) * KM + k];
+            cj[j] = fbb_centre(bt, d + j);
+            m[j] = (float)(bt.mean_t[(int64_t)(d + j) * KM + k] - cj[j]);
             q[j] = (float)bt.q_t[(int64_t)(d + j) * KM + k];
         }
 #pragma unroll
         for (int j = 0; j < 4; j++) {
 #pragma unroll
             for (int r = 0; r < NR; r++) {
-                const float delta = m[j] - (float)xs[r * D + d + j];
+                const float delta = m[j] - (float)(xs[r * D + d + j] - cj[j]);
                 acc[r] += __builtin_amdgcn_logf(1.f + (delta * delta) * q[j]);
             }
         }
     }
     for (; d < D; d++) {
-        const float m = (float)bt.mean_t[(int64_t)d * KM + k], q = (float)bt.q_t[(int64_t)d * KM + k];
+        const double cd = fbb_centre(bt, d);
+        const float m = (float)(bt.mean_t[(int64_t)d * KM + k] - cd), q = (float)bt.q_t[(int64_t)d * KM + k];
 #pragma unroll
         for (int r = 0; r < NR; r++) {
-            const float delta = m - (float)xs[r * D + d];
+            const float delta = m - (float)(xs[r * D + d] - cd);
             acc[r] += __builtin_amdgcn_logf(1.f + (delta * delta) * q);
         }
     }
@@ -721,13 +734,24 @@ __global__ __launch_bounds__(256) void k_fbb_score_diag32(segk_corpus c, segk_fb
     const XT *X = (const XT *)c.X;
     for (int j = tid; j < FBB_R32 * D; j += nt) {
         const int r = j / D, d = j - r * D;
-        xs[d * FBB_R32 + r] = r < nr ? (float)X[(row0 + r) * c.ldx + d] : 0.f;
+        xs[d * FBB_R32 + r] = r < nr ? (float)((double)X[(row0 + r) * c.ldx + d] - fbb_centre(bt, d)) : 0.f;
     }
-    if (TLDS && !(dbg & 1))                       // (dbg, make DEV=1 only: 1 no table fill, 2 no terms, 4 no reductions -- timing)
-        for (int j = tid; j < D * KM; j += nt) {
-            tm[j] = (float)bt.mean_t[j];
-            tq[j] = (float)bt.q_t[j];
-        }
+    if (TLDS && !(dbg & 1)) {                     // (dbg, make DEV=1 only: 1 no table fill, 2 no terms, 4 no reductions -- timing)
+        const int dstep = nt / KM, rstep = nt - dstep * KM;
+        if (bt.tab32)                             // (segk_fbb_prepare's float32 copy: the same values)
+            for (int j = tid; j < D * KM; j += nt) {
+                tm[j] = bt.tab32[j];
+                tq[j] = bt.tab32[D * KM + j];
+            }
+        else                                      // (the dimension of entry j = j / KM, stepped along with j)
+            for (int j = tid, d = tid / KM, r = tid - (tid / KM) * KM; j < D * KM; j += nt) {
+                tm[j] = (float)(bt.mean_t[j] - fbb_centre(bt, d));
+                tq[j] = (float)bt.q_t[j];
+                d += dstep;
+                r += rstep;
+                if (r >= KM) { r -= KM; d++; }
+            }
+    }
     // the prior predictive of every row (an empty slot's likelihood): fp64 as in the fp64 kernel, once per row -- from
     // segk_fbb_prior_rows' table when the caller keeps one (the values are constants of the corpus: 16 x D software
     // logarithms and four barriers per workgroup and Gibbs step otherwise)
@@ -785,14 +809,15 @@ __global__ __launch_bounds__(256) void k_fbb_score_diag32(segk_corpus c, segk_fb
                 float m[4], q[4];
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
-                    m[j] = TLDS ? tm[(d + j) * KM + k] : (float)bt.mean_t[(int64_t)(d + j) * KM + k];
+                    m[j] = TLDS ? tm[(d + j) * KM + k] : (float)(bt.mean_t[(int64_t)(d + j) * KM + k] - fbb_centre(bt, d + j));
                     q[j] = TLDS ? tq[(d + j) * KM + k] : (float)bt.q_t[(int64_t)(d + j) * KM + k];
                 }
 #pragma unroll
                 for (int j = 0; j < 4; j++) term(d + j, m[j], q[j]);
             }
             for (; d < D; d++)
-                term(d, TLDS ? tm[d * KM + k] : (float)bt.mean_t[(int64_t)d * KM + k], TLDS ? tq[d * KM + k] : (float)bt.q_t[(int64_t)d * KM + k]);
+                term(d, TLDS ? tm[d * KM + k] : (float)(bt.mean_t[(int64_t)d * KM + k] - fbb_centre(bt, d)),
+                     TLDS ? tq[d * KM + k] : (float)bt.q_t[(int64_t)d * KM + k]);
             const double zc = k == kk ? zc_first : bt.zconst[k], hl = (k == kk ? half_first : bt.half[k]) * 0.6931471805599453;
 #pragma unroll
             for (int r = 0; r < RPG; r++) z2[r] = (float)((zc - hl * (double)acc2[r >> 1][r & 1]) * 1.4426950408889634);
@@ -916,9 +941,21 @@ __global__ __launch_bounds__(512) void k_fbb_step_diag32(segk_corpus c, segk_fbg
     uint8_t *bnd_g = A.boundaries + (int64_t)utt * NM;
     const XT *X = (const XT *)c.X;
     // ---- (1) tables, span table, flags
-    for (int j = tid; j < D * KM; j += nt) {
-        tm[j] = (float)bt.mean_t[j];
-        tq[j] = (float)bt.q_t[j];
+    {
+        const int dstep = nt / KM, rstep = nt - dstep * KM;
+        if (bt.tab32)                             // (segk_fbb_prepare's float32 copy: the same values)
+            for (int j = tid; j < D * KM; j += nt) {
+                tm[j] = bt.tab32[j];
+                tq[j] = bt.tab32[D * KM + j];
+            }
+        else                                      // (the dimension of entry j = j / KM, stepped along with j)
+            for (int j = tid, d = tid / KM, r = tid - (tid / KM) * KM; j < D * KM; j += nt) {
+                tm[j] = (float)(bt.mean_t[j] - fbb_centre(bt, d));
+                tq[j] = (float)bt.q_t[j];
+                d += dstep;
+                r += rstep;
+                if (r >= KM) { r -= KM; d++; }
+            }
     }
     for (int j = tid; j < N; j += nt) bnd_l[j] = bnd_g[j];
     for (int j = tid; j < tri; j += nt) { vid_l[j] = -1; dur_l[j] = 0.0; ent_of[j] = -1; }
@@ -976,7 +1013,7 @@ __global__ __launch_bounds__(512) void k_fbb_step_diag32(segk_corpus c, segk_fbg
     const int n_pad = (n_ent + 7) & ~7;
     for (int j = tid; j < n_pad * D; j += nt) {
         const int i = j / D, d = j - i * D;
-        xs[d * RC + i] = i < n_ent ? (float)X[(int64_t)ent_id[i] * c.ldx + d] : 0.f;
+        xs[d * RC + i] = i < n_ent ? (float)((double)X[(int64_t)ent_id[i] * c.ldx + d] - fbb_centre(bt, d)) : 0.f;
     }
     for (int i = tid; i < n_pad; i += nt) lpr[i] = i < n_ent ? bt.prior_rows[ent_id[i]] : 0.0;
     const double zc_empty = f.lms * fb_log_fast(A.prior_alpha / (double)KM);
@@ -1840,17 +1877,20 @@ __global__ void k_fbb_apply_remap(segk_fbgmm f, segk_fbatch bt, int64_t n_emb, c
 
 // ---------------------------------------------------------------------------------------
 // fp32 matrix-core span score of fixed-variance components (the MFMA kernel of segk_score_f32.hip in
-// log-sum-exp mode): operands.
-//   Y[row] = [x_0^2, x_0, x_1^2, x_1, ...]                                    (once per corpus)
-//   tile row of slot k (count > 0):  [-pp_kd/2, pp_kd*mu_kd]_d * log2(e),
-//       constant (zconst_k - sum_d pp_kd mu_kd^2 / 2) * log2(e)
-//   pseudo-component K_max = all empty slots: [-p0_d/2, p0_d*mu0_d]_d * log2(e), constant
-//       (lms*log(alpha/K_max) + log(#empty) + kconst[K_max] - sum_d p0_d mu0_d^2 / 2) * log2(e)
+// log-sum-exp mode): operands, in coordinates centred on c = segk_fbatch.centre (x~ = x - c, mu~ = mu - c; c = 0 when NULL).
+//   Y[row] = [x~_0^2, x~_0, x~_1^2, x~_1, ...]                                (once per corpus)
+//   tile row of slot k (count > 0):  [-pp_kd/2, pp_kd*mu~_kd]_d * log2(e),
+//       constant (zconst_k - sum_d pp_kd mu~_kd^2 / 2) * log2(e)
+//   pseudo-component K_max = all empty slots: [-p0_d/2, p0_d*mu~0_d]_d * log2(e), constant
+//       (lms*log(alpha/K_max) + log(#empty) + kconst[K_max] - sum_d p0_d mu~0_d^2 / 2) * log2(e)
 //   so that acc_k = z_k * log2(e) and sum_k 2^acc_k = sum over ALL K_max slots of exp(z).
+// The centring is exact in real arithmetic (-q/2 (x - mu)^2 is invariant under the shift); it keeps the three terms of the
+// expanded quadratic, each of size q |x|^2, as small as the data's spread instead of its distance from the origin -- without
+// it a corpus offset of 1 already costs the float32 operands and constants more than the 1e-4 contract.
 // Tile image layout: segk_internal.h (32 slots per tile, dims 4g + 2(lane>>5) + {0,1}).
 // ---------------------------------------------------------------------------------------
 template <typename XT>
-__global__ void k_fbb_make_y(segk_corpus c, float *y, int64_t ldy)
+__global__ void k_fbb_make_y(segk_corpus c, float *y, int64_t ldy, const double *centre)
 {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= c.n_emb * ldy) return;
@@ -1858,7 +1898,7 @@ __global__ void k_fbb_make_y(segk_corpus c, float *y, int64_t ldy)
     const int j = (int)(idx - row * ldy), d = j >> 1;
     float v = 0.f;
     if (d < c.D) {
-        const float x = (float)((const XT *)c.X)[row * c.ldx + d];
+        const float x = (float)((double)((const XT *)c.X)[row * c.ldx + d] - (centre ? centre[d] : 0.0));
         v = (j & 1) ? x : x * x;
     }
     y[idx] = v;
@@ -1877,11 +1917,14 @@ __global__ void k_fbb_tiles32(segk_fbgmm f, segk_fbatch bt, int D, double prior_
         double s = 0.0;
         if (k < KM && bt.cnt[k] > 0.0)
             for (int d = sub; d < D; d += 8) {
-                const double m = bt.mean_t[(int64_t)d * KM + k];
+                const double m = bt.mean_t[(int64_t)d * KM + k] - fbb_centre(bt, d);
                 s += bt.q_t[(int64_t)d * KM + k] * m * m;
             }
         else if (k == KM)
-            for (int d = sub; d < D; d += 8) s += f.prior_c[d] * f.prior_b[d] * f.prior_b[d];
+            for (int d = sub; d < D; d += 8) {
+                const double m = f.prior_b[d] - fbb_centre(bt, d);
+                s += f.prior_c[d] * m * m;
+            }
         s += __shfl_xor(s, 1);
         s += __shfl_xor(s, 2);
         s += __shfl_xor(s, 4);
@@ -1908,9 +1951,9 @@ __global__ void k_fbb_tiles32(segk_fbgmm f, segk_fbatch bt, int D, double prior_
             if (d < D) {
                 if (k < KM && bt.cnt[k] > 0.0) {
                     const double q = bt.q_t[(int64_t)d * KM + k];
-                    v = (float)(((j & 1) ? q * bt.mean_t[(int64_t)d * KM + k] : -0.5 * q) * LOG2E);
+                    v = (float)(((j & 1) ? q * (bt.mean_t[(int64_t)d * KM + k] - fbb_centre(bt, d)) : -0.5 * q) * LOG2E);
                 } else if (k == KM) {
-                    v = (float)(((j & 1) ? f.prior_c[d] * f.prior_b[d] : -0.5 * f.prior_c[d]) * LOG2E);
+                    v = (float)(((j & 1) ? f.prior_c[d] * (f.prior_b[d] - fbb_centre(bt, d)) : -0.5 * f.prior_c[d]) * LOG2E);
                 }
             }
         } else if (idx < G * 128 + 32) {
@@ -1973,14 +2016,15 @@ __global__ void k_fbb_rows16(segk_fbgmm f, segk_fbatch bt, int D, double prior_a
     for (int d = lane; d < D; d += 64) {
         double t0 = 0.0, t1 = 0.0;
         if (occupied) {
-            const double q = bt.q_t[(int64_t)d * KM + k], m = bt.mean_t[(int64_t)d * KM + k];
+            const double q = bt.q_t[(int64_t)d * KM + k], m = bt.mean_t[(int64_t)d * KM + k] - fbb_centre(bt, d);
             t0 = -0.5 * q * LOG2E;
             t1 = q * m * LOG2E;
             s += q * m * m;
         } else if (k == KM) {
+            const double m = f.prior_b[d] - fbb_centre(bt, d);
             t0 = -0.5 * f.prior_c[d] * LOG2E;
-            t1 = f.prior_c[d] * f.prior_b[d] * LOG2E;
-            s += f.prior_c[d] * f.prior_b[d] * f.prior_b[d];
+            t1 = f.prior_c[d] * m * LOG2E;
+            s += f.prior_c[d] * m * m;
         }
         const float r0 = (float)t0, r1 = (float)t1;
         bt.rows32[(int64_t)col * D2 + 2 * d] = r0;
@@ -2143,7 +2187,7 @@ int32_t segk_fbb_make_y(segk_ctx *ctx, const segk_corpus *c, const segk_fbatch *
     SEGK_REQUIRE(c && bt && bt->y && bt->ldy >= 2 * c->D && (bt->ldy & 3) == 0, "y buffer / ldy");
     const int64_t tot = c->n_emb * bt->ldy;
     DISPATCH_XT(c, hipLaunchKernelGGL(k_fbb_make_y<XT>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                                       *c, bt->y, bt->ldy););
+                                       *c, bt->y, bt->ldy, bt->centre););
     SEGK_LAUNCH_CHECK();
     if (bt->y16) {
         SEGK_REQUIRE(2 * c->D <= 208, "the fp16x2 span score supports 2D <= 208");

@@ -998,7 +998,20 @@ class FbgmmBatchSweeper(object):
         # instead of in the score and assignment kernels of every Gibbs step (same values)
         self.prior_rows = torch.zeros(c.n_emb, dtype=f64, device=dev)
         check(df._L.segk_fbb_prior_rows(df._ctx, df._cp(), C.byref(self.f), self.prior_rows.data_ptr(), _abi.stream()))
+        # the reduced-precision kernels work in coordinates centred on the corpus column mean (segk_fbatch.centre): the
+        # rounding of their float32 / fp16x2 operands then follows the data's spread, not its distance from the origin.  One
+        # pass over X per sampler, in fp64 and in row order on the host, so every rank (each holds the whole corpus) gets the
+        # same bits
+        self.centre = None
+        if score_precision != "f64":
+            xh = c.X.cpu().numpy()
+            mean = np.add.reduce(xh, axis=0, dtype=np.float64) / max(c.n_emb, 1)
+            self.centre = torch.from_numpy(np.ascontiguousarray(mean[:D])).to(dev)
+        # diagonal float32 mode: segk_fbb_prepare writes the float32 slot tables the score / step kernels stage
+        self.tab32 = torch.zeros(2 * D * K, dtype=torch.float32, device=dev) if self.score_diag32 else None
         self.bt = _abi.FbatchDev(
+            centre=self.centre.data_ptr() if self.centre is not None else None,
+            tab32=self.tab32.data_ptr() if self.tab32 is not None else None,
             prior_rows=self.prior_rows.data_ptr(),
             y16=self.y16.data_ptr() if self.y16 is not None else None,
             tiles16=self.tiles16.data_ptr() if self.tiles16 is not None else None,

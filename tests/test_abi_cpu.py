@@ -72,6 +72,9 @@ def test_struct_layout_matches_header(built):
     # field order/size of the ctypes mirrors (LP64): segk_corpus 16 fields, segk_kmeans 10
     assert ctypes.sizeof(built.Corpus) == 8 + 8 + 4 + 4 + 8 * 4 + 8 * 3 + 4 + 4 + 8 + 4 + 4 + 8 + 8      # + band_ids, band_dur
     assert ctypes.sizeof(built.KMeansDev) == 8 * 6 + 8 + 8 + 8 + 8     # K_max padded to 8
+    # segk_fbatch: 4 int32, 12 pointers, seed, y, ldy, tiles32, the four fp16x2 buffers, prior_rows, centre, tab32
+    assert ctypes.sizeof(built.FbatchDev) == 4 * 4 + 8 * 12 + 8 * 4 + 8 * 4 + 8 + 8 + 8
+    assert [f[0] for f in built.FbatchDev._fields_[-3:]] == ["prior_rows", "centre", "tab32"]
 
 
 def test_host_shims_match_oracle(built, golden):

@@ -10,6 +10,7 @@ import pytest
 
 from oracle import np_fbgmm_batch as nb
 from oracle import np_oracle as no
+from tests import affine
 from tests.golden import cases
 
 pytestmark = pytest.mark.gpu
@@ -25,13 +26,20 @@ def gpu():
     return torch
 
 
-def _pair(kind, n_utt, D, K, cseed, nmax, B, S, seed=5, dtype="float32", score_precision="f64", n_landmarks=0, **kw):
+def _pair(kind, n_utt, D, K, cseed, nmax, B, S, seed=5, dtype="float32", score_precision="f64", n_landmarks=0,
+          transform=None, **kw):
     """(oracle segmenter + batch state, product segmenter) from identical initial states.  n_landmarks > 0: every utterance
-    that long (default: ragged, 3 to 9 landmarks)."""
+    that long (default: ragged, 3 to 9 landmarks).  transform: a name of tests/affine.py -- the corpus and the prior moved
+    to new coordinates together."""
     from segmentalist_amd import bigram_acoustic_wordseg as baw, fbgmm, unigram_acoustic_wordseg as uaw
     from segmentalist_amd.gaussian_components_fixedvar import FixedVarPrior
     from segmentalist_amd.niw import NIW
     corpus = cases.chain_corpus(n_utt, D, K, cseed, n_landmarks == 0, n_landmarks, nmax, dtype)
+    fixed, niw = cases.fixed_prior_params(D), cases.diag_prior_params(D)
+    if transform is not None:
+        s, c = affine.params(transform, D)
+        corpus = affine.corpus(corpus, s, c)
+        fixed, niw = affine.fixed_prior(*fixed, s, c), affine.niw_prior(*niw, s, c)
     args = dict(n_slices_min=0, n_slices_max=nmax, p_boundary_init=0.5, beta_sent_boundary=-1, lms=1.0, wip=0.0,
                 init_am_assignments="rand", time_power_term=1.0)
     args.update(kw)
@@ -42,19 +50,18 @@ def _pair(kind, n_utt, D, K, cseed, nmax, B, S, seed=5, dtype="float32", score_p
         np.random.seed(seed)
         if kind == "bigram":
             if side == "oracle":
-                seg = no.BigramAcousticWordseg(K, no.FixedVarPrior(*cases.fixed_prior_params(D)), dict(cases.BIGRAM_LM),
+                seg = no.BigramAcousticWordseg(K, no.FixedVarPrior(*fixed), dict(cases.BIGRAM_LM),
                                                *corpus, covariance_type="fixed", fb_type="unigram", **args)
             else:
-                seg = baw.BigramAcousticWordseg(K, FixedVarPrior(*cases.fixed_prior_params(D)), dict(cases.BIGRAM_LM),
+                seg = baw.BigramAcousticWordseg(K, FixedVarPrior(*fixed), dict(cases.BIGRAM_LM),
                                                 *corpus, covariance_type="fixed", fb_type="unigram", **args, **bargs)
         else:
             if side == "oracle":
-                prior = (no.FixedVarPrior(*cases.fixed_prior_params(D)) if kind == "fixed"
-                         else no.NIW(*cases.diag_prior_params(D)))
+                prior = no.FixedVarPrior(*fixed) if kind == "fixed" else no.NIW(*niw)
                 seg = no.UnigramAcousticWordseg(no.FBGMM, 1.0, K, prior, *corpus, covariance_type=kind,
                                                 fb_type="standard", **args)
             else:
-                prior = FixedVarPrior(*cases.fixed_prior_params(D)) if kind == "fixed" else NIW(*cases.diag_prior_params(D))
+                prior = FixedVarPrior(*fixed) if kind == "fixed" else NIW(*niw)
                 seg = uaw.UnigramAcousticWordseg(fbgmm.FBGMM, 1.0, K, prior, *corpus, covariance_type=kind,
                                                  fb_type="standard", **args, **bargs)
         out.append(seg)
@@ -78,7 +85,19 @@ CASES = [
 @pytest.mark.parametrize("kind,n_utt,D,K,cseed,nmax,B,S,kw", CASES,
                          ids=["%s_u%d_D%d_K%d_B%d_S%d" % (c[0], c[1], c[2], c[3], c[6], c[7]) for c in CASES])
 def test_batch_sweeps_match_specification(gpu, kind, n_utt, D, K, cseed, nmax, B, S, kw):
-    ref, spec, seg = _pair(kind, n_utt, D, K, cseed, nmax, B, S, **kw)
+    _sweeps_match_specification(gpu, kind, n_utt, D, K, cseed, nmax, B, S, kw)
+
+
+@pytest.mark.parametrize("transform", [n for n in affine.NAMES if n != "identity"])
+@pytest.mark.parametrize("kind", ["fixed", "diag", "bigram"])
+def test_batch_sweeps_match_specification_on_transformed_corpora(gpu, kind, transform):
+    """score_precision="f64" on corpora moved away from the origin and rescaled (tests/affine.py), configs[1] shape: still
+    the specification's chain bit for bit."""
+    _sweeps_match_specification(gpu, kind, 25, 39, 100, 86, 5, 3, 4, {}, transform)
+
+
+def _sweeps_match_specification(gpu, kind, n_utt, D, K, cseed, nmax, B, S, kw, transform=None):
+    ref, spec, seg = _pair(kind, n_utt, D, K, cseed, nmax, B, S, transform=transform, **kw)
     for sw in range(3):
         lp = spec.sweep(sw)
         seg.batch_sweep_async()
@@ -211,8 +230,21 @@ def test_sequential_after_batch_continues_from_the_materialised_state(gpu):
 def test_matrix_core_span_scores_within_tolerance(gpu, kind, n_utt, D, K, nmax, prec):
     """score_precision="f32": the MFMA log-sum-exp kernel against the specification's log_marg_i on the
     same state -- 1e-4 relative is the contract of the path (BASELINE north_star); measured ~1e-6."""
+    _matrix_core_span_scores(gpu, kind, n_utt, D, K, nmax, prec)
+
+
+@pytest.mark.parametrize("transform", affine.NAMES)
+@pytest.mark.parametrize("prec", ["f32", "f16"])
+@pytest.mark.parametrize("kind,n_utt,D,K", [("fixed", 30, 39, 100), ("fixed", 30, 13, 100), ("bigram", 30, 39, 100)])
+def test_matrix_core_span_scores_on_transformed_corpora(gpu, kind, n_utt, D, K, prec, transform):
+    """The same contract on corpora moved away from the origin and rescaled (tests/affine.py): the expanded quadratic of the
+    operands, [x^2, x] . [-q/2, q*mu], cancels terms that grow with |x|^2 -- D = 13: 2D = 26, the zero tail of the rows."""
+    _matrix_core_span_scores(gpu, kind, n_utt, D, K, 6, prec, transform)
+
+
+def _matrix_core_span_scores(gpu, kind, n_utt, D, K, nmax, prec, transform=None):
     from segmentalist_amd._abi import check, ptr
-    ref, spec, seg = _pair(kind, n_utt, D, K, 123, nmax, 3, 2, score_precision=prec)
+    ref, spec, seg = _pair(kind, n_utt, D, K, 123, nmax, 3, 2, score_precision=prec, transform=transform)
     sw = seg._get_sweeper()
     assert sw.score_f32 and sw.score_f16 == (prec == "f16")
     sw.enter(seg._dev_bounds)
@@ -233,8 +265,8 @@ def test_matrix_core_span_scores_within_tolerance(gpu, kind, n_utt, D, K, nmax, 
                 mags.append(abs(want))
                 worst_abs = max(worst_abs, abs(score[row] - want))
                 worst = max(worst, abs(score[row] - want) / max(abs(want), 1.0))
-    print("%s span score: worst abs err %.3g, worst err relative to max(|log_marg_i|, 1) %.3g, median |log_marg| %.3g"
-          % (prec, worst_abs, worst, float(np.median(mags))))
+    print("%s %s D=%d%s span score: worst abs err %.3g, worst err relative to max(|log_marg_i|, 1) %.3g, median |log_marg| %.3g"
+          % (kind, prec, D, "" if transform is None else " " + transform, worst_abs, worst, float(np.median(mags))))
     # 1e-4 relative is the contract of the path; a span whose log-marginal is within 1 of zero is held to the same
     # absolute error as a span of magnitude 1 (the same floor as the diagonal and the token-likelihood tests)
     assert worst < 1e-4, (worst, worst_abs)
@@ -270,6 +302,18 @@ def test_matrix_core_mode_samples_a_valid_chain(gpu, kind, prec):
 @pytest.mark.parametrize("n_utt,D,K,nmax,scale", [(40, 12, 30, 6, 1.0), (25, 39, 100, 6, 1.0), (30, 8, 12, 5, 1.0)],
                          ids=["D12_K30_with_near_zero_values", "c2_shape_D39_K100", "D8_K12"])
 def test_diag_float32_span_scores_within_the_contract(gpu, n_utt, D, K, nmax, scale):
+    _diag_float32_span_scores(gpu, n_utt, D, K, nmax, scale)
+
+
+@pytest.mark.parametrize("transform", affine.NAMES)
+@pytest.mark.parametrize("n_utt,D,K", [(25, 39, 100), (30, 13, 100)], ids=["c2_shape_D39_K100", "D13_K100"])
+def test_diag_float32_span_scores_on_transformed_corpora(gpu, n_utt, D, K, transform):
+    """k_fbb_score_diag32 on corpora moved away from the origin and rescaled (tests/affine.py): m - x in float32 from a mean
+    rounded to float32 loses digits that grow with the offset."""
+    _diag_float32_span_scores(gpu, n_utt, D, K, 6, 1.0, transform)
+
+
+def _diag_float32_span_scores(gpu, n_utt, D, K, nmax, scale, transform=None):
     """score_precision="f32" with diagonal components (k_fbb_score_diag32: Student-t terms in float32 with v_log_f32)
     against the specification's log_marg_i (fbgmm.py:256-285 over gaussian_components_diag.py:237-259) on the same
     state.  The contract of the path is 1e-4 RELATIVE to |log_marg_i|; a span whose log-marginal is within 1 of zero
@@ -281,14 +325,18 @@ def test_diag_float32_span_scores_within_the_contract(gpu, n_utt, D, K, nmax, sc
     corpus = cases.chain_corpus(n_utt, D, K, 321, True, 0, nmax, "float32")
     if scale != 1.0:
         corpus = ({k: (v * scale).astype(np.float32) for k, v in corpus[0].items()},) + tuple(corpus[1:])
+    niw = cases.diag_prior_params(D)
+    if transform is not None:
+        s, c = affine.params(transform, D)
+        corpus, niw = affine.corpus(corpus, s, c), affine.niw_prior(*niw, s, c)
     args = dict(n_slices_min=0, n_slices_max=nmax, p_boundary_init=0.5, beta_sent_boundary=-1, lms=1.0, wip=0.0,
                 init_am_assignments="rand", time_power_term=1.0)
     random.seed(5); np.random.seed(5)
-    ref = no.UnigramAcousticWordseg(no.FBGMM, 1.0, K, no.NIW(*cases.diag_prior_params(D)), *corpus, covariance_type="diag",
+    ref = no.UnigramAcousticWordseg(no.FBGMM, 1.0, K, no.NIW(*niw), *corpus, covariance_type="diag",
                                     fb_type="standard", **args)
     spec = nb.FbgmmBatch(ref, n_gibbs_blocks=3, n_stat_blocks=2, seed=11)
     random.seed(5); np.random.seed(5)
-    seg = uaw.UnigramAcousticWordseg(fbgmm.FBGMM, 1.0, K, NIW(*cases.diag_prior_params(D)), *corpus, covariance_type="diag",
+    seg = uaw.UnigramAcousticWordseg(fbgmm.FBGMM, 1.0, K, NIW(*niw), *corpus, covariance_type="diag",
                                      fb_type="standard", sync="batch", n_gibbs_blocks=3, n_stat_blocks=2, batch_seed=11,
                                      score_precision="f32", **args)
     sw = seg._get_sweeper()
@@ -308,8 +356,9 @@ def test_diag_float32_span_scores_within_the_contract(gpu, n_utt, D, K, nmax, sc
                 mags.append(abs(want))
                 n_small += abs(want) < 1.0
                 worst = max(worst, abs(score[row] - want) / max(abs(want), 1.0))
-    print("diag f32 span score: worst error relative to max(|log_marg_i|, 1) = %.3g; %d of %d spans with |log_marg_i| < 1, "
-          "median |log_marg_i| %.3g" % (worst, n_small, len(mags), float(np.median(mags))))
+    print("diag f32 D=%d%s span score: worst error relative to max(|log_marg_i|, 1) = %.3g; %d of %d spans with |log_marg_i| < 1, "
+          "median |log_marg_i| %.3g" % (D, "" if transform is None else " " + transform, worst, n_small, len(mags),
+                                        float(np.median(mags))))
     assert worst < 1e-4, worst
     if D == 12:
         assert n_small >= len(mags) // 20, (n_small, len(mags))

@@ -11,6 +11,7 @@ import random
 import numpy as np
 import pytest
 
+from tests import affine
 from tests.golden import cases
 
 pytestmark = pytest.mark.gpu
@@ -154,6 +155,60 @@ def test_a1_hinted_path_vs_oracle_random(gpu, monkeypatch, D, K, n):
     k, s = run(inv[want_k], ids=ids, remap=torch.from_numpy(perm).cuda())
     live = ids[ids >= 0]
     assert np.array_equal(k[live], want_k[live]) and np.array_equal(s[live], want_s[live].astype(np.float64))
+
+
+@pytest.mark.parametrize("transform", affine.NAMES)
+def test_hinted_path_and_batch_sweep_on_transformed_corpora(gpu, monkeypatch, transform):
+    """Rows and means moved away from the origin and rescaled (tests/affine.py) at the configs[1] shape: the hinted path
+    (SEGK_SCORE_HINT=1; right and wrong hints) gives cand_k / cand_s of the C oracle bit for bit, and batch sweeps give the
+    specification's state bit for bit.  An offset can only cost the certificate rows (they go to the exact scan), never
+    correctness: the certified fraction is printed, not asserted."""
+    import ctypes as C
+    import torch
+    from oracle import c_oracle as co
+    from oracle import np_oracle as no
+    from segmentalist_amd import _abi, kmeans_acoustic_wordseg as kaw
+    monkeypatch.setenv("SEGK_SCORE_HINT", "1")
+    D, K, n = 39, 100, 3000
+    s_, c_ = affine.params(transform, D)
+    rs = np.random.RandomState(4321)
+    mu = rs.randn(K // 2, D)
+    X = mu[rs.randint(0, K // 2, n)] + 0.3 * rs.randn(n, D)
+    X /= np.linalg.norm(X, axis=1, keepdims=True)
+    means = mu[rs.randint(0, K // 2, K)] + 0.05 * rs.randn(K, D)
+    means /= np.linalg.norm(means, axis=1, keepdims=True)
+    X, means = affine.rows(X.astype(np.float32), s_, c_), affine.rows(means.astype(np.float32), s_, c_)
+    c = _components(X, means)
+    _abi.check(_abi.lib().segk_kmeans_mark_duplicates(c.dev._ctx, c.dev._cp(), C.byref(c.dev.m), None, _abi.stream()))
+    want_s, want_k = co.kmeans_max_argmax(means, X)
+    ident = torch.arange(K, dtype=torch.int32, device="cuda")
+    certified = []
+    for hints in (want_k, rs.randint(0, K, n)):
+        c.dev.cand_k.copy_(torch.from_numpy(hints.astype(np.int32)).cuda())
+        c.dev.cand_s.fill_(float("nan"))
+        c.dev.score_rows(hint_remap=ident)
+        torch.cuda.synchronize()
+        launched, seen, permille = C.c_uint32(), C.c_uint32(), C.c_int32()
+        _abi.check(_abi.lib().segk_kmeans_hint_feedback(c.dev._ctx, C.byref(launched), C.byref(seen), C.byref(permille)))
+        certified.append(1.0 - permille.value / 1000.0 if seen.value == launched.value > 0 else float("nan"))
+        assert np.array_equal(c.dev.cand_k.cpu().numpy(), want_k)
+        assert np.array_equal(c.dev.cand_s.cpu().numpy(), want_s.astype(np.float64))
+    print("k-means %s: certified fraction of rows %.3f with right hints, %.3f with random hints" % (transform, *certified))
+    # batch sweeps against the specification
+    monkeypatch.delenv("SEGK_SCORE_HINT")
+    corpus = affine.corpus(cases.chain_corpus(40, D, K, 1040, True, 0, 6, "float32"), s_, c_)
+    random.seed(5); np.random.seed(5)
+    ref = no.SegmentalKMeansWordseg(K, *corpus, n_slices_max=6, init_am_assignments="spread")
+    random.seed(5); np.random.seed(5)
+    seg = kaw.SegmentalKMeansWordseg(K, *corpus, n_slices_max=6, init_am_assignments="spread", sync="batch", n_stat_blocks=8)
+    cr, cd = ref.acoustic_model.components, seg.acoustic_model.components
+    for it in range(2):
+        want = no.kmeans_batch_sweep(ref, n_blocks=8)
+        rec = seg.segment(1)
+        assert np.array_equal(seg.utterances.boundaries, ref.utterances.boundaries), it
+        assert np.array_equal(cd.assignments, cr.assignments), it
+        assert np.array_equal(cd.means, cr.means), it
+        assert rec["sum_neg_len_sqrd_norm"][0] == want
 
 
 @pytest.mark.parametrize("K,spread", [(40, 3e-4), (200, 1e-7), (1000, 2e-4)], ids=["tens_of_candidates", "band_overflow", "four_ranges"])

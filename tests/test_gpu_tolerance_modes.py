@@ -22,6 +22,7 @@ import pytest
 
 from oracle import np_fbgmm_batch as nb
 from oracle import np_oracle as no
+from tests import affine
 
 pytestmark = pytest.mark.gpu
 
@@ -38,7 +39,8 @@ def gpu():
     return torch
 
 
-def _pair(kind, n_utt, D, K, prec, B=3, S=2, seed=5):
+def _pair(kind, n_utt, D, K, prec, B=3, S=2, seed=5, transform=None):
+    """transform: a name of tests/affine.py -- the corpus and the prior moved to new coordinates together."""
     from segmentalist_amd import bigram_acoustic_wordseg as baw, fbgmm, unigram_acoustic_wordseg as uaw
     from segmentalist_amd.gaussian_components_fixedvar import FixedVarPrior
     from segmentalist_amd.niw import NIW
@@ -50,6 +52,10 @@ def _pair(kind, n_utt, D, K, prec, B=3, S=2, seed=5):
     fixed = (0.002 * np.ones(D), np.zeros(D), 0.002 / 0.05 * np.ones(D))
     niw = (np.zeros(D), 0.05, D + 3, 0.002 * (D + 3) * np.ones(D))
     lm = {"type": "smooth", "intrp_lambda": 0.1, "a": 0.5, "b": 0.5}
+    if transform is not None:
+        s, c = affine.params(transform, D)
+        corpus = affine.corpus(corpus, s, c)
+        fixed, niw = affine.fixed_prior(*fixed, s, c), affine.niw_prior(*niw, s, c)
     out = []
     for side in ("oracle", "product"):
         random.seed(seed)
@@ -132,13 +138,41 @@ CASES = [
                          ids=["%s_%s_D%d_K%d%s" % (c[0], c[1], c[3], c[4], "" if c[5] is None else "_fused" if c[5] == "fused" else "_blockwide")
                               for c in CASES])
 def test_token_likelihoods_and_forward_filter_within_the_contract(gpu, monkeypatch, kind, prec, n_utt, D, K, wave):
+    _token_likelihoods_and_forward_filter(gpu, monkeypatch, kind, prec, n_utt, D, K, wave)
+
+
+# the same measurements on corpora moved away from the origin and rescaled (tests/affine.py): the configs[1] shape (D = 39 is
+# odd: 2D = 78, ldy = 80, the zero tail of the operand rows), the three forms of the fp16x2 token likelihoods (block-wide, one
+# wave per utterance with a language model, the bigram model at the configs[4] shape).  (A small odd D -- 13, 21 -- has span
+# scores of both signs: some alphas pass within 1 of zero, where max(|alpha|, 1) no longer scales with the sum of the span
+# errors times their durations, and the comparison fails at the identity transform in every mode.  Its span scores are
+# measured in test_gpu_fbgmm_batch.py.)
+AFFINE_CASES = [
+    ("diag", "f32", 30, 39, 100, None),
+    ("diag", "f32", 30, 39, 100, "fused"),
+    ("fixed", "f32", 30, 39, 100, None),
+    ("fixed", "f16", 30, 39, 100, None),
+    ("bigram", "f16", 30, 39, 100, None),
+    ("bigram", "f16", 25, 100, 1000, None),
+]
+
+
+@pytest.mark.parametrize("transform", affine.NAMES)
+@pytest.mark.parametrize("kind,prec,n_utt,D,K,wave", AFFINE_CASES,
+                         ids=["%s_%s_D%d_K%d%s" % (c[0], c[1], c[3], c[4], "" if c[5] is None else "_fused") for c in AFFINE_CASES])
+def test_token_likelihoods_and_forward_filter_on_transformed_corpora(gpu, monkeypatch, kind, prec, n_utt, D, K, wave,
+                                                                     transform):
+    _token_likelihoods_and_forward_filter(gpu, monkeypatch, kind, prec, n_utt, D, K, wave, transform)
+
+
+def _token_likelihoods_and_forward_filter(gpu, monkeypatch, kind, prec, n_utt, D, K, wave, transform=None):
     torch = gpu
     from segmentalist_amd import _abi
     from segmentalist_amd._abi import check, ptr
     fused = wave == "fused"
     if wave is not None and not fused:
         monkeypatch.setenv("SEGK_FBB_ASSIGN_WAVE", wave)
-    ref, spec, seg = _pair(kind, n_utt, D, K, prec)
+    ref, spec, seg = _pair(kind, n_utt, D, K, prec, transform=transform)
     sw = seg._get_sweeper()
     assert sw.bt.fast_dp == 1
     sw.enter(seg._dev_bounds)
@@ -157,6 +191,7 @@ def test_token_likelihoods_and_forward_filter_within_the_contract(gpu, monkeypat
     score = seg._df.score.cpu().numpy()
     new_tok, n_new = seg._df.new_tok.cpu().numpy(), seg._df.n_new.cpu().numpy()
     worst_ll = worst_a_own = worst_a_spec = worst_draw = 0.0
+    at_a_spec = (0.0, 0.0)             # (|got - want|, |want|) where worst_a_spec was found
     n_tok = n_occ = n_drawn_empty = 0
     slots = sw.slot.cpu().numpy()
     for b in range(sw.B):
@@ -186,7 +221,10 @@ def test_token_likelihoods_and_forward_filter_within_the_contract(gpu, monkeypat
                 got = alpha[i, :N]
                 assert np.all(np.isfinite(got)), (i, got)
                 worst_a_own = max(worst_a_own, float(np.max(np.abs(got - a_own) / np.maximum(np.abs(a_own), 1.0))))
-                worst_a_spec = max(worst_a_spec, float(np.max(np.abs(got - a_spec) / np.maximum(np.abs(a_spec), 1.0))))
+                rel = np.abs(got - a_spec) / np.maximum(np.abs(a_spec), 1.0)
+                if float(np.max(rel)) > worst_a_spec:
+                    worst_a_spec = float(np.max(rel))
+                    at_a_spec = (float(np.abs(got - a_spec)[np.argmax(rel)]), float(np.abs(a_spec)[np.argmax(rel)]))
                 # --- token log-likelihoods, every slot
                 assert n_new[i] > 0
                 for t in range(n_new[i]):
@@ -213,9 +251,10 @@ def test_token_likelihoods_and_forward_filter_within_the_contract(gpu, monkeypat
                         worst_draw = max(worst_draw, below - uu, uu - cum[k])
                         n_drawn_empty += int(not d["active"][k])
                         j_prev = k if kind == "bigram" else None
-    print("%s %s D=%d K=%d: token log-likelihoods worst %.3g (over %d tokens x %d slots, %.0f occupied per token); "
-          "alphas worst %.3g against fp64 on the device's scores, %.3g against the specification"
-          % (kind, prec, D, K, worst_ll, n_tok, K, n_occ / max(n_tok, 1), worst_a_own, worst_a_spec))
+    print("%s %s D=%d K=%d%s%s: token log-likelihoods worst %.3g (over %d tokens x %d slots, %.0f occupied per token); "
+          "alphas worst %.3g against fp64 on the device's scores, %.3g against the specification (%.3g at |alpha| %.3g)"
+          % (kind, prec, D, K, " fused" if fused else "", "" if transform is None else " " + transform, worst_ll, n_tok, K,
+             n_occ / max(n_tok, 1), worst_a_own, worst_a_spec, *at_a_spec))
     if kind == "bigram" or fused:
         print("draws: worst distance of a token's uniform from its slot's interval %.3g; %d of %d tokens drew an empty slot"
               % (worst_draw, n_drawn_empty, n_tok))
@@ -227,13 +266,22 @@ def test_token_likelihoods_and_forward_filter_within_the_contract(gpu, monkeypat
 
 
 def test_fused_gibbs_step_gives_the_span_scores_and_boundaries_of_the_three_launches(gpu):
+    _fused_against_three_launches(None)
+
+
+@pytest.mark.parametrize("transform", ["shift16", "mfcc"])
+def test_fused_gibbs_step_gives_the_span_scores_and_boundaries_of_the_three_launches_on_transformed_corpora(gpu, transform):
+    _fused_against_three_launches(transform)
+
+
+def _fused_against_three_launches(transform):
     """segk_fbb_step_diag32 against segk_fbb_score_diag32 + segk_fbb_segment + segk_fbb_assign_diag32 from identical states,
     every block of a sweep: the span scores and the boundaries bit for bit (the same arithmetic and the same uniforms); the
     slots agree wherever the token's uniform does not fall within the last bits of a cumulative boundary (the token
     likelihoods of the two forms differ in their last float32 bits)."""
     out = []
     for fused in (False, True):
-        ref, spec, seg = _pair("diag", 64, 39, 100, "f32")
+        ref, spec, seg = _pair("diag", 64, 39, 100, "f32", transform=transform)
         sw = seg._get_sweeper()
         sw.enter(seg._dev_bounds)
         for b in range(sw.B):
