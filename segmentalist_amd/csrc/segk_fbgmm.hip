@@ -30,7 +30,12 @@ struct FbLocal {
     const double *ktab;    // fb_diag_const(count), count < ktab_n (diagonal components), or NULL
     int64_t ktab_n;
 };
-#define FB_RELOG 16
+// Pairs the log holds: one per component emptied within one utterance.  Only fb_del_item deletes, once per old segment with an
+// embedding (the assignment loop only adds): at most N <= N_max <= 64 (the launcher's limit on landmarks per utterance).
+#define FB_RELOG 64
+// Control words of the persistent chain (FbChainArgs.ctl): [0 .. 8) as segk_chain_barrier.h and below, the release words of
+// the barrier at 32 (1 + f), f < CH_FLAGS, then the log of the utterance that stopped the launch
+#define FB_CTL_LOG (32 * (1 + CH_FLAGS))
 
 // ---------------------------------------------------------------------------------------
 // derived statistics of component k (all threads of the block cooperate over D)
@@ -682,7 +687,7 @@ struct FbChainArgs {
     double *out_logprob;
     int32_t *status;
     int32_t *ctl;                   // [0] barrier counter, [2] utterances completed, [3] error, [4] relabels logged, [5] utterance of
-                                    // the relabels, [8 ..] the pairs, [32 (1 + f)] release words
+                                    // the relabels, [32 (1 + f)] release words, [FB_CTL_LOG ..] the pairs
     unsigned long long *stamp;      // development (make DEV=1, SEGK_CHAIN_STAMP=1): wall_clock64 of workgroup 0 at the phase boundaries
     const double *ktab;             // fb_diag_const by count (diagonal components), [ktab_n], or NULL
     int64_t ktab_n;
@@ -991,7 +996,7 @@ __global__ __launch_bounds__(512) void k_fb_chain(FbChainArgs A)
                 if (stop) {
                     A.ctl[4] = n_relog;
                     A.ctl[5] = u;
-                    for (int i = 0; i < 2 * FB_RELOG; i++) A.ctl[8 + i] = relog[i];
+                    for (int i = 0; i < 2 * n_relog; i++) A.ctl[FB_CTL_LOG + i] = relog[i];     // (the logged pairs only)
                 }
             }
         }
@@ -1061,11 +1066,17 @@ __global__ void k_fb_kconst_tab(segk_fbgmm f, int D, int64_t n, double *out)
     if (i < n) out[i] = fb_diag_const(f, D, (double)i);
 }
 
-// the rows of every utterance but `skip_lo .. skip_hi` relabelled from -> to (a component moved into an emptied slot)
-__global__ void k_fb_relabel(int32_t *assignments, int64_t n, int64_t skip_lo, int64_t skip_hi, int from, int to)
+// the rows of every utterance but `skip_lo .. skip_hi` relabelled through the logged pairs (from, to), in order (a component
+// moved into an emptied slot; the log is read where the chain left it)
+__global__ void k_fb_relabel(int32_t *assignments, int64_t n, int64_t skip_lo, int64_t skip_hi, const int32_t *relog, int n_relog)
 {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < n && (e < skip_lo || e >= skip_hi) && assignments[e] == from) assignments[e] = to;
+    if (e >= n || (e >= skip_lo && e < skip_hi)) return;
+    const int a0 = assignments[e];
+    int a = a0;
+    for (int i = 0; i < n_relog; i++)
+        if (a == relog[2 * i]) a = relog[2 * i + 1];
+    if (a != a0) assignments[e] = a;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1436,8 +1447,8 @@ int32_t segk_fbgmm_sequential_sweep(segk_ctx *ctx, const segk_corpus *c, segk_fb
     // component per segment as before; the same results)
     const size_t lds_terms = (size_t)((size_t)NM * KM) * sizeof(double) + (size_t)NM * sizeof(int32_t) + (((size_t)KM + 15) & ~(size_t)15) + 16;
     const bool terms = lds + lds_terms <= 150 * 1024 && segk_env_int("SEGK_FB_CHAIN_TERMS", 1) != 0;
-    // control words + the order, owned by the context
-    const size_t ctl_bytes = 32 * (1 + CH_FLAGS) * sizeof(int32_t), need = ctl_bytes + (size_t)n_order * sizeof(int32_t);
+    // control words, the relabel log + the order, owned by the context
+    const size_t ctl_bytes = (FB_CTL_LOG + 2 * FB_RELOG) * sizeof(int32_t), need = ctl_bytes + (size_t)n_order * sizeof(int32_t);
     if (ctx->fbchain_bytes < need) {
         if (ctx->fbchain_buf) (void)hipFree(ctx->fbchain_buf);
         ctx->fbchain_buf = nullptr;
@@ -1546,7 +1557,7 @@ int32_t segk_fbgmm_sequential_sweep(segk_ctx *ctx, const segk_corpus *c, segk_fb
         }
 #undef FB_CHAIN_LAUNCH
         SEGK_LAUNCH_CHECK();
-        int32_t ctl[8 + 2 * FB_RELOG];
+        int32_t ctl[8];
         SEGK_CHECK_HIP(hipMemcpyAsync(ctl, A.ctl, sizeof(ctl), hipMemcpyDeviceToHost, st));
         SEGK_CHECK_HIP(hipStreamSynchronize(st));
         if (ctl[3] != 0) {
@@ -1576,14 +1587,13 @@ int32_t segk_fbgmm_sequential_sweep(segk_ctx *ctx, const segk_corpus *c, segk_fb
         }
         q = ctl[2];
         if (ctl[4] > 0) {                 // components emptied during utterance ctl[5]: the other utterances' rows follow
+            // (an invariant: an utterance empties at most one component per old segment, FB_RELOG >= N_max)
             SEGK_REQUIRE(ctl[4] <= FB_RELOG, "FBGMM chain: more components emptied within one utterance than the log holds");
+            // (one launch reads the pairs where the chain logged them: reading them back first was one more synchronisation per
+            // emptied component, 1.7 % of fbgmm_c2_sequential)
             const int u = ctl[5];
-            for (int i = 0; i < ctl[4]; i++) {
-                const int from = ctl[8 + 2 * i], to = ctl[8 + 2 * i + 1];
-                if (from != to)
-                    hipLaunchKernelGGL(k_fb_relabel, dim3((unsigned)((c->n_emb + 255) / 256)), dim3(256), 0, st, f->assignments,
-                                       c->n_emb, (int64_t)rs[u], (int64_t)rs[u + 1], from, to);
-            }
+            hipLaunchKernelGGL(k_fb_relabel, dim3((unsigned)((c->n_emb + 255) / 256)), dim3(256), 0, st, f->assignments, c->n_emb,
+                               (int64_t)rs[u], (int64_t)rs[u + 1], (const int32_t *)(A.ctl + FB_CTL_LOG), (int)ctl[4]);
             SEGK_LAUNCH_CHECK();
         }
     }

@@ -96,9 +96,9 @@ def test_batch_sweeps_match_specification_on_transformed_corpora(gpu, kind, tran
     _sweeps_match_specification(gpu, kind, 25, 39, 100, 86, 5, 3, 4, {}, transform)
 
 
-def _sweeps_match_specification(gpu, kind, n_utt, D, K, cseed, nmax, B, S, kw, transform=None):
+def _sweeps_match_specification(gpu, kind, n_utt, D, K, cseed, nmax, B, S, kw, transform=None, sweeps=3):
     ref, spec, seg = _pair(kind, n_utt, D, K, cseed, nmax, B, S, transform=transform, **kw)
-    for sw in range(3):
+    for sw in range(sweeps):
         lp = spec.sweep(sw)
         seg.batch_sweep_async()
         gpu.cuda.synchronize()
