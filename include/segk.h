@@ -608,7 +608,8 @@ int32_t segk_fbb_collect(segk_ctx *ctx, const segk_corpus *c, const uint8_t *bou
  * (gaussian_components_diag.py:125).  SIDE EFFECT: bt->scal (the totals segk_fbb_prepare accumulates into) is left
  * zeroed, so that a segk_fbb_prepare enqueued next on the same stream need not clear it; the totals are therefore only
  * valid between a segk_fbb_prepare and the next segk_fbb_partials -- call segk_fbb_prepare before reading them (or before
- * segk_fbb_score / _assign / _token_scores) after any segk_fbb_partials.                                              */
+ * segk_fbb_score / _assign / _token_scores) after any segk_fbb_partials.  Any number of tokens per utterance (N_max > 64:
+ * the lists are walked 64 tokens at a time, in order).                                                                */
 int32_t segk_fbb_partials(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f,
                           const segk_fbatch *bt, int32_t s_lo, int32_t s_n, int32_t b,
                           const int32_t *new_tok, const int32_t *n_new, void *stream);
@@ -649,7 +650,15 @@ int32_t segk_fbb_score_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_fb
                               const int32_t *n_rows, double *score, void *stream);
 /* get_vec_embed_log_probs + forward_backward (unigram...:474-511, 653-756) for every utterance of
  * block b of the local slices with the uniforms u01(seed, sweep, utt, 0, 1, ...); the slots of the
- * old segments are cleared.  n_utts [host] [s_n].  status bit 16: log_prob == -inf.            */
+ * old segments are cleared.  n_utts [host] [s_n].  status bit 16: log_prob == -inf.
+ * Utterances of any length up to c->N_max: a corpus with N_max <= 64 keeps the utterance's span tables as triangles in LDS
+ * (12 N_max (N_max + 1) / 2 bytes and a little more, at most 64 KB); a corpus with N_max > 64 keeps them as a BAND of
+ * W = n_slices_max columns, the layout of c->band_ids (12 N_max W + 28 N_max + 16 + (N_max rounded up to 16) bytes of
+ * the 160 KB a workgroup has), same arithmetic and same draws (N_max = 256, W = 6: 26 KB).  SEGK_ERR_ARG for such a corpus
+ * when n_slices_max is 0 (unbounded) or above 64, when c has no complete band for this window (band_ids NULL or
+ * band_W != n_slices_max: some span longer than the window has an embedding), or when the band does not fit.
+ * With bt->fast_dp the float32 DP of the tolerance modes covers N_max <= 64 and windows <= 16; elsewhere, so for every
+ * longer corpus, the fp64 recurrence runs with the hardware exponential and logarithm (inside the 1e-4 contract).   */
 int32_t segk_fbb_segment(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f,
                          const segk_fbatch *bt, int32_t s_lo, int32_t s_n, int32_t b,
                          const int32_t *n_utts, uint64_t sweep, int32_t n_slices_min,
@@ -680,8 +689,8 @@ int32_t segk_fbb_assign_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_f
  * of segk_fbb_score_diag32, and the boundaries are those segk_fbb_segment samples from them; the token likelihoods are
  * float32 terms with one multiply-add where segk_fbb_assign_diag32 multiplies and adds (both within the 1e-4 contract).
  * Needs bt->prior_rows; honours segk_fbb_set_probe.  Returns SEGK_ERR_UNSUPPORTED, with nothing enqueued, where it does not
- * apply (a language model, K_max > 256, tables + logits beyond a workgroup's LDS, SEGK_FBB_FUSED=0): the caller then makes
- * the three calls.                                                                                                        */
+ * apply (a language model, K_max > 256, more than 64 landmarks per utterance, tables + logits beyond a workgroup's LDS,
+ * SEGK_FBB_FUSED=0): the caller then makes the three calls.                                                                                                        */
 int32_t segk_fbb_step_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt,
                              int32_t s_lo, int32_t s_n, int32_t b, const int32_t *n_utts, uint64_t sweep,
                              int32_t n_slices_min, int32_t n_slices_max, double wip, double time_power_term,

@@ -236,6 +236,31 @@ static __device__ int fb_collect_tokens_wave(const int32_t *vid, const uint8_t *
 }
 
 
+// The same from the BANDED span ids ([N][W], entry (t, w) at [(t - 1) W + w]) for an utterance of any length: the flags are
+// walked 64 at a time, the position behind the last set flag and the running token count are carried from chunk to chunk.
+// A segment longer than the window lies outside the band: it has no embedding (the band is complete, see FbSpanTab).
+static __device__ int fb_collect_tokens_wave_band(const int32_t *bandi, int W, const uint8_t *bnd, int N, int32_t *tok, int lane)
+{
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    int nn = 0, start = 0;                                           // tokens kept so far; first landmark of the open segment
+    for (int c0 = 0; c0 < N; c0 += 64) {
+        const int j = c0 + lane;
+        const uint8_t flag = j < N ? __hip_atomic_load(&bnd[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (uint8_t)0;
+        const unsigned long long mask = __ballot(flag != 0);
+        const bool bit = j < N && ((mask >> lane) & 1ull);
+        const unsigned long long below = mask & ((1ull << lane) - 1ull);
+        const int jp = below ? c0 + 64 - __clzll((long long)below) : start;
+        int id = -1;
+        if (bit && j - jp < W) id = bandi[(int64_t)j * W + (j - jp)];
+        const unsigned long long keep = __ballot(bit && id >= 0);
+        if (bit && id >= 0) tok[nn + __popcll(keep & ((1ull << lane) - 1ull))] = id;
+        nn += __popcll(keep);
+        if (mask) start = c0 + 64 - __clzll((long long)mask);
+    }
+    return nn;
+}
+
+
 // utils.draw (utils.py:10-21): the first q with u - p[0] - ... - p[q] < 0, subtractions in index
 // order (else n - 1).  Executed redundantly by every calling lane (uniform LDS addresses are
 // broadcast reads): sixteen probabilities are fetched per step, then sixteen dependent
@@ -384,6 +409,49 @@ static __device__ void fb_fill_vec(const FbSpanTab &T, int N, int tri, SC score_
     }
 }
 
+// The same as a BAND in LDS (utterances longer than the triangle allows): vec[(t - 1) W + w] is the span [t - 1 - w, t), the
+// layout of the corpus' band, entry i filled by thread i; `ids` receives the span ids.  Entries that are no span (w >= t) are
+// -1 in the corpus' band: -inf here, and never read by the DP.  The caller's barrier follows.
+template <typename SC>
+static __device__ void fb_fill_vec_band(const int32_t *bandi, const double *bandd, int N, int W, SC score_of, double time_power_term,
+                                        double wip, double *vec, int32_t *ids, int tid, int nt)
+{
+    for (int i = tid; i < N * W; i += nt) {
+        const int id = bandi[i];
+        ids[i] = id;
+        double v = NEG_INF_D;
+        if (id >= 0) {
+            const double dd = bandd[i];
+            v = isnan(dd) ? NEG_INF_D : score_of(id) * (time_power_term == 1.0 ? dd : pow(dd, time_power_term));
+        }
+        vec[i] = v + wip;
+    }
+}
+
+// How the DP below addresses the score of the span [s, t) -- `i` is the triangular row base t (t - 1) / 2 the DP carries
+// along -- and the score of the segment a backward step chose (k slices ending at t; t = 0, the reference's vec[-1], is the
+// utterance's last one-slice span).  The triangle: utterances.py:91-105.  The band: [(t - 1) W + (t - 1 - s)], spans of at
+// most W slices, which is all a DP with a window of W reads.
+struct FbTriVec {
+    static constexpr bool triangular = true;
+    const double *vec;
+    int tri;
+    __device__ __forceinline__ double at(int i, int, int s) const { return vec[i + s]; }
+    __device__ __forceinline__ double chosen(int i, int t, int k) const
+    {
+        int idx = i + t - k;
+        if (idx < 0) idx += tri;
+        return vec[idx];
+    }
+};
+struct FbBandVec {
+    static constexpr bool triangular = false;
+    const double *vec;
+    int W, N;
+    __device__ __forceinline__ double at(int, int t, int s) const { return vec[(t - 1) * W + (t - 1 - s)]; }
+    __device__ __forceinline__ double chosen(int, int t, int k) const { return t > 0 ? vec[(t - 1) * W + (k - 1)] : vec[(N - 1) * W]; }
+};
+
 // A6 / A7 by one full wave (unigram_acoustic_wordseg.py:653-864): forward filtering, then backward
 // sampling (or Viterbi back-tracking) writing the boundaries; returns the summed score of the chosen
 // segments.  Control flow and values are wave-uniform; the exponentials of each logsumexp /
@@ -485,14 +553,15 @@ static __device__ double fb_dp_sample_fast32(const double *vec, double *a, int N
     return total;
 }
 
-//   vec [tri] scores (LDS), a [N], w [N+1], pr [N+1] scratch (LDS), bnd [N] boundaries (global)
-template <typename USRC>
-static __device__ double fb_dp_sample(const double *vec, double *a, double *w, double *pr, int N, int tri, int n_max,
-                                      int viterbi, double log_p_continue, double anneal_temp, uint8_t *bnd, int lane,
-                                      USRC &usrc, int fast = 0)
+//   V scores (LDS: FbTriVec / FbBandVec), a [N], w [N+1], pr [N+1] scratch (LDS), bnd [N] boundaries
+template <typename USRC, typename VA>
+static __device__ double fb_dp_sample_on(const VA V, double *a, double *w, double *pr, int N, int n_max, int viterbi,
+                                         double log_p_continue, double anneal_temp, uint8_t *bnd, int lane, USRC &usrc, int fast)
 {
-    if (fast && !viterbi && n_max > 0 && n_max <= 16 && N <= 64)
-        return fb_dp_sample_fast32(vec, a, N, tri, n_max, (float)log_p_continue, anneal_temp, bnd, lane, usrc);
+    if constexpr (VA::triangular) {      // the tolerance modes' float32 DP: triangular tables, at most 64 landmarks
+        if (fast && !viterbi && n_max > 0 && n_max <= 16 && N <= 64)
+            return fb_dp_sample_fast32(V.vec, a, N, V.tri, n_max, (float)log_p_continue, anneal_temp, bnd, lane, usrc);
+    }
     for (int j = lane; j < N; j += 64) { a[j] = 1.0; bnd[j] = (j == N - 1) ? 1 : 0; }
     __builtin_amdgcn_wave_barrier();
     a[0] = 0.0;
@@ -511,7 +580,7 @@ static __device__ double fb_dp_sample(const double *vec, double *a, double *w, d
         int n = t - lo;
         double at;
         if (lanes16) {
-            const double v = lane < n ? vec[i + t - 1 - lane] + g : NEG_INF_D;
+            const double v = lane < n ? V.at(i, t, t - 1 - lane) + g : NEG_INF_D;
             const bool all_inf = __ballot(lane < n && v != NEG_INF_D) == 0ull;
             const double m0 = fb_wave_max(v, one_row);
             if (viterbi) at = m0;
@@ -528,7 +597,7 @@ static __device__ double fb_dp_sample(const double *vec, double *a, double *w, d
             // one candidate per lane: the same maximum, the same exponentials and the same left-to-right sum as
             // fb_logsumexp_wave, without the trip of the candidates through LDS (a serial loop of n dependent reads and
             // stores per step)
-            const double v = lane < n ? vec[i + lo + lane] + a[lo + lane] : NEG_INF_D;
+            const double v = lane < n ? V.at(i, t, lo + lane) + a[lo + lane] : NEG_INF_D;
             const bool all_inf = __ballot(lane < n && v != NEG_INF_D) == 0ull;
             double mx = v;
             for (int o = 32; o > 0; o >>= 1) {
@@ -547,7 +616,7 @@ static __device__ double fb_dp_sample(const double *vec, double *a, double *w, d
             bool all_inf = true;
             double best = NEG_INF_D;
             for (int s = lo; s < t; s++) {
-                double v = vec[i + s] + a[s];
+                double v = V.at(i, t, s) + a[s];
                 if (lane == 0) w[s - lo] = v;
                 if (v != NEG_INF_D) all_inf = false;
                 if (v > best) best = v;
@@ -568,11 +637,11 @@ static __device__ double fb_dp_sample(const double *vec, double *a, double *w, d
         bool all_inf = true;
         double xw = NEG_INF_D;                                       // (register path) candidate lo + lane of span end t
         if (lanes16) {
-            xw = lane < t - lo ? vec[i + lo + lane] + a[lo + lane] : NEG_INF_D;
+            xw = lane < t - lo ? V.at(i, t, lo + lane) + a[lo + lane] : NEG_INF_D;
             all_inf = __ballot(lane < t - lo && xw != NEG_INF_D) == 0ull;
         } else
         for (int s = lo; s < t; s++)
-            if (vec[i + s] + a[s] != NEG_INF_D) { all_inf = false; break; }
+            if (V.at(i, t, s) + a[s] != NEG_INF_D) { all_inf = false; break; }
         if (all_inf) {
             while (all_inf) {
                 t = t - 1;
@@ -581,11 +650,11 @@ static __device__ double fb_dp_sample(const double *vec, double *a, double *w, d
                 lo = (n_max == 0 || t - n_max < 0) ? 0 : t - n_max;
                 all_inf = true;
                 if (lanes16) {
-                    xw = lane < t - lo ? vec[i + lo + lane] + a[lo + lane] : NEG_INF_D;
+                    xw = lane < t - lo ? V.at(i, t, lo + lane) + a[lo + lane] : NEG_INF_D;
                     all_inf = __ballot(lane < t - lo && xw != NEG_INF_D) == 0ull;
                 } else
                 for (int s = lo; s < t; s++)
-                    if (vec[i + s] + a[s] != NEG_INF_D) { all_inf = false; break; }
+                    if (V.at(i, t, s) + a[s] != NEG_INF_D) { all_inf = false; break; }
             }
             if (lane == 0) bnd[(t - 1 + N) % N] = 1;
         }
@@ -607,9 +676,7 @@ static __device__ double fb_dp_sample(const double *vec, double *a, double *w, d
                 if (uu < 0) { kk = j; break; }
             }
             k = kk + 1;
-            int idx = i + t - k;
-            if (idx < 0) idx += tri;
-            total += vec[idx];
+            total += V.chosen(i, t, k);
             if (t - k - 1 < 0) break;
             if (lane == 0) bnd[t - k - 1] = 1;
             t = t - k;
@@ -617,7 +684,7 @@ static __device__ double fb_dp_sample(const double *vec, double *a, double *w, d
         }
         if (t > 0) {
             n = t - lo;
-            for (int j = lane; j < n; j += 64) w[j] = vec[i + lo + j] + a[lo + j];
+            for (int j = lane; j < n; j += 64) w[j] = V.at(i, t, lo + j) + a[lo + j];
         } else {
             if (lane == 0) w[0] = NEG_INF_D;
         }
@@ -655,12 +722,19 @@ static __device__ double fb_dp_sample(const double *vec, double *a, double *w, d
             }
             k = kk + 1;
         }
-        int idx = i + t - k;
-        if (idx < 0) idx += tri;
-        total += vec[idx];
+        total += V.chosen(i, t, k);
         if (t - k - 1 < 0) break;
         if (lane == 0) bnd[t - k - 1] = 1;
         t = t - k;
     }
     return total;
+}
+
+//   vec [tri] scores, triangular (LDS)
+template <typename USRC>
+static __device__ double fb_dp_sample(const double *vec, double *a, double *w, double *pr, int N, int tri, int n_max,
+                                      int viterbi, double log_p_continue, double anneal_temp, uint8_t *bnd, int lane,
+                                      USRC &usrc, int fast = 0)
+{
+    return fb_dp_sample_on(FbTriVec{vec, tri}, a, w, pr, N, n_max, viterbi, log_p_continue, anneal_temp, bnd, lane, usrc, fast);
 }

@@ -13,7 +13,8 @@
 //   k_fbb_score     log_marg_i of every candidate span of the block: R rows x all slots per
 //                   workgroup, online logsumexp per row                         (fp64 VALU)
 //   k_fbb_segment   one workgroup per utterance: score vector, DP, backward sampling with the
-//                   counter-based uniforms, new token list
+//                   counter-based uniforms, new token list (corpora with an utterance of more than 64
+//                   landmarks: k_fbb_segment_band, the span tables as a band of n_slices_max columns)
 //   k_fbb_assign    one workgroup per utterance: logits -> softmax -> draw for each new token
 //                   (with a language model: the bigram prior of the previous token's slot)
 //   k_fbb_partials  the block's partial sums from its new tokens (token order per slot)
@@ -66,7 +67,9 @@ static __device__ __forceinline__ bool fbb_locate(const FbbMap &m, int wg, int *
 // ---------------------------------------------------------------------------------------
 // partial sums of (slice s, block b) from the current token lists: one wave per (s, slot)
 // ---------------------------------------------------------------------------------------
-template <typename XT>
+// LONG: utterances of more than 64 tokens (N_max > 64) -- the tokens of an utterance are taken 64 at a time, chunk after
+// chunk, so the additions keep the specification's order (utterance, then token)
+template <typename XT, bool LONG = false>
 __global__ void k_fbb_partials(segk_corpus c, segk_fbgmm f, segk_fbatch bt, int s_lo, int s_n, int b,
                                const int32_t *new_tok, const int32_t *n_new)
 {
@@ -86,6 +89,36 @@ __global__ void k_fbb_partials(segk_corpus c, segk_fbgmm f, segk_fbatch bt, int 
     double n = 0.0;
     // four utterances per trip, stage by stage (token counts, tokens, slots: three round trips for four utterances instead of
     // three per utterance); the matches are then taken in utterance and token order as before
+    auto add_row = [&](int64_t e) {
+        n += 1.0;
+#pragma unroll
+        for (int q = 0; q < FBB_MAXCH; q++) {
+            const int d = q * 64 + lane;
+            if (d < D) {
+                const XT x = X[e * c.ldx + d];
+                ax[q] += (double)x;
+                axx[q] += fbb_sq<XT>(x);
+            }
+        }
+    };
+    if constexpr (LONG) {
+        for (int ub = u0; ub < u1; ub += 4) {
+            int nn4[4];
+#pragma unroll
+            for (int v = 0; v < 4; v++) nn4[v] = ub + v < u1 ? n_new[ub + v] : 0;
+            for (int v = 0; v < 4; v++)
+                for (int t0 = 0; t0 < nn4[v]; t0 += 64) {
+                    const int id = t0 + lane < nn4[v] ? new_tok[(int64_t)(ub + v) * c.N_max + t0 + lane] : -1;
+                    const int match = id >= 0 ? (bt.slot[id] == k) : 0;
+                    unsigned long long bal = __ballot(match);
+                    while (bal) {                               // token order
+                        const int src = __ffsll((long long)bal) - 1;
+                        bal &= bal - 1;
+                        add_row(__shfl(id, src));
+                    }
+                }
+        }
+    } else
     for (int ub = u0; ub < u1; ub += 4) {
         int nn4[4], id4[4], match4[4];
 #pragma unroll
@@ -100,17 +133,7 @@ __global__ void k_fbb_partials(segk_corpus c, segk_fbgmm f, segk_fbatch bt, int 
             while (bal) {                                   // token order
                 const int src = __ffsll((long long)bal) - 1;
                 bal &= bal - 1;
-                const int64_t e = __shfl(id4[v], src);
-                n += 1.0;
-#pragma unroll
-                for (int q = 0; q < FBB_MAXCH; q++) {
-                    const int d = q * 64 + lane;
-                    if (d < D) {
-                        const XT x = X[e * c.ldx + d];
-                        ax[q] += (double)x;
-                        axx[q] += fbb_sq<XT>(x);
-                    }
-                }
+                add_row(__shfl(id4[v], src));
             }
         }
     }
@@ -1285,6 +1308,57 @@ __global__ __launch_bounds__(128) void k_fbb_segment(segk_corpus c, segk_fbatch 
 }
 
 // ---------------------------------------------------------------------------------------
+// The same for corpora with utterances of more than 64 landmarks (N_max > 64): the scores and the span ids of
+// the utterance are held as a BAND -- [N][W], W = n_slices_max <= 64, the corpus' band layout -- instead of triangles, so LDS
+// grows with N_max * W and not with N_max^2.  The DP is fb_dp_sample_on with the band's addressing (its register path: lane w
+// reads entry (t, w)); the token lists are taken 64 flags at a time.  Every utterance of such a corpus runs here, short ones
+// too: an utterance of N <= W landmarks reads the rows t <= N of the corpus' band, whose entries w >= t are -1.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(128) void k_fbb_segment_band(segk_corpus c, segk_fbatch bt, FbbMap map, int b, uint64_t sweep, double wip,
+                              double time_power_term, double anneal_temp, const double *score, uint8_t *boundaries,
+                              int32_t *new_tok, int32_t *n_new, double *out_logprob, int32_t *status, double *probe_alpha)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int s, idx;
+    if (!fbb_locate(map, blockIdx.x, &s, &idx)) return;
+    const int slice = map.lo[s];
+    const int utt = bt.utt_range[(slice * bt.n_blocks + b) * 2] + idx;
+    const int N = c.lengths[utt], NM = c.N_max, W = c.band_W;
+    double *vec = (double *)smem;                      // [N_max W]
+    double *a = vec + (int64_t)NM * W;                 // [N_max]
+    double *w = a + NM;                                // [N_max + 1]
+    double *pr = w + NM + 1;                           // [N_max + 1]
+    int32_t *old = (int32_t *)(pr + NM + 1);           // [N_max]
+    int32_t *bid_l = old + NM;                         // [N_max W]
+    uint8_t *bnd_l = (uint8_t *)(bid_l + (int64_t)NM * W);      // [N_max]
+    uint8_t *bnd_g = boundaries + (int64_t)utt * NM;
+    for (int j = threadIdx.x; j < N; j += blockDim.x) bnd_l[j] = bnd_g[j];
+    fb_fill_vec_band(c.band_ids + (int64_t)utt * NM * W, c.band_dur + (int64_t)utt * NM * W, N, W, [&](int id) { return score[id]; },
+                     time_power_term, wip, vec, bid_l, threadIdx.x, blockDim.x);
+    __syncthreads();
+    if (threadIdx.x >= 64) return;
+    const int lane = threadIdx.x;
+    const int n_old = fb_collect_tokens_wave_band(bid_l, W, bnd_l, N, old, lane);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    CounterUniforms usrc = {bt.seed, sweep, (uint64_t)utt, 0};
+    // (the tolerance modes' float32 DP is built for N <= 64: here their hardware exponentials enter the fp64 recurrence)
+    const double total = fb_dp_sample_on(FbBandVec{vec, W, N}, a, w, pr, N, W, 0, 0.0, anneal_temp, bnd_l, lane, usrc, bt.fast_dp);
+    if (probe_alpha)
+        for (int j = lane; j < N; j += 64) probe_alpha[(int64_t)utt * NM + j] = a[j];
+    for (int j = lane; j < n_old; j += 64) bt.slot[old[j]] = -1;
+    // (the boundary flags were written by lane 0 of this wave)
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const int nn = fb_collect_tokens_wave_band(bid_l, W, bnd_l, N, new_tok + (int64_t)utt * NM, lane);
+    for (int j = lane; j < N; j += 64) bnd_g[j] = bnd_l[j];
+    if (lane != 0) return;
+    if (total == NEG_INF_D) atomicOr(status, 16);
+    out_logprob[utt] = total;
+    n_new[utt] = nn;
+}
+
+// ---------------------------------------------------------------------------------------
 // slots of the new tokens of one utterance per workgroup
 // ---------------------------------------------------------------------------------------
 template <typename XT, int COV, int F32 = 0>
@@ -2065,10 +2139,43 @@ static int check_fbb(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatc
     SEGK_REQUIRE(c && f && bt, "NULL corpus / fbgmm / batch state");
     SEGK_REQUIRE(f->cov_type == 0 || f->cov_type == 1, "cov_type must be 0 (fixed) or 1 (diag)");
     SEGK_REQUIRE(c->D > 0 && c->D <= 64 * FBB_MAXCH, "batch mode supports D <= 256");
-    SEGK_REQUIRE(c->N_max > 0 && c->N_max <= 64, "batch mode supports at most 64 landmarks per utterance");
+    SEGK_REQUIRE(c->N_max > 0, "corpus without landmarks");       // (more than 64 per utterance: check_fbb_long)
     SEGK_REQUIRE(bt->n_slices >= 1 && bt->n_slices <= 16, "n_slices must be in 1..16");
     SEGK_REQUIRE(bt->n_blocks >= 2, "n_blocks must be >= 2 (with one block nothing is conditioned on)");
     SEGK_REQUIRE(f->kconst != NULL, "kconst buffer missing");
+    return SEGK_OK;
+}
+
+// LDS of k_fbb_segment_band: band of scores (double) and of span ids (int32), alpha and the DP's two scratch rows, the old
+// token list, the boundary flags
+#define FBB_BAND_LDS_MAX (160 * 1024)
+static size_t fbb_band_lds(int64_t NM, int64_t W)
+{
+    return (size_t)(NM * W + 3 * NM + 2) * sizeof(double) + (size_t)(NM + NM * W) * sizeof(int32_t) + (size_t)((NM + 15) & ~15);
+}
+
+// What a corpus with an utterance of more than 64 landmarks needs from the boundary step (N_max <= 64: nothing).
+static int check_fbb_long(const segk_corpus *c, int n_slices_max)
+{
+    if (c->N_max <= 64) return SEGK_OK;
+    if (n_slices_max <= 0 || n_slices_max > 64) {
+        segk_set_error("batch mode takes utterances of more than 64 landmarks (N_max = %d) with a window of 1..64 slices only "
+                       "(n_slices_max = %d): set n_slices_max, or use sync=\"sequential\"", c->N_max, n_slices_max);
+        return SEGK_ERR_ARG;
+    }
+    if (!c->band_ids || !c->band_dur || c->band_W != n_slices_max) {
+        segk_set_error("batch mode takes utterances of more than 64 landmarks (N_max = %d) only when no span longer than the "
+                       "window has an embedding (no complete band for n_slices_max = %d): build the corpus for this window, or "
+                       "use sync=\"sequential\"", c->N_max, n_slices_max);
+        return SEGK_ERR_ARG;
+    }
+    const size_t lds = fbb_band_lds(c->N_max, c->band_W);
+    if (lds > FBB_BAND_LDS_MAX) {
+        segk_set_error("the banded span table of the longest utterance does not fit in LDS: N_max = %d landmarks, window W = %d: "
+                       "12 N_max W + 28 N_max + 16 + (N_max rounded up to 16) = %zu bytes needed, %d available: shorten the "
+                       "window (n_slices_max) or split the longest utterances", c->N_max, c->band_W, lds, FBB_BAND_LDS_MAX);
+        return SEGK_ERR_ARG;
+    }
     return SEGK_OK;
 }
 
@@ -2130,6 +2237,10 @@ int32_t segk_fbb_partials(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm 
         ctx->fbb_scal_stream = stream;                             //  enqueued on THIS stream)
         return SEGK_OK;
     }
+    if (c->N_max > 64)
+        DISPATCH_XT(c, hipLaunchKernelGGL((k_fbb_partials<XT, true>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0,
+                                           (hipStream_t)stream, *c, *f, *bt, s_lo, s_n, b, new_tok, n_new););
+    else
     DISPATCH_XT(c, hipLaunchKernelGGL(k_fbb_partials<XT>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0,
                                        (hipStream_t)stream, *c, *f, *bt, s_lo, s_n, b, new_tok, n_new););
     SEGK_LAUNCH_CHECK();
@@ -2318,7 +2429,17 @@ int32_t segk_fbb_segment(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *
     FbbMap m;
     rc = make_map(&m, s_lo, s_n, n_utts, 1);
     if (rc) return rc;
+    rc = check_fbb_long(c, n_slices_max);
+    if (rc) return rc;
     if (m.off[s_n] == 0) return SEGK_OK;
+    if (c->N_max > 64) {
+        const size_t ldsb = fbb_band_lds(c->N_max, c->band_W);
+        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbb_segment_band, ldsb));
+        hipLaunchKernelGGL(k_fbb_segment_band, dim3(m.off[s_n]), dim3(128), ldsb, (hipStream_t)stream, *c, *bt, m, b, sweep, wip,
+                           time_power_term, anneal_temp, score, boundaries, new_tok, n_new, out_logprob, status, ctx->probe_alpha);
+        SEGK_LAUNCH_CHECK();
+        return SEGK_OK;
+    }
     const int64_t triMax = (int64_t)c->N_max * (c->N_max + 1) / 2;
     const size_t lds = (size_t)(triMax + 3 * c->N_max + 2) * sizeof(double) + (size_t)(c->N_max + triMax) * sizeof(int32_t) +
                        (size_t)((c->N_max + 15) & ~15);
@@ -2442,6 +2563,10 @@ int32_t segk_fbb_step_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_fbg
     SEGK_REQUIRE(n_slices_min == 0 || n_slices_min == 1, "n_slices_min must be 0 or 1");
     SEGK_REQUIRE(score && boundaries && new_tok && n_new && out_logprob && status, "step operands");
     if (segk_env_int("SEGK_FBB_FUSED", 1) == 0) { segk_set_error("segk_fbb_step_diag32: disabled (SEGK_FBB_FUSED=0)"); return SEGK_ERR_UNSUPPORTED; }
+    if (c->N_max > 64) {          // its DP and token lists are one lane per landmark: the caller's score / segment / assign launches take over
+        segk_set_error("segk_fbb_step_diag32: at most 64 landmarks per utterance (N_max = %d)", c->N_max);
+        return SEGK_ERR_UNSUPPORTED;
+    }
     if (f->lm_unigram || !bt->prior_rows || f->K_max > 256 || c->D > 256) {
         segk_set_error("segk_fbb_step_diag32: needs prior_rows, no language model, K_max <= 256, D <= 256");
         return SEGK_ERR_UNSUPPORTED;

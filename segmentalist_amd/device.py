@@ -973,6 +973,9 @@ class FbgmmBatchSweeper(object):
         self.slot = torch.zeros(c.n_emb, dtype=torch.int32, device=dev)
         self.remap = torch.zeros(K, dtype=torch.int32, device=dev)
         self.u_max = int((ur[:, :, 1] - ur[:, :, 0]).max())
+        if self.u_max * max(c.N_max, 1) >= 2 ** 31:
+            raise SegkError("a block of %d utterances x %d landmarks has more token positions than the kernels' int32 "
+                            "counters hold: use more blocks or slices" % (self.u_max, c.N_max))
         self.lm_tok = None
         # the batch state keeps its own bigram table (indexed by slots); the sequential-mode tables of
         # the LM object are only written by materialise()
