@@ -27,13 +27,14 @@ def gpu():
 
 
 def _pair(kind, n_utt, D, K, cseed, nmax, B, S, seed=5, dtype="float32", score_precision="f64", n_landmarks=0,
-          transform=None, **kw):
+          transform=None, product=True, **kw):
     """(oracle segmenter + batch state, product segmenter) from identical initial states.  n_landmarks > 0: every utterance
     that long (default: ragged, 3 to 9 landmarks).  transform: a name of tests/affine.py -- the corpus and the prior moved
-    to new coordinates together."""
-    from segmentalist_amd import bigram_acoustic_wordseg as baw, fbgmm, unigram_acoustic_wordseg as uaw
-    from segmentalist_amd.gaussian_components_fixedvar import FixedVarPrior
-    from segmentalist_amd.niw import NIW
+    to new coordinates together.  product=False: the oracle's side alone (no device), None in the product's place."""
+    if product:
+        from segmentalist_amd import bigram_acoustic_wordseg as baw, fbgmm, unigram_acoustic_wordseg as uaw
+        from segmentalist_amd.gaussian_components_fixedvar import FixedVarPrior
+        from segmentalist_amd.niw import NIW
     corpus = cases.chain_corpus(n_utt, D, K, cseed, n_landmarks == 0, n_landmarks, nmax, dtype)
     fixed, niw = cases.fixed_prior_params(D), cases.diag_prior_params(D)
     if transform is not None:
@@ -46,6 +47,9 @@ def _pair(kind, n_utt, D, K, cseed, nmax, B, S, seed=5, dtype="float32", score_p
     bargs = dict(sync="batch", n_gibbs_blocks=B, n_stat_blocks=S, batch_seed=11, score_precision=score_precision)
     out = []
     for side in ("oracle", "product"):
+        if side == "product" and not product:
+            out.append(None)
+            continue
         random.seed(seed)
         np.random.seed(seed)
         if kind == "bigram":
@@ -98,14 +102,22 @@ def test_batch_sweeps_match_specification_on_transformed_corpora(gpu, kind, tran
 
 def _sweeps_match_specification(gpu, kind, n_utt, D, K, cseed, nmax, B, S, kw, transform=None, sweeps=3):
     ref, spec, seg = _pair(kind, n_utt, D, K, cseed, nmax, B, S, transform=transform, **kw)
+    _chains_match(gpu, ref, spec, seg, sweeps)
+
+
+def _chains_match(gpu, ref, spec, seg, sweeps, anneal_temp=1.0, anneal_gibbs_am=False):
+    """Sweep by sweep, the product against the specification from identical states: boundaries, slots (and the bigram table)
+    equal, log-probabilities to 1e-9 relative, the reference's view (canonical assignments, counts) equal."""
     for sw in range(sweeps):
-        lp = spec.sweep(sw)
-        seg.batch_sweep_async()
+        lp = spec.sweep(sw, anneal_temp, anneal_gibbs_am)
+        seg.batch_sweep_async(anneal_temp, anneal_gibbs_am)
         gpu.cuda.synchronize()
         seg._df.check_status()
         assert np.array_equal(seg.utterances.boundaries, ref.utterances.boundaries), sw
         slots = seg._get_sweeper().slot.cpu().numpy()
         assert np.array_equal(slots, spec.slot), sw
+        if spec.lm is not None:
+            assert np.array_equal(seg._get_sweeper().lm_big.cpu().numpy(), spec.big), sw
         npt.assert_allclose(seg._df.out_logprob.cpu().numpy(), lp, rtol=1e-9)
         # the reference's view
         seg.materialise()

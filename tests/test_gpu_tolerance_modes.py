@@ -39,15 +39,18 @@ def gpu():
     return torch
 
 
-def _pair(kind, n_utt, D, K, prec, B=3, S=2, seed=5, transform=None):
-    """transform: a name of tests/affine.py -- the corpus and the prior moved to new coordinates together."""
-    from segmentalist_amd import bigram_acoustic_wordseg as baw, fbgmm, unigram_acoustic_wordseg as uaw
-    from segmentalist_amd.gaussian_components_fixedvar import FixedVarPrior
-    from segmentalist_amd.niw import NIW
+def _pair(kind, n_utt, D, K, prec, B=3, S=2, seed=5, transform=None, product=True, **kw):
+    """transform: a name of tests/affine.py -- the corpus and the prior moved to new coordinates together.  product=False: the
+    oracle's side alone (no device), None in the product's place.  kw: segmenter keywords over the defaults below."""
+    if product:
+        from segmentalist_amd import bigram_acoustic_wordseg as baw, fbgmm, unigram_acoustic_wordseg as uaw
+        from segmentalist_amd.gaussian_components_fixedvar import FixedVarPrior
+        from segmentalist_amd.niw import NIW
     from segmentalist_amd.synth import make_corpus
     corpus = make_corpus(n_utt, D, K, seed=17, N=20, n_slices_max=6)          # the bench generator: 105 spans per utterance
     args = dict(n_slices_min=0, n_slices_max=6, p_boundary_init=0.5, beta_sent_boundary=-1, lms=1.0, wip=0.0,
                 init_am_assignments="rand", time_power_term=1.0)
+    args.update(kw)
     bargs = dict(sync="batch", n_gibbs_blocks=B, n_stat_blocks=S, batch_seed=11, score_precision=prec)
     fixed = (0.002 * np.ones(D), np.zeros(D), 0.002 / 0.05 * np.ones(D))
     niw = (np.zeros(D), 0.05, D + 3, 0.002 * (D + 3) * np.ones(D))
@@ -58,6 +61,9 @@ def _pair(kind, n_utt, D, K, prec, B=3, S=2, seed=5, transform=None):
         fixed, niw = affine.fixed_prior(*fixed, s, c), affine.niw_prior(*niw, s, c)
     out = []
     for side in ("oracle", "product"):
+        if side == "product" and not product:
+            out.append(None)
+            continue
         random.seed(seed)
         np.random.seed(seed)
         if kind == "bigram":
@@ -77,9 +83,13 @@ def _pair(kind, n_utt, D, K, prec, B=3, S=2, seed=5, transform=None):
     return ref, nb.FbgmmBatch(ref, n_gibbs_blocks=B, n_stat_blocks=S, seed=11), seg
 
 
-def _one_step(sw, seg, b, sweep=0, fused=False):
+def _one_step(sw, seg, b, sweep=0, fused=False, anneal_temp_fb=1.0, anneal_temp_am=1.0):
     """Gibbs step b of the sampler as FbgmmBatchSweeper.sweep enqueues it, without the partial-sum refresh (so that every
-    step of this test conditions on the INITIAL state of the other blocks, which is what the specification object holds)."""
+    step of this test conditions on the INITIAL state of the other blocks, which is what the specification object holds).
+    The segmenter's own window, word insertion penalty and time power term; the temperatures of the boundary draws and of the
+    slot draws as given."""
+    n_min, n_max, wip, tpt = int(seg.n_slices_min), int(seg.n_slices_max), float(seg.wip), float(seg.time_power_term)
+    T_fb, T_am = float(anneal_temp_fb), float(anneal_temp_am)
     import torch
     from segmentalist_amd._abi import check, ptr
     df = seg._df
@@ -88,7 +98,7 @@ def _one_step(sw, seg, b, sweep=0, fused=False):
         check(L.segk_fbb_lm_apply(ctx, cp, fp, bp, b, -1, st))
     check(L.segk_fbb_prepare(ctx, cp, fp, bp, b, st))
     if fused:                  # the three calls below as one launch (diagonal components, float32 terms)
-        check(L.segk_fbb_step_diag32(ctx, cp, fp, bp, sw.s_lo, sw.s_n, b, sw._n_utts[b], sweep, 0, 6, 0.0, 1.0, 1.0, 1.0,
+        check(L.segk_fbb_step_diag32(ctx, cp, fp, bp, sw.s_lo, sw.s_n, b, sw._n_utts[b], sweep, n_min, n_max, wip, tpt, T_fb, T_am,
                                      ptr(df.score), ptr(seg._dev_bounds), ptr(df.new_tok), ptr(df.n_new), ptr(df.out_logprob),
                                      ptr(df.status), st))
         torch.cuda.synchronize()
@@ -100,20 +110,20 @@ def _one_step(sw, seg, b, sweep=0, fused=False):
         check(L.segk_fbb_score_diag32(ctx, cp, fp, bp, sw.s_lo, sw.s_n, b, sw._n_rows[b], ptr(df.score), st))
     else:
         check(L.segk_fbb_score(ctx, cp, fp, bp, sw.s_lo, sw.s_n, b, sw._n_rows[b], ptr(df.score), st))
-    check(L.segk_fbb_segment(ctx, cp, fp, bp, sw.s_lo, sw.s_n, b, sw._n_utts[b], sweep, 0, 6, 0.0, 1.0, 1.0, ptr(df.score),
+    check(L.segk_fbb_segment(ctx, cp, fp, bp, sw.s_lo, sw.s_n, b, sw._n_utts[b], sweep, n_min, n_max, wip, tpt, T_fb, ptr(df.score),
                              ptr(seg._dev_bounds), ptr(df.new_tok), ptr(df.n_new), ptr(df.out_logprob), ptr(df.status), st))
     if sw.ll_mat is not None:
         tm = sw._tok_map[b]
         rows = sw._tok_rows[:tm.numel()]
         torch.index_select(df.new_tok.view(-1), 0, tm, out=rows)
         check(L.segk_fbb_token_scores(ctx, cp, fp, bp, ptr(rows), tm.numel(), ptr(sw.ll_mat), sw.ll_ld, st))
-        check(L.segk_fbb_assign(ctx, cp, fp, bp, sw.s_lo, sw.s_n, b, sw._n_utts[b], sweep, 1.0, ptr(df.new_tok), ptr(df.n_new),
+        check(L.segk_fbb_assign(ctx, cp, fp, bp, sw.s_lo, sw.s_n, b, sw._n_utts[b], sweep, T_am, ptr(df.new_tok), ptr(df.n_new),
                                 ptr(sw.ll_mat), sw.ll_ld, st))
     elif sw.score_diag32:
-        check(L.segk_fbb_assign_diag32(ctx, cp, fp, bp, sw.s_lo, sw.s_n, b, sw._n_utts[b], sweep, 1.0, ptr(df.new_tok),
+        check(L.segk_fbb_assign_diag32(ctx, cp, fp, bp, sw.s_lo, sw.s_n, b, sw._n_utts[b], sweep, T_am, ptr(df.new_tok),
                                        ptr(df.n_new), st))
     else:
-        check(L.segk_fbb_assign(ctx, cp, fp, bp, sw.s_lo, sw.s_n, b, sw._n_utts[b], sweep, 1.0, ptr(df.new_tok), ptr(df.n_new),
+        check(L.segk_fbb_assign(ctx, cp, fp, bp, sw.s_lo, sw.s_n, b, sw._n_utts[b], sweep, T_am, ptr(df.new_tok), ptr(df.n_new),
                                 None, 0, st))
     if sw.lm_tok is not None:          # put the block's old transcripts back: the next step starts from the initial tables
         check(L.segk_fbb_lm_apply(ctx, cp, fp, bp, b, 1, st))
@@ -274,18 +284,19 @@ def test_fused_gibbs_step_gives_the_span_scores_and_boundaries_of_the_three_laun
     _fused_against_three_launches(transform)
 
 
-def _fused_against_three_launches(transform):
+def _fused_against_three_launches(transform, anneal_temp=1.0, **kw):
     """segk_fbb_step_diag32 against segk_fbb_score_diag32 + segk_fbb_segment + segk_fbb_assign_diag32 from identical states,
     every block of a sweep: the span scores and the boundaries bit for bit (the same arithmetic and the same uniforms); the
     slots agree wherever the token's uniform does not fall within the last bits of a cumulative boundary (the token
-    likelihoods of the two forms differ in their last float32 bits)."""
+    likelihoods of the two forms differ in their last float32 bits).  anneal_temp: the temperature of the boundary draws
+    and of the slot draws; kw: segmenter keywords."""
     out = []
     for fused in (False, True):
-        ref, spec, seg = _pair("diag", 64, 39, 100, "f32", transform=transform)
+        ref, spec, seg = _pair("diag", 64, 39, 100, "f32", transform=transform, **kw)
         sw = seg._get_sweeper()
         sw.enter(seg._dev_bounds)
         for b in range(sw.B):
-            _one_step(sw, seg, b, fused=fused)
+            _one_step(sw, seg, b, fused=fused, anneal_temp_fb=anneal_temp, anneal_temp_am=anneal_temp)
         out.append((seg._df.score.cpu().numpy().copy(), seg._dev_bounds.cpu().numpy().copy(), sw.slot.cpu().numpy().copy(),
                     seg._df.out_logprob.cpu().numpy().copy(), seg._df.n_new.cpu().numpy().copy()))
     a, b_ = out
@@ -294,3 +305,4 @@ def _fused_against_three_launches(transform):
     assert np.array_equal(a[3], b_[3]) and np.array_equal(a[4], b_[4])
     both = (a[2] >= 0) | (b_[2] >= 0)
     assert np.mean(a[2][both] == b_[2][both]) > 0.98, np.mean(a[2][both] == b_[2][both])
+    return a
