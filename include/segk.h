@@ -54,8 +54,9 @@ const char *segk_last_error(void);
  *              constants) and the token-likelihood matrix has the image's columns; the FBGMM / bigram kernels read
  *              segk_corpus.band_ids / band_dur (a COMPLETE band only); segk_fbgmm_sequential_sweep with a language model
  *   8 round 4: segk_fbb_step_diag32
- *   9 segk_fbatch.centre (the reduced-precision FBGMM kernels work in coordinates centred on it), segk_fbatch.tab32         */
-#define SEGK_ABI_VERSION 9
+ *   9 segk_fbatch.centre (the reduced-precision FBGMM kernels work in coordinates centred on it), segk_fbatch.tab32
+ *  10 segk_kmeans_delta_stats                                                                                              */
+#define SEGK_ABI_VERSION 10
 int32_t segk_abi_version(void);
 
 /* Timing of the MAIN launch of the MFMA score kernel (k_kmeans_score<..., 0>) with HIP events
@@ -246,6 +247,14 @@ int32_t segk_kmeans_stage_counts(segk_ctx *ctx, const segk_cand *cand, int32_t *
  * wrong -- the first sweeps of a chain --, where the hinted path would be the slower one; results do not depend on it.
  * launched, seen [host] uint32, permille [host] int32.                                                                  */
 int32_t segk_kmeans_hint_feedback(segk_ctx *ctx, uint32_t *launched, uint32_t *seen, int32_t *permille);
+
+/* What the delta score pass of segk_kmeans_score_hinted did, WITHOUT touching any stream (no reference counterpart; figures of
+ * the latest hinted call that has reached its certificate kernel, written by the device into pinned host memory): out[0] =
+ * mode, 1 delta (only the component columns whose image changed since the base pass were multiplied), 0 full, -1 the call kept
+ * no delta state (SEGK_SCORE_DELTA=0, an id list, a table beyond the band stage); out[1] = image columns that differed from
+ * the base pass's; out[2] = tiles of 32 packed columns multiplied (0 in full mode); out[3] = positions whose hinted score was
+ * taken over from the previous call.  Results never depend on the mode.  out [host] int32 [4].                          */
+int32_t segk_kmeans_delta_stats(segk_ctx *ctx, int32_t *out);
 
 /* Gather of the A1 results for rows ids[0..n) (0..n-1 when NULL): out_max[r] (double, widened
  * from the dtype of X) and out_arg[r] = np.max / np.argmax of neg_sqrd_norm(ids[r])

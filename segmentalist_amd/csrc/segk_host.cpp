@@ -84,6 +84,17 @@ int32_t segk_create(int32_t device_id, segk_ctx **out_ctx)
                 (void)hipHostFree(hp);
             }
         }
+        // the figures of the delta score pass (segk_kmeans_delta_stats), written by the device the same way
+        hp = nullptr; dp = nullptr;
+        if (hipHostMalloc(&hp, 64, hipHostMallocMapped) == hipSuccess) {
+            memset(hp, 0, 64);
+            if (hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
+                c->delta_host = (volatile int32_t *)hp;
+                c->delta_host_dev = (int32_t *)dp;
+            } else {
+                (void)hipHostFree(hp);
+            }
+        }
         (void)hipGetLastError();
     }
     if (prev >= 0) {
@@ -119,6 +130,8 @@ int32_t segk_destroy(segk_ctx *ctx)
         if (ctx->hint_map) (void)hipFree(ctx->hint_map);
         if (ctx->ws_u64) (void)hipFree(ctx->ws_u64);
         if (ctx->hint_fb) (void)hipFree(ctx->hint_fb);
+        if (ctx->delta_buf) (void)hipFree(ctx->delta_buf);
+        if (ctx->delta_host) (void)hipHostFree((void *)ctx->delta_host);
         if (ctx->pre_thr) (void)hipFree(ctx->pre_thr);
         if (ctx->band_mask) (void)hipFree(ctx->band_mask);
         if (ctx->miss_host) (void)hipHostFree((void *)ctx->miss_host);
@@ -264,6 +277,21 @@ int32_t segk_kmeans_hint_feedback(segk_ctx *ctx, uint32_t *launched, uint32_t *s
         const unsigned long long w = *ctx->miss_host;
         *seen = (uint32_t)(w >> 32);
         *permille = (int32_t)(w & 0xffffffffull);
+    }
+    return SEGK_OK;
+}
+
+// What the delta score pass did in the last hinted call whose figures have arrived, WITHOUT touching the stream (the merge
+// kernel writes them into pinned host memory): out[0] = mode (0 full, 1 delta; -1: the call did not keep delta state at all),
+// out[1] = tile-image columns that differed from the base pass's snapshot, out[2] = tiles of the packed delta image that were
+// multiplied (0 in full mode), out[3] = positions whose hinted score the hint waves took over from the previous call.
+int32_t segk_kmeans_delta_stats(segk_ctx *ctx, int32_t *out)
+{
+    SEGK_REQUIRE(ctx && out, "arguments");
+    out[0] = -1; out[1] = 0; out[2] = 0; out[3] = 0;
+    if (ctx->delta_host) {
+        out[0] = ctx->delta_host[0] - 1;
+        for (int i = 1; i < 4; i++) out[i] = ctx->delta_host[i];
     }
     return SEGK_OK;
 }

@@ -80,6 +80,16 @@ struct segk_ctx {
     volatile unsigned long long *miss_host;
     unsigned long long *miss_dev;
     unsigned int miss_seq;
+    // delta score pass (segk_score_hint.hip): the base pass's image snapshot, its certified labels, the packed changed columns,
+    // the previous call's means, the delta pass's (m1, m2) -- one allocation; valid only for the call tuple in delta_key
+    void *delta_buf;
+    size_t delta_bytes;
+    unsigned int delta_seq;      // launches of k_delta_prep
+    int delta_valid;             // the state in delta_buf / hint_part is that of the call delta_key describes
+    const void *delta_key[6];    // row image, float32 rows, tile image, means, cand.k, cand.s
+    int64_t delta_key_n[5];      // row0, n, n_emb, K_max, D
+    volatile int32_t *delta_host;    // host-mapped [4]: last call's mode, changed columns, packed tiles, positions the hint waves skipped
+    int32_t *delta_host_dev;
     void *hint_fb;               // per-XCD shares and wave lifetimes of the matrix kernel's last launches, [3][8] floats + [3][8] uint32
     unsigned int hint_fb_launch;
     // full scan with the components in LDS (k_kmeans_brute_ls): (score, component) per queue entry, zero between uses

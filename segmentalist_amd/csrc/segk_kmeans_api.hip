@@ -47,6 +47,7 @@ int32_t segk_kmeans_filter(segk_ctx *ctx, const segk_corpus *c, const segk_kmean
     int rc = score_checks(c, m, ids, row0, n, cand);
     if (rc) return rc;
     if (n <= 0) return SEGK_OK;
+    ctx->delta_valid = 0;                              // any score call but the hinted one drops the delta pass's state
     hipStream_t st = (hipStream_t)stream;
     // 4-wave workgroups, two per CU: the two waves sharing a SIMD belong to DIFFERENT workgroups
     // and drift apart, covering each other's barrier/staging gaps.  (Measured: an 8-wave
@@ -106,7 +107,7 @@ int32_t segk_kmeans_score_hinted(segk_ctx *ctx, const segk_corpus *c, const segk
     hipStream_t st = (hipStream_t)stream;
     ctx->defer_zero = cand->count;                     // cleared by the path's first kernel, with its own queue length
     const ScoreArgs A = make_score_args(c, m, ids, row0, n, cand, true);
-    rc = segk_dispatch_score_hint(ctx, A, hint_remap, c->n_emb, segk_b3_kp(c->D) / 16, st);
+    rc = segk_dispatch_score_hint(ctx, A, hint_remap, m->K, c->n_emb, segk_b3_kp(c->D) / 16, st);
     segk_flush_deferred_zero(ctx, st);                 // (an early error return: nothing was launched)
     if (rc) return rc;
     return segk_resolve_on(ctx, c, m, ids, row0, n, cand, status, stream);
@@ -143,6 +144,7 @@ int32_t segk_kmeans_sequential_sweep(segk_ctx *ctx, const segk_corpus *c, segk_k
     if (rc) return rc;
     SEGK_REQUIRE(order && n_order >= 0 && cand && cand->k && cand->s && keys_scratch, "sequential sweep operands");
     SEGK_REQUIRE(c->vec_ids && c->lengths && c->n_utt > 0, "corpus without utterances");
+    ctx->delta_valid = 0;
     if (c->x_dtype != SEGK_F32) {
         segk_set_error("segk_kmeans_sequential_sweep: float32 data only (use the per-utterance calls for float64)");
         return SEGK_ERR_UNSUPPORTED;

@@ -769,7 +769,7 @@ int segk_launch_seq_chain(segk_ctx *ctx, const segk_corpus *c, segk_kmeans *m, c
 // segk_score_h1.hip: one-product pre-filter + exact pair stage + second stage
 int segk_dispatch_score_pre(segk_ctx *ctx, const ScoreArgs &A, int ks, hipStream_t st);
 // segk_score_hint.hip: value-only top-2 on the matrix cores + exact stage that verifies a hint per row (cand.k on entry)
-int segk_dispatch_score_hint(segk_ctx *ctx, const ScoreArgs &A, const int32_t *remap, int64_t n_emb, int ks, hipStream_t st);
+int segk_dispatch_score_hint(segk_ctx *ctx, const ScoreArgs &A, const int32_t *remap, const int32_t *K_dev, int64_t n_emb, int ks, hipStream_t st);
 // segk_score_band.hip: the hinted path's undecided rows -- candidates inside the band of the filter's maximum, exact scores
 bool segk_band_applies(const ScoreArgs &A);
 int segk_launch_band(segk_ctx *ctx, const ScoreArgs &A, const float *thr, int64_t call_rows, int ks, hipStream_t st);

@@ -28,6 +28,18 @@
 //       component the filters' images carry as "absent" (an exact duplicate of a lower row, segk_kmeans_mark_duplicates)
 //       is no hint: its F is not a bound on anything.
 //
+//       The certificate holds on a SUPERSET of the filter values (the delta score pass rests on this).  Let S' be any multiset
+//       that contains F_h and, for every other current column k, a value >= F_k, and top1' >= top2' its two largest.  Suppose
+//           top1' - top2' > tau   and   f_h >= top1' - tau + E + dl.
+//       Then F_h >= f_h - E - dl >= top1' - tau > top2': F_h is the single largest member of S', every other member is
+//       <= top2', hence for every k != h: f_k <= F_k + E <= top2' + E < top1' - tau + E <= f_h - dl -- h is the reference's
+//       argmax.  Extra members (stale values of columns that have changed since) can only make the certificate fail, never
+//       pass wrongly.
+//
+//   Delta score pass (k_delta_prep, the delta launch of K1, k_hint_merge): while a call repeats on the same rows, (m1, m2) of
+//       the last FULL launch stay as the base, K1 multiplies only the columns whose image differs from that launch's snapshot
+//       (packed into leading tiles), and the merge certifies against base U delta, a superset as above.  See k_delta_prep.
+//
 // Results are those of segk_kmeans_score whatever the hints are (a wrong hint costs time, never correctness); the
 // full-size parity tests run this path against the C oracle row by row.
 #include "segk_kmeans_dev.h"
@@ -47,7 +59,8 @@ struct HintArgs {
     const unsigned char *ximg;      // fp16x2 row image (segk_corpus.Xb3): header, then plane 0 [n_emb][KP]
     const int32_t *ids;
     int64_t row0, n;
-    const float *tiles;             // first tile of the fp16x2 tile image (tiles_b3 + 1024)
+    const float *tiles;             // first tile of the fp16x2 tile image (tiles_b3 + 1024) K1 multiplies; a delta launch: of the packed image
+    const float *all_tiles;         // first tile of the model's whole image (the "absent" marks of the label map)
     int n_tiles, tpr, n_ranges;     // tiles per range, ranges
     float2 *part;                   // [n_ranges][n] (m1, m2) in the scaled domain of the images
     int K_max;
@@ -72,7 +85,22 @@ struct HintArgs {
     const int32_t *map;             // [K_max] previous label -> current label, or -1 (k_hint_map)
     const float *nxx;               // -|x|^2 per row in the reference's summation order (k_corpus_resid_sp)
     float4 *hint_out;               // [n] by position in the launch: {s = -|x - m_h|^2, f_h = x.m_h - |m_h|^2/2, bits of h (-1: no hint), 0}
+    // delta score pass (NULL / 0: none): the control words k_delta_prep left, which of the two launches this one is, the rows of
+    // `means` whose bits changed since the previous call
+    int32_t *ctl;
+    int delta;
+    const int32_t *meanchg;
+    float *snap_img;                // the base pass's image, refreshed by the full launch: [4 floats: exponent][n_tiles][KS * 256 + 32]
 };
+
+// ---- delta score pass: state and control ----------------------------------------------------------------------------------
+// ctl[0] mode word (SEGK_DELTA_*), [1] columns of the image that differ from the base pass's snapshot, [2] tiles of the packed
+// delta image (0 in full mode), [3] positions the hint waves skipped (cleared by k_delta_prep, added to by K1), [4] packed tiles
+// multiplied since the base pass, [5 + parity] rows of `means` that changed during the call of that parity, [7] ctl[1] of the
+// previous call, [8] the number of active components at the previous call
+#define SEGK_DELTA_MODE 1            /* K1 multiplies the packed changed columns only */
+#define SEGK_DELTA_SKIP 2            /* hint_out and snap_means32 are the previous call's, the relabelling is the identity */
+#define SEGK_MEANCHG_BIT 0x40000000  /* in the hint waves' label map: the float32 mean of this component changed since the previous call */
 
 // ---- K1 ---------------------------------------------------------------------------------------------------------------
 // NW waves per workgroup, one workgroup per CU.  NW = 4: ONE wave per SIMD with the whole register file (512 per lane) --
@@ -126,7 +154,7 @@ struct HintArgs {
 // 48 bytes per row.  Round 3 did this as a kernel of its own behind K1 (k_kmeans_hint_exact: 129 us, 572 MB fetched because
 // its range workgroups picked scattered rows); fused, the float32 corpus crosses HBM once per sweep, under the matrix work.
 template <int KS, int V>
-__device__ __forceinline__ void hint_wave_rows(const HintArgs &H, const int32_t *map /* LDS */, int64_t w, int64_t n_w)
+__device__ __forceinline__ void hint_wave_rows(const HintArgs &H, const int32_t *map /* LDS */, int64_t w, int64_t n_w, bool skip_ok)
 {
     constexpr int D = 16 * KS - 4 * V;
     constexpr int nfull = D & ~7, nblk = nfull >> 3, rem = D & 7;
@@ -149,16 +177,32 @@ __device__ __forceinline__ void hint_wave_rows(const HintArgs &H, const int32_t 
     int64_t s = w;
     // row ids two steps ahead, previous labels one step ahead: no load of a step waits for another load of the same step
     int32_t rid = -1, rid_n = -1, kprev = -1;
+    // delta score pass: the component the previous call scored for this position (its hint_out entry), one step ahead like the
+    // labels.  Where it is the current hint and that mean's bits have not changed, the entry IS this call's result: same row,
+    // same mean, same arithmetic -- no row, no mean, no store.
+    auto pz_of = [&](int64_t s_) -> int32_t {
+        const int64_t p_ = s_ * 32 + row;
+        return (skip_ok && p_ < H.n) ? __float_as_int(H.hint_out[p_].z) : -2;
+    };
+    int32_t pz = -2;
+    int n_skipped = 0;
     if (s < n_steps) {
         rid = rid_of(s);
         if (s + n_w < n_steps) rid_n = rid_of(s + n_w);
         kprev = rid >= 0 ? H.cand_k[rid] : -1;
+        pz = pz_of(s);
     }
     for (; s < n_steps; s += n_w) {
-        const int32_t hint = (rid >= 0 && kprev >= 0 && kprev < H.K_max) ? map[kprev] : -1;
+        int32_t hint = (rid >= 0 && kprev >= 0 && kprev < H.K_max) ? map[kprev] : -1;
+        const bool mchg = hint >= 0 && (hint & SEGK_MEANCHG_BIT) != 0;
+        if (hint >= 0) hint &= ~SEGK_MEANCHG_BIT;
         const int32_t rid_c = rid;
+        const bool skip = skip_ok && rid_c >= 0 && hint >= 0 && !mchg && pz == hint;
+        n_skipped += __popcll(__ballot(skip && h == 0));
         f32x4_t xv[NX], mv[NX];
-        {
+#pragma unroll
+        for (int b = 0; b < NX; b++) { xv[b] = f32x4_t{0.f, 0.f, 0.f, 0.f}; mv[b] = xv[b]; }
+        if (!skip) {
             int64_t r_any = rid_c >= 0 ? (int64_t)rid_c : (H.ids ? 0 : H.row0);
             if (H.dbg & 16) r_any &= 1023;                          // development: the rows from a cache-resident corner (timing)
             const uintptr_t xa = (uintptr_t)(H.xrows32 + r_any * H.ld32);
@@ -178,6 +222,7 @@ __device__ __forceinline__ void hint_wave_rows(const HintArgs &H, const int32_t 
             kprev = rid >= 0 ? H.cand_k[rid] : -1;
             const int64_t s2 = s + 2 * n_w;
             rid_n = s2 < n_steps ? rid_of(s2) : -1;
+            pz = s + n_w < n_steps ? pz_of(s + n_w) : -2;
         }
         // the reference's float32 -(deltas*deltas).sum() in numpy's pairwise order: this lane owns the strided accumulators
         // r_{4h..4h+3}
@@ -202,8 +247,9 @@ __device__ __forceinline__ void hint_wave_rows(const HintArgs &H, const int32_t 
         }
         const float sc = -res;                                     // -|x - m_h|^2
         const int64_t p = s * 32 + row;
-        if (h == 0 && p < H.n) H.hint_out[p] = make_float4(sc, 0.5f * (sc - nx), __int_as_float(rid_c >= 0 ? hint : -1), 0.f);
+        if (h == 0 && p < H.n && !skip) H.hint_out[p] = make_float4(sc, 0.5f * (sc - nx), __int_as_float(rid_c >= 0 ? hint : -1), 0.f);
     }
+    if (skip_ok && n_skipped > 0 && lane == 0) atomicAdd(H.ctl + 3, n_skipped);
 }
 
 // (launch bounds "two waves per SIMD" for both: 256 registers per lane, all of them vector registers.  Given 512 the compiler
@@ -225,6 +271,16 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 31, h = lane >> 5;
     const int R = H.n_ranges;
+    // delta score pass: the launch the mode word does not name returns at once; the delta launch reads its tile count from
+    // device memory (one range over the packed changed columns; none: no matrix work, the hint waves only)
+    int n_tiles = H.n_tiles;
+    bool skip_ok = false;
+    if (H.ctl) {
+        const int mw = H.ctl[0];
+        if ((mw & SEGK_DELTA_MODE) != H.delta) return;
+        skip_ok = (mw & SEGK_DELTA_SKIP) != 0;
+        if (H.delta) n_tiles = H.ctl[2];
+    }
     const bool is_hint = wave >= NW;                // waves NW .. 2 NW - 1: hint_wave_rows
     if (!is_hint) __builtin_amdgcn_s_setprio(2);    // the matrix waves first wherever the two kinds meet at an issue port
 #ifdef SEGK_STAMP
@@ -245,7 +301,7 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
         wgr = blockIdx.x / R;
     }
     const int t_lo = range * H.tpr;
-    int nt = H.n_tiles - t_lo;
+    int nt = n_tiles - t_lo;
     if (nt > H.tpr) nt = H.tpr;
     // (a workgroup without matrix work -- beyond the last whole set of ranges, or a range without tiles -- still runs its hint waves)
     const bool mm_on = wgr < n_wgr && nt > 0;
@@ -260,7 +316,7 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
     // then / the lifetime of its waves, half-way blended; k_hint_map, the small launch in front, does the arithmetic): nothing is
     // exchanged during the launch, and the results do not depend on who computes which rows.
     const unsigned long long fb_t0 = __builtin_amdgcn_s_memrealtime();
-    const bool fb = xcd_aware && H.fb_t != nullptr;
+    const bool fb = xcd_aware && H.fb_t != nullptr && !H.delta;     // (a delta launch is not power-limited: equal shares)
     int64_t own_lo = 0, own_hi = 0;
     if (H.own) {
         if (blockIdx.x == 0 && tid == 0) {
@@ -297,8 +353,12 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
         own_lo = __shfl(split, xcd);
         own_hi = xcd == 7 ? H.total_groups : __shfl(split, (xcd + 1) & 7);
         if (blockIdx.x == 0 && wave == 0 && lane < 8) {
-            H.fb_w[cur * 8 + x] = w / wsum;
-            if (H.fb_t) H.fb_t[next * 8 + x] = 0u;
+            // (a delta launch measures nothing: it hands the last full launch's shares and lifetimes on to the next launch)
+            H.fb_w[cur * 8 + x] = H.delta ? (wp > 0.f ? wp : 0.125f) : w / wsum;
+            if (H.fb_t) {
+                H.fb_t[next * 8 + x] = 0u;
+                if (H.delta) H.fb_t[cur * 8 + x] = tp;
+            }
         }
     }
     if (fb) {
@@ -469,7 +529,8 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
             for (int k = tid; k < H.K_max; k += 128 * NW) {
                 int v = H.remap ? H.remap[k] : k;
                 if (v < 0 || v >= H.K_max) v = -1;
-                else if (H.tiles[(int64_t)(v >> 5) * STRIDE + KS * P * 256 + (v & 31)] < -1.0e37f) v = -1;
+                else if (H.all_tiles[(int64_t)(v >> 5) * STRIDE + KS * P * 256 + (v & 31)] < -1.0e37f) v = -1;
+                if (skip_ok && v >= 0 && H.meanchg[v]) v |= SEGK_MEANCHG_BIT;
                 map_l[k] = v;
             }
         } else {
@@ -490,9 +551,16 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
     }
     __syncthreads();
     if (is_hint) {
+        // a full launch of the delta score pass is the new base: the first workgroup of every range leaves the image it
+        // multiplies (its LDS, the snapshot's layout) for k_delta_prep to compare the next calls' images with
+        if (H.ctl && !H.delta && mm_on && wgr == 0) {
+            float4 *dst = reinterpret_cast<float4 *>(H.snap_img + 4 + (int64_t)t_lo * TL);
+            const float4 *src = reinterpret_cast<const float4 *>(lds);
+            for (int i = tid - 64 * NW; i < nt * (TL / 4); i += 64 * NW) dst[i] = src[i];
+        }
         // every workgroup's hint waves take steps of 32 rows, strided over the whole grid: the chip walks the corpus front to back
         hint_wave_rows<KS, V>(H, reinterpret_cast<const int32_t *>(lds + H.tpr * TL), (int64_t)blockIdx.x * NW + (wave - NW),
-                              (int64_t)gridDim.x * NW);
+                              (int64_t)gridDim.x * NW, skip_ok);
         return;
     }
 #ifdef SEGK_STAMP
@@ -637,12 +705,164 @@ __global__ void k_hint_map(const int32_t *remap, const float *tiles_sp /* first 
     }
 }
 
+// ---- delta score pass: what changed since the base pass ------------------------------------------------------------------
+// One small launch in front of K1.  A workgroup per tile: every column of the image K1 multiplies (piece 0 of every k-step and the
+// constant, "absent" marks included) against the snapshot of the base pass, bit for bit; a changed image exponent changes the
+// scale of every filter value and so marks every column.  The changed columns are compacted into the leading tiles of the packed
+// delta image (any order: K1 keeps values, not indices; the free slots of the last tile carry the absent constant), and the mode
+// word says which of K1's two launches runs: FULL when there is no valid state, when the relabelling is not the identity, or when
+// the packed tiles exceed `cap` -- and then K1's full launch, which makes the new base, refreshes the snapshot.
+// A base is never built from delta results, so the changed columns only accumulate against the snapshot; two more reasons for a
+// full launch bring them back down: the chain has come to rest on changed columns (no new column in this call and no mean moved
+// during the previous one: one full pass, and every later call multiplies nothing), or the packed tiles multiplied since the base
+// add up to a whole table (the delta passes have then cost what the new base costs).
+// The workgroups behind the tiles': the rows of the float32 `means` against their copy of the previous call (a wave per row),
+// for the hint waves, and the copy refreshed.
+struct DeltaPrepArgs {
+    const float *tiles_hdr;         // tiles_b3 (header, then the tiles)
+    int n_tiles, stride;            // stride: floats per tile of the global image
+    int K_max, D;
+    const float *means32;
+    const int32_t *remap;
+    const int32_t *K_dev;           // [1] active components (NULL: all K_max)
+    int valid;                      // the state (snapshot, part_base, lab_base) belongs to this call's tuple
+    int hint_valid;                 // hint_out and snap_means32 are the previous call's on the same tuple
+    int cap;                        // packed tiles at most
+    int budget;                     // packed tiles multiplied since the base at most
+    int seq;                        // number of this launch on the context (the parity of the means-changed counters)
+    int32_t *ctl, *colchg, *meanchg;
+    float *snap_img;                // [4 floats: image exponent][n_tiles][KS * 256 + 32]
+    float *packed;                  // [n_tiles][stride]
+    float *snap_means;              // [K_max][D]
+};
+
+#define SEGK_PREP_THREADS 256
+#define SEGK_PREP_COLS 4            /* at most 32 * SEGK_PREP_COLS tiles (four LDS ranges of 32) */
+// Workgroups 0 .. n_tiles - 1: one tile each (a lane per (lane half, column), the k-steps over the four waves); the changed
+// columns take their packed slots by one atomic per tile and are copied there at once (a call that turns out FULL never reads
+// them); the workgroup that finishes last knows the count and writes the mode.  The snapshot itself is refreshed by K1's full
+// launch, which has every tile in LDS anyway.  The workgroups behind: the rows of `means`.
+template <int KS>
+__global__ __launch_bounds__(SEGK_PREP_THREADS) void k_delta_prep(DeltaPrepArgs P)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr int NWV = SEGK_PREP_THREADS / 64;
+    if ((int)blockIdx.x >= P.n_tiles) {
+        const int n_w = (gridDim.x - P.n_tiles) * NWV;
+        for (int k = (blockIdx.x - P.n_tiles) * NWV + wave; k < P.K_max; k += n_w) {
+            const int *cur = (const int *)(P.means32 + (int64_t)k * P.D);
+            int *snap = (int *)(P.snap_means + (int64_t)k * P.D);
+            bool chg = false;
+            for (int d = lane; d < P.D; d += 64) {
+                const int c = cur[d];
+                chg |= c != snap[d];
+                snap[d] = c;
+            }
+            const bool any = __any(chg);
+            if (lane == 0) {
+                P.meanchg[k] = (any || !P.hint_valid) ? 1 : 0;
+                if (any) atomicAdd(P.ctl + 5 + (P.seq & 1), 1);
+            }
+        }
+        return;
+    }
+    __shared__ int s_chg[32], s_slot[32], s_last, s_nonid;
+    constexpr int TL = KS * 256 + 32, c_off = KS * 512;
+    const int t = blockIdx.x, c = lane & 31;
+    const float *g = P.tiles_hdr + 1024 + (int64_t)t * P.stride;
+    const float *q = P.snap_img + 4 + (int64_t)t * TL;
+    const int e_cur = ((const int *)P.tiles_hdr)[0];
+    const bool all = !P.valid || e_cur != ((const int *)P.snap_img)[0];
+    if (tid < 32) s_chg[tid] = 0;
+    if (tid == 0) s_nonid = 0;
+    __syncthreads();
+    if (!all) {
+        bool chg = false;
+        for (int ks = wave; ks < KS; ks += NWV) {
+            const int4 a = *reinterpret_cast<const int4 *>(g + ks * 512 + lane * 4);
+            const int4 b = *reinterpret_cast<const int4 *>(q + ks * 256 + lane * 4);
+            chg |= a.x != b.x || a.y != b.y || a.z != b.z || a.w != b.w;
+        }
+        if (tid < 32) chg |= __float_as_int(g[c_off + c]) != __float_as_int(q[KS * 256 + c]);
+        if (chg) atomicOr(&s_chg[c], 1);
+    }
+    __syncthreads();
+    if (wave == 0) {
+        const bool chg = lane < 32 && (all || s_chg[lane] != 0);
+        if (lane < 32) P.colchg[t * 32 + lane] = chg ? 1 : 0;
+        const unsigned long long mask = __ballot(chg);
+        int base = 0;
+        if (lane == 0 && mask != 0ull) base = atomicAdd(P.ctl + 9, __popcll(mask));
+        base = __shfl(base, 0);
+        if (lane < 32) s_slot[lane] = chg ? base + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0)) : -1;
+    }
+    __syncthreads();
+    {
+        const int sl = s_slot[c];
+        if (P.valid && sl >= 0 && sl < P.cap * 32) {
+            float *o = P.packed + (int64_t)(sl >> 5) * P.stride;
+            const int l2 = (lane & 32) + (sl & 31);
+            for (int ks = wave; ks < KS; ks += NWV)
+                *reinterpret_cast<int4 *>(o + ks * 512 + l2 * 4) = *reinterpret_cast<const int4 *>(g + ks * 512 + lane * 4);
+            if (tid < 32) o[c_off + (sl & 31)] = g[c_off + c];
+        }
+    }
+    // the workgroup that finishes last: the count is complete
+    __threadfence();
+    __syncthreads();
+    if (tid == 0) s_last = atomicAdd(P.ctl + 10, 1) == P.n_tiles - 1 ? 1 : 0;
+    __syncthreads();
+    if (!s_last) return;
+    __threadfence();
+    if (P.remap) {
+        // the labels rows can carry: below the number of active components at the previous call, or now (the batch finalize
+        // rewrites the table's entries beyond as it compacts freshly emptied rows: no row names those)
+        int K_lab = P.K_dev ? *P.K_dev : P.K_max;
+        if (K_lab < P.ctl[8]) K_lab = P.ctl[8];
+        if (K_lab > P.K_max || !P.valid) K_lab = P.K_max;
+        bool bad = false;
+        for (int k = tid; k < K_lab; k += SEGK_PREP_THREADS) bad |= P.remap[k] != k;
+        if (bad) s_nonid = 1;
+    }
+    __syncthreads();
+    const int n_chg = atomicAdd(P.ctl + 9, 0), n_packed = (n_chg + 31) >> 5;
+    // (the counter of the previous call's parity: complete, that launch is over; this launch's other workgroups use the other)
+    const int moved_prev = P.ctl[5 + ((P.seq + 1) & 1)], acc = P.ctl[4], chg_prev = P.ctl[7];
+    const bool at_rest = n_chg > 0 && n_chg == chg_prev && moved_prev == 0;
+    const bool delta = P.valid && !s_nonid && n_packed <= P.cap && !at_rest && acc + n_packed <= P.budget;
+    __syncthreads();
+    if (tid == 0) {
+        P.ctl[4] = delta ? acc + n_packed : 0;
+        P.ctl[5 + ((P.seq + 1) & 1)] = 0;
+        P.ctl[7] = delta ? n_chg : 0;
+        P.ctl[8] = P.K_dev ? *P.K_dev : P.K_max;
+        P.ctl[0] = (delta ? SEGK_DELTA_MODE : 0) | ((P.hint_valid && !s_nonid) ? SEGK_DELTA_SKIP : 0);
+        P.ctl[1] = n_chg;
+        P.ctl[2] = delta ? n_packed : 0;
+        P.ctl[3] = 0;
+        P.ctl[9] = 0;
+        P.ctl[10] = 0;
+        if (!delta) ((int *)P.snap_img)[0] = e_cur;
+    }
+    // the free slots of the last packed tile: absent (their operands are whatever finite column was there before, or zero)
+    if (delta && tid < 32 && n_chg + tid < n_packed * 32) {
+        const int sl = n_chg + tid;
+        P.packed[(int64_t)(sl >> 5) * P.stride + c_off + (sl & 31)] = -3.0e38f;
+    }
+}
+
 struct HintMergeArgs {
     const float2 *part;             // K1's matrix waves: (m1, m2) per (range, position)
     const float4 *hint_out;         // K1's hint waves: {s, f_h, bits of h, 0} per position
     int n_ranges;
     const float *tiles_hdr;         // tiles_b3: [0] exponent b, [1] E_m
     const unsigned char *ximg;      // row image header: [1] exponent a
+    // delta score pass (ctl NULL: none)
+    const int32_t *ctl;
+    const float2 *part_delta;       // (m1, m2) per position over the packed changed columns
+    int32_t *lab_base;              // per position: the label the base pass certified, or -1
+    const int32_t *colchg;          // per column: its image differs from the base pass's
+    int32_t *stats_host;            // host-mapped [4] (segk_kmeans_delta_stats)
 };
 
 // K2 (round 4): the certificate.  Per row the filter's top-2 merged over the ranges, the hinted component's exact score s and its
@@ -663,6 +883,23 @@ __global__ __launch_bounds__(SEGK_MERGE_THREADS) void k_hint_merge(ScoreArgs A, 
     __shared__ int32_t ucnt, ubase;
     const int tid = threadIdx.x, lane = tid & 63;
     if (tid == 0) ucnt = 0;
+    // delta score pass.  In delta mode `part` is still the BASE pass's (m1, m2): values of the columns as they were then.  For a
+    // column whose image has not changed that is its current filter value F_k; for a changed one it is stale, and the current
+    // value is in part_delta.  The certificate holds on such a superset (head of the file): the stale values can only make it
+    // fail.  One case is worth repairing: the row's hint h is the label the base pass certified (lab_base) and column h has
+    // changed.  Then the base's largest value over all ranges is the stale F_h -- the certificate made it the single largest --,
+    // and with it in the set the fresh F_h could never lead by tau.  Drop it: every OTHER column's base value is at most the
+    // base's second largest t2 (the larger of the ranges' m2 and of their m1 but the largest), so {t2, t2} stands for all of them
+    // (a value >= F_k for every unchanged k != h; the changed ones have their current value in part_delta, F_h among them).
+    const int mw = H.ctl ? H.ctl[0] : 0;
+    const bool delta = (mw & SEGK_DELTA_MODE) != 0;
+    const int n_chg = H.ctl ? H.ctl[1] : 0, n_packed = H.ctl ? H.ctl[2] : 0;
+    if (H.stats_host && blockIdx.x == 0 && tid == 0) {
+        H.stats_host[1] = n_chg;
+        H.stats_host[2] = n_packed;
+        H.stats_host[3] = H.ctl ? H.ctl[3] : 0;
+        __hip_atomic_store(H.stats_host, H.ctl ? 1 + (delta ? 1 : 0) : 0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
     __syncthreads();
     const int64_t p_lo = (int64_t)blockIdx.x * per, p_hi = p_lo + per < A.n ? p_lo + per : A.n;
     const int e_ab = ((const int *)H.ximg)[1] + ((const int *)H.tiles_hdr)[0];
@@ -675,7 +912,7 @@ __global__ __launch_bounds__(SEGK_MERGE_THREADS) void k_hint_merge(ScoreArgs A, 
     for (int64_t p0 = p_lo; p0 < p_hi; p0 += SEGK_MERGE_THREADS * U) {
         int32_t rid[U];
         float4 ho[U];
-        float t1[U], t2[U], xnb[U], xer[U];
+        float t1[U], t2[U], xnb[U], xer[U], d1[U];
 #pragma unroll
         for (int j = 0; j < U; j++) {
             const int64_t p = p0 + j * SEGK_MERGE_THREADS + tid;
@@ -698,6 +935,20 @@ __global__ __launch_bounds__(SEGK_MERGE_THREADS) void k_hint_merge(ScoreArgs A, 
                 xnb[j] = A.xnorm[rid[j]];
                 xer[j] = A.xerr[rid[j]];
             }
+            d1[j] = NEG_INF_F;
+            if (rid[j] >= 0 && delta) {
+                const int32_t hint = __float_as_int(ho[j].z);
+                if (hint >= 0 && H.colchg[hint] && H.lab_base[p] == hint) {
+                    t1[j] = t2[j];
+                }
+                if (n_packed > 0) {
+                    const float2 pv = H.part_delta[p];
+                    d1[j] = pv.x;
+                    const float n1 = fmaxf(t1[j], pv.x);
+                    t2[j] = fmaxf(fminf(t1[j], pv.x), fmaxf(t2[j], pv.y));
+                    t1[j] = n1;
+                }
+            }
         }
 #pragma unroll
         for (int j = 0; j < U; j++) {
@@ -713,8 +964,11 @@ __global__ __launch_bounds__(SEGK_MERGE_THREADS) void k_hint_merge(ScoreArgs A, 
                 const float tau = filter_tau_h1(xnb[j], M, A.D, xer[j], Em);
                 // the band the reference's argmax lies in: F >= top1 - tau (scaled domain; the subtraction's own rounding and a
                 // little more taken off)
+                // (delta mode with changed columns: t1 may be a stale value, no bound on anything -- below)
+                float lower = t1[j];
                 thr = t1[j] - tau * scale * 1.000001f;
                 thr -= 4e-7f * fabsf(t1[j]);
+                bool ok = false;
                 if (hint >= 0) {
                     const float top1 = t1[j] * unscale, top2 = t2[j] * unscale;          // powers of two: exact
                     const float u = 5.9604645e-8f;
@@ -723,11 +977,29 @@ __global__ __launch_bounds__(SEGK_MERGE_THREADS) void k_hint_merge(ScoreArgs A, 
                     const float rnd = 1.00001f * fminf((xnb[j] + xer[j]) * Em + xer[j] * M, 1.01f * 9.765625e-4f * xnb[j] * M);
                     const float s2 = xnb[j] + M;
                     const float dl = ((float)(A.D / 8 + 13) + 4.f) * u * s2 * s2;
-                    const bool ok = (top1 - top2 > tau) && (ho[j].y >= top1 - tau + (e1 + rnd + dl) * 1.0001f);
+                    ok = (top1 - top2 > tau) && (ho[j].y >= top1 - tau + (e1 + rnd + dl) * 1.0001f);
                     if (ok) {
                         A.cand.k[rid[j]] = hint;
                         A.cand.s[rid[j]] = (double)ho[j].x;
                         und = false;
+                    }
+                    // the current F_h is at least f_h - E - dl: a lower bound of the current top1 whatever the base holds
+                    lower = (ho[j].y - (e1 + rnd + dl) * 1.0001f) * scale;
+                    lower -= 4e-7f * fabsf(lower);
+                }
+                if (H.lab_base && !delta) H.lab_base[p0 + j * SEGK_MERGE_THREADS + tid] = ok ? hint : -1;
+                if (und && delta && n_chg > 0) {
+                    // The band threshold must stay a LOWER bound of (current top1) - tau.  Current values this row has: those of
+                    // the changed columns (d1, their largest) and the bound from the hinted score; a lower threshold only yields
+                    // more candidates.  Without a hint there is no usable bound: the full scan.
+                    if (hint < 0) {
+                        und = false;
+                        const int q2 = atomicAdd(A.cand.count, 1);
+                        if (q2 < A.amb_cap) A.cand.queue[q2] = rid[j];
+                    } else {
+                        lower = fmaxf(lower, d1[j]);
+                        thr = lower - tau * scale * 1.000001f;
+                        thr -= 4e-7f * fabsf(lower);
                     }
                 }
             }
@@ -765,7 +1037,7 @@ __global__ __launch_bounds__(SEGK_MERGE_THREADS) void k_hint_merge(ScoreArgs A, 
 
 // ---------------------------------------------------------------------------------------------------------------------
 template <int KS>
-static int launch_score_hint(segk_ctx *ctx, ScoreArgs A, const int32_t *remap, int64_t n_emb, hipStream_t st)
+static int launch_score_hint(segk_ctx *ctx, ScoreArgs A, const int32_t *remap, const int32_t *K_dev, int64_t n_emb, hipStream_t st)
 {
     const int n_cu = ctx->n_cu;
     // ---- workspaces: the second stage's queue (as the pre-filter path), K1's partial top-2, the hint map
@@ -804,7 +1076,8 @@ static int launch_score_hint(segk_ctx *ctx, ScoreArgs A, const int32_t *remap, i
     // [n_ranges][n] (m1, m2) of the matrix waves, then [n] {s, f_h, h, 0} of the hint waves
     const size_t part_bytes = ((size_t)n_ranges * (size_t)A.n * sizeof(float2) + 255) & ~(size_t)255;
     const size_t need_part = part_bytes + (size_t)A.n * sizeof(float4);
-    if (ctx->hint_part_bytes < need_part || !ctx->hint_map || ctx->hint_map_k < A.K_max) {
+    const bool realloc_part = ctx->hint_part_bytes < need_part;
+    if (realloc_part || !ctx->hint_map || ctx->hint_map_k < A.K_max) {
         SEGK_REQUIRE(!ctx->capturing, "workspaces must exist before a graph capture (run the sequence once first)");
         SEGK_CHECK_HIP(hipStreamSynchronize(st));
         if (ctx->hint_part_bytes < need_part) {
@@ -865,6 +1138,58 @@ static int launch_score_hint(segk_ctx *ctx, ScoreArgs A, const int32_t *remap, i
     }
     // k_hint_map's work is K1's own (H.own) unless rows are left out (their (m1, m2) must be initialised in front of K1)
     const bool own = k1_groups == total_groups;
+
+    // ---- delta score pass: K1's (m1, m2) of the last FULL launch stay in hint_part as the base; while the call tuple repeats,
+    // k_delta_prep finds the columns whose image changed since and K1 multiplies those alone.  SEGK_SCORE_DELTA=0: never.
+    const bool delta_on = segk_env_int("SEGK_SCORE_DELTA", 1) != 0 && band && own && A.ids == nullptr && A.n_tiles <= 32 * SEGK_PREP_COLS;
+    const void *key[6] = {A.X32, A.xrows32, A.tiles, A.means32, A.cand.k, A.cand.s};
+    const int64_t key_n[5] = {A.row0, A.n, n_emb, A.K_max, A.D};
+    bool state_valid = delta_on && !realloc_part && ctx->delta_valid && memcmp(key, ctx->delta_key, sizeof(key)) == 0 &&
+                       memcmp(key_n, ctx->delta_key_n, sizeof(key_n)) == 0;
+    ctx->delta_valid = 0;
+    int32_t *d_ctl = nullptr, *d_colchg = nullptr, *d_meanchg = nullptr, *d_lab = nullptr;
+    float2 *d_part = nullptr;
+    float *d_packed = nullptr, *d_snap = nullptr;
+    int delta_cap = 0;
+    if (delta_on) {
+        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const size_t o_col = 256, o_mean = o_col + up((size_t)A.n_tiles * 32 * 4), o_snap = o_mean + up((size_t)A.K_max * 4),
+                     o_pack = o_snap + up(((size_t)A.n_tiles * TL + 4) * 4), o_sm = o_pack + up((size_t)A.n_tiles * stride_sp * 4),
+                     o_pd = o_sm + up((size_t)A.K_max * A.D * 4), o_lab = o_pd + up((size_t)A.n * 8), need = o_lab + up((size_t)A.n * 4);
+        if (ctx->delta_bytes != need) {
+            SEGK_CHECK_HIP(hipStreamSynchronize(st));
+            if (ctx->delta_buf) (void)hipFree(ctx->delta_buf);
+            ctx->delta_buf = nullptr;
+            ctx->delta_bytes = 0;
+            SEGK_CHECK_HIP(hipMalloc(&ctx->delta_buf, need));
+            ctx->delta_bytes = need;
+            state_valid = false;
+            // (the packed image's free slots must hold finite operands: zero now, copies of real columns ever after)
+            SEGK_CHECK_HIP(hipMemsetAsync(ctx->delta_buf, 0, o_sm, st));
+        }
+        unsigned char *b = (unsigned char *)ctx->delta_buf;
+        d_ctl = (int32_t *)b; d_colchg = (int32_t *)(b + o_col); d_meanchg = (int32_t *)(b + o_mean);
+        d_snap = (float *)(b + o_snap);
+        d_packed = (float *)(b + o_pack); d_part = (float2 *)(b + o_pd); d_lab = (int32_t *)(b + o_lab);
+        // packed tiles at most: a full launch's range (measured on the headline corpus against 2, 4, 8, 12 and 20 tiles:
+        // profiles/README.md), never more than fit in K1's LDS
+        delta_cap = segk_env_int("SEGK_DELTA_CAP", tpr);
+        if (delta_cap > max_tiles) delta_cap = max_tiles;
+        if (delta_cap < 1) delta_cap = 1;
+        DeltaPrepArgs P{};
+        P.tiles_hdr = A.tiles; P.n_tiles = A.n_tiles; P.stride = stride_sp;
+        P.K_max = A.K_max; P.D = A.D; P.means32 = A.means32; P.remap = remap; P.K_dev = K_dev;
+        P.valid = state_valid ? 1 : 0; P.hint_valid = state_valid ? 1 : 0; P.cap = delta_cap;
+        P.budget = segk_env_int("SEGK_DELTA_BUDGET", A.n_tiles);
+        P.seq = (int)(ctx->delta_seq++ & 1u);
+        P.ctl = d_ctl; P.colchg = d_colchg; P.meanchg = d_meanchg;
+        P.snap_img = (float *)(b + o_snap); P.packed = d_packed; P.snap_means = (float *)(b + o_sm);
+        const int rows_blocks = (A.K_max + 7) / 8 < 128 ? (A.K_max + 7) / 8 : 128;
+        hipLaunchKernelGGL(k_delta_prep<KS>, dim3(A.n_tiles + rows_blocks), dim3(SEGK_PREP_THREADS), 0, st, P);
+        memcpy(ctx->delta_key, key, sizeof(key));
+        memcpy(ctx->delta_key_n, key_n, sizeof(key_n));
+        ctx->delta_valid = 1;
+    }
     if (!own) {
         const int64_t skipped = A.n - k1_groups * 64 > 0 ? A.n - k1_groups * 64 : 0;
         const int64_t nthr = skipped > A.K_max ? skipped : A.K_max;
@@ -878,6 +1203,10 @@ static int launch_score_hint(segk_ctx *ctx, ScoreArgs A, const int32_t *remap, i
     H.ximg = (const unsigned char *)A.X32;
     H.ids = A.ids; H.row0 = A.row0; H.n = A.n;
     H.tiles = A.tiles + 1024;
+    H.all_tiles = A.tiles + 1024;
+    H.ctl = d_ctl;
+    H.meanchg = d_meanchg;
+    H.snap_img = d_snap;
     H.n_tiles = A.n_tiles; H.tpr = tpr; H.n_ranges = n_ranges;
     H.part = (float2 *)ctx->hint_part;
     H.K_max = A.K_max;
@@ -903,13 +1232,23 @@ static int launch_score_hint(segk_ctx *ctx, ScoreArgs A, const int32_t *remap, i
     H.nxx = A.xerr + n_emb;                                      // -|x|^2 per row, behind the residual norms
     H.hint_out = (float4 *)((unsigned char *)ctx->hint_part + part_bytes);
     const size_t lds1 = (size_t)tpr * TL * sizeof(float) + map_bytes;
+    // the delta launch: one range over the packed image, its tile count in ctl[2]; every workgroup's slots over all rows
+    HintArgs HD = H;
+    HD.delta = 1;
+    HD.tiles = d_packed;
+    HD.n_tiles = 0; HD.tpr = delta_cap; HD.n_ranges = 1;
+    HD.part = d_part;
+    const size_t lds_d = (size_t)delta_cap * TL * sizeof(float) + map_bytes;
+    int grid_d = n_cu;
+    if ((int64_t)grid_d > (A.n + 255) / 256) grid_d = (int)((A.n + 255) / 256);
     const bool prof = segk_prof_now(ctx);
     const int slot = ctx->prof_n % SEGK_PROF_SLOTS;
 #define SEGK_K1_LAUNCH(VV)                                                                                                  \
     do {                                                                                                                     \
-        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_kmeans_top2_rs<KS, VV, 4>, lds1));                                       \
+        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_kmeans_top2_rs<KS, VV, 4>, lds1 > lds_d ? lds1 : lds_d));                                     \
         if (prof) SEGK_CHECK_HIP(hipEventRecord(ctx->prof_ev[slot][0], st));                                                 \
         hipLaunchKernelGGL((k_kmeans_top2_rs<KS, VV, 4>), dim3((unsigned)grid1), dim3(512), lds1, st, H);                    \
+        if (delta_on) hipLaunchKernelGGL((k_kmeans_top2_rs<KS, VV, 4>), dim3((unsigned)grid_d), dim3(512), lds_d, st, HD);   \
     } while (0)
     switch ((16 * KS - A.D) / 4) {
         case 0: SEGK_K1_LAUNCH(0); break;
@@ -933,6 +1272,11 @@ static int launch_score_hint(segk_ctx *ctx, ScoreArgs A, const int32_t *remap, i
     E.n_ranges = n_ranges;
     E.tiles_hdr = A.tiles;
     E.ximg = (const unsigned char *)A.X32;
+    E.ctl = d_ctl;
+    E.part_delta = d_part;
+    E.lab_base = d_lab;
+    E.colchg = d_colchg;
+    E.stats_host = ctx->delta_host_dev;
     {
         // one workgroup per CU, each a contiguous run of at most SEGK_MERGE_ROWS rows
         int64_t grid2 = (int64_t)n_cu;
@@ -959,17 +1303,17 @@ static int launch_score_hint(segk_ctx *ctx, ScoreArgs A, const int32_t *remap, i
     return SEGK_OK;
 }
 
-int segk_dispatch_score_hint(segk_ctx *ctx, const ScoreArgs &A, const int32_t *remap, int64_t n_emb, int ks, hipStream_t st)
+int segk_dispatch_score_hint(segk_ctx *ctx, const ScoreArgs &A, const int32_t *remap, const int32_t *K_dev, int64_t n_emb, int ks, hipStream_t st)
 {
     switch (ks) {
-        case 1: return launch_score_hint<1>(ctx, A, remap, n_emb, st);
-        case 2: return launch_score_hint<2>(ctx, A, remap, n_emb, st);
-        case 3: return launch_score_hint<3>(ctx, A, remap, n_emb, st);
-        case 4: return launch_score_hint<4>(ctx, A, remap, n_emb, st);
-        case 5: return launch_score_hint<5>(ctx, A, remap, n_emb, st);
-        case 6: return launch_score_hint<6>(ctx, A, remap, n_emb, st);
-        case 7: return launch_score_hint<7>(ctx, A, remap, n_emb, st);
-        case 8: return launch_score_hint<8>(ctx, A, remap, n_emb, st);
+        case 1: return launch_score_hint<1>(ctx, A, remap, K_dev, n_emb, st);
+        case 2: return launch_score_hint<2>(ctx, A, remap, K_dev, n_emb, st);
+        case 3: return launch_score_hint<3>(ctx, A, remap, K_dev, n_emb, st);
+        case 4: return launch_score_hint<4>(ctx, A, remap, K_dev, n_emb, st);
+        case 5: return launch_score_hint<5>(ctx, A, remap, K_dev, n_emb, st);
+        case 6: return launch_score_hint<6>(ctx, A, remap, K_dev, n_emb, st);
+        case 7: return launch_score_hint<7>(ctx, A, remap, K_dev, n_emb, st);
+        case 8: return launch_score_hint<8>(ctx, A, remap, K_dev, n_emb, st);
         default: break;
     }
     segk_set_error("hinted score path: D out of range");

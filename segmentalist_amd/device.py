@@ -318,6 +318,14 @@ class DeviceKMeans(object):
         check(self._L.segk_kmeans_score(self._ctx, self._cp(), C.byref(self.m), p, int(row0), int(n),
                                         C.byref(self.cand), ptr(self.status), _abi.stream()))
 
+    def delta_stats(self):
+        """What the delta score pass did in the latest hinted call whose figures have arrived (segk_kmeans_delta_stats, no
+        synchronisation): (mode: 1 delta, 0 full, -1 no delta state; changed image columns; packed tiles multiplied;
+        positions whose hinted score was taken over from the previous call)."""
+        out = (C.c_int32 * 4)()
+        check(self._L.segk_kmeans_delta_stats(self._ctx, out))
+        return tuple(int(v) for v in out)
+
     def score_ptr(self, ids_ptr, n):
         check(self._L.segk_kmeans_score(self._ctx, self._cp(), C.byref(self.m), C.c_void_p(ids_ptr), 0, int(n),
                                         C.byref(self.cand), ptr(self.status), _abi.stream()))
