@@ -36,9 +36,12 @@
 //       argmax.  Extra members (stale values of columns that have changed since) can only make the certificate fail, never
 //       pass wrongly.
 //
-//   Delta score pass (k_delta_prep, the delta launch of K1, k_hint_merge): while a call repeats on the same rows, (m1, m2) of
+//   Delta score pass (k_delta_prep, K1 in delta mode, k_hint_merge): while a call repeats on the same rows, (m1, m2) of
 //       the last FULL launch stay as the base, K1 multiplies only the columns whose image differs from that launch's snapshot
 //       (packed into leading tiles), and the merge certifies against base U delta, a superset as above.  See k_delta_prep.
+//       K1 is ONE launch either way: it reads the mode word k_delta_prep left and takes the full or the delta parameter set
+//       (HintArgs), with the larger of the two grids and LDS sizes.  The hint waves decide which positions take their score
+//       over from the previous call for a chunk of steps per round trip (hint_wave_rows).
 //
 // Results are those of segk_kmeans_score whatever the hints are (a wrong hint costs time, never correctness); the
 // full-size parity tests run this path against the C oracle row by row.
@@ -48,6 +51,7 @@
 // workgroups (one table range each) all scan every row: the mark tells a row that still waits for its range's workgroup from
 // one that workgroup has already given its final label.
 #define SEGK_HINT_BIT 0x20000000
+#define SEGK_HINT_CHUNK 8            /* steps of 32 rows whose skip a hint wave decides in one round trip (delta score pass) */
 #define SEGK_HINT_MAX_TPR 32         /* tiles per LDS range of K1 at most (its fill: one thread per float4 of the constants) */
 
 // development, timing only (-DSEGK_K1_ABL=n, results wrong): 1 no drain in the tile loop, 2 no operand refill from LDS
@@ -59,10 +63,10 @@ struct HintArgs {
     const unsigned char *ximg;      // fp16x2 row image (segk_corpus.Xb3): header, then plane 0 [n_emb][KP]
     const int32_t *ids;
     int64_t row0, n;
-    const float *tiles;             // first tile of the fp16x2 tile image (tiles_b3 + 1024) K1 multiplies; a delta launch: of the packed image
+    const float *tiles;             // first tile of the fp16x2 tile image (tiles_b3 + 1024) K1 multiplies in full mode
     const float *all_tiles;         // first tile of the model's whole image (the "absent" marks of the label map)
-    int n_tiles, tpr, n_ranges;     // tiles per range, ranges
-    float2 *part;                   // [n_ranges][n] (m1, m2) in the scaled domain of the images
+    int n_tiles, tpr, n_ranges;     // full mode: tiles, tiles per range, ranges
+    float2 *part;                   // full mode: [n_ranges][n] (m1, m2) in the scaled domain of the images
     int K_max;
     int dbg;                        // development (SEGK_HINT_DBG, results wrong): 1 no result stores, 2 no hint loads / marks
     unsigned long long *stamp;      // development (-DSEGK_STAMP builds): per wave {cycles in the row waits, in the tile loops, total, groups}
@@ -85,11 +89,16 @@ struct HintArgs {
     const int32_t *map;             // [K_max] previous label -> current label, or -1 (k_hint_map)
     const float *nxx;               // -|x|^2 per row in the reference's summation order (k_corpus_resid_sp)
     float4 *hint_out;               // [n] by position in the launch: {s = -|x - m_h|^2, f_h = x.m_h - |m_h|^2/2, bits of h (-1: no hint), 0}
-    // delta score pass (NULL / 0: none): the control words k_delta_prep left, which of the two launches this one is, the rows of
-    // `means` whose bits changed since the previous call
+    // delta score pass (NULL / 0: none): the control words k_delta_prep left and the rows of `means` whose bits changed since the
+    // previous call.  ONE launch serves both modes: the kernel reads the mode word and takes the full parameter set above or the
+    // delta set below (one range over the packed image, its tile count in ctl[2]); the launch has the larger of the two grids
+    // and LDS sizes, and a workgroup beyond the grid of the mode that runs returns.
     int32_t *ctl;
-    int delta;
     const int32_t *meanchg;
+    const float *d_tiles;           // first tile of the packed image of the changed columns
+    int d_tpr;                      // tiles of the packed image at most (the label map sits behind them in LDS)
+    float2 *d_part;                 // [n] (m1, m2) over the packed columns
+    int grid_f, grid_d;             // the grid of either mode
     float *snap_img;                // the base pass's image, refreshed by the full launch: [4 floats: exponent][n_tiles][KS * 256 + 32]
 };
 
@@ -174,31 +183,9 @@ __device__ __forceinline__ void hint_wave_rows(const HintArgs &H, const int32_t 
         const int64_t p_ = s_ * 32 + row;
         return p_ < H.n ? (H.ids ? H.ids[p_] : (int32_t)(H.row0 + p_)) : -1;
     };
-    int64_t s = w;
-    // row ids two steps ahead, previous labels one step ahead: no load of a step waits for another load of the same step
-    int32_t rid = -1, rid_n = -1, kprev = -1;
-    // delta score pass: the component the previous call scored for this position (its hint_out entry), one step ahead like the
-    // labels.  Where it is the current hint and that mean's bits have not changed, the entry IS this call's result: same row,
-    // same mean, same arithmetic -- no row, no mean, no store.
-    auto pz_of = [&](int64_t s_) -> int32_t {
-        const int64_t p_ = s_ * 32 + row;
-        return (skip_ok && p_ < H.n) ? __float_as_int(H.hint_out[p_].z) : -2;
-    };
-    int32_t pz = -2;
-    int n_skipped = 0;
-    if (s < n_steps) {
-        rid = rid_of(s);
-        if (s + n_w < n_steps) rid_n = rid_of(s + n_w);
-        kprev = rid >= 0 ? H.cand_k[rid] : -1;
-        pz = pz_of(s);
-    }
-    for (; s < n_steps; s += n_w) {
-        int32_t hint = (rid >= 0 && kprev >= 0 && kprev < H.K_max) ? map[kprev] : -1;
-        const bool mchg = hint >= 0 && (hint & SEGK_MEANCHG_BIT) != 0;
-        if (hint >= 0) hint &= ~SEGK_MEANCHG_BIT;
-        const int32_t rid_c = rid;
-        const bool skip = skip_ok && rid_c >= 0 && hint >= 0 && !mchg && pz == hint;
-        n_skipped += __popcll(__ballot(skip && h == 0));
+    // one step: the hinted component `hint` (-1: none) of row rid_c (-1: no row) scored and stored unless `skip`; `mid` runs
+    // between the step's loads and its arithmetic (the serial loop's prefetch of the next step)
+    auto step_body = [&](int64_t s, int32_t rid_c, int32_t hint, bool skip, auto &&mid) {
         f32x4_t xv[NX], mv[NX];
 #pragma unroll
         for (int b = 0; b < NX; b++) { xv[b] = f32x4_t{0.f, 0.f, 0.f, 0.f}; mv[b] = xv[b]; }
@@ -216,14 +203,7 @@ __device__ __forceinline__ void hint_wave_rows(const HintArgs &H, const int32_t 
         }
         const float nx = rid_c >= 0 ? H.nxx[rid_c] : 0.f;
         if (H.dbg & 64) __builtin_amdgcn_s_sleep(64);               // development: paced hint waves
-        // the next step's previous labels and the row ids of the step after it travel under this step's arithmetic
-        {
-            rid = rid_n;
-            kprev = rid >= 0 ? H.cand_k[rid] : -1;
-            const int64_t s2 = s + 2 * n_w;
-            rid_n = s2 < n_steps ? rid_of(s2) : -1;
-            pz = s + n_w < n_steps ? pz_of(s + n_w) : -2;
-        }
+        mid();
         // the reference's float32 -(deltas*deltas).sum() in numpy's pairwise order: this lane owns the strided accumulators
         // r_{4h..4h+3}
         f32x2_t rl = {0.f, 0.f}, rh = {0.f, 0.f};
@@ -248,8 +228,89 @@ __device__ __forceinline__ void hint_wave_rows(const HintArgs &H, const int32_t 
         const float sc = -res;                                     // -|x - m_h|^2
         const int64_t p = s * 32 + row;
         if (h == 0 && p < H.n && !skip) H.hint_out[p] = make_float4(sc, 0.5f * (sc - nx), __int_as_float(rid_c >= 0 ? hint : -1), 0.f);
+    };
+    int n_skipped = 0;
+    if (skip_ok) {
+        // delta score pass.  Where the component the previous call scored for a position (its hint_out entry) is the current hint
+        // and that mean's bits have not changed, the entry IS this call's result: same row, same mean, same arithmetic -- no row,
+        // no mean, no store.  Once the chain has settled that is nearly every position, and a step that waits for its labels
+        // only to find nothing to do is a bare round trip (32 of them in a row per wave on the headline corpus).  So the test is
+        // taken for a CHUNK of the wave's steps at once, one lane per position and SEGK_HINT_CHUNK / 2 positions per lane, all
+        // its loads in flight together; only steps with a position that is not skipped run the body, their labels handed over
+        // by shuffles.
+        constexpr int CH = SEGK_HINT_CHUNK, PPL = CH / 2;
+        const int crow = lane & 31, chalf = lane >> 5;             // the test's lane: position crow of the chunk's step 2 u + chalf
+        auto chunk_load = [&](int64_t s0, int32_t (&rd)[PPL], int32_t (&kp)[PPL], int32_t (&pzv)[PPL]) {
+#pragma unroll
+            for (int u = 0; u < PPL; u++) {
+                const int64_t s_ = s0 + (int64_t)(2 * u + chalf) * n_w, p_ = s_ * 32 + crow;
+                const bool in = s_ < n_steps && p_ < H.n;
+                rd[u] = in ? (H.ids ? H.ids[p_] : (int32_t)(H.row0 + p_)) : -1;
+                pzv[u] = in ? __float_as_int(H.hint_out[p_].z) : -2;
+            }
+#pragma unroll
+            for (int u = 0; u < PPL; u++) kp[u] = rd[u] >= 0 ? H.cand_k[rd[u]] : -1;
+        };
+        for (int64_t s0 = w; s0 < n_steps; s0 += (int64_t)CH * n_w) {
+            int32_t rd[PPL], hv[PPL];                              // per position: row, hint (| SEGK_MEANCHG_BIT here: skipped)
+            unsigned long long live[PPL];
+            {
+                int32_t kp[PPL], pzv[PPL];
+                chunk_load(s0, rd, kp, pzv);
+#pragma unroll
+                for (int u = 0; u < PPL; u++) {
+                    const int64_t s_ = s0 + (int64_t)(2 * u + chalf) * n_w;
+                    const bool in = s_ < n_steps && s_ * 32 + crow < H.n;
+                    int32_t hint = (rd[u] >= 0 && kp[u] >= 0 && kp[u] < H.K_max) ? map[kp[u]] : -1;
+                    const bool mchg = hint >= 0 && (hint & SEGK_MEANCHG_BIT) != 0;
+                    if (hint >= 0) hint &= ~SEGK_MEANCHG_BIT;
+                    const bool skip = rd[u] >= 0 && hint >= 0 && !mchg && pzv[u] == hint;
+                    hv[u] = skip ? (hint | SEGK_MEANCHG_BIT) : hint;
+                    live[u] = __ballot(in && !skip);
+                    n_skipped += __popcll(__ballot(skip));
+                }
+            }
+#pragma unroll 1
+            for (int i = 0; i < CH; i++) {
+                const int64_t s_ = s0 + (int64_t)i * n_w;
+                if (s_ >= n_steps) break;
+                int32_t rd_s = rd[0], hv_s = hv[0];
+                unsigned long long lv = live[0];
+#pragma unroll
+                for (int u = 1; u < PPL; u++)
+                    if ((i >> 1) == u) { rd_s = rd[u]; hv_s = hv[u]; lv = live[u]; }
+                const int sh = 32 * (i & 1);
+                if ((unsigned)(lv >> sh) == 0u) continue;           // every position of the step skipped (or beyond the rows)
+                const int src = sh + row;
+                const int32_t rid_c = __shfl(rd_s, src);
+                int32_t hint = __shfl(hv_s, src);
+                const bool skip = hint >= 0 && (hint & SEGK_MEANCHG_BIT) != 0;
+                if (hint >= 0) hint &= ~SEGK_MEANCHG_BIT;
+                step_body(s_, rid_c, rid_c >= 0 ? hint : -1, skip, [] {});
+            }
+        }
+        if (n_skipped > 0 && lane == 0) atomicAdd(H.ctl + 3, n_skipped);
+        return;
     }
-    if (skip_ok && n_skipped > 0 && lane == 0) atomicAdd(H.ctl + 3, n_skipped);
+    int64_t s = w;
+    // row ids two steps ahead, previous labels one step ahead: no load of a step waits for another load of the same step
+    int32_t rid = -1, rid_n = -1, kprev = -1;
+    if (s < n_steps) {
+        rid = rid_of(s);
+        if (s + n_w < n_steps) rid_n = rid_of(s + n_w);
+        kprev = rid >= 0 ? H.cand_k[rid] : -1;
+    }
+    for (; s < n_steps; s += n_w) {
+        int32_t hint = (rid >= 0 && kprev >= 0 && kprev < H.K_max) ? map[kprev] : -1;
+        if (hint >= 0) hint &= ~SEGK_MEANCHG_BIT;
+        // the next step's previous labels and the row ids of the step after it travel under this step's arithmetic
+        step_body(s, rid, hint, false, [&] {
+            rid = rid_n;
+            kprev = rid >= 0 ? H.cand_k[rid] : -1;
+            const int64_t s2 = s + 2 * n_w;
+            rid_n = s2 < n_steps ? rid_of(s2) : -1;
+        });
+    }
 }
 
 // (launch bounds "two waves per SIMD" for both: 256 registers per lane, all of them vector registers.  Given 512 the compiler
@@ -270,17 +331,24 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 31, h = lane >> 5;
-    const int R = H.n_ranges;
-    // delta score pass: the launch the mode word does not name returns at once; the delta launch reads its tile count from
-    // device memory (one range over the packed changed columns; none: no matrix work, the hint waves only)
-    int n_tiles = H.n_tiles;
-    bool skip_ok = false;
+    // delta score pass: the mode word picks the parameter set.  Delta mode: one range over the packed changed columns, the tile
+    // count from device memory (none: no matrix work, the hint waves only).  Everything below that depends on the grid uses the
+    // mode's own (`grid`), never gridDim.x: the launch has the larger of the two.
+    int n_tiles = H.n_tiles, tpr = H.tpr, R = H.n_ranges, grid = (int)gridDim.x;
+    const float *tiles = H.tiles;
+    float2 *part = H.part;
+    bool skip_ok = false, delta = false;
     if (H.ctl) {
-        const int mw = H.ctl[0];
-        if ((mw & SEGK_DELTA_MODE) != H.delta) return;
+        // (readfirstlane: the words are the same for every lane, and what follows from them -- the mode's grid, pointers, tile and
+        // group counts -- belongs in scalar registers, not in a copy per lane)
+        const int mw = __builtin_amdgcn_readfirstlane(H.ctl[0]);
+        delta = (mw & SEGK_DELTA_MODE) != 0;
         skip_ok = (mw & SEGK_DELTA_SKIP) != 0;
-        if (H.delta) n_tiles = H.ctl[2];
+        grid = delta ? H.grid_d : H.grid_f;
+        if (delta) { n_tiles = __builtin_amdgcn_readfirstlane(H.ctl[2]); tpr = H.d_tpr; R = 1; tiles = H.d_tiles; part = H.d_part; }
+        if ((int)blockIdx.x >= grid) return;
     }
+    const int map_off = tpr * TL;                                         // floats: the label map behind the mode's tiles
     const bool is_hint = wave >= NW;                // waves NW .. 2 NW - 1: hint_wave_rows
     if (!is_hint) __builtin_amdgcn_s_setprio(2);    // the matrix waves first wherever the two kinds meet at an issue port
 #ifdef SEGK_STAMP
@@ -289,20 +357,20 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
     // workgroup -> (range, slot).  Workgroups b and b + 8 share an XCD (round-robin placement, speed only): the R
     // workgroups that stream the same rows sit on one XCD when the grid allows, so that the rows cross HBM once
     int range, wgr, n_wgr;
-    const bool xcd_aware = (gridDim.x & 7) == 0 && ((gridDim.x >> 3) % R) == 0;
+    const bool xcd_aware = (grid & 7) == 0 && ((grid >> 3) % R) == 0;
     if (xcd_aware) {
         const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
         range = idx % R;
         wgr = (idx / R) * 8 + xcd;
-        n_wgr = gridDim.x / R;
+        n_wgr = grid / R;
     } else {
-        n_wgr = gridDim.x / R;
+        n_wgr = grid / R;
         range = blockIdx.x % R;
         wgr = blockIdx.x / R;
     }
-    const int t_lo = range * H.tpr;
+    const int t_lo = range * tpr;
     int nt = n_tiles - t_lo;
-    if (nt > H.tpr) nt = H.tpr;
+    if (nt > tpr) nt = tpr;
     // (a workgroup without matrix work -- beyond the last whole set of ranges, or a range without tiles -- still runs its hint waves)
     const bool mm_on = wgr < n_wgr && nt > 0;
     if (nt < 1) nt = 1;
@@ -316,7 +384,7 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
     // then / the lifetime of its waves, half-way blended; k_hint_map, the small launch in front, does the arithmetic): nothing is
     // exchanged during the launch, and the results do not depend on who computes which rows.
     const unsigned long long fb_t0 = __builtin_amdgcn_s_memrealtime();
-    const bool fb = xcd_aware && H.fb_t != nullptr && !H.delta;     // (a delta launch is not power-limited: equal shares)
+    const bool fb = xcd_aware && H.fb_t != nullptr && !delta;     // (a delta launch is not power-limited: equal shares)
     int64_t own_lo = 0, own_hi = 0;
     if (H.own) {
         if (blockIdx.x == 0 && tid == 0) {
@@ -354,10 +422,10 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
         own_hi = xcd == 7 ? H.total_groups : __shfl(split, (xcd + 1) & 7);
         if (blockIdx.x == 0 && wave == 0 && lane < 8) {
             // (a delta launch measures nothing: it hands the last full launch's shares and lifetimes on to the next launch)
-            H.fb_w[cur * 8 + x] = H.delta ? (wp > 0.f ? wp : 0.125f) : w / wsum;
+            H.fb_w[cur * 8 + x] = delta ? (wp > 0.f ? wp : 0.125f) : w / wsum;
             if (H.fb_t) {
                 H.fb_t[next * 8 + x] = 0u;
-                if (H.delta) H.fb_t[cur * 8 + x] = tp;
+                if (delta) H.fb_t[cur * 8 + x] = tp;
             }
         }
     }
@@ -466,7 +534,7 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
         if (pend_g >= 0) {                                                                                                 \
             _Pragma("unroll") for (int b = 0; b < NBLK; b++) {                                                             \
                 const int64_t r = pend_g * (32 * NBLK) + 32 * b + j;                                                       \
-                if (h == 0 && r < H.n && !(H.dbg & 1)) H.part[(int64_t)range * H.n + r] = make_float2(pend1[b], pend2[b]); \
+                if (h == 0 && r < H.n && !(H.dbg & 1)) part[(int64_t)range * H.n + r] = make_float2(pend1[b], pend2[b]); \
                 (void)pend_row[b]; (void)pend_k[b];                                                                        \
             }                                                                                                              \
         }                                                                                                                  \
@@ -489,7 +557,8 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
     int64_t pend_g = -1;
     V8 xa[NBLK][KS];
     int32_t hrow_a[NBLK], hk_a[NBLK];
-    if (!is_hint && mm_on && g < n_groups && !(H.dbg & 4)) SEGK_RS_LOAD(g, xa, hrow_a, hk_a);      // the first rows travel while the tile images are copied
+    typedef __attribute__((address_space(3))) void *lptr_t;
+    if (!is_hint && mm_on && g < n_groups && !(H.dbg & 4)) SEGK_RS_LOAD(g, xa, hrow_a, hk_a);      // the first rows are requested in front of the tile images (the wait for those, below, covers them)
 #ifdef SEGK_STAMP
     const unsigned long long st_k1 = __builtin_amdgcn_s_memtime();
 #endif
@@ -503,26 +572,35 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
         constexpr int MAXB = MAXT * KS;                                 // blocks of the largest range (LDS, SEGK_HINT_MAX_TPR)
         constexpr int NWF = 2 * NW;                                     // all eight waves copy
         constexpr int PER_W = (MAXB + NWF - 1) / NWF;
-        const int n_blk = nt * KS;                                      // (without matrix work: tile 0's blocks are loaded and dropped)
-        const int t_ld = mm_on ? t_lo : 0;
+        const int n_blk = nt * KS;
         // every workgroup of a range copies the same bytes at the same moment: started at the same block they all queue on
         // the same L2 channel (5.8 bytes per cycle and CU measured).  Each starts somewhere else in the range instead.
         const int rot = (int)(((unsigned)wgr * 2654435761u) >> 8) % n_blk;
-        float4 v[PER_W];
+        // (a block lands in LDS as it lies in the image, 16 bytes per lane: LDS-DMA, no register in between; the wave waits
+        // for its own pieces in front of the barrier)
+        const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(lptr_t)lds);
 #pragma unroll
         for (int u = 0; u < PER_W; u++) {
             int c = wave + u * NWF;
-            if (c >= n_blk) c = n_blk - 1;                              // clamped, unconditional load
-            c += rot;
-            if (c >= n_blk) c -= n_blk;
-            const int t = c / KS, ks = c - t * KS;
-            v[u] = *reinterpret_cast<const float4 *>(H.tiles + (int64_t)(t_ld + t) * STRIDE + ks * (P * 256) + lane * 4);
+            if (mm_on && c < n_blk) {
+                c += rot;
+                if (c >= n_blk) c -= n_blk;
+                const int t = __builtin_amdgcn_readfirstlane(c / KS), ks = __builtin_amdgcn_readfirstlane(c) - t * KS;
+                const float *src = tiles + (int64_t)(t_lo + t) * STRIDE + ks * (P * 256) + lane * 4;
+                const unsigned dst = lds0 + (unsigned)(t * TL + ks * 256) * 4u;
+                unsigned keep_;
+                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                             "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                             : "=&s"(keep_)
+                             : "v"(src), "s"(dst)
+                             : "memory");
+            }
         }
         float4 cv4 = make_float4(0.f, 0.f, 0.f, 0.f);
         const bool has_c = mm_on && tid < nt * 8;                       // the 32 constants of every tile: one float4 per thread
-        if (has_c) cv4 = *reinterpret_cast<const float4 *>(H.tiles + (int64_t)(t_lo + (tid >> 3)) * STRIDE + KS * P * 256 + (tid & 7) * 4);
+        if (has_c) cv4 = *reinterpret_cast<const float4 *>(tiles + (int64_t)(t_lo + (tid >> 3)) * STRIDE + KS * P * 256 + (tid & 7) * 4);
         // the label map of the hint waves behind the tile images
-        int32_t *map_l = reinterpret_cast<int32_t *>(lds + H.tpr * TL);
+        int32_t *map_l = reinterpret_cast<int32_t *>(lds + map_off);
         if (H.own) {
             // the label a hint of the previous call stands for now (the relabelling of clean_components), or -1 when the
             // filters' images carry that component as absent (a marked duplicate: such a hint proves nothing)
@@ -536,31 +614,22 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
         } else {
             for (int k = tid; k < H.K_max; k += 128 * NW) map_l[k] = H.map[k];
         }
-#pragma unroll
-        for (int u = 0; u < PER_W; u++) {
-            int c = wave + u * NWF;
-            if (mm_on && c < n_blk) {
-                c += rot;
-                if (c >= n_blk) c -= n_blk;
-                const int t = c / KS, ks = c - t * KS;
-                *reinterpret_cast<float4 *>(lds + t * TL + ks * 256 + lane * 4) = v[u];
-            }
-        }
         if (has_c) *reinterpret_cast<float4 *>(lds + (tid >> 3) * TL + KS * 256 + (tid & 7) * 4) = cv4;
         static_assert(128 * NW >= MAXT * 8, "one thread per float4 of the constants");
     }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (is_hint) {
         // a full launch of the delta score pass is the new base: the first workgroup of every range leaves the image it
         // multiplies (its LDS, the snapshot's layout) for k_delta_prep to compare the next calls' images with
-        if (H.ctl && !H.delta && mm_on && wgr == 0) {
+        if (H.ctl && !delta && mm_on && wgr == 0) {
             float4 *dst = reinterpret_cast<float4 *>(H.snap_img + 4 + (int64_t)t_lo * TL);
             const float4 *src = reinterpret_cast<const float4 *>(lds);
             for (int i = tid - 64 * NW; i < nt * (TL / 4); i += 64 * NW) dst[i] = src[i];
         }
         // every workgroup's hint waves take steps of 32 rows, strided over the whole grid: the chip walks the corpus front to back
-        hint_wave_rows<KS, V>(H, reinterpret_cast<const int32_t *>(lds + H.tpr * TL), (int64_t)blockIdx.x * NW + (wave - NW),
-                              (int64_t)gridDim.x * NW, skip_ok);
+        hint_wave_rows<KS, V>(H, reinterpret_cast<const int32_t *>(lds + map_off), (int64_t)blockIdx.x * NW + (wave - NW),
+                              (int64_t)grid * NW, skip_ok);
         return;
     }
 #ifdef SEGK_STAMP
@@ -710,8 +779,8 @@ __global__ void k_hint_map(const int32_t *remap, const float *tiles_sp /* first 
 // constant, "absent" marks included) against the snapshot of the base pass, bit for bit; a changed image exponent changes the
 // scale of every filter value and so marks every column.  The changed columns are compacted into the leading tiles of the packed
 // delta image (any order: K1 keeps values, not indices; the free slots of the last tile carry the absent constant), and the mode
-// word says which of K1's two launches runs: FULL when there is no valid state, when the relabelling is not the identity, or when
-// the packed tiles exceed `cap` -- and then K1's full launch, which makes the new base, refreshes the snapshot.
+// word says which parameter set K1's launch takes: FULL when there is no valid state, when the relabelling is not the identity, or when
+// the packed tiles exceed `cap` -- and then K1 in full mode, which makes the new base, refreshes the snapshot.
 // A base is never built from delta results, so the changed columns only accumulate against the snapshot; two more reasons for a
 // full launch bring them back down: the chain has come to rest on changed columns (no new column in this call and no mean moved
 // during the previous one: one full pass, and every later call multiplies nothing), or the packed tiles multiplied since the base
@@ -1232,23 +1301,29 @@ static int launch_score_hint(segk_ctx *ctx, ScoreArgs A, const int32_t *remap, c
     H.nxx = A.xerr + n_emb;                                      // -|x|^2 per row, behind the residual norms
     H.hint_out = (float4 *)((unsigned char *)ctx->hint_part + part_bytes);
     const size_t lds1 = (size_t)tpr * TL * sizeof(float) + map_bytes;
-    // the delta launch: one range over the packed image, its tile count in ctl[2]; every workgroup's slots over all rows
-    HintArgs HD = H;
-    HD.delta = 1;
-    HD.tiles = d_packed;
-    HD.n_tiles = 0; HD.tpr = delta_cap; HD.n_ranges = 1;
-    HD.part = d_part;
-    const size_t lds_d = (size_t)delta_cap * TL * sizeof(float) + map_bytes;
-    int grid_d = n_cu;
-    if ((int64_t)grid_d > (A.n + 255) / 256) grid_d = (int)((A.n + 255) / 256);
+    // the delta parameter set of the same launch: one range over the packed image, its tile count in ctl[2]; every workgroup's
+    // slots over all rows
+    H.d_tiles = d_packed;
+    H.d_tpr = delta_cap;
+    H.d_part = d_part;
+    size_t lds_k1 = lds1;
+    int grid_k1 = grid1;
+    H.grid_f = grid1;
+    if (delta_on) {
+        const size_t lds_d = (size_t)delta_cap * TL * sizeof(float) + map_bytes;
+        int grid_d = n_cu;
+        if ((int64_t)grid_d > (A.n + 255) / 256) grid_d = (int)((A.n + 255) / 256);
+        H.grid_d = grid_d;
+        if (grid_d > grid_k1) grid_k1 = grid_d;
+        if (lds_d > lds_k1) lds_k1 = lds_d;
+    }
     const bool prof = segk_prof_now(ctx);
     const int slot = ctx->prof_n % SEGK_PROF_SLOTS;
 #define SEGK_K1_LAUNCH(VV)                                                                                                  \
     do {                                                                                                                     \
-        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_kmeans_top2_rs<KS, VV, 4>, lds1 > lds_d ? lds1 : lds_d));                                     \
+        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_kmeans_top2_rs<KS, VV, 4>, lds_k1));                                     \
         if (prof) SEGK_CHECK_HIP(hipEventRecord(ctx->prof_ev[slot][0], st));                                                 \
-        hipLaunchKernelGGL((k_kmeans_top2_rs<KS, VV, 4>), dim3((unsigned)grid1), dim3(512), lds1, st, H);                    \
-        if (delta_on) hipLaunchKernelGGL((k_kmeans_top2_rs<KS, VV, 4>), dim3((unsigned)grid_d), dim3(512), lds_d, st, HD);   \
+        hipLaunchKernelGGL((k_kmeans_top2_rs<KS, VV, 4>), dim3((unsigned)grid_k1), dim3(512), lds_k1, st, H);                \
     } while (0)
     switch ((16 * KS - A.D) / 4) {
         case 0: SEGK_K1_LAUNCH(0); break;
