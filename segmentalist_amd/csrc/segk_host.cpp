@@ -18,6 +18,16 @@ void segk_set_error(const char *fmt, ...)
     va_end(ap);
 }
 
+int segk_ws_realloc(segk_ctx *ctx, void **buf, size_t bytes, hipStream_t st)
+{
+    SEGK_REQUIRE(!ctx->capturing, "workspaces must exist before a graph capture (run the sequence once first)");
+    SEGK_CHECK_HIP(hipStreamSynchronize(st));
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr;
+    SEGK_CHECK_HIP(hipMalloc(buf, bytes));
+    return SEGK_OK;
+}
+
 extern "C" {
 
 const char *segk_last_error(void) { return g_err; }
@@ -127,7 +137,6 @@ int32_t segk_destroy(segk_ctx *ctx)
         if (ctx->fbs_buf) (void)hipFree(ctx->fbs_buf);
         if (ctx->flag_ovf) (void)hipFree(ctx->flag_ovf);
         if (ctx->hint_part) (void)hipFree(ctx->hint_part);
-        if (ctx->hint_map) (void)hipFree(ctx->hint_map);
         if (ctx->ws_u64) (void)hipFree(ctx->ws_u64);
         if (ctx->hint_fb) (void)hipFree(ctx->hint_fb);
         if (ctx->delta_buf) (void)hipFree(ctx->delta_buf);

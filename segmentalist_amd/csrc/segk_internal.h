@@ -66,11 +66,9 @@ struct segk_ctx {
     int rb_K;
     int32_t *rb_misc;            // blk_lo [68], dummy K, flags; then doubles (part_tot, scalars, terms)
     double *rb_term;             // [rb_K] per-component terms of the record metrics
-    // hinted score path (segk_score_hint.hip): the filter's partial top-2 per (range, row), the hint map [K_max]
+    // hinted score path (segk_score_hint.hip): the filter's partial top-2 per (range, row), then the hint waves' result per row
     void *hint_part;
     size_t hint_part_bytes;
-    int32_t *hint_map;
-    int hint_map_k;
     float *pre_thr;              // band stage (segk_score_band.hip): threshold per entry of pre_queue
     int64_t pre_thr_cap;
     void *band_mask;             // its candidate masks, [ranges][queue capacity][2] x 16 bytes
@@ -160,6 +158,21 @@ int segk_rows_by_label(segk_ctx *ctx, const int32_t *labels, int64_t n, int K_ma
     } while (0)
 
 #define SEGK_LAUNCH_CHECK() SEGK_CHECK_HIP(hipGetLastError())
+
+// A workspace the context owns, grown on demand: *buf replaced by a fresh allocation of `bytes`.  Refuses during a graph capture
+// (workspaces must exist before it), waits for `st` first (work in flight may still use the old block), frees the old block.
+// The contents are gone.  On failure *buf is NULL.
+int segk_ws_realloc(segk_ctx *ctx, void **buf, size_t bytes, hipStream_t st);
+// ... when its recorded size *have (in the caller's unit: rows, bytes) is below `need`; records `need`.
+template <class T, class N>
+static inline int segk_ws_grow(segk_ctx *ctx, T **buf, N *have, N need, size_t bytes, hipStream_t st)
+{
+    if (*have >= need) return SEGK_OK;
+    *have = 0;
+    if (int rc = segk_ws_realloc(ctx, (void **)buf, bytes, st)) return rc;
+    *have = need;
+    return SEGK_OK;
+}
 
 // hipFuncAttributeMaxDynamicSharedMemorySize for `fn` on the CURRENT device, raised when `lds` exceeds 48 KB and what has been set
 // there before.  The attribute is per device: a function-local static flag (rounds 1-2) skipped it for a second context on

@@ -769,6 +769,29 @@ int segk_launch_seq_chain(segk_ctx *ctx, const segk_corpus *c, segk_kmeans *m, c
 // segk_score_h1.hip: one-product pre-filter + exact pair stage + second stage
 int segk_dispatch_score_pre(segk_ctx *ctx, const ScoreArgs &A, int ks, hipStream_t st);
 // segk_score_hint.hip: value-only top-2 on the matrix cores + exact stage that verifies a hint per row (cand.k on entry)
+// K1's LDS (160 KB, one workgroup per CU) holds one RANGE of the table's tile images (ks * 256 + 32 floats each) and, behind them,
+// the hint waves' label map [K_max].  The plan: as many tiles per range as fit, SEGK_HINT_MAX_TPR at most, in as few ranges as
+// that allows, the tiles spread evenly over them.  false: the path does not apply (K_max too large for the map beside one tile, or
+// for SEGK_HINT_MAX_RANGES ranges).
+#define SEGK_HINT_MAX_TPR 32         /* tiles per LDS range of K1 at most (its fill: one thread per float4 of the constants) */
+#define SEGK_HINT_MAX_RANGES 4
+struct HintPlan {
+    int max_tiles;                  // tiles that fit beside the map (SEGK_HINT_MAX_TPR at most)
+    int n_ranges, tpr;              // ranges, tiles per range
+    size_t map_bytes;               // the label map's share of LDS
+};
+static inline bool segk_hint_plan(int K_max, int ks, int n_tiles, HintPlan *p)
+{
+    const size_t lds_bytes = 160 * 1024, tile_bytes = (size_t)(ks * 256 + 32) * sizeof(float);
+    p->map_bytes = (size_t)((K_max + 3) & ~3) * sizeof(int32_t);
+    if (p->map_bytes + tile_bytes > lds_bytes) return false;
+    p->max_tiles = (int)((lds_bytes - p->map_bytes) / tile_bytes);
+    if (p->max_tiles > SEGK_HINT_MAX_TPR) p->max_tiles = SEGK_HINT_MAX_TPR;
+    p->n_ranges = (n_tiles + p->max_tiles - 1) / p->max_tiles;
+    if (p->n_ranges < 1) p->n_ranges = 1;
+    p->tpr = (n_tiles + p->n_ranges - 1) / p->n_ranges;
+    return p->n_ranges <= SEGK_HINT_MAX_RANGES;
+}
 int segk_dispatch_score_hint(segk_ctx *ctx, const ScoreArgs &A, const int32_t *remap, const int32_t *K_dev, int64_t n_emb, int ks, hipStream_t st);
 // segk_score_band.hip: the hinted path's undecided rows -- candidates inside the band of the filter's maximum, exact scores
 bool segk_band_applies(const ScoreArgs &A);

@@ -411,15 +411,7 @@ static int launch_band(segk_ctx *ctx, const ScoreArgs &A, const float *thr, int6
     SEGK_REQUIRE(n_ranges >= 1 && n_ranges <= SEGK_BAND_MAX_RANGES, "band stage: K_max out of range");
     const int cap = A.pre_cap;
     const size_t need = (size_t)n_ranges * (size_t)cap * 2 * sizeof(int4);
-    if (ctx->band_mask_bytes < need) {
-        SEGK_REQUIRE(!ctx->capturing, "workspaces must exist before a graph capture (run the sequence once first)");
-        SEGK_CHECK_HIP(hipStreamSynchronize(st));
-        if (ctx->band_mask) (void)hipFree(ctx->band_mask);
-        ctx->band_mask = nullptr;
-        ctx->band_mask_bytes = 0;
-        SEGK_CHECK_HIP(hipMalloc(&ctx->band_mask, need));
-        ctx->band_mask_bytes = need;
-    }
+    if (int rc = segk_ws_grow(ctx, &ctx->band_mask, &ctx->band_mask_bytes, need, need, st)) return rc;
     BandArgs B{};
     B.ximg = (const unsigned char *)A.X32;
     B.queue = A.pre_queue;

@@ -1,5 +1,5 @@
-// segk_score_hint.hip -- A1 with a HINT per row (round 3): the dense one-product fp16 contraction with a value-only top-2
-// drain, and an exact stage that verifies the hinted component against it.
+// segk_score_hint.hip -- A1 with a HINT per row: the dense one-product fp16 contraction with a value-only top-2 drain, the
+// hinted component scored in the reference's arithmetic beside it, and a certificate that verifies the hint against both.
 // (one of the translation units of the k-means path; shared helpers: segk_kmeans_dev.h)
 //
 // KMeansComponents.argmax_neg_sqrd_norm_i (kmeans_components.py:225-232) is evaluated for every row in every sweep, and from
@@ -9,24 +9,24 @@
 // of them only to remember WHICH pair won -- as its matrix pipe spends on the products, and pays a staging barrier per
 // tile: 41 % matrix-pipe occupancy.  With a hint the index does not have to be tracked at all:
 //
-//   K1  k_kmeans_top2_rs   every (row, component) product on the matrix cores exactly as before (all K_max slots, nothing
-//       skipped), but the drain keeps only the two largest VALUES per row: m1' = max3(m1, a, b), m2' = max(m2, med3(m1, a, b))
-//       -- three operations per two values.  Range-stationary: a workgroup (8 waves, one per CU) copies the fp16 tile
-//       images of ONE range of components into LDS once (16 tiles = 114 KB for the headline model) and its waves stream
-//       row blocks past them without a single barrier; the constants -|m|^2/2 enter as the C operand of each block's
-//       first MFMA.  Output: (m1, m2) per (row, range).
-//   K2  k_kmeans_hint_exact   the component table in LDS as float32 (ranges, like k_kmeans_exact_pair4): for each row the
-//       hinted component h is scored in the reference's arithmetic, s = -|x - m_h|^2, together with |x|^2 in the same
-//       summation order, so that f_h = (s + |x|^2) / 2 = x.m_h - |m_h|^2/2 is known to within the reference's own
-//       rounding.  With F the filter values (|F_k - f_k| <= E for every k), top1 >= top2 their two largest and
-//       tau >= 2 E + E2 the pre-filter's margin (filter_tau_h1):
+//   K1  k_kmeans_top2_rs   matrix waves: every (row, component) product on the matrix cores exactly as before (all K_max
+//       slots, nothing skipped), but the drain keeps only the two largest VALUES per row: m1' = max3(m1, a, b),
+//       m2' = max(m2, med3(m1, a, b)) -- three operations per two values.  Range-stationary: a workgroup (one per CU) copies
+//       the fp16 tile images of ONE range of components into LDS once (16 tiles = 114 KB for the headline model) and its
+//       matrix waves stream row blocks past them without a single barrier; the constants -|m|^2/2 enter as the C operand of
+//       each block's first MFMA.  Output: (m1, m2) per (row, range).
+//       hint waves (hint_wave_rows): for each row the hinted component h is scored in the reference's arithmetic,
+//       s = -|x - m_h|^2; with -|x|^2 in the same summation order (nxx), f_h = (s + |x|^2) / 2 = x.m_h - |m_h|^2/2 is known
+//       to within the reference's own rounding.  Output: {s, f_h, h} per row.
+//   K2  k_hint_merge   the certificate, one thread per row.  With F the filter values (|F_k - f_k| <= E for every k),
+//       top1 >= top2 their two largest (merged over the ranges) and tau >= 2 E + E2 the pre-filter's margin (filter_tau_h1):
 //           top1 - top2 > tau            =>  the filter's argmax k1 is the reference's argmax      (as in the pre-filter)
 //           f_h >= top1 - tau + E + dl   =>  h = k1: any other k has F_k <= top2, so f_k <= top2 + E < top1 - tau + E
 //       (dl bounds the error of the computed f_h).  Both hold -> cand.k = h, cand.s = s: the reference's bits.  Otherwise
-//       the row is queued for the existing second stage (k_kmeans_score_sp, all three products) and, from there, the full
-//       scan -- exactly the rows the pre-filter would have queued plus the rows whose hint was wrong.  A hint that names a
-//       component the filters' images carry as "absent" (an exact duplicate of a lower row, segk_kmeans_mark_duplicates)
-//       is no hint: its F is not a bound on anything.
+//       the row is queued for the second stage (the band stage, segk_score_band.hip; tables beyond its reach:
+//       k_kmeans_score_sp, all three products) and, from there, the full scan -- exactly the rows the pre-filter would have
+//       queued plus the rows whose hint was wrong.  A hint that names a component the filters' images carry as "absent" (an
+//       exact duplicate of a lower row, segk_kmeans_mark_duplicates) is no hint: its F is not a bound on anything.
 //
 //       The certificate holds on a SUPERSET of the filter values (the delta score pass rests on this).  Let S' be any multiset
 //       that contains F_h and, for every other current column k, a value >= F_k, and top1' >= top2' its two largest.  Suppose
@@ -47,58 +47,52 @@
 // full-size parity tests run this path against the C oracle row by row.
 #include "segk_kmeans_dev.h"
 
-// cand.k in K2 (marked by k_hint_map): (previous label | SEGK_HINT_BIT) = a hint to be translated by the map; -1 = none.  K2's
-// workgroups (one table range each) all scan every row: the mark tells a row that still waits for its range's workgroup from
-// one that workgroup has already given its final label.
-#define SEGK_HINT_BIT 0x20000000
+#define SEGK_K1_NW 4                 /* matrix waves per workgroup of K1, and as many hint waves */
 #define SEGK_HINT_CHUNK 8            /* steps of 32 rows whose skip a hint wave decides in one round trip (delta score pass) */
-#define SEGK_HINT_MAX_TPR 32         /* tiles per LDS range of K1 at most (its fill: one thread per float4 of the constants) */
 
 // development, timing only (-DSEGK_K1_ABL=n, results wrong): 1 no drain in the tile loop, 2 no operand refill from LDS
 #ifndef SEGK_K1_ABL
 #define SEGK_K1_ABL 0
 #endif
 
+// What K1's matrix waves multiply and where the result goes.  A launch carries two sets, one for a full and one for a delta
+// pass (one range over the packed image of the changed columns), and takes the one the mode word k_delta_prep left names.
+struct K1Set {
+    const float *tiles;             // first tile of the fp16x2 image the matrix waves multiply
+    int n_tiles;                    // its tiles (delta set: at launch time unknown, read from ctl[2])
+    int tpr, n_ranges;              // tiles per LDS range (the label map sits behind them in LDS), ranges
+    float2 *part;                   // [n_ranges][n] (m1, m2) in the scaled domain of the images
+    int grid;                       // workgroups; the launch has the larger of the two sets', and a workgroup beyond this one returns
+};
+
 struct HintArgs {
     const unsigned char *ximg;      // fp16x2 row image (segk_corpus.Xb3): header, then plane 0 [n_emb][KP]
     const int32_t *ids;
     int64_t row0, n;
-    const float *tiles;             // first tile of the fp16x2 tile image (tiles_b3 + 1024) K1 multiplies in full mode
-    const float *all_tiles;         // first tile of the model's whole image (the "absent" marks of the label map)
-    int n_tiles, tpr, n_ranges;     // full mode: tiles, tiles per range, ranges
-    float2 *part;                   // full mode: [n_ranges][n] (m1, m2) in the scaled domain of the images
+    K1Set full, delta;              // full: the model's whole image (tiles_b3 + 1024; also the "absent" marks of the label map);
+                                    // delta: the packed image, unused without `ctl`
     int K_max;
-    int dbg;                        // development (SEGK_HINT_DBG, results wrong): 1 no result stores, 2 no hint loads / marks
+    // development (SEGK_HINT_DBG, results wrong; bits): 1 no result stores, 4 the first rows loaded behind the LDS fill, 8 no hint
+    // waves, 16 their rows from a cache-resident corner, 32 one block of their arithmetic, 64 paced, 128 no matrix waves
+    int dbg;
     unsigned long long *stamp;      // development (-DSEGK_STAMP builds): per wave {cycles in the row waits, in the tile loops, total, groups}
     float *fb_w;                    // [3][8] share of the row groups each XCD took in the launches L - 1, L, L + 1 (slot = launch % 3)
     unsigned int *fb_t;             // [3][8] how long its waves lived (s_memrealtime ticks, maximum); NULL: equal shares
     int fb_cur;                     // this launch's slot
-    const int64_t *fb_split;        // [9] this launch's first group per XCD (k_hint_map; unused with `own`)
-    // own != 0: the kernel does k_hint_map's work itself (the label map straight into LDS, the XCDs' shares by every wave, the
-    // queue counters by its first thread): one launch and one kernel boundary (~5 us) less per score call
-    int own;
     const int32_t *remap;           // previous label -> current label (NULL: identity)
-    int32_t *zero_cnt, *pre_hdr;    // the caller's ambiguity-queue length (may be NULL) and the undecided-row queue's header [16]
-    int64_t total_groups;
-    int64_t k1_groups;              // groups this kernel multiplies (the few behind the last whole round of all waves go to the second stage)
-    // the hint waves (waves NW .. 2 NW - 1 of every workgroup): the hinted component of every row scored in reference arithmetic
+    int32_t *zero_cnt, *pre_hdr;    // the caller's ambiguity-queue length (may be NULL) and the undecided-row queue's header [16]: cleared here
+    int64_t k1_groups;              // groups this kernel multiplies (the few behind the last whole round of all waves go to the full scan)
+    // the hint waves (waves 4 .. 7 of every workgroup): the hinted component of every row scored in reference arithmetic
     const float *xrows32;           // float32 rows [n_emb][ld32]
     int64_t ld32;
     const float *means32;           // float32 `means` [K_max][D]
     const int32_t *cand_k;          // per row: the label the previous call left (the hint, in that call's labelling)
-    const int32_t *map;             // [K_max] previous label -> current label, or -1 (k_hint_map)
     const float *nxx;               // -|x|^2 per row in the reference's summation order (k_corpus_resid_sp)
     float4 *hint_out;               // [n] by position in the launch: {s = -|x - m_h|^2, f_h = x.m_h - |m_h|^2/2, bits of h (-1: no hint), 0}
-    // delta score pass (NULL / 0: none): the control words k_delta_prep left and the rows of `means` whose bits changed since the
-    // previous call.  ONE launch serves both modes: the kernel reads the mode word and takes the full parameter set above or the
-    // delta set below (one range over the packed image, its tile count in ctl[2]); the launch has the larger of the two grids
-    // and LDS sizes, and a workgroup beyond the grid of the mode that runs returns.
+    // delta score pass (NULL: none, the full set): the control words k_delta_prep left and the rows of `means` whose bits changed
+    // since the previous call
     int32_t *ctl;
     const int32_t *meanchg;
-    const float *d_tiles;           // first tile of the packed image of the changed columns
-    int d_tpr;                      // tiles of the packed image at most (the label map sits behind them in LDS)
-    float2 *d_part;                 // [n] (m1, m2) over the packed columns
-    int grid_f, grid_d;             // the grid of either mode
     float *snap_img;                // the base pass's image, refreshed by the full launch: [4 floats: exponent][n_tiles][KS * 256 + 32]
 };
 
@@ -112,12 +106,11 @@ struct HintArgs {
 #define SEGK_MEANCHG_BIT 0x40000000  /* in the hint waves' label map: the float32 mean of this component changed since the previous call */
 
 // ---- K1 ---------------------------------------------------------------------------------------------------------------
-// NW waves per workgroup, one workgroup per CU.  NW = 4: ONE wave per SIMD with the whole register file (512 per lane) --
-// the rows of the wave's next group are prefetched into a second register set while the current group is multiplied, and
+// SEGK_K1_NW = 4 matrix waves per workgroup (and as many hint waves), one workgroup per CU: ONE matrix wave per SIMD -- the
+// rows of the wave's next group are prefetched into a second register set while the current group is multiplied, and
 // nothing but the wave's own instruction stream decides whether the matrix pipe idles: per 32-cycle MFMA slot the MFMA's
-// issue (8 cycles) and 3-4 vector operations of the other block's drain.  NW = 8: two waves per SIMD with 256 registers
-// each (no prefetch), which fill each other's gaps at group boundaries but compete for the SIMD's vector issue inside the
-// tile loop.
+// issue (8 cycles) and 3-4 vector operations of the other block's drain.  (Two matrix waves per SIMD without prefetch fill
+// each other's gaps at group boundaries but compete for the SIMD's vector issue inside the tile loop: 6 % slower, retired.)
 //
 // Drain of a block's 16 values per lane, four at a time, value-only (no index): with x1 = max3(m1, a, b),
 // t1 = med3(m1, a, b) [the second largest of m1, a, b], u = med3(x1, c, d) [the second largest of x1, c, d]:
@@ -313,43 +306,84 @@ __device__ __forceinline__ void hint_wave_rows(const HintArgs &H, const int32_t 
     }
 }
 
-// (launch bounds "two waves per SIMD" for both: 256 registers per lane, all of them vector registers.  Given 512 the compiler
-// keeps the accumulators in the accumulator file and copies every value out for the drain, 16 v_accvgpr_read per block)
-template <int KS, int V, int NW>
-__global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
+// ---- the XCDs' shares of K1's row groups ----------------------------------------------------------------------------------
+// Under K1 the chip runs into its power limit, and the eight XCDs then hold DIFFERENT clocks (1.65-1.77 GHz measured, the same
+// XCDs slow launch after launch): with equal shares the fast ones idle for the last 10-20 us of 200.  So an XCD takes a
+// contiguous share of the groups in proportion to the rate it showed in the previous launch: its share then / the lifetime of
+// its waves = the rate; new share = half the old one, half the rate's.  Nothing is exchanged during the launch, and the results
+// do not depend on who computes which rows.  Every wave does the arithmetic for itself (one load round trip, sums and prefix by
+// shuffles; lane x & 7 = XCD x) and gets the groups [lo, hi) of its workgroup's XCD; `record`: this wave leaves the shares for the
+// next launch (a delta launch measures nothing: it hands the last full launch's shares and lifetimes on).
+struct XcdShare { int64_t lo, hi; };
+__device__ __forceinline__ XcdShare k1_xcd_share(const HintArgs &H, int64_t total_groups, bool delta, bool record)
 {
-    static_assert(NW == 4, "four matrix waves (one per SIMD, rows prefetched) + four hint waves per workgroup");
+    const int lane = threadIdx.x & 63, x = lane & 7;
+    const int cur = H.fb_cur, prev = (cur + 2) % 3, next = (cur + 1) % 3;
+    const float wp = H.fb_w[prev * 8 + x];
+    const unsigned int tp = H.fb_t ? H.fb_t[prev * 8 + x] : 0u;
+    const bool ok = __all(tp > 0u && wp > 0.f);
+    const float rate = ok ? wp / (float)tp : 0.f;
+    float rsum = rate;
+    rsum += __shfl_xor(rsum, 1);
+    rsum += __shfl_xor(rsum, 2);
+    rsum += __shfl_xor(rsum, 4);
+    float w = !(wp > 0.f) ? 0.125f : ok ? 0.5f * wp + 0.5f * (rate / rsum) : wp;
+    w = fminf(fmaxf(w, 0.0625f), 0.25f);
+    float wsum = w;
+    wsum += __shfl_xor(wsum, 1);
+    wsum += __shfl_xor(wsum, 2);
+    wsum += __shfl_xor(wsum, 4);
+    double cum = 0.0;                                        // exclusive prefix in XCD order, every lane the same additions
+    for (int y = 0; y < 8; y++) {
+        const float wy = __shfl(w, y);
+        if (y < x) cum += (double)wy;
+    }
+    const int64_t split = (int64_t)(cum * ((double)total_groups / (double)wsum));
+    const int xcd = blockIdx.x & 7;
+    XcdShare s;
+    s.lo = __shfl(split, xcd);
+    s.hi = xcd == 7 ? total_groups : __shfl(split, (xcd + 1) & 7);
+    if (record && lane < 8) {
+        H.fb_w[cur * 8 + x] = delta ? (wp > 0.f ? wp : 0.125f) : w / wsum;
+        if (H.fb_t) {
+            H.fb_t[next * 8 + x] = 0u;
+            if (delta) H.fb_t[cur * 8 + x] = tp;
+        }
+    }
+    return s;
+}
+
+// (launch bounds "two waves per SIMD", a matrix and a hint wave: 256 registers per lane, all of them vector registers.  Given
+// 512 the compiler keeps the accumulators in the accumulator file and copies every value out for the drain, 16 v_accvgpr_read
+// per block)
+template <int KS, int V>
+__global__ __launch_bounds__(128 * SEGK_K1_NW, 1) void k_kmeans_top2_rs(HintArgs H)
+{
     typedef _Float16 T;
     typedef SegkPiece::V8 V8;
-    // (only 256 of a lone wave's 512 registers are addressable by vector instructions, the rest is the accumulator file: a
-    // second 4-block row set lands there and is copied back and forth -- 5 000 v_accvgpr moves.  So: two blocks per group with
-    // prefetch for NW = 4, four without for NW = 8)
-    constexpr int P = 2, KP = KS * 16, NBLK = NW == 4 ? 2 : 4;
+    // (only 256 of a wave's registers are addressable by vector instructions: a second 4-block row set lands in the accumulator
+    // file and is copied back and forth -- 5 000 v_accvgpr moves.  So: two blocks of 32 rows per group, the next group's prefetched)
+    constexpr int P = 2, KP = KS * 16, NBLK = 2;
     constexpr int STRIDE = (KS * P * 256 + 32 + 1023) / 1024 * 1024;      // floats per tile of the global image
     constexpr int TL = KS * 256 + 32;                                     // floats per tile in LDS: KS piece-0 blocks + constants
-    constexpr bool PREFETCH = NW == 4;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 31, h = lane >> 5;
-    // delta score pass: the mode word picks the parameter set.  Delta mode: one range over the packed changed columns, the tile
-    // count from device memory (none: no matrix work, the hint waves only).  Everything below that depends on the grid uses the
-    // mode's own (`grid`), never gridDim.x: the launch has the larger of the two.
-    int n_tiles = H.n_tiles, tpr = H.tpr, R = H.n_ranges, grid = (int)gridDim.x;
-    const float *tiles = H.tiles;
-    float2 *part = H.part;
-    bool skip_ok = false, delta = false;
-    if (H.ctl) {
-        // (readfirstlane: the words are the same for every lane, and what follows from them -- the mode's grid, pointers, tile and
-        // group counts -- belongs in scalar registers, not in a copy per lane)
-        const int mw = __builtin_amdgcn_readfirstlane(H.ctl[0]);
-        delta = (mw & SEGK_DELTA_MODE) != 0;
-        skip_ok = (mw & SEGK_DELTA_SKIP) != 0;
-        grid = delta ? H.grid_d : H.grid_f;
-        if (delta) { n_tiles = __builtin_amdgcn_readfirstlane(H.ctl[2]); tpr = H.d_tpr; R = 1; tiles = H.d_tiles; part = H.d_part; }
-        if ((int)blockIdx.x >= grid) return;
-    }
+    // The mode word picks the parameter set (no control words: the full one).  Everything below that depends on the grid uses
+    // the set's own (`grid`), never gridDim.x: the launch has the larger of the two.
+    // (readfirstlane: the words are the same for every lane, and what follows from them -- the set's grid, pointers, tile and
+    // group counts -- belongs in scalar registers, not in a copy per lane)
+    const int mw = H.ctl ? __builtin_amdgcn_readfirstlane(H.ctl[0]) : 0;
+    const bool delta = (mw & SEGK_DELTA_MODE) != 0, skip_ok = (mw & SEGK_DELTA_SKIP) != 0;
+    const K1Set S = delta ? H.delta : H.full;
+    // (delta mode: the tile count from device memory; none: no matrix work, the hint waves only)
+    const int n_tiles = delta ? __builtin_amdgcn_readfirstlane(H.ctl[2]) : S.n_tiles;
+    const int tpr = S.tpr, R = S.n_ranges, grid = S.grid;
+    const float *tiles = S.tiles;
+    float2 *part = S.part;
+    if ((int)blockIdx.x >= grid) return;
     const int map_off = tpr * TL;                                         // floats: the label map behind the mode's tiles
-    const bool is_hint = wave >= NW;                // waves NW .. 2 NW - 1: hint_wave_rows
+    const bool is_hint = wave >= SEGK_K1_NW;                // waves SEGK_K1_NW .. 2 SEGK_K1_NW - 1: hint_wave_rows
     if (!is_hint) __builtin_amdgcn_s_setprio(2);    // the matrix waves first wherever the two kinds meet at an issue port
 #ifdef SEGK_STAMP
     const unsigned long long st_k0 = __builtin_amdgcn_s_memtime(), st_r0 = __builtin_amdgcn_s_memrealtime();
@@ -377,79 +411,34 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
     const T *plane0 = (const T *)(H.ximg + SEGK_SP_HEADER);
     // this wave's row groups: g_first, g_first + n_slots, ... below n_groups
     const int64_t total_groups = (H.n + 32 * NBLK - 1) / (32 * NBLK);
-    int64_t n_groups = H.k1_groups < total_groups ? H.k1_groups : total_groups, n_slots = (int64_t)n_wgr * NW, g_first = (int64_t)wgr * NW + wave;
-    // Under this kernel the chip runs into its power limit, and the eight XCDs then hold DIFFERENT clocks (1.65-1.77 GHz
-    // measured, the same XCDs slow launch after launch): with equal shares the fast ones idle for the last 10-20 us of 200.
-    // So an XCD takes a contiguous share of the groups in proportion to the rate it showed in the previous launch (its share
-    // then / the lifetime of its waves, half-way blended; k_hint_map, the small launch in front, does the arithmetic): nothing is
-    // exchanged during the launch, and the results do not depend on who computes which rows.
+    int64_t n_groups = H.k1_groups < total_groups ? H.k1_groups : total_groups, n_slots = (int64_t)n_wgr * SEGK_K1_NW, g_first = (int64_t)wgr * SEGK_K1_NW + wave;
     const unsigned long long fb_t0 = __builtin_amdgcn_s_memrealtime();
-    const bool fb = xcd_aware && H.fb_t != nullptr && !delta;     // (a delta launch is not power-limited: equal shares)
-    int64_t own_lo = 0, own_hi = 0;
-    if (H.own) {
-        if (blockIdx.x == 0 && tid == 0) {
-            if (H.zero_cnt) *H.zero_cnt = 0;
+    // the queue lengths of the call cleared: the caller's ambiguity queue (when segk_kmeans_score_hinted deferred it) and the
+    // second stage's counters
+    if (blockIdx.x == 0 && tid == 0) {
+        if (H.zero_cnt) *H.zero_cnt = 0;
 #pragma unroll
-            for (int i = 0; i < 16; i++) H.pre_hdr[i] = 0;
-        }
-        // the XCDs' shares for this launch (k_hint_map's arithmetic, by every wave: one load round trip, sums and prefix by
-        // shuffles; lane x & 7 = XCD x): share of the previous launch / lifetime of its waves = the rate an XCD showed; new
-        // share = half the old one, half the rate's
-        const int x = lane & 7;
-        const int cur = H.fb_cur, prev = (cur + 2) % 3, next = (cur + 1) % 3;
-        const float wp = H.fb_w[prev * 8 + x];
-        const unsigned int tp = H.fb_t ? H.fb_t[prev * 8 + x] : 0u;
-        const bool ok = __all(tp > 0u && wp > 0.f);
-        const float rate = ok ? wp / (float)tp : 0.f;
-        float rsum = rate;
-        rsum += __shfl_xor(rsum, 1);
-        rsum += __shfl_xor(rsum, 2);
-        rsum += __shfl_xor(rsum, 4);
-        float w = !(wp > 0.f) ? 0.125f : ok ? 0.5f * wp + 0.5f * (rate / rsum) : wp;
-        w = fminf(fmaxf(w, 0.0625f), 0.25f);
-        float wsum = w;
-        wsum += __shfl_xor(wsum, 1);
-        wsum += __shfl_xor(wsum, 2);
-        wsum += __shfl_xor(wsum, 4);
-        double cum = 0.0;                                        // exclusive prefix in XCD order, every lane the same additions
-        for (int y = 0; y < 8; y++) {
-            const float wy = __shfl(w, y);
-            if (y < x) cum += (double)wy;
-        }
-        const int64_t split = (int64_t)(cum * ((double)H.total_groups / (double)wsum));
-        const int xcd = blockIdx.x & 7;
-        own_lo = __shfl(split, xcd);
-        own_hi = xcd == 7 ? H.total_groups : __shfl(split, (xcd + 1) & 7);
-        if (blockIdx.x == 0 && wave == 0 && lane < 8) {
-            // (a delta launch measures nothing: it hands the last full launch's shares and lifetimes on to the next launch)
-            H.fb_w[cur * 8 + x] = delta ? (wp > 0.f ? wp : 0.125f) : w / wsum;
-            if (H.fb_t) {
-                H.fb_t[next * 8 + x] = 0u;
-                if (delta) H.fb_t[cur * 8 + x] = tp;
-            }
-        }
+        for (int i = 0; i < 16; i++) H.pre_hdr[i] = 0;
     }
+    const XcdShare share = k1_xcd_share(H, total_groups, delta, blockIdx.x == 0 && wave == 0);
+    const bool fb = xcd_aware && H.fb_t != nullptr && !delta;     // (a delta launch is not power-limited: equal shares)
     if (fb) {
-        const int xcd = blockIdx.x & 7;
-        const int64_t lo = H.own ? own_lo : H.fb_split[xcd], hi = H.own ? own_hi : H.fb_split[xcd + 1];
-        n_slots = (int64_t)(n_wgr >> 3) * NW;
-        g_first = lo + (int64_t)(wgr >> 3) * NW + wave;
-        n_groups = hi;
+        n_slots = (int64_t)(n_wgr >> 3) * SEGK_K1_NW;
+        g_first = share.lo + (int64_t)(wgr >> 3) * SEGK_K1_NW + wave;
+        n_groups = share.hi;
     }
 
     // the rows of group g into a register set
-#define SEGK_RS_LOAD(g_, XB, HROW, HK)                                                                          \
+#define SEGK_RS_LOAD(g_, XB)                                                                                    \
     do {                                                                                                         \
         _Pragma("unroll") for (int b = 0; b < NBLK; b++) {                                                       \
             const int64_t r = (g_) * (32 * NBLK) + 32 * b + j;                                                   \
             int64_t rowid = -1;                                                                                  \
             if (r < H.n) rowid = H.ids ? (int64_t)H.ids[r] : H.row0 + r;                                         \
-            HROW[b] = -1;                                                                                        \
             if (rowid < 0) rowid = 0;          /* a skipped entry of the id list: some valid row, result unused */ \
             const T *xp = plane0 + rowid * KP + 8 * h;                                                           \
             _Pragma("unroll") for (int s = 0; s < KS; s++) XB[b][s] = *reinterpret_cast<const V8 *>(xp + 16 * s); \
         }                                                                                                        \
-        _Pragma("unroll") for (int b = 0; b < NBLK; b++) HK[b] = -1;                                             \
     } while (0)
 
     // MFMAs of block N_ (accumulator AN) over the drain of block O_'s values (accumulator AO).  The twenty operations of the
@@ -482,24 +471,17 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
         }                                                                                                             \
     } while (0)
 
-    // (two tiles per trip: with one, the accumulator of block 3 and the constants of the next tile change registers
-    // across the back edge -- 24 moves and an s_nop 11 per tile)
+    // one tile: its two units.  (SEGK_RS_GROUP takes two tiles per trip: with one, the accumulator of the last block and the
+    // constants of the next tile change registers across the back edge -- 24 moves and an s_nop 11 per tile)
 #define SEGK_RS_TILE(XB, t_)                                        \
     do {                                                            \
         const int tn = (t_) + 1 < nt ? (t_) + 1 : 0;     /* the last tile refills tile 0's operands: the next group's */ \
-        if constexpr (NBLK == 4) {                                  \
-            SEGK_RS_UNIT(XB, 0, acc0, 3, acc1, false);              \
-            SEGK_RS_UNIT(XB, 1, acc1, 0, acc0, false);              \
-            SEGK_RS_UNIT(XB, 2, acc0, 1, acc1, false);              \
-            SEGK_RS_UNIT(XB, 3, acc1, 2, acc0, true);               \
-        } else {                                                    \
-            SEGK_RS_UNIT(XB, 0, acc0, 1, acc1, false);              \
-            SEGK_RS_UNIT(XB, 1, acc1, 0, acc0, true);               \
-        }                                                           \
+        SEGK_RS_UNIT(XB, 0, acc0, 1, acc1, false);                  \
+        SEGK_RS_UNIT(XB, 1, acc1, 0, acc0, true);                   \
     } while (0)
 
-    // one group: all the range's tiles against the rows in XB, then the (m1, m2) of its rows and the marks of their hints
-#define SEGK_RS_GROUP(g_, XB, HROW, HK)                                                                                   \
+    // one group: all the range's tiles against the rows in XB, then the (m1, m2) of its rows
+#define SEGK_RS_GROUP(g_, XB)                                                                                             \
     do {                                                                                                                   \
         float m1[NBLK], m2[NBLK];                                                                                          \
         _Pragma("unroll") for (int b = 0; b < NBLK; b++) { m1[b] = NEG_INF_F; m2[b] = NEG_INF_F; }                         \
@@ -522,8 +504,6 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
             const float o1 = __shfl_xor(m1[b], 32), o2 = __shfl_xor(m2[b], 32);                                            \
             pend1[b] = fmaxf(m1[b], o1);                                                                                   \
             pend2[b] = fmaxf(fminf(m1[b], o1), fmaxf(m2[b], o2));                                                          \
-            pend_row[b] = HROW[b];                                                                                         \
-            pend_k[b] = HK[b];                                                                                             \
         }                                                                                                                  \
         pend_g = (g_);                                                                                                     \
     } while (0)
@@ -535,7 +515,6 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
             _Pragma("unroll") for (int b = 0; b < NBLK; b++) {                                                             \
                 const int64_t r = pend_g * (32 * NBLK) + 32 * b + j;                                                       \
                 if (h == 0 && r < H.n && !(H.dbg & 1)) part[(int64_t)range * H.n + r] = make_float2(pend1[b], pend2[b]); \
-                (void)pend_row[b]; (void)pend_k[b];                                                                        \
             }                                                                                                              \
         }                                                                                                                  \
     } while (0)
@@ -553,24 +532,22 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
     };
     int64_t g = g_first;
     float pend1[NBLK], pend2[NBLK];
-    int32_t pend_row[NBLK], pend_k[NBLK];
     int64_t pend_g = -1;
     V8 xa[NBLK][KS];
-    int32_t hrow_a[NBLK], hk_a[NBLK];
     typedef __attribute__((address_space(3))) void *lptr_t;
-    if (!is_hint && mm_on && g < n_groups && !(H.dbg & 4)) SEGK_RS_LOAD(g, xa, hrow_a, hk_a);      // the first rows are requested in front of the tile images (the wait for those, below, covers them)
+    if (!is_hint && mm_on && g < n_groups && !(H.dbg & 4)) SEGK_RS_LOAD(g, xa);      // the first rows are requested in front of the tile images (the wait for those, below, covers them)
 #ifdef SEGK_STAMP
     const unsigned long long st_k1 = __builtin_amdgcn_s_memtime();
 #endif
     // ---- the range's tile images into LDS, once.  The unit of the copy is one 1 KiB piece-0 block (a k-step of a tile:
-    // 64 lanes x 16 bytes, contiguous in both images): wave w takes the blocks w, w + NW, ...; source and destination of a
+    // 64 lanes x 16 bytes, contiguous in both images): wave w takes the blocks w, w + SEGK_K1_NW, ...; source and destination of a
     // block are wave-uniform (scalar arithmetic), and ALL of a wave's loads -- 28 for the headline model -- are in flight
     // together: one round trip for the 114 KB.  (Element-wise with a division per 16 bytes and 16 loads in flight per thread
     // the fill took 21 700 cycles, 12 us of a 200 us kernel -- and a third of a 1 250-utterance shard's.)
     {
         constexpr int MAXT = (160 * 1024 / (TL * 4)) < SEGK_HINT_MAX_TPR ? (160 * 1024 / (TL * 4)) : SEGK_HINT_MAX_TPR;
         constexpr int MAXB = MAXT * KS;                                 // blocks of the largest range (LDS, SEGK_HINT_MAX_TPR)
-        constexpr int NWF = 2 * NW;                                     // all eight waves copy
+        constexpr int NWF = 2 * SEGK_K1_NW;                                     // all eight waves copy
         constexpr int PER_W = (MAXB + NWF - 1) / NWF;
         const int n_blk = nt * KS;
         // every workgroup of a range copies the same bytes at the same moment: started at the same block they all queue on
@@ -601,21 +578,17 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
         if (has_c) cv4 = *reinterpret_cast<const float4 *>(tiles + (int64_t)(t_lo + (tid >> 3)) * STRIDE + KS * P * 256 + (tid & 7) * 4);
         // the label map of the hint waves behind the tile images
         int32_t *map_l = reinterpret_cast<int32_t *>(lds + map_off);
-        if (H.own) {
-            // the label a hint of the previous call stands for now (the relabelling of clean_components), or -1 when the
-            // filters' images carry that component as absent (a marked duplicate: such a hint proves nothing)
-            for (int k = tid; k < H.K_max; k += 128 * NW) {
-                int v = H.remap ? H.remap[k] : k;
-                if (v < 0 || v >= H.K_max) v = -1;
-                else if (H.all_tiles[(int64_t)(v >> 5) * STRIDE + KS * P * 256 + (v & 31)] < -1.0e37f) v = -1;
-                if (skip_ok && v >= 0 && H.meanchg[v]) v |= SEGK_MEANCHG_BIT;
-                map_l[k] = v;
-            }
-        } else {
-            for (int k = tid; k < H.K_max; k += 128 * NW) map_l[k] = H.map[k];
+        // the label a hint of the previous call stands for now (the relabelling of clean_components), or -1 when the
+        // filters' images carry that component as absent (seed constant <= -1e37, a marked duplicate: such a hint proves nothing)
+        for (int k = tid; k < H.K_max; k += 128 * SEGK_K1_NW) {
+            int v = H.remap ? H.remap[k] : k;
+            if (v < 0 || v >= H.K_max) v = -1;
+            else if (H.full.tiles[(int64_t)(v >> 5) * STRIDE + KS * P * 256 + (v & 31)] < -1.0e37f) v = -1;
+            if (skip_ok && v >= 0 && H.meanchg[v]) v |= SEGK_MEANCHG_BIT;
+            map_l[k] = v;
         }
         if (has_c) *reinterpret_cast<float4 *>(lds + (tid >> 3) * TL + KS * 256 + (tid & 7) * 4) = cv4;
-        static_assert(128 * NW >= MAXT * 8, "one thread per float4 of the constants");
+        static_assert(128 * SEGK_K1_NW >= MAXT * 8, "one thread per float4 of the constants");
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -625,84 +598,70 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
         if (H.ctl && !delta && mm_on && wgr == 0) {
             float4 *dst = reinterpret_cast<float4 *>(H.snap_img + 4 + (int64_t)t_lo * TL);
             const float4 *src = reinterpret_cast<const float4 *>(lds);
-            for (int i = tid - 64 * NW; i < nt * (TL / 4); i += 64 * NW) dst[i] = src[i];
+            for (int i = tid - 64 * SEGK_K1_NW; i < nt * (TL / 4); i += 64 * SEGK_K1_NW) dst[i] = src[i];
         }
         // every workgroup's hint waves take steps of 32 rows, strided over the whole grid: the chip walks the corpus front to back
-        hint_wave_rows<KS, V>(H, reinterpret_cast<const int32_t *>(lds + map_off), (int64_t)blockIdx.x * NW + (wave - NW),
-                              (int64_t)grid * NW, skip_ok);
+        hint_wave_rows<KS, V>(H, reinterpret_cast<const int32_t *>(lds + map_off), (int64_t)blockIdx.x * SEGK_K1_NW + (wave - SEGK_K1_NW),
+                              (int64_t)grid * SEGK_K1_NW, skip_ok);
         return;
     }
 #ifdef SEGK_STAMP
     const unsigned long long st_k2 = __builtin_amdgcn_s_memtime();
 #endif
     if (!mm_on || g >= n_groups || (H.dbg & 128)) return;       // (dbg 128, make DEV=1: timing of the hint waves alone)
-    if (H.dbg & 4) SEGK_RS_LOAD(g, xa, hrow_a, hk_a);
+    if (H.dbg & 4) SEGK_RS_LOAD(g, xa);
 #pragma unroll
     for (int s = 0; s < KS; s++) load_a(0, s);          // tile 0's operands for the first group; every group's last tile reloads them
     load_cs(0);
-    if constexpr (PREFETCH) {
-        V8 xb[NBLK][KS];
-        int32_t hrow_b[NBLK], hk_b[NBLK];
-        // The explicit waits (the builtin, which the compiler's wait-count pass understands; an asm wait it would not) tell
-        // it that the current set has landed BEFORE the other set's loads are issued: left to itself it waits for the
-        // current set inside the tile loop with counted vmcnt, which -- the counter being in issue order -- waits out the
-        // prefetch too.  What is outstanding at such a wait was issued a whole group earlier (the rows, the stores of the
-        // group before).
+    V8 xb[NBLK][KS];                                    // the second register set: groups alternate between xa and xb
+    // The explicit waits (the builtin, which the compiler's wait-count pass understands; an asm wait it would not) tell
+    // it that the current set has landed BEFORE the other set's loads are issued: left to itself it waits for the
+    // current set inside the tile loop with counted vmcnt, which -- the counter being in issue order -- waits out the
+    // prefetch too.  What is outstanding at such a wait was issued a whole group earlier (the rows, the stores of the
+    // group before).
 #ifdef SEGK_STAMP
-        unsigned long long st_wait = 0, st_loop = 0, st_groups = 0;
-        const unsigned long long st_begin = __builtin_amdgcn_s_memtime();
+    unsigned long long st_wait = 0, st_loop = 0, st_groups = 0;
+    const unsigned long long st_begin = __builtin_amdgcn_s_memtime();
 #define SEGK_ST(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
 #else
 #define SEGK_ST(var) do { } while (0)
 #endif
-        for (;;) {
-            SEGK_ST(s0);
-            __builtin_amdgcn_s_waitcnt(0x0F70);                             // vmcnt(0): the rows of group g are in xa
-            SEGK_ST(s1);
-            const int64_t g1 = g + n_slots;
-            if (g1 < n_groups) SEGK_RS_LOAD(g1, xb, hrow_b, hk_b);          // in flight under this group's tile loop
-            SEGK_RS_STORE();
-            SEGK_ST(s2);
-            SEGK_RS_GROUP(g, xa, hrow_a, hk_a);
-            SEGK_ST(s3);
+    for (;;) {
+        SEGK_ST(s0);
+        __builtin_amdgcn_s_waitcnt(0x0F70);                             // vmcnt(0): the rows of group g are in xa
+        SEGK_ST(s1);
+        const int64_t g1 = g + n_slots;
+        if (g1 < n_groups) SEGK_RS_LOAD(g1, xb);          // in flight under this group's tile loop
+        SEGK_RS_STORE();
+        SEGK_ST(s2);
+        SEGK_RS_GROUP(g, xa);
+        SEGK_ST(s3);
 #ifdef SEGK_STAMP
-            st_wait += s1 - s0; st_loop += s3 - s2; st_groups++;
+        st_wait += s1 - s0; st_loop += s3 - s2; st_groups++;
 #endif
-            if (g1 >= n_groups) break;
-            SEGK_ST(s4);
-            __builtin_amdgcn_s_waitcnt(0x0F70);
-            SEGK_ST(s5);
-            g = g1 + n_slots;
-            if (g < n_groups) SEGK_RS_LOAD(g, xa, hrow_a, hk_a);
-            SEGK_RS_STORE();
-            SEGK_ST(s6);
-            SEGK_RS_GROUP(g1, xb, hrow_b, hk_b);
-            SEGK_ST(s7);
+        if (g1 >= n_groups) break;
+        SEGK_ST(s4);
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+        SEGK_ST(s5);
+        g = g1 + n_slots;
+        if (g < n_groups) SEGK_RS_LOAD(g, xa);
+        SEGK_RS_STORE();
+        SEGK_ST(s6);
+        SEGK_RS_GROUP(g1, xb);
+        SEGK_ST(s7);
 #ifdef SEGK_STAMP
-            st_wait += s5 - s4; st_loop += s7 - s6; st_groups++;
+        st_wait += s5 - s4; st_loop += s7 - s6; st_groups++;
 #endif
-            if (g >= n_groups) break;
-        }
+        if (g >= n_groups) break;
+    }
 #ifdef SEGK_STAMP
-        if (H.stamp && lane == 0) {
-            unsigned long long *o = H.stamp + ((int64_t)blockIdx.x * NW + wave) * 8;
-            o[0] = st_wait; o[1] = st_loop; o[2] = __builtin_amdgcn_s_memtime() - st_begin; o[3] = st_groups;
-            o[4] = st_begin - st_k0; o[5] = st_r0; o[6] = __builtin_amdgcn_s_memrealtime(); o[7] = ((st_k1 - st_k0) << 32) | (st_k2 - st_k1);
-        }
+    if (H.stamp && lane == 0) {
+        unsigned long long *o = H.stamp + ((int64_t)blockIdx.x * SEGK_K1_NW + wave) * 8;
+        o[0] = st_wait; o[1] = st_loop; o[2] = __builtin_amdgcn_s_memtime() - st_begin; o[3] = st_groups;
+        o[4] = st_begin - st_k0; o[5] = st_r0; o[6] = __builtin_amdgcn_s_memrealtime(); o[7] = ((st_k1 - st_k0) << 32) | (st_k2 - st_k1);
+    }
 #endif
 #undef SEGK_ST
-    } else {
-        for (;;) {
-            SEGK_RS_GROUP(g, xa, hrow_a, hk_a);
-            const int64_t gp = pend_g;
-            g += n_slots;
-            if (g < n_groups) SEGK_RS_LOAD(g, xa, hrow_a, hk_a);            // the next rows first, the stores behind them
-            pend_g = gp;
-            SEGK_RS_STORE();
-            pend_g = -1;
-            if (g >= n_groups) break;
-        }
-    }
     SEGK_RS_STORE();
     if (fb && lane == 0) atomicMax(&H.fb_t[H.fb_cur * 8 + (blockIdx.x & 7)], (unsigned int)(__builtin_amdgcn_s_memrealtime() - fb_t0));
 #undef SEGK_RS_STORE
@@ -712,67 +671,6 @@ __global__ __launch_bounds__(128 * NW, 1) void k_kmeans_top2_rs(HintArgs H)
 #undef SEGK_RS_LOAD
 }
 #undef SEGK_RS_DRAIN_QUAD
-
-// One small launch in front of K1:
-//   map[k] = the label a hint k of the previous call stands for now (remap, identity when NULL), or -1 when that component
-//            is carried as "absent" by the filters' images (seed constant <= -1e37: a marked duplicate) -- such a hint
-//            proves nothing;
-//   the queue lengths of the call cleared: the caller's ambiguity queue (when segk_kmeans_score_hinted deferred it) and the
-//   second stage's counters; the XCDs' shares of K1's row groups; (m1, m2) = (0, 0) for the rows K1 leaves out.
-__global__ void k_hint_map(const int32_t *remap, const float *tiles_sp /* first tile */, int K_max, int stride, int const_off, int32_t *map,
-                           int64_t n, int32_t *zero_cnt, int32_t *pre_hdr,
-                           float *fb_w, unsigned int *fb_t, int fb_cur, int64_t *fb_split, int64_t total_groups, int64_t first_skipped,
-                           float2 *part, int n_ranges)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (blockIdx.x == 0) {
-        if (threadIdx.x == 0 && zero_cnt) *zero_cnt = 0;
-        if (threadIdx.x < 16) pre_hdr[threadIdx.x] = 0;
-        // the XCDs' shares of the matrix kernel's row groups for the launch behind this one (see k_kmeans_top2_rs): share of
-        // the previous launch / lifetime of its waves = the rate an XCD showed; new share = half the old one, half the rate's
-        if (threadIdx.x < 64 && fb_split) {                     // lane x < 8 = XCD x (one load round trip, sums and prefix by shuffles)
-            const int x = threadIdx.x & 7;
-            const bool mine = threadIdx.x < 8;
-            const int cur = fb_cur, prev = (cur + 2) % 3, next = (cur + 1) % 3;
-            const float wp = fb_w[prev * 8 + x];
-            const unsigned int tp = fb_t ? fb_t[prev * 8 + x] : 0u;
-            const bool ok = __all(tp > 0u && wp > 0.f);           // (lanes 8.. repeat lanes 0..7)
-            const float rate = ok ? wp / (float)tp : 0.f;
-            float rsum = rate;
-            rsum += __shfl_xor(rsum, 1);
-            rsum += __shfl_xor(rsum, 2);
-            rsum += __shfl_xor(rsum, 4);
-            float w = !(wp > 0.f) ? 0.125f : ok ? 0.5f * wp + 0.5f * (rate / rsum) : wp;
-            w = fminf(fmaxf(w, 0.0625f), 0.25f);
-            float wsum = w;
-            wsum += __shfl_xor(wsum, 1);
-            wsum += __shfl_xor(wsum, 2);
-            wsum += __shfl_xor(wsum, 4);
-            // exclusive prefix over the eight lanes, added in XCD order (every lane the same sequence of additions)
-            double cum = 0.0;
-            for (int y = 0; y < 8; y++) {
-                const float wy = __shfl(w, y);
-                if (y < x) cum += (double)wy;
-            }
-            if (mine) {
-                fb_split[x] = (int64_t)(cum * ((double)total_groups / (double)wsum));
-                fb_w[cur * 8 + x] = w / wsum;
-                if (fb_t) fb_t[next * 8 + x] = 0u;
-                if (x == 0) fb_split[8] = total_groups;
-            }
-        }
-    }
-    // rows the matrix kernel leaves out (the groups behind the last whole round of all its waves, when they are few): (m1, m2) =
-    // (0, 0) in every range reads as "undecided" to the merge, which queues them for the second stage
-    if (first_skipped + i < n)
-        for (int rg = 0; rg < n_ranges; rg++) part[(int64_t)rg * n + first_skipped + i] = make_float2(0.f, 0.f);
-    if (i < K_max) {
-        int v = remap ? remap[i] : (int)i;
-        if (v < 0 || v >= K_max) v = -1;
-        else if (tiles_sp[(int64_t)(v >> 5) * stride + const_off + (v & 31)] < -1.0e37f) v = -1;
-        map[i] = v;
-    }
-}
 
 // ---- delta score pass: what changed since the base pass ------------------------------------------------------------------
 // One small launch in front of K1.  A workgroup per tile: every column of the image K1 multiplies (piece 0 of every k-step and the
@@ -1104,226 +1002,203 @@ __global__ __launch_bounds__(SEGK_MERGE_THREADS) void k_hint_merge(ScoreArgs A, 
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-template <int KS>
-static int launch_score_hint(segk_ctx *ctx, ScoreArgs A, const int32_t *remap, const int32_t *K_dev, int64_t n_emb, hipStream_t st)
+// ---- host side: workspaces -> plan -> delta prep -> K1 -> merge -> second stage ---------------------------------------------
+// How one call is laid out over K1
+struct HintLaunch {
+    HintPlan lds;                   // the LDS ranges of a full launch
+    bool band;                      // the band stage takes the undecided rows (else: the three-product second stage)
+    int grid;                       // a full launch's workgroups
+    int64_t k1_groups;              // row groups K1 multiplies; the rows from k1_groups * 64 on take the full scan
+    float *fb_w;                    // the XCD shares' three slots, this call's slot (k1_xcd_share)
+    unsigned int *fb_t;             // NULL: equal shares
+    int fb_cur;
+    float4 *hint_out;               // the hint waves' result, behind the matrix waves' in hint_part
+    bool part_fresh;                // hint_part has just been reallocated: it holds no base pass
+};
+
+// The second stage's queue (as the pre-filter path) and its thresholds, K1's partial top-2 and hint scores, the XCD shares
+static int hint_workspaces(segk_ctx *ctx, ScoreArgs &A, HintLaunch &L, hipStream_t st)
 {
-    const int n_cu = ctx->n_cu;
-    // ---- workspaces: the second stage's queue (as the pre-filter path), K1's partial top-2, the hint map
-    if (ctx->pre_cap < A.n) {
-        SEGK_REQUIRE(!ctx->capturing, "workspaces must exist before a graph capture (run the sequence once first)");
-        if (ctx->pre_queue) SEGK_CHECK_HIP(hipFree(ctx->pre_queue));
-        ctx->pre_queue = nullptr;
-        ctx->pre_cap = 0;
-        SEGK_CHECK_HIP(hipMalloc((void **)&ctx->pre_queue, sizeof(int32_t) * (size_t)(A.n + 16)));
-        ctx->pre_cap = A.n;
-    }
+    if (int rc = segk_ws_grow(ctx, &ctx->pre_queue, &ctx->pre_cap, A.n, sizeof(int32_t) * (size_t)(A.n + 16), st)) return rc;
     A.pre_queue = ctx->pre_queue + 16;
     A.pre_count = ctx->pre_queue;
     A.pre_cap = (int)A.n;
-    const bool band = segk_band_applies(A);
-    if (band && ctx->pre_thr_cap < A.n) {
-        SEGK_REQUIRE(!ctx->capturing, "workspaces must exist before a graph capture (run the sequence once first)");
-        SEGK_CHECK_HIP(hipStreamSynchronize(st));
-        if (ctx->pre_thr) (void)hipFree(ctx->pre_thr);
-        ctx->pre_thr = nullptr;
-        ctx->pre_thr_cap = 0;
-        SEGK_CHECK_HIP(hipMalloc((void **)&ctx->pre_thr, sizeof(float) * (size_t)A.n));
-        ctx->pre_thr_cap = A.n;
-    }
-    // K1's ranges: as many tiles as fit in LDS beside nothing else (one workgroup per CU)
-    constexpr int TL = KS * 256 + 32;
-    const size_t map_bytes = (size_t)((A.K_max + 3) & ~3) * sizeof(int32_t);          // the hint waves' label map behind the images
-    SEGK_REQUIRE(map_bytes + TL * sizeof(float) <= 160 * 1024, "hinted score path: K_max too large for the label map in LDS");
-    int max_tiles = (int)((160 * 1024 - map_bytes) / (TL * sizeof(float)));
-    if (max_tiles > SEGK_HINT_MAX_TPR) max_tiles = SEGK_HINT_MAX_TPR;
-    int n_ranges = (A.n_tiles + max_tiles - 1) / max_tiles;
-    // two ranges at least when that halves the LDS fill per workgroup without starving the grid (the fill is per workgroup)
-    if (n_ranges < 1) n_ranges = 1;
-    const int tpr = (A.n_tiles + n_ranges - 1) / n_ranges;
-    SEGK_REQUIRE(n_ranges <= 4, "hinted score path: K_max too large (more than four LDS ranges of tile images)");
+    if (L.band)
+        if (int rc = segk_ws_grow(ctx, &ctx->pre_thr, &ctx->pre_thr_cap, A.n, sizeof(float) * (size_t)A.n, st)) return rc;
     // [n_ranges][n] (m1, m2) of the matrix waves, then [n] {s, f_h, h, 0} of the hint waves
-    const size_t part_bytes = ((size_t)n_ranges * (size_t)A.n * sizeof(float2) + 255) & ~(size_t)255;
+    const size_t part_bytes = ((size_t)L.lds.n_ranges * (size_t)A.n * sizeof(float2) + 255) & ~(size_t)255;
     const size_t need_part = part_bytes + (size_t)A.n * sizeof(float4);
-    const bool realloc_part = ctx->hint_part_bytes < need_part;
-    if (realloc_part || !ctx->hint_map || ctx->hint_map_k < A.K_max) {
-        SEGK_REQUIRE(!ctx->capturing, "workspaces must exist before a graph capture (run the sequence once first)");
-        SEGK_CHECK_HIP(hipStreamSynchronize(st));
-        if (ctx->hint_part_bytes < need_part) {
-            if (ctx->hint_part) (void)hipFree(ctx->hint_part);
-            ctx->hint_part = nullptr;
-            ctx->hint_part_bytes = 0;
-            SEGK_CHECK_HIP(hipMalloc((void **)&ctx->hint_part, need_part));
-            ctx->hint_part_bytes = need_part;
-        }
-        if (!ctx->hint_map || ctx->hint_map_k < A.K_max) {
-            if (ctx->hint_map) (void)hipFree(ctx->hint_map);
-            ctx->hint_map = nullptr;
-            SEGK_CHECK_HIP(hipMalloc((void **)&ctx->hint_map, sizeof(int32_t) * (size_t)A.K_max));
-            ctx->hint_map_k = A.K_max;
-        }
-    }
-    // queue lengths of the call (the caller's ambiguity queue, deferred by segk_kmeans_score, and the second stage's)
-    int32_t *zero_cnt = ctx->defer_zero;
-    ctx->defer_zero = nullptr;
-    const int stride_sp = segk_sp_tile_stride(A.D, 2);
-    // per-XCD shares of the row groups (see the kernel): three slots of (shares, lifetimes), owned by the context
+    L.part_fresh = ctx->hint_part_bytes < need_part;
+    if (int rc = segk_ws_grow(ctx, &ctx->hint_part, &ctx->hint_part_bytes, need_part, need_part, st)) return rc;
+    L.hint_out = (float4 *)((unsigned char *)ctx->hint_part + part_bytes);
+    // per-XCD shares of the row groups (k1_xcd_share): three slots of (shares, lifetimes), owned by the context
     if (!ctx->hint_fb) {
-        SEGK_CHECK_HIP(hipMalloc(&ctx->hint_fb, 3 * 8 * (sizeof(float) + sizeof(unsigned int)) + 16 * sizeof(int64_t)));
         float init[3 * 8 + 3 * 8];
+        SEGK_CHECK_HIP(hipMalloc(&ctx->hint_fb, sizeof(init)));
         for (int i = 0; i < 24; i++) init[i] = 0.125f;
         memset(init + 24, 0, 24 * sizeof(unsigned int));
         SEGK_CHECK_HIP(hipMemcpyAsync(ctx->hint_fb, init, sizeof(init), hipMemcpyHostToDevice, st));
         SEGK_CHECK_HIP(hipStreamSynchronize(st));                            // (`init` lives on this stack frame)
         ctx->hint_fb_launch = 0;
     }
-    const bool fb_off = segk_env_int("SEGK_HINT_BALANCE", 1) == 0;
-    float *fb_w = (float *)ctx->hint_fb;
+    return SEGK_OK;
+}
+
+// A full launch's grid, the XCD shares' slot, and the row groups K1 multiplies
+static void hint_plan_rows(segk_ctx *ctx, const ScoreArgs &A, HintLaunch &L)
+{
+    const int n_ranges = L.lds.n_ranges;
+    const int64_t total_groups = (A.n + 63) / 64;                // K1: two blocks of 32 rows per group
+    L.fb_w = (float *)ctx->hint_fb;
     // (only where a wave has a few dozen groups to shift: at shard sizes -- 4 to 8 groups of 5 us per wave -- shares other
     // than equal ones only make the last round ragged: 1 250 utterances 5 960 against 6 215 sweeps/s, 2 500: 4 878 against 4 948)
-    const bool fb_big = (A.n + 63) / 64 >= 192 * 64;
-    unsigned int *fb_t = (fb_off || !fb_big) ? nullptr : (unsigned int *)(fb_w + 24);
-    int64_t *fb_split = (int64_t *)(fb_w + 48);                  // [9] (+ padding), rewritten by every launch of k_hint_map
-    const int fb_cur = (int)(ctx->hint_fb_launch++ % 3u);
-    const int64_t total_groups = (A.n + 63) / 64;                // k_kmeans_top2_rs<KS, 4>: two blocks of 32 rows per group
-    // K1's grid: four waves per workgroup (one per SIMD with the next group's rows prefetched into registers; the eight-wave
-    // instantiation -- two per SIMD, no prefetch: +6 % -- is still in the kernel's template, no longer launched)
-    constexpr int nw1 = 4;
-    int grid1 = (n_cu / n_ranges) * n_ranges;
-    {   // no more workgroups than there are steps per range (each wave takes 64 rows at a time)
-        const int64_t rows_ws = 64 * (int64_t)nw1;                          // rows a workgroup takes per step
-        const int64_t steps = (A.n + rows_ws - 1) / rows_ws;
-        if ((int64_t)grid1 / n_ranges > steps) grid1 = (int)steps * n_ranges;
-    }
+    const bool fb_big = total_groups >= 192 * 64;
+    L.fb_t = (segk_env_int("SEGK_HINT_BALANCE", 1) == 0 || !fb_big) ? nullptr : (unsigned int *)(L.fb_w + 24);
+    L.fb_cur = (int)(ctx->hint_fb_launch++ % 3u);
+    // one workgroup per CU in whole sets of ranges, no more than there are steps per range (a workgroup's four matrix waves
+    // take 64 rows each at a time)
+    L.grid = (ctx->n_cu / n_ranges) * n_ranges;
+    const int64_t steps = (A.n + 64 * SEGK_K1_NW - 1) / (64 * SEGK_K1_NW);
+    if ((int64_t)L.grid / n_ranges > steps) L.grid = (int)steps * n_ranges;
     // With equal shares every wave walks the groups slot, slot + slots, ...: when a handful of groups is left behind the last
     // whole round (a 1 250-utterance shard: 2 051 groups = 4 x 512 + 3) three waves would take a fifth group, 5 us, for all
-    // the others to wait on.  Those few rows skip the filter: marked undecided (k_hint_map), they take the second stage.
-    // (with the band stage the rows K1 leaves out would take the full scan, 9 us for a shard's 192 rows: no skipping then)
-    int64_t k1_groups = total_groups;
-    if (!fb_t && !band) {
-        const int64_t slots = (int64_t)(grid1 / n_ranges) * nw1;
+    // the others to wait on.  Those few rows skip the filter: k_hint_merge sends them to the full scan.
+    // (in front of the band stage that is 9 us for a shard's 192 rows: no skipping then)
+    L.k1_groups = total_groups;
+    if (!L.fb_t && !L.band) {
+        const int64_t slots = (int64_t)(L.grid / n_ranges) * SEGK_K1_NW;
         const int64_t whole = slots > 0 ? (total_groups / slots) * slots : 0;
-        if (whole > 0 && total_groups - whole <= 32) k1_groups = whole;
+        if (whole > 0 && total_groups - whole <= 32) L.k1_groups = whole;
     }
-    // k_hint_map's work is K1's own (H.own) unless rows are left out (their (m1, m2) must be initialised in front of K1)
-    const bool own = k1_groups == total_groups;
+}
 
-    // ---- delta score pass: K1's (m1, m2) of the last FULL launch stay in hint_part as the base; while the call tuple repeats,
-    // k_delta_prep finds the columns whose image changed since and K1 multiplies those alone.  SEGK_SCORE_DELTA=0: never.
-    const bool delta_on = segk_env_int("SEGK_SCORE_DELTA", 1) != 0 && band && own && A.ids == nullptr && A.n_tiles <= 32 * SEGK_PREP_COLS;
+// ---- delta score pass: K1's (m1, m2) of the last FULL launch stay in hint_part as the base; while the call tuple repeats,
+// k_delta_prep finds the columns whose image changed since and K1 multiplies those alone.
+// Its state, one allocation (ctx->delta_buf); every part starts on a 256-byte boundary:
+struct DeltaBuf {
+    int32_t *ctl;                   // [64] control words (see SEGK_DELTA_MODE); NULL: no delta pass in this call
+    int32_t *colchg, *meanchg;      // per column of the image / row of `means`: changed
+    float *snap_img;                // the base pass's image [4 floats: exponent][n_tiles][KS * 256 + 32]
+    float *packed;                  // the packed image of the changed columns [n_tiles][stride]
+    float *snap_means;              // the previous call's `means` [K_max][D]
+    float2 *part;                   // [n] (m1, m2) over the packed columns
+    int32_t *lab_base;              // [n] the label the base pass certified, or -1
+    size_t zero_bytes;              // what a fresh allocation must have cleared: everything in front of snap_means
+};
+// the parts of a buffer at `b` (NULL: the sizes only); returns its bytes
+static size_t delta_layout(unsigned char *b, int n_tiles, int K_max, int D, int64_t n, int stride, DeltaBuf *B)
+{
+    const size_t TL = (size_t)(segk_b3_kp(D) / 16) * 256 + 32;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        unsigned char *p = b ? b + off : nullptr;
+        off += (bytes + 255) & ~(size_t)255;
+        return p;
+    };
+    B->ctl = (int32_t *)take(256);
+    B->colchg = (int32_t *)take((size_t)n_tiles * 32 * 4);
+    B->meanchg = (int32_t *)take((size_t)K_max * 4);
+    B->snap_img = (float *)take(((size_t)n_tiles * TL + 4) * 4);
+    B->packed = (float *)take((size_t)n_tiles * stride * 4);
+    B->zero_bytes = off;
+    B->snap_means = (float *)take((size_t)K_max * D * 4);
+    B->part = (float2 *)take((size_t)n * 8);
+    B->lab_base = (int32_t *)take((size_t)n * 4);
+    return off;
+}
+
+// k_delta_prep in front of K1 where the delta pass applies (SEGK_SCORE_DELTA=0: never); B->ctl == NULL where it does not.
+// *cap: packed tiles a delta launch takes at most.
+template <int KS>
+static int launch_delta_prep(segk_ctx *ctx, const ScoreArgs &A, const int32_t *remap, const int32_t *K_dev, int64_t n_emb,
+                             const HintLaunch &L, hipStream_t st, DeltaBuf *B, int *cap)
+{
+    *B = DeltaBuf{};
+    *cap = 0;
+    const bool delta_on = segk_env_int("SEGK_SCORE_DELTA", 1) != 0 && L.band && A.ids == nullptr && A.n_tiles <= 32 * SEGK_PREP_COLS;
     const void *key[6] = {A.X32, A.xrows32, A.tiles, A.means32, A.cand.k, A.cand.s};
     const int64_t key_n[5] = {A.row0, A.n, n_emb, A.K_max, A.D};
-    bool state_valid = delta_on && !realloc_part && ctx->delta_valid && memcmp(key, ctx->delta_key, sizeof(key)) == 0 &&
+    bool state_valid = delta_on && !L.part_fresh && ctx->delta_valid && memcmp(key, ctx->delta_key, sizeof(key)) == 0 &&
                        memcmp(key_n, ctx->delta_key_n, sizeof(key_n)) == 0;
     ctx->delta_valid = 0;
-    int32_t *d_ctl = nullptr, *d_colchg = nullptr, *d_meanchg = nullptr, *d_lab = nullptr;
-    float2 *d_part = nullptr;
-    float *d_packed = nullptr, *d_snap = nullptr;
-    int delta_cap = 0;
-    if (delta_on) {
-        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t o_col = 256, o_mean = o_col + up((size_t)A.n_tiles * 32 * 4), o_snap = o_mean + up((size_t)A.K_max * 4),
-                     o_pack = o_snap + up(((size_t)A.n_tiles * TL + 4) * 4), o_sm = o_pack + up((size_t)A.n_tiles * stride_sp * 4),
-                     o_pd = o_sm + up((size_t)A.K_max * A.D * 4), o_lab = o_pd + up((size_t)A.n * 8), need = o_lab + up((size_t)A.n * 4);
-        if (ctx->delta_bytes != need) {
-            SEGK_CHECK_HIP(hipStreamSynchronize(st));
-            if (ctx->delta_buf) (void)hipFree(ctx->delta_buf);
-            ctx->delta_buf = nullptr;
-            ctx->delta_bytes = 0;
-            SEGK_CHECK_HIP(hipMalloc(&ctx->delta_buf, need));
-            ctx->delta_bytes = need;
-            state_valid = false;
-            // (the packed image's free slots must hold finite operands: zero now, copies of real columns ever after)
-            SEGK_CHECK_HIP(hipMemsetAsync(ctx->delta_buf, 0, o_sm, st));
-        }
-        unsigned char *b = (unsigned char *)ctx->delta_buf;
-        d_ctl = (int32_t *)b; d_colchg = (int32_t *)(b + o_col); d_meanchg = (int32_t *)(b + o_mean);
-        d_snap = (float *)(b + o_snap);
-        d_packed = (float *)(b + o_pack); d_part = (float2 *)(b + o_pd); d_lab = (int32_t *)(b + o_lab);
-        // packed tiles at most: a full launch's range (measured on the headline corpus against 2, 4, 8, 12 and 20 tiles:
-        // profiles/README.md), never more than fit in K1's LDS
-        delta_cap = segk_env_int("SEGK_DELTA_CAP", tpr);
-        if (delta_cap > max_tiles) delta_cap = max_tiles;
-        if (delta_cap < 1) delta_cap = 1;
-        DeltaPrepArgs P{};
-        P.tiles_hdr = A.tiles; P.n_tiles = A.n_tiles; P.stride = stride_sp;
-        P.K_max = A.K_max; P.D = A.D; P.means32 = A.means32; P.remap = remap; P.K_dev = K_dev;
-        P.valid = state_valid ? 1 : 0; P.hint_valid = state_valid ? 1 : 0; P.cap = delta_cap;
-        P.budget = segk_env_int("SEGK_DELTA_BUDGET", A.n_tiles);
-        P.seq = (int)(ctx->delta_seq++ & 1u);
-        P.ctl = d_ctl; P.colchg = d_colchg; P.meanchg = d_meanchg;
-        P.snap_img = (float *)(b + o_snap); P.packed = d_packed; P.snap_means = (float *)(b + o_sm);
-        const int rows_blocks = (A.K_max + 7) / 8 < 128 ? (A.K_max + 7) / 8 : 128;
-        hipLaunchKernelGGL(k_delta_prep<KS>, dim3(A.n_tiles + rows_blocks), dim3(SEGK_PREP_THREADS), 0, st, P);
-        memcpy(ctx->delta_key, key, sizeof(key));
-        memcpy(ctx->delta_key_n, key_n, sizeof(key_n));
-        ctx->delta_valid = 1;
+    if (!delta_on) return SEGK_OK;
+    const int stride_sp = segk_sp_tile_stride(A.D, 2);
+    const size_t need = delta_layout(nullptr, A.n_tiles, A.K_max, A.D, A.n, stride_sp, B);
+    if (ctx->delta_bytes != need) {
+        ctx->delta_bytes = 0;
+        if (int rc = segk_ws_realloc(ctx, &ctx->delta_buf, need, st)) return rc;
+        ctx->delta_bytes = need;
+        state_valid = false;
+        // (the packed image's free slots must hold finite operands: zero now, copies of real columns ever after)
+        SEGK_CHECK_HIP(hipMemsetAsync(ctx->delta_buf, 0, B->zero_bytes, st));
     }
-    if (!own) {
-        const int64_t skipped = A.n - k1_groups * 64 > 0 ? A.n - k1_groups * 64 : 0;
-        const int64_t nthr = skipped > A.K_max ? skipped : A.K_max;
-        hipLaunchKernelGGL(k_hint_map, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, st, remap, A.tiles + 1024, A.K_max, stride_sp,
-                           KS * 2 * 256, ctx->hint_map, A.n, zero_cnt, ctx->pre_queue, fb_w, fb_t, fb_cur,
-                           fb_split, total_groups, k1_groups * 64, (float2 *)ctx->hint_part, n_ranges);
-    }
+    delta_layout((unsigned char *)ctx->delta_buf, A.n_tiles, A.K_max, A.D, A.n, stride_sp, B);
+    // packed tiles at most: a full launch's range (measured on the headline corpus against 2, 4, 8, 12 and 20 tiles:
+    // profiles/README.md), never more than fit in K1's LDS
+    *cap = segk_env_int("SEGK_DELTA_CAP", L.lds.tpr);
+    if (*cap > L.lds.max_tiles) *cap = L.lds.max_tiles;
+    if (*cap < 1) *cap = 1;
+    DeltaPrepArgs P{};
+    P.tiles_hdr = A.tiles; P.n_tiles = A.n_tiles; P.stride = stride_sp;
+    P.K_max = A.K_max; P.D = A.D; P.means32 = A.means32; P.remap = remap; P.K_dev = K_dev;
+    P.valid = state_valid ? 1 : 0; P.hint_valid = state_valid ? 1 : 0; P.cap = *cap;
+    P.budget = segk_env_int("SEGK_DELTA_BUDGET", A.n_tiles);
+    P.seq = (int)(ctx->delta_seq++ & 1u);
+    P.ctl = B->ctl; P.colchg = B->colchg; P.meanchg = B->meanchg;
+    P.snap_img = B->snap_img; P.packed = B->packed; P.snap_means = B->snap_means;
+    const int rows_blocks = (A.K_max + 7) / 8 < 128 ? (A.K_max + 7) / 8 : 128;
+    hipLaunchKernelGGL(k_delta_prep<KS>, dim3(A.n_tiles + rows_blocks), dim3(SEGK_PREP_THREADS), 0, st, P);
+    memcpy(ctx->delta_key, key, sizeof(key));
+    memcpy(ctx->delta_key_n, key_n, sizeof(key_n));
+    ctx->delta_valid = 1;
+    return SEGK_OK;
+}
 
-    // ---- K1: matrix waves (top-2 values per row and range) + hint waves (the hinted component in reference arithmetic)
+// K1: matrix waves (top-2 values per row and range) + hint waves (the hinted component in reference arithmetic).  One launch
+// with both parameter sets, the larger of their grids and LDS sizes.
+template <int KS>
+static int launch_k1(segk_ctx *ctx, const ScoreArgs &A, const int32_t *remap, int64_t n_emb, const HintLaunch &L, const DeltaBuf &B,
+                     int delta_cap, hipStream_t st)
+{
+    constexpr int TL = KS * 256 + 32;
     HintArgs H{};
     H.ximg = (const unsigned char *)A.X32;
     H.ids = A.ids; H.row0 = A.row0; H.n = A.n;
-    H.tiles = A.tiles + 1024;
-    H.all_tiles = A.tiles + 1024;
-    H.ctl = d_ctl;
-    H.meanchg = d_meanchg;
-    H.snap_img = d_snap;
-    H.n_tiles = A.n_tiles; H.tpr = tpr; H.n_ranges = n_ranges;
-    H.part = (float2 *)ctx->hint_part;
     H.K_max = A.K_max;
     H.dbg = segk_dev_env("SEGK_HINT_DBG");
 #ifdef SEGK_STAMP
     H.stamp = getenv("SEGK_STAMP_PTR") ? (unsigned long long *)strtoull(getenv("SEGK_STAMP_PTR"), nullptr, 0) : nullptr;
 #endif
-    H.fb_w = fb_w;
-    H.fb_t = fb_t;
-    H.fb_cur = fb_cur;
-    H.fb_split = fb_split;
-    H.k1_groups = k1_groups;
-    H.xrows32 = A.xrows32;
-    H.ld32 = A.ld32;
-    H.means32 = A.means32;
-    H.cand_k = A.cand.k;
-    H.map = ctx->hint_map;
-    H.own = own ? 1 : 0;
+    H.fb_w = L.fb_w; H.fb_t = L.fb_t; H.fb_cur = L.fb_cur;
     H.remap = remap;
-    H.zero_cnt = zero_cnt;
+    // queue lengths of the call (the caller's ambiguity queue, deferred by segk_kmeans_score_hinted, and the second stage's)
+    H.zero_cnt = ctx->defer_zero;
+    ctx->defer_zero = nullptr;
     H.pre_hdr = ctx->pre_queue;
-    H.total_groups = total_groups;
+    H.k1_groups = L.k1_groups;
+    H.xrows32 = A.xrows32; H.ld32 = A.ld32; H.means32 = A.means32;
+    H.cand_k = A.cand.k;
     H.nxx = A.xerr + n_emb;                                      // -|x|^2 per row, behind the residual norms
-    H.hint_out = (float4 *)((unsigned char *)ctx->hint_part + part_bytes);
-    const size_t lds1 = (size_t)tpr * TL * sizeof(float) + map_bytes;
-    // the delta parameter set of the same launch: one range over the packed image, its tile count in ctl[2]; every workgroup's
-    // slots over all rows
-    H.d_tiles = d_packed;
-    H.d_tpr = delta_cap;
-    H.d_part = d_part;
-    size_t lds_k1 = lds1;
-    int grid_k1 = grid1;
-    H.grid_f = grid1;
-    if (delta_on) {
-        const size_t lds_d = (size_t)delta_cap * TL * sizeof(float) + map_bytes;
-        int grid_d = n_cu;
-        if ((int64_t)grid_d > (A.n + 255) / 256) grid_d = (int)((A.n + 255) / 256);
-        H.grid_d = grid_d;
-        if (grid_d > grid_k1) grid_k1 = grid_d;
-        if (lds_d > lds_k1) lds_k1 = lds_d;
+    H.hint_out = L.hint_out;
+    H.ctl = B.ctl; H.meanchg = B.meanchg; H.snap_img = B.snap_img;
+    H.full = K1Set{A.tiles + 1024, A.n_tiles, L.lds.tpr, L.lds.n_ranges, (float2 *)ctx->hint_part, L.grid};
+    size_t lds = (size_t)L.lds.tpr * TL * sizeof(float) + L.lds.map_bytes;
+    int grid = L.grid;
+    if (B.ctl) {
+        // one range over the packed image, every workgroup's slots over all rows
+        const int64_t steps = (A.n + 64 * SEGK_K1_NW - 1) / (64 * SEGK_K1_NW);
+        H.delta = K1Set{B.packed, 0, delta_cap, 1, B.part, (int64_t)ctx->n_cu > steps ? (int)steps : ctx->n_cu};
+        const size_t lds_d = (size_t)delta_cap * TL * sizeof(float) + L.lds.map_bytes;
+        if (H.delta.grid > grid) grid = H.delta.grid;
+        if (lds_d > lds) lds = lds_d;
     }
     const bool prof = segk_prof_now(ctx);
     const int slot = ctx->prof_n % SEGK_PROF_SLOTS;
 #define SEGK_K1_LAUNCH(VV)                                                                                                  \
     do {                                                                                                                     \
-        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_kmeans_top2_rs<KS, VV, 4>, lds_k1));                                     \
+        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_kmeans_top2_rs<KS, VV>, lds));                                           \
         if (prof) SEGK_CHECK_HIP(hipEventRecord(ctx->prof_ev[slot][0], st));                                                 \
-        hipLaunchKernelGGL((k_kmeans_top2_rs<KS, VV, 4>), dim3((unsigned)grid_k1), dim3(512), lds_k1, st, H);                \
+        hipLaunchKernelGGL((k_kmeans_top2_rs<KS, VV>), dim3((unsigned)grid), dim3(128 * SEGK_K1_NW), lds, st, H);            \
     } while (0)
     switch ((16 * KS - A.D) / 4) {
         case 0: SEGK_K1_LAUNCH(0); break;
@@ -1339,41 +1214,56 @@ static int launch_score_hint(segk_ctx *ctx, ScoreArgs A, const int32_t *remap, c
         ctx->prof_launches = 1;
         ctx->prof_n++;
     }
+    return SEGK_OK;
+}
 
-    // ---- K2: the certificate, one thread per row
+// K2: the certificate, one thread per row
+static void launch_merge(segk_ctx *ctx, const ScoreArgs &A, const HintLaunch &L, const DeltaBuf &B, int ks, hipStream_t st)
+{
     HintMergeArgs E{};
     E.part = (const float2 *)ctx->hint_part;
-    E.hint_out = H.hint_out;
-    E.n_ranges = n_ranges;
+    E.hint_out = L.hint_out;
+    E.n_ranges = L.lds.n_ranges;
     E.tiles_hdr = A.tiles;
     E.ximg = (const unsigned char *)A.X32;
-    E.ctl = d_ctl;
-    E.part_delta = d_part;
-    E.lab_base = d_lab;
-    E.colchg = d_colchg;
+    E.ctl = B.ctl;
+    E.part_delta = B.part;
+    E.lab_base = B.lab_base;
+    E.colchg = B.colchg;
     E.stats_host = ctx->delta_host_dev;
-    {
-        // one workgroup per CU, each a contiguous run of at most SEGK_MERGE_ROWS rows
-        int64_t grid2 = (int64_t)n_cu;
-        if (grid2 * SEGK_MERGE_THREADS > A.n) grid2 = (A.n + SEGK_MERGE_THREADS - 1) / SEGK_MERGE_THREADS;
-        if (grid2 * SEGK_MERGE_ROWS < A.n) grid2 = (A.n + SEGK_MERGE_ROWS - 1) / SEGK_MERGE_ROWS;
-        const int64_t per = (A.n + grid2 - 1) / grid2;
-        hipLaunchKernelGGL(k_hint_merge, dim3((unsigned)grid2), dim3(SEGK_MERGE_THREADS), 0, st, A, E, KS * 16, per, band ? ctx->pre_thr : nullptr,
-                           k1_groups * 64);
-    }
+    // one workgroup per CU, each a contiguous run of at most SEGK_MERGE_ROWS rows
+    int64_t grid = (int64_t)ctx->n_cu;
+    if (grid * SEGK_MERGE_THREADS > A.n) grid = (A.n + SEGK_MERGE_THREADS - 1) / SEGK_MERGE_THREADS;
+    if (grid * SEGK_MERGE_ROWS < A.n) grid = (A.n + SEGK_MERGE_ROWS - 1) / SEGK_MERGE_ROWS;
+    const int64_t per = (A.n + grid - 1) / grid;
+    hipLaunchKernelGGL(k_hint_merge, dim3((unsigned)grid), dim3(SEGK_MERGE_THREADS), 0, st, A, E, ks * 16, per,
+                       L.band ? ctx->pre_thr : nullptr, L.k1_groups * 64);
+}
+
+template <int KS>
+static int launch_score_hint(segk_ctx *ctx, ScoreArgs A, const int32_t *remap, const int32_t *K_dev, int64_t n_emb, hipStream_t st)
+{
+    HintLaunch L{};
+    L.band = segk_band_applies(A);
+    SEGK_REQUIRE(segk_hint_plan(A.K_max, KS, A.n_tiles, &L.lds),
+                 "hinted score path: K_max too large for K1's LDS (the label map beside four ranges of tile images at most)");
+    if (int rc = hint_workspaces(ctx, A, L, st)) return rc;
+    hint_plan_rows(ctx, A, L);
+    DeltaBuf B;
+    int delta_cap;
+    if (int rc = launch_delta_prep<KS>(ctx, A, remap, K_dev, n_emb, L, st, &B, &delta_cap)) return rc;
+    if (int rc = launch_k1<KS>(ctx, A, remap, n_emb, L, B, delta_cap, st)) return rc;
+    launch_merge(ctx, A, L, B, KS, st);
     // ---- the rows the certificate could not decide: candidates inside the band of the filter's maximum, scored in the
-    // reference's arithmetic (segk_score_band.hip); tables beyond its reach keep round 3's three-product second stage
-    if (band) {
-        if (int rc = segk_launch_band(ctx, A, ctx->pre_thr, A.n, KS, st)) return rc;
-        return SEGK_OK;
-    }
+    // reference's arithmetic (segk_score_band.hip); tables beyond its reach keep the three-product second stage
+    if (L.band) return segk_launch_band(ctx, A, ctx->pre_thr, A.n, KS, st);
     // ---- the rows K2 queued: all three products (the pre-filter's second stage); its own undecided rows go to cand.queue
-    ScoreArgs B = A;
-    B.ids = A.pre_queue;
-    B.row0 = 0;
-    B.n = A.n;
-    B.n_dev = ctx->pre_queue;
-    if (int rc = segk_launch_sp_second(ctx, B, KS, st)) return rc;
+    ScoreArgs B2 = A;
+    B2.ids = A.pre_queue;
+    B2.row0 = 0;
+    B2.n = A.n;
+    B2.n_dev = ctx->pre_queue;
+    if (int rc = segk_launch_sp_second(ctx, B2, KS, st)) return rc;
     SEGK_LAUNCH_CHECK();
     return SEGK_OK;
 }

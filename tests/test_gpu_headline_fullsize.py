@@ -163,8 +163,8 @@ def _hinted(gpu, dk, hints, remap):
 
 def test_a_hinted_path_gives_the_oracle_bits_whatever_the_hints(gpu, headline, scored, monkeypatch):
     """segk_kmeans_score_hinted on the 1.05 M rows and the statistics of test_a (whose cand_k / cand_s are the C oracle's):
-    the value-only top-2 on the matrix cores (k_kmeans_top2_rs) + the exact stage that verifies a hint per row
-    (k_kmeans_hint_exact) must return the same bits for ANY hints -- the true winners (the steady state of a chain), the
+    the value-only top-2 on the matrix cores beside the hinted component's exact score (k_kmeans_top2_rs) + the certificate
+    that verifies a hint per row (k_hint_merge) must return the same bits for ANY hints -- the true winners (the steady state of a chain), the
     winners under another labelling through the relabel table, every hint wrong, garbage, and the adversarial one: a hint
     that names an exact duplicate (higher row) of the true winner, which the dense filter values alone cannot tell from the
     winner (np.argmax takes the first; the library carries marked duplicates as absent, so such a hint proves nothing)."""

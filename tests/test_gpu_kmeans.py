@@ -89,15 +89,11 @@ def test_a1_max_argmax_vs_oracle_random(gpu, monkeypatch, D, K, n, dtype, b3):
 
 
 
-@pytest.mark.parametrize("D,K,n", [(100, 1000, 6000), (8, 33, 3000), (40, 257, 5000), (128, 2300, 4000), (12, 64, 2000),
-                                    (64, 700, 9000)])
-def test_a1_hinted_path_vs_oracle_random(gpu, monkeypatch, D, K, n):
-    """segk_kmeans_score_hinted forced at small sizes (SEGK_SCORE_HINT=1) on random data with engineered exact ties: hints
-    that are right, wrong, garbage and duplicates of the winner; row ranges and id lists (with -1 entries and an offset);
-    one, two and four LDS ranges of tile images (K = 2300: 72 tiles).  cand_k / cand_s == the C oracle, bit for bit."""
+def _hinted_case(D, K, n):
+    """Random rows and means with an engineered exact tie (a duplicate mean, a row sitting on it), the C oracle's answer, and
+    `run`: one forced hinted call (the caller sets SEGK_SCORE_HINT=1) with the given hints -> (cand_k, cand_s)."""
     import torch
     from oracle import c_oracle as co
-    monkeypatch.setenv("SEGK_SCORE_HINT", "1")
     rs = np.random.RandomState(D * 7 + K)
     K_true = max(2, K // 2)
     mu = rs.randn(K_true, D)
@@ -111,7 +107,6 @@ def test_a1_hinted_path_vs_oracle_random(gpu, monkeypatch, D, K, n):
     X[5] = means[1]                   # ... and a data point sitting on it
     c = _components(X, means)
     from segmentalist_amd import _abi
-    from segmentalist_amd._abi import ptr
     import ctypes as C
     _abi.check(_abi.lib().segk_kmeans_mark_duplicates(c.dev._ctx, c.dev._cp(), C.byref(c.dev.m), None, _abi.stream()))
     want_s, want_k = co.kmeans_max_argmax(means, X)
@@ -130,6 +125,19 @@ def test_a1_hinted_path_vs_oracle_random(gpu, monkeypatch, D, K, n):
         _abi.check(_abi.lib().segk_profile_enable(c.dev._ctx, 0))
         assert kind == 5, kind
         return c.dev.cand_k.cpu().numpy(), c.dev.cand_s.cpu().numpy()
+
+    return c, rs, want_s, want_k, run
+
+
+@pytest.mark.parametrize("D,K,n", [(100, 1000, 6000), (8, 33, 3000), (40, 257, 5000), (128, 2300, 4000), (12, 64, 2000),
+                                    (64, 700, 9000)])
+def test_a1_hinted_path_vs_oracle_random(gpu, monkeypatch, D, K, n):
+    """segk_kmeans_score_hinted forced at small sizes (SEGK_SCORE_HINT=1) on random data with engineered exact ties: hints
+    that are right, wrong, garbage and duplicates of the winner; row ranges and id lists (with -1 entries and an offset);
+    one, two and four LDS ranges of tile images (K = 2300: 72 tiles).  cand_k / cand_s == the C oracle, bit for bit."""
+    import torch
+    monkeypatch.setenv("SEGK_SCORE_HINT", "1")
+    c, rs, want_s, want_k, run = _hinted_case(D, K, n)
 
     # right hints, whole range
     k, s = run(want_k)
@@ -155,6 +163,26 @@ def test_a1_hinted_path_vs_oracle_random(gpu, monkeypatch, D, K, n):
     k, s = run(inv[want_k], ids=ids, remap=torch.from_numpy(perm).cuda())
     live = ids[ids >= 0]
     assert np.array_equal(k[live], want_k[live]) and np.array_equal(s[live], want_s[live].astype(np.float64))
+
+
+def test_a1_hinted_path_rows_left_out_of_k1(gpu, monkeypatch):
+    """The hinted path with row groups left out of K1.  D = 8, K = 2300: 72 tiles, three LDS ranges, beyond the band stage.
+    With W = CUs // 3 workgroups per range, n = 64 (4 W + 3) rows are four whole rounds of the matrix waves plus three groups:
+    those 192 rows skip the filter and reach the full scan through the ambiguity queue alone (cand_count >= 192 shows that
+    the case was hit).  cand_k / cand_s == the C oracle, bit for bit, with right hints and with a wrong / garbage mix."""
+    import torch
+    monkeypatch.setenv("SEGK_SCORE_HINT", "1")
+    D, K = 8, 2300
+    W = torch.cuda.get_device_properties(0).multi_processor_count // 3
+    n = 64 * (4 * W + 3)
+    c, rs, want_s, want_k, run = _hinted_case(D, K, n)
+    k, s = run(want_k)
+    assert np.array_equal(k, want_k) and np.array_equal(s, want_s.astype(np.float64))
+    assert int(c.dev.cand_count.item()) >= 192
+    junk = rs.choice(np.array([-1, -5, K, 2 ** 29 | 1, 2 ** 30 | 2, 2 ** 31 - 1], dtype=np.int64), n)
+    hints = np.where(rs.rand(n) < 0.3, want_k, np.where(rs.rand(n) < 0.5, rs.randint(0, K, n), junk))
+    k, s = run(hints)
+    assert np.array_equal(k, want_k) and np.array_equal(s, want_s.astype(np.float64))
 
 
 @pytest.mark.parametrize("transform", affine.NAMES)
