@@ -795,7 +795,7 @@ static inline bool segk_hint_plan(int K_max, int ks, int n_tiles, HintPlan *p)
 int segk_dispatch_score_hint(segk_ctx *ctx, const ScoreArgs &A, const int32_t *remap, const int32_t *K_dev, int64_t n_emb, int ks, hipStream_t st);
 // segk_score_band.hip: the hinted path's undecided rows -- candidates inside the band of the filter's maximum, exact scores
 bool segk_band_applies(const ScoreArgs &A);
-int segk_launch_band(segk_ctx *ctx, const ScoreArgs &A, const float *thr, int64_t call_rows, int ks, hipStream_t st);
+int segk_launch_band(segk_ctx *ctx, const ScoreArgs &A, const float *thr, int64_t call_rows, int32_t *lab_last, int ks, hipStream_t st);
 // segk_exact.hip / segk_stats.hip: the pieces of the sequential (reference-chain) sweep
 int segk_launch_seq_score(const segk_corpus *c, const segk_kmeans *m, int utt, const segk_cand *cand, unsigned long long *keys,
                           hipStream_t st);

@@ -280,6 +280,8 @@ struct BandExactArgs {
     const float *means32;
     segk_cand cand;
     int amb_cap;
+    int32_t *lab_last;              // per position of the call (row id - row0): the decided row's winner, for the next call's carry-over
+    int64_t row0;                   // (segk_score_hint.hip; NULL: the call keeps no delta state)
 };
 
 // K4.  One thread per (queue entry, mask word): words per row = n_ranges x 2 lane halves x 4.  Bit pb of word ww of (range,
@@ -393,6 +395,7 @@ __global__ __launch_bounds__(256) void k_band_exact(BandExactArgs E)
                 const unsigned int bits = (ord & 0x80000000u) ? (ord & 0x7fffffffu) : ~ord;
                 E.cand.k[rid] = (int32_t)(0xffffffffu - (unsigned int)(mine & 0xffffffffu));
                 E.cand.s[rid] = (double)__uint_as_float(bits);
+                if (E.lab_last) E.lab_last[(int64_t)rid - E.row0] = (int32_t)(0xffffffffu - (unsigned int)(mine & 0xffffffffu));
             } else {                                       // no candidate inside the band (or too many): the full scan decides
                 const int q2 = atomicAdd(E.cand.count, 1);
                 if (q2 < E.amb_cap) E.cand.queue[q2] = rid;
@@ -404,7 +407,7 @@ __global__ __launch_bounds__(256) void k_band_exact(BandExactArgs E)
 
 // ---------------------------------------------------------------------------------------------------------------------
 template <int KS>
-static int launch_band(segk_ctx *ctx, const ScoreArgs &A, const float *thr, int64_t call_rows, hipStream_t st)
+static int launch_band(segk_ctx *ctx, const ScoreArgs &A, const float *thr, int64_t call_rows, int32_t *lab_last, hipStream_t st)
 {
     const int n_cu = ctx->n_cu;
     const int n_ranges = (A.n_tiles + SEGK_BAND_TPR - 1) / SEGK_BAND_TPR;
@@ -449,6 +452,8 @@ static int launch_band(segk_ctx *ctx, const ScoreArgs &A, const float *thr, int6
     E.means32 = A.means32;
     E.cand = A.cand;
     E.amb_cap = A.amb_cap;
+    E.lab_last = A.ids ? nullptr : lab_last;              // (positions are row id - row0: no id list)
+    E.row0 = A.row0;
     // (the queue length is on the device: a grid for the queue lengths that occur -- 5 to 20 % of the rows --, waves stride)
     const int rpw = 64 / (n_ranges * 8);
     int64_t grid4 = ((int64_t)cap + 4 * rpw - 1) / (4 * rpw);
@@ -470,17 +475,17 @@ bool segk_band_applies(const ScoreArgs &A)
     return n_ranges >= 1 && n_ranges <= SEGK_BAND_MAX_RANGES && A.D % 4 == 0 && A.D >= 8 && A.D <= 128;
 }
 
-int segk_launch_band(segk_ctx *ctx, const ScoreArgs &A, const float *thr, int64_t call_rows, int ks, hipStream_t st)
+int segk_launch_band(segk_ctx *ctx, const ScoreArgs &A, const float *thr, int64_t call_rows, int32_t *lab_last, int ks, hipStream_t st)
 {
     switch (ks) {
-        case 1: return launch_band<1>(ctx, A, thr, call_rows, st);
-        case 2: return launch_band<2>(ctx, A, thr, call_rows, st);
-        case 3: return launch_band<3>(ctx, A, thr, call_rows, st);
-        case 4: return launch_band<4>(ctx, A, thr, call_rows, st);
-        case 5: return launch_band<5>(ctx, A, thr, call_rows, st);
-        case 6: return launch_band<6>(ctx, A, thr, call_rows, st);
-        case 7: return launch_band<7>(ctx, A, thr, call_rows, st);
-        case 8: return launch_band<8>(ctx, A, thr, call_rows, st);
+        case 1: return launch_band<1>(ctx, A, thr, call_rows, lab_last, st);
+        case 2: return launch_band<2>(ctx, A, thr, call_rows, lab_last, st);
+        case 3: return launch_band<3>(ctx, A, thr, call_rows, lab_last, st);
+        case 4: return launch_band<4>(ctx, A, thr, call_rows, lab_last, st);
+        case 5: return launch_band<5>(ctx, A, thr, call_rows, lab_last, st);
+        case 6: return launch_band<6>(ctx, A, thr, call_rows, lab_last, st);
+        case 7: return launch_band<7>(ctx, A, thr, call_rows, lab_last, st);
+        case 8: return launch_band<8>(ctx, A, thr, call_rows, lab_last, st);
         default: break;
     }
     segk_set_error("band stage: D out of range");

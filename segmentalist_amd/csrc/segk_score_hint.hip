@@ -43,6 +43,49 @@
 //       (HintArgs), with the larger of the two grids and LDS sizes.  The hint waves decide which positions take their score
 //       over from the previous call for a chunk of steps per round trip (hint_wave_rows).
 //
+//   Carry-over of a row's winner across the unchanged means (k_hint_merge in delta mode).  The certificate above cannot decide
+//       a near-tie row -- its runner-up sits in the base within tau, sweep after sweep -- and the band stage then finds the
+//       same winner among the same unchanged means every time.  A different argument decides such a row without the base.
+//       Take a hinted call on the same call tuple as the previous hinted call (ctx->delta_key), the relabelling the identity.
+//       For a row x let (k*, s*) be the reference's result of the PREVIOUS call: the first maximum over all K_max rows of
+//       `means` as they were then.  Let U be the rows of `means` whose float32 bits are unchanged since that call
+//       (meanchg[k] == 0), C the others.
+//         (a) For k in U the reference's score of x against k is bit for bit what it was: same row, same mean, same
+//             arithmetic.  So if k* is in U, k* is still the first maximum over U (scores and indices are what they were),
+//             and the current result is the first maximum over {k*} u C.
+//         (b) Hence x keeps (k*, s*) if every c in C scores strictly below s* in the reference.  (Strictly: with a tie a
+//             c < k* would take the first maximum.)
+//       The merge kernel proves (b) for a row at position p with hint h when ALL of these hold:
+//         1. Mode: the mode word has SEGK_DELTA_MODE and SEGK_DELTA_SKIP -- the state is valid for this tuple, the previous
+//            hinted call was on it, the relabelling is the identity.  Nothing else switches the carry-over on or off.
+//         2. h >= 0 and h == lab_last[p], the label THIS LIBRARY recorded for the position in the previous call (DeltaBuf):
+//            the hint where a certificate passed -- then h was the reference's argmax of that call --, the band stage's winner
+//            where k_band_exact decided the row, -1 otherwise (full scan: such a row takes the normal route).  cand.k is the
+//            caller's to write, so the hint alone proves nothing about the previous call; lab_last is private.  With it
+//            h = k*.  (lab_base is another thing -- the label the BASE pass certified, whose stale F_h the merge drops -- and
+//            stays apart: that repair needs F_h to have been the single largest base value, which a band winner's is not.)
+//         3. meanchg[h] == 0: k* is in U, and the hint waves' {s, f_h} for h -- recomputed, or taken over under the same
+//            condition -- is s* itself and its filter-domain value.
+//         4. Every c in C has its CURRENT filter value in the packed delta image: no k with meanchg[k] && !colchg[k].  (A
+//            float32 mean can move below the resolution of the fp16 image: no image bit changes, nothing is packed, and the
+//            base's top-2 say nothing about that column alone.)  Decided per call by every workgroup from the two flag arrays;
+//            if it fails, no row is carried in this call.  Exempt: a column the current image marks "absent" -- an exact
+//            duplicate of a lower row i.  Its score is i's bit for bit and its index is higher, so it is the first maximum of
+//            no set that contains i; and i is in U (score <= s*, and i > k* where equal, or i = k*), or in C and bounded here,
+//            or absent itself with a still lower original.
+//         5. Margin: f_h > d1 * unscale + (e1 + rnd + dl) * 1.0001, d1 = the row's part_delta m1, the largest current filter
+//            value over the packed columns (-inf: nothing packed).  With 4 every c in C that is not absent has F_c <= d1, and
+//            this is the slack the certificate above leaves between any competitor's filter value and f_h
+//            (top2 < top1 - tau <= f_h - (E + dl), E = e1 + rnd): f_c <= F_c + E < f_h - dl, so c loses to h in the
+//            reference's arithmetic exactly as every k != h does there.  The bounds are those tests/test_filter_bounds_cpu.py
+//            proves for the certificate; the carry-over adds none.  (A packed column that is h's own -- changed against the
+//            base earlier, unchanged since the previous call -- makes d1 >= F_h: the test fails and the row takes the
+//            normal route.  A changed mean bit-identical to h's has F_c = F_h: likewise.)
+//       Then cand.k = h, cand.s = s, lab_last[p] = h, and the row is not queued.  A wrong or garbage hint fails 2 and costs
+//       only time.  Every call that has delta state writes lab_last for every position, full mode included; a call without
+//       (another table, an id list, a sub-range, an un-hinted call in between, a reallocation) clears delta_valid, the next
+//       mode word has no SEGK_DELTA_SKIP, and lab_last is rewritten before it is read again.
+//
 // Results are those of segk_kmeans_score whatever the hints are (a wrong hint costs time, never correctness); the
 // full-size parity tests run this path against the C oracle row by row.
 #include "segk_kmeans_dev.h"
@@ -829,14 +872,18 @@ struct HintMergeArgs {
     const float2 *part_delta;       // (m1, m2) per position over the packed changed columns
     int32_t *lab_base;              // per position: the label the base pass certified, or -1
     const int32_t *colchg;          // per column: its image differs from the base pass's
+    const int32_t *meanchg;         // per row of `means`: its bits changed since the previous call
+    int32_t *lab_last;              // per position: the label this library decided in the previous call, or -1 (the carry-over)
     int32_t *stats_host;            // host-mapped [4] (segk_kmeans_delta_stats)
 };
 
 // K2 (round 4): the certificate.  Per row the filter's top-2 merged over the ranges, the hinted component's exact score s and its
 // filter-domain value f_h (see the head of the file):
 //     top1 - top2 > tau   and   f_h >= top1 - tau + E + dl      =>   cand.k = h, cand.s = s  (the reference's bits)
-// anything else -- no hint, a wrong hint, a near-tie -- is queued for the second stage (one reservation per wave).  One thread
-// per row, 48 bytes read and 12 written: the whole exact stage of round 3 (k_kmeans_hint_exact, 129 us) shrunk to this pass,
+// anything else -- no hint, a wrong hint, a near-tie -- is queued for the second stage (one reservation per wave), unless the
+// call is a delta call and the row's winner of the previous call carries over the unchanged means (head of the file: no base
+// value enters that test, only the changed columns' maximum and f_h).  One thread
+// per row, 48 bytes read and 12 written (with delta state 4 more each way for lab_last, the store only where it changes): the whole exact stage of round 3 (k_kmeans_hint_exact, 129 us) shrunk to this pass,
 // its arithmetic moved under K1's matrix work.
 #define SEGK_MERGE_ROWS 6144        /* rows per workgroup at most (its list of undecided rows in LDS) */
 #define SEGK_MERGE_THREADS 1024
@@ -868,6 +915,17 @@ __global__ __launch_bounds__(SEGK_MERGE_THREADS) void k_hint_merge(ScoreArgs A, 
         __hip_atomic_store(H.stats_host, H.ctl ? 1 + (delta ? 1 : 0) : 0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     __syncthreads();
+    // the carry-over (head of the file), conditions 1 and 4: per call, the same answer in every workgroup -- the two flag arrays
+    // are 8 KB from L2.  A changed mean whose column is not packed switches it off unless the current image marks it absent.
+    bool carry = false;
+    if (delta && (mw & SEGK_DELTA_SKIP) != 0 && H.lab_last) {              // (workgroup-uniform)
+        const int c_off = (KP / 16) * 512;
+        bool bad = false;
+        for (int k = tid; k < A.K_max; k += SEGK_MERGE_THREADS)
+            if (H.meanchg[k] && !H.colchg[k])
+                bad |= !(H.tiles_hdr[1024 + (int64_t)(k >> 5) * A.tile_stride + c_off + (k & 31)] < -1.0e37f);
+        carry = __syncthreads_or(bad ? 1 : 0) == 0;
+    }
     const int64_t p_lo = (int64_t)blockIdx.x * per, p_hi = p_lo + per < A.n ? p_lo + per : A.n;
     const int e_ab = ((const int *)H.ximg)[1] + ((const int *)H.tiles_hdr)[0];
     const float unscale = ldexpf(1.f, -e_ab), scale = ldexpf(1.f, e_ab);
@@ -880,6 +938,8 @@ __global__ __launch_bounds__(SEGK_MERGE_THREADS) void k_hint_merge(ScoreArgs A, 
         int32_t rid[U];
         float4 ho[U];
         float t1[U], t2[U], xnb[U], xer[U], d1[U];
+        int32_t last[U];                // lab_last of the position where the carry-over is on (else -2: matches no hint, no label)
+        bool cw[U];                     // conditions 2 and 3 of the carry-over hold for the row
 #pragma unroll
         for (int j = 0; j < U; j++) {
             const int64_t p = p0 + j * SEGK_MERGE_THREADS + tid;
@@ -903,6 +963,13 @@ __global__ __launch_bounds__(SEGK_MERGE_THREADS) void k_hint_merge(ScoreArgs A, 
                 xer[j] = A.xerr[rid[j]];
             }
             d1[j] = NEG_INF_F;
+            last[j] = -2;
+            cw[j] = false;
+            if (rid[j] >= 0 && carry) {
+                const int32_t hint = __float_as_int(ho[j].z);
+                last[j] = H.lab_last[p];
+                cw[j] = hint >= 0 && last[j] == hint && H.meanchg[hint] == 0;
+            }
             if (rid[j] >= 0 && delta) {
                 const int32_t hint = __float_as_int(ho[j].z);
                 if (hint >= 0 && H.colchg[hint] && H.lab_base[p] == hint) {
@@ -921,6 +988,7 @@ __global__ __launch_bounds__(SEGK_MERGE_THREADS) void k_hint_merge(ScoreArgs A, 
         for (int j = 0; j < U; j++) {
             bool und = false;
             float thr = 0.f;
+            int32_t keep = -1;          // what lab_last gets: the label decided here, -1 for a row that goes on
             if (rid[j] >= 0 && p0 + j * SEGK_MERGE_THREADS + tid >= first_skipped) {
                 // a row K1 left out (the few groups behind the last whole round of its waves): no filter values, full scan
                 const int q2 = atomicAdd(A.cand.count, 1);
@@ -945,10 +1013,14 @@ __global__ __launch_bounds__(SEGK_MERGE_THREADS) void k_hint_merge(ScoreArgs A, 
                     const float s2 = xnb[j] + M;
                     const float dl = ((float)(A.D / 8 + 13) + 4.f) * u * s2 * s2;
                     ok = (top1 - top2 > tau) && (ho[j].y >= top1 - tau + (e1 + rnd + dl) * 1.0001f);
-                    if (ok) {
+                    // the carry-over, condition 5: every changed mean's current filter value (at most d1) leaves f_h the slack the
+                    // certificate leaves a competitor; d1 = -inf where nothing is packed
+                    const bool carried = !ok && cw[j] && ho[j].y > d1[j] * unscale + (e1 + rnd + dl) * 1.0001f;
+                    if (ok || carried) {
                         A.cand.k[rid[j]] = hint;
                         A.cand.s[rid[j]] = (double)ho[j].x;
                         und = false;
+                        keep = hint;
                     }
                     // the current F_h is at least f_h - E - dl: a lower bound of the current top1 whatever the base holds
                     lower = (ho[j].y - (e1 + rnd + dl) * 1.0001f) * scale;
@@ -970,6 +1042,8 @@ __global__ __launch_bounds__(SEGK_MERGE_THREADS) void k_hint_merge(ScoreArgs A, 
                     }
                 }
             }
+            // every position, every call with delta state (full mode too); k_band_exact puts its winner over the -1 of a queued row
+            if (H.lab_last && rid[j] >= 0 && last[j] != keep) H.lab_last[p0 + j * SEGK_MERGE_THREADS + tid] = keep;
             const unsigned long long mask = __ballot(und);
             if (mask != 0ull) {
                 const int before = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
@@ -1083,6 +1157,8 @@ struct DeltaBuf {
     float *snap_means;              // the previous call's `means` [K_max][D]
     float2 *part;                   // [n] (m1, m2) over the packed columns
     int32_t *lab_base;              // [n] the label the base pass certified, or -1
+    int32_t *lab_last;              // [n] the label the previous call decided for the position (a certificate, the carry-over, or the
+                                    // band stage), or -1: the full scan did, or the row was not covered
     size_t zero_bytes;              // what a fresh allocation must have cleared: everything in front of snap_means
 };
 // the parts of a buffer at `b` (NULL: the sizes only); returns its bytes
@@ -1104,6 +1180,7 @@ static size_t delta_layout(unsigned char *b, int n_tiles, int K_max, int D, int6
     B->snap_means = (float *)take((size_t)K_max * D * 4);
     B->part = (float2 *)take((size_t)n * 8);
     B->lab_base = (int32_t *)take((size_t)n * 4);
+    B->lab_last = (int32_t *)take((size_t)n * 4);
     return off;
 }
 
@@ -1230,6 +1307,8 @@ static void launch_merge(segk_ctx *ctx, const ScoreArgs &A, const HintLaunch &L,
     E.part_delta = B.part;
     E.lab_base = B.lab_base;
     E.colchg = B.colchg;
+    E.meanchg = B.meanchg;
+    E.lab_last = B.lab_last;
     E.stats_host = ctx->delta_host_dev;
     // one workgroup per CU, each a contiguous run of at most SEGK_MERGE_ROWS rows
     int64_t grid = (int64_t)ctx->n_cu;
@@ -1256,7 +1335,8 @@ static int launch_score_hint(segk_ctx *ctx, ScoreArgs A, const int32_t *remap, c
     launch_merge(ctx, A, L, B, KS, st);
     // ---- the rows the certificate could not decide: candidates inside the band of the filter's maximum, scored in the
     // reference's arithmetic (segk_score_band.hip); tables beyond its reach keep the three-product second stage
-    if (L.band) return segk_launch_band(ctx, A, ctx->pre_thr, A.n, KS, st);
+    // (with delta state the band stage records its winners in lab_last, for the next call's carry-over)
+    if (L.band) return segk_launch_band(ctx, A, ctx->pre_thr, A.n, B.lab_last, KS, st);
     // ---- the rows K2 queued: all three products (the pre-filter's second stage); its own undecided rows go to cand.queue
     ScoreArgs B2 = A;
     B2.ids = A.pre_queue;
