@@ -55,8 +55,9 @@ const char *segk_last_error(void);
  *              segk_corpus.band_ids / band_dur (a COMPLETE band only); segk_fbgmm_sequential_sweep with a language model
  *   8 round 4: segk_fbb_step_diag32
  *   9 segk_fbatch.centre (the reduced-precision FBGMM kernels work in coordinates centred on it), segk_fbatch.tab32
- *  10 segk_kmeans_delta_stats                                                                                              */
-#define SEGK_ABI_VERSION 10
+ *  10 segk_kmeans_delta_stats
+ *  11 segk_fbb_segment_map, segk_fbb_assign_map (batch sweeps with fb_type "viterbi")                                       */
+#define SEGK_ABI_VERSION 11
 int32_t segk_abi_version(void);
 
 /* Timing of the MAIN launch of the MFMA score kernel (k_kmeans_score<..., 0>) with HIP events
@@ -691,6 +692,33 @@ int32_t segk_fbb_assign_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_f
                                const segk_fbatch *bt, int32_t s_lo, int32_t s_n, int32_t b,
                                const int32_t *n_utts, uint64_t sweep, double anneal_temp,
                                const int32_t *new_tok, const int32_t *n_new, void *stream);
+/* Batch sweeps with fb_type "viterbi" (ABI 11): the point estimate a sampler run ends with, without leaving batch mode.
+ * segk_fbb_segment_map is segk_fbb_segment with forward_backward_viterbi (unigram_acoustic_wordseg.py:759-864) in place of
+ * forward_backward: a max-plus recurrence that keeps one backpointer per landmark (the candidate of the largest
+ * vec + alpha, the shortest span among equal maxima: the reference's argmax(p[::-1])), and a backward pass that chases
+ * them, dead ends included (:815-825).  No exponential, no logarithm, no uniform (`sweep` is accepted and ignored), no
+ * temperature (the reference's Viterbi ignores it); bt->fast_dp changes nothing.  `status` is never written: a total of
+ * -inf raises nothing here, as in the serial kernel, which sets bit 16 only when it samples.  Same span tables (triangles
+ * for N_max <= 64, the band above), same SEGK_ERR_ARG conditions for the band, same clearing of the old segments' slots;
+ * honours segk_fbb_set_probe (alpha_out receives the forward maxima).                                                     */
+int32_t segk_fbb_segment_map(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f,
+                             const segk_fbatch *bt, int32_t s_lo, int32_t s_n, int32_t b,
+                             const int32_t *n_utts, uint64_t sweep, int32_t n_slices_min,
+                             int32_t n_slices_max, double wip, double time_power_term,
+                             const double *score, uint8_t *boundaries, int32_t *new_tok,
+                             int32_t *n_new, double *out_logprob, int32_t *status, void *stream);
+/* slot of every new segment by FBGMM.map_assign_i (fbgmm.py:465-494) on slots: the FIRST index of the maximum of
+ * log(alpha / K_max + n_k) + log predictive_k(x) over all K_max slots -- no `lms` on the prior term (fbgmm.py:475-479
+ * has none), no temperature, no uniform (`sweep` is accepted and ignored), no `k > K` clamp; an empty slot scores the prior
+ * predictive, so all empty slots of a token tie exactly and the first one stands for them.  The token likelihoods are fp64
+ * (fixed-variance: the quadratic; diagonal: the Student-t terms) or, with f32_terms != 0 (diagonal components only), the
+ * float32 Student-t terms of segk_fbb_assign_diag32.  There is no ll_mat: the fp16x2 token-likelihood matrix is never
+ * consumed.  SEGK_ERR_UNSUPPORTED with a language model (bigram_acoustic_wordseg.py has no Viterbi mode).  Honours
+ * segk_fbb_set_probe (ll_out).                                                                                              */
+int32_t segk_fbb_assign_map(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f,
+                            const segk_fbatch *bt, int32_t s_lo, int32_t s_n, int32_t b,
+                            const int32_t *n_utts, uint64_t sweep, const int32_t *new_tok,
+                            const int32_t *n_new, int32_t f32_terms, void *stream);
 /* One Gibbs step of the diagonal (Student-t) sampler in float32 terms as ONE launch (ABI 8): segk_fbb_score_diag32,
  * segk_fbb_segment and segk_fbb_assign_diag32 of block b fused -- the workgroup that owns an utterance scores its spans,
  * samples its boundaries (the same uniforms, unigram_acoustic_wordseg.py:653-864) and draws the new segments' slots from the
@@ -719,7 +747,7 @@ int32_t segk_fbb_token_scores(segk_ctx *ctx, const segk_corpus *c, const segk_fb
  * they feed).  While set, on this context:
  *   segk_fbb_segment also writes the forward filter's alpha[t] (unigram_acoustic_wordseg.py:691-703), t < N, of every
  *     utterance it samples to alpha_out[utt * N_max + t]                     (alpha_out [dev] double [n_utt, N_max]);
- *   segk_fbb_assign / segk_fbb_assign_diag32 also write, for token t of utterance utt and every slot k < K_max, the
+ *   segk_fbb_assign / segk_fbb_assign_diag32 / segk_fbb_assign_map also write, for token t of utterance utt and every slot k < K_max, the
  *     log predictive density of the token under slot k that enters its logits (posterior predictive of an occupied
  *     slot, prior predictive of an empty one: oracle/np_fbgmm_batch.py `loglik`) to
  *     ll_out[(utt * N_max + t) * ll_ld + k]                                 (ll_out [dev] double [n_utt * N_max, ll_ld]).

@@ -730,6 +730,83 @@ static __device__ double fb_dp_sample_on(const VA V, double *a, double *w, doubl
     return total;
 }
 
+// A7 (unigram_acoustic_wordseg.py:759-864) as a pure max-plus recurrence with backpointers, by one full wave: no exponential
+// and no logarithm anywhere.  The reference's backward pass takes argmax(exp(q[::-1] - logsumexp(q))): the candidate of the
+// largest q, the shortest span (largest s) among equal maxima -- exp is monotone, so the argmax over q with that tie rule is
+// the definition (oracle: tests/map_batch.py).  The forward pass therefore keeps, per landmark t = 1..N (t = N is one more
+// forward step), the LARGEST s attaining max_s vec[s, t) + alpha[s] -- -1 where the whole window is -inf -- and the backward
+// pass is pointer chasing: one LDS read per chosen segment.
+//   Windows of at most 64 slices (n_max in 1..64, or unbounded with N <= 64): lane w holds candidate s = t - 1 - w and
+//   alpha[s] in a register, the delay line of fb_dp_sample_on (DPP wave_shr:1, the new alpha entering at lane 0); the maximum
+//   by DPP inside the rows of sixteen (v_readlane across them when the window is wider than one row); the backpointer is the
+//   lowest lane of the ballot of v == max.  Wider windows (triangular tables only): candidates s = t - 1 - lane - 64 j per
+//   lane with strict >, alpha from LDS, then the largest s among the lanes that hold the maximum.
+//   V scores (LDS: FbTriVec / FbBandVec), a [N] receives alpha (a[t] = -inf for a dead window), bp [N + 1] the backpointers,
+//   bnd [N] the boundaries; returns the summed score of the chosen segments.  Values and control flow are wave-uniform.
+template <typename VA>
+static __device__ double fb_dp_viterbi_on(const VA V, double *a, int32_t *bp, int N, int n_max, uint8_t *bnd, int lane)
+{
+    for (int j = lane; j < N; j += 64) bnd[j] = (j == N - 1) ? 1 : 0;
+    if (lane == 0) { a[0] = 0.0; bp[0] = -1; }
+    const bool lanes = (n_max > 0 && n_max <= 64) || N <= 64;
+    const bool one_row = n_max > 0 && n_max <= 16;
+    int i = 0;
+    double g = 0.0;                                                  // alpha[t - 1 - lane]; alpha[0] = 0
+    for (int t = 1; t <= N; t++) {
+        const int lo = (n_max == 0 || t - n_max < 0) ? 0 : t - n_max;
+        const int n = t - lo;
+        double m;
+        int arg;
+        if (lanes) {
+            const double v = lane < n ? V.at(i, t, t - 1 - lane) + g : NEG_INF_D;
+            m = fb_wave_max(v, one_row);
+            const unsigned long long hit = __ballot(lane < n && v == m);
+            arg = m == NEG_INF_D ? -1 : t - 1 - (int)__builtin_ctzll(hit);
+            const double gs = fb_dpp_f64<0x138>(g);                  // wave_shr:1: lane w takes lane w - 1's
+            g = lane == 0 ? m : gs;
+        } else {
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // a[t - 1] was written by lane 0 a step ago
+            __builtin_amdgcn_wave_barrier();
+            double best = NEG_INF_D;
+            int bs = -1;
+            for (int s = t - 1 - lane; s >= lo; s -= 64) {
+                const double v = V.at(i, t, s) + a[s];
+                if (v > best) { best = v; bs = s; }
+            }
+            m = fb_wave_max(best, false);
+            arg = best == m ? bs : -1;                               // (-1 everywhere when the window is all -inf)
+            for (int o = 32; o > 0; o >>= 1) {
+                const int other = __shfl_xor(arg, o);
+                arg = other > arg ? other : arg;
+            }
+        }
+        if (lane == 0) {
+            if (t < N) a[t] = m;
+            bp[t] = arg;
+        }
+        i += t;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    int t = N;
+    double total = 0.0;
+    for (;;) {
+        if (bp[t] < 0) {                                             // :815-825: step back to a landmark that can end a segment
+            while (bp[t] < 0) {
+                t = t - 1;
+                if (t == 0) break;
+            }
+            if (lane == 0) bnd[(t - 1 + N) % N] = 1;
+        }
+        const int k = t > 0 ? t - bp[t] : 1;                         // (t == 0: the reference's argmax of an all-nan vector)
+        total += V.chosen((t - 1) * t / 2, t, k);
+        if (t - k - 1 < 0) break;
+        if (lane == 0) bnd[t - k - 1] = 1;
+        t = t - k;
+    }
+    return total;
+}
+
 //   vec [tri] scores, triangular (LDS)
 template <typename USRC>
 static __device__ double fb_dp_sample(const double *vec, double *a, double *w, double *pr, int N, int tri, int n_max,

@@ -1359,6 +1359,106 @@ __global__ __launch_bounds__(128) void k_fbb_segment_band(segk_corpus c, segk_fb
 }
 
 // ---------------------------------------------------------------------------------------
+// The MAP boundaries (fb_type "viterbi": unigram_acoustic_wordseg.py:759-864) of one utterance per workgroup: k_fbb_segment
+// and k_fbb_segment_band with the max-plus DP (fb_dp_viterbi_on) in place of the sampling one -- the same staging of the span
+// tables and boundary flags in LDS, the same token lists, the same clearing of the old segments' slots, the same probe.  No
+// uniforms, no temperature; the backpointers live where the sampling DP keeps its scratch row `w`.  A total of -inf sets no
+// status bit (the serial kernel raises it only when it samples).
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(128) void k_fbb_segment_map(segk_corpus c, segk_fbatch bt, FbbMap map, int b, int n_max, double wip,
+                              double time_power_term, const double *score, uint8_t *boundaries, int32_t *new_tok,
+                              int32_t *n_new, double *out_logprob, double *probe_alpha)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int s, idx;
+    if (!fbb_locate(map, blockIdx.x, &s, &idx)) return;
+    const int slice = map.lo[s];
+    const int utt = bt.utt_range[(slice * bt.n_blocks + b) * 2] + idx;
+    const int N = c.lengths[utt];                      // <= 64: corpora with longer utterances take k_fbb_segment_map_band
+    const int tri = N * (N + 1) / 2;
+    const int64_t triMax = (int64_t)c.N_max * (c.N_max + 1) / 2;
+    const FbSpanTab tab = fb_span_tab(c, utt, N, n_max);
+    double *vec = (double *)smem;                      // [tri]
+    double *a = vec + triMax;                          // [N]
+    int32_t *bp = (int32_t *)(a + c.N_max);            // [N+1] (the layout of k_fbb_segment: its w and pr rows)
+    int32_t *old = (int32_t *)(a + 3 * c.N_max + 2);   // [N_max]
+    int32_t *vid_l = old + c.N_max;                    // [triMax]
+    uint8_t *bnd_l = (uint8_t *)(vid_l + triMax);      // [N_max]
+    uint8_t *bnd_g = boundaries + (int64_t)utt * c.N_max;
+    for (int j = threadIdx.x; j < N; j += blockDim.x) bnd_l[j] = bnd_g[j];
+    if (tab.band) {
+        for (int j = threadIdx.x; j < tri; j += blockDim.x) vid_l[j] = -1;
+        __syncthreads();
+        const int W = tab.W;
+        for (int i = threadIdx.x; i < N * W; i += blockDim.x) {
+            const int t = i / W + 1, s2 = t - 1 - (i - (t - 1) * W);
+            if (s2 >= 0) vid_l[t * (t - 1) / 2 + s2] = tab.bandi[i];
+        }
+    } else {
+        for (int j = threadIdx.x; j < tri; j += blockDim.x) vid_l[j] = tab.vid[j];
+    }
+    fb_fill_vec(tab, N, tri, [&](int id) { return score[id]; }, time_power_term, wip, vec, threadIdx.x, blockDim.x);
+    __syncthreads();
+    if (threadIdx.x >= 64) return;
+    const int lane = threadIdx.x;
+    const int n_old = fb_collect_tokens_wave(vid_l, bnd_l, N, old, lane);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const double total = fb_dp_viterbi_on(FbTriVec{vec, tri}, a, bp, N, n_max, bnd_l, lane);
+    if (probe_alpha)            // segk_fbb_set_probe: the forward maxima (the backward pass only reads the backpointers)
+        for (int j = lane; j < N; j += 64) probe_alpha[(int64_t)utt * c.N_max + j] = a[j];
+    for (int j = lane; j < n_old; j += 64) bt.slot[old[j]] = -1;
+    // (the boundary flags were written by lane 0 of this wave)
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const int nn = fb_collect_tokens_wave(vid_l, bnd_l, N, new_tok + (int64_t)utt * c.N_max, lane);
+    for (int j = lane; j < N; j += 64) bnd_g[j] = bnd_l[j];
+    if (lane != 0) return;
+    out_logprob[utt] = total;
+    n_new[utt] = nn;
+}
+
+__global__ __launch_bounds__(128) void k_fbb_segment_map_band(segk_corpus c, segk_fbatch bt, FbbMap map, int b, double wip,
+                              double time_power_term, const double *score, uint8_t *boundaries, int32_t *new_tok,
+                              int32_t *n_new, double *out_logprob, double *probe_alpha)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int s, idx;
+    if (!fbb_locate(map, blockIdx.x, &s, &idx)) return;
+    const int slice = map.lo[s];
+    const int utt = bt.utt_range[(slice * bt.n_blocks + b) * 2] + idx;
+    const int N = c.lengths[utt], NM = c.N_max, W = c.band_W;
+    double *vec = (double *)smem;                      // [N_max W]
+    double *a = vec + (int64_t)NM * W;                 // [N_max]
+    int32_t *bp = (int32_t *)(a + NM);                 // [N_max + 1] (the layout of k_fbb_segment_band: its w and pr rows)
+    int32_t *old = (int32_t *)(a + 3 * NM + 2);        // [N_max]
+    int32_t *bid_l = old + NM;                         // [N_max W]
+    uint8_t *bnd_l = (uint8_t *)(bid_l + (int64_t)NM * W);      // [N_max]
+    uint8_t *bnd_g = boundaries + (int64_t)utt * NM;
+    for (int j = threadIdx.x; j < N; j += blockDim.x) bnd_l[j] = bnd_g[j];
+    fb_fill_vec_band(c.band_ids + (int64_t)utt * NM * W, c.band_dur + (int64_t)utt * NM * W, N, W, [&](int id) { return score[id]; },
+                     time_power_term, wip, vec, bid_l, threadIdx.x, blockDim.x);
+    __syncthreads();
+    if (threadIdx.x >= 64) return;
+    const int lane = threadIdx.x;
+    const int n_old = fb_collect_tokens_wave_band(bid_l, W, bnd_l, N, old, lane);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const double total = fb_dp_viterbi_on(FbBandVec{vec, W, N}, a, bp, N, W, bnd_l, lane);
+    if (probe_alpha)
+        for (int j = lane; j < N; j += 64) probe_alpha[(int64_t)utt * NM + j] = a[j];
+    for (int j = lane; j < n_old; j += 64) bt.slot[old[j]] = -1;
+    // (the boundary flags were written by lane 0 of this wave)
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const int nn = fb_collect_tokens_wave_band(bid_l, W, bnd_l, N, new_tok + (int64_t)utt * NM, lane);
+    for (int j = lane; j < N; j += 64) bnd_g[j] = bnd_l[j];
+    if (lane != 0) return;
+    out_logprob[utt] = total;
+    n_new[utt] = nn;
+}
+
+// ---------------------------------------------------------------------------------------
 // slots of the new tokens of one utterance per workgroup
 // ---------------------------------------------------------------------------------------
 template <typename XT, int COV, int F32 = 0>
@@ -1580,6 +1680,148 @@ __global__ __launch_bounds__(512) void k_fbb_assign(segk_corpus c, segk_fbgmm f,
             }
             __syncthreads();
             if (f.lm_unigram) j_prev = sh_k;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// The MAP slot of every new token (FBGMM.map_assign_i, fbgmm.py:465-494, on slots): k = the first index of the maximum of
+// z_k = log(alpha / K_max + n_k) + loglik_k(x) -- no `lms` on the prior term (fbgmm.py:475-479 has none), no temperature, no
+// uniform, no softmax (the reference's argmax(exp(z - logsumexp z)) is the argmax of z: tests/test_map_batch_cpu.py holds
+// that on every token of the test corpora).  k_fbb_assign without a language model with the draw replaced: one workgroup per
+// utterance; the prior terms once per workgroup into LDS; the likelihoods of a chunk of tokens by the same accumulation
+// (fbb_accumulate / fbb_accumulate_rows / fbb_accumulate_rows32, the same row groups) into LDS; then one WAVE per token: a
+// per-lane (value, index) over k = lane, lane + 64, ... with strict >, the wave's maximum by DPP and the lowest index among
+// the lanes that hold it.  All empty slots of a token carry one value, so the first of them wins a tie among them without
+// being treated apart.  Never reads ll_mat: in the fixed-variance tolerance modes the token likelihood is the fp64 quadratic
+// (F32 = 1: the float32 Student-t terms of segk_fbb_assign_diag32).
+// ---------------------------------------------------------------------------------------
+static __device__ __forceinline__ int fbb_wave_min_i32(int v)       // minimum over the 64 lanes, wave-uniform
+{
+    int o = __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false);
+    v = o < v ? o : v;
+    o = __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, false);
+    v = o < v ? o : v;
+    o = __builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, false);
+    v = o < v ? o : v;
+    o = __builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false);
+    v = o < v ? o : v;
+    const int r0 = __builtin_amdgcn_readlane(v, 0), r1 = __builtin_amdgcn_readlane(v, 16);
+    const int r2 = __builtin_amdgcn_readlane(v, 32), r3 = __builtin_amdgcn_readlane(v, 48);
+    const int a = r1 < r0 ? r1 : r0, c = r3 < r2 ? r3 : r2;
+    return c < a ? c : a;
+}
+
+template <typename XT, int COV, int F32 = 0>
+__global__ __launch_bounds__(512) void k_fbb_assign_map(segk_corpus c, segk_fbgmm f, segk_fbatch bt, FbbMap map, int b, double prior_alpha,
+                                 const int32_t *new_tok, const int32_t *n_new, int rcap, double *probe_ll, int64_t probe_ld)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int D = c.D, KM = f.K_max, tid = threadIdx.x, nt = blockDim.x;
+    double *pz = (double *)smem;                 // [K_max] log(alpha / K_max + n_k)
+    double *ll = pz + KM;                        // [rcap][K_max]
+    double *xs = ll + (int64_t)rcap * KM;        // [FBA_R][D]
+    double *lpr = xs + FBA_R * D;                // [FBA_R]
+    int s, idx;
+    if (!fbb_locate(map, blockIdx.x, &s, &idx)) return;
+    const int slice = map.lo[s];
+    const int utt = bt.utt_range[(slice * bt.n_blocks + b) * 2] + idx;
+    const XT *X = (const XT *)c.X;
+    const int nn = n_new[utt];
+    if (nn == 0) return;
+    for (int k = tid; k < KM; k += nt) pz[k] = log(prior_alpha / (double)KM + bt.cnt[k]);      // fbgmm.py:475-479
+    for (int t0 = 0; t0 < nn; t0 += rcap) {
+        const int nr = nn - t0 < rcap ? nn - t0 : rcap;
+        __syncthreads();
+        for (int j = tid; j < (rcap > FBB_R ? rcap : FBB_R) * D; j += nt) {
+            const int r = j / D, d = j - r * D;
+            xs[j] = r < nr ? (double)X[(int64_t)new_tok[(int64_t)utt * c.N_max + t0 + r] * c.ldx + d] : 0.0;
+        }
+        __syncthreads();
+        {
+            const int w = tid >> 6, lane = tid & 63, nw = nt >> 6;
+            for (int r = w; r < nr; r += nw) {
+                const double v = bt.prior_rows ? bt.prior_rows[new_tok[(int64_t)utt * c.N_max + t0 + r]]
+                                               : fbb_prior_row<XT>(f, D, xs + r * D, lane);
+                if (lane == 0) lpr[r] = v;
+            }
+        }
+        __syncthreads();
+        if (nt >= 4 * 128 && KM <= 128) {
+            // few slots: four groups of threads take two rows each, four when the chunk holds sixteen tokens (k_fbb_assign)
+            auto rows_of_group = [&](auto NRC) {
+                constexpr int NR = decltype(NRC)::value;
+                const int k = tid & 127, r0 = NR * (tid >> 7);
+                if (k < KM && r0 < nr) {
+                    if (bt.cnt[k] > 0.0) {
+                        double acc[NR];
+#pragma unroll
+                        for (int r = 0; r < NR; r++) acc[r] = 0.0;
+                        if (F32) {
+                            float a32[NR];
+#pragma unroll
+                            for (int r = 0; r < NR; r++) a32[r] = 0.f;
+                            fbb_accumulate_rows32<NR>(bt, KM, k, D, xs + r0 * D, a32);
+#pragma unroll
+                            for (int r = 0; r < NR; r++) acc[r] = 0.6931471805599453 * (double)a32[r];
+                        } else
+                        fbb_accumulate_rows<COV, NR>(bt, KM, k, D, xs + r0 * D, acc);
+                        const double lc = bt.lconst[k], h = bt.half[k];
+#pragma unroll
+                        for (int r = 0; r < NR; r++)
+                            if (r0 + r < nr) ll[(int64_t)(r0 + r) * KM + k] = lc - h * acc[r];
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < NR; r++)
+                            if (r0 + r < nr) ll[(int64_t)(r0 + r) * KM + k] = lpr[r0 + r];
+                    }
+                }
+            };
+            if (rcap > FBB_R) rows_of_group(std::integral_constant<int, 4>());
+            else rows_of_group(std::integral_constant<int, 2>());
+        } else
+        for (int k = tid; k < KM; k += nt) {
+            if (bt.cnt[k] > 0.0) {
+                double acc[FBB_R];
+#pragma unroll
+                for (int r = 0; r < FBB_R; r++) acc[r] = 0.0;
+                if (F32) {
+                    float a32[FBB_R];
+#pragma unroll
+                    for (int r = 0; r < FBB_R; r++) a32[r] = 0.f;
+                    fbb_accumulate_rows32<FBB_R>(bt, KM, k, D, xs, a32);
+#pragma unroll
+                    for (int r = 0; r < FBB_R; r++) acc[r] = 0.6931471805599453 * (double)a32[r];
+                } else
+                fbb_accumulate<COV>(bt, KM, k, D, xs, acc);
+                const double lc = bt.lconst[k], h = bt.half[k];
+#pragma unroll
+                for (int r = 0; r < FBB_R; r++)
+                    if (r < nr) ll[(int64_t)r * KM + k] = lc - h * acc[r];
+            } else {
+#pragma unroll
+                for (int r = 0; r < FBB_R; r++)
+                    if (r < nr) ll[(int64_t)r * KM + k] = lpr[r];
+            }
+        }
+        __syncthreads();
+        if (probe_ll)           // segk_fbb_set_probe: the likelihood part of the logits, as the argmax below uses it
+            for (int j = tid; j < nr * KM; j += nt) {
+                const int r = j / KM, k = j - r * KM;
+                probe_ll[((int64_t)utt * c.N_max + t0 + r) * probe_ld + k] = ll[(int64_t)r * KM + k];
+            }
+        const int w = tid >> 6, lane = tid & 63, nw = nt >> 6;
+        for (int r = w; r < nr; r += nw) {
+            const double *zr = ll + (int64_t)r * KM;
+            double best = NEG_INF_D;
+            int bk = KM;
+            for (int k = lane; k < KM; k += 64) {
+                const double z = pz[k] + zr[k];
+                if (z > best) { best = z; bk = k; }
+            }
+            const double m = fb_wave_max(best, false);
+            const int k = fbb_wave_min_i32(best == m ? bk : KM);
+            if (lane == 0) bt.slot[new_tok[(int64_t)utt * c.N_max + t0 + r]] = k < KM ? k : 0;
         }
     }
 }
@@ -2451,6 +2693,42 @@ int32_t segk_fbb_segment(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *
     return SEGK_OK;
 }
 
+int32_t segk_fbb_segment_map(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,
+                             int32_t s_n, int32_t b, const int32_t *n_utts, uint64_t sweep, int32_t n_slices_min,
+                             int32_t n_slices_max, double wip, double time_power_term, const double *score,
+                             uint8_t *boundaries, int32_t *new_tok, int32_t *n_new, double *out_logprob, int32_t *status,
+                             void *stream)
+{
+    (void)sweep;                  // no uniforms are consumed
+    (void)status;                 // (a total of -inf raises nothing: the serial kernel sets bit 16 only when it samples)
+    SEGK_REQUIRE(ctx, "context");
+    int rc = check_fbb(c, f, bt);
+    if (rc) return rc;
+    SEGK_REQUIRE(n_slices_min == 0 || n_slices_min == 1, "n_slices_min must be 0 or 1");
+    FbbMap m;
+    rc = make_map(&m, s_lo, s_n, n_utts, 1);
+    if (rc) return rc;
+    rc = check_fbb_long(c, n_slices_max);
+    if (rc) return rc;
+    if (m.off[s_n] == 0) return SEGK_OK;
+    if (c->N_max > 64) {
+        const size_t ldsb = fbb_band_lds(c->N_max, c->band_W);
+        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbb_segment_map_band, ldsb));
+        hipLaunchKernelGGL(k_fbb_segment_map_band, dim3(m.off[s_n]), dim3(128), ldsb, (hipStream_t)stream, *c, *bt, m, b, wip,
+                           time_power_term, score, boundaries, new_tok, n_new, out_logprob, ctx->probe_alpha);
+        SEGK_LAUNCH_CHECK();
+        return SEGK_OK;
+    }
+    const int64_t triMax = (int64_t)c->N_max * (c->N_max + 1) / 2;
+    const size_t lds = (size_t)(triMax + 3 * c->N_max + 2) * sizeof(double) + (size_t)(c->N_max + triMax) * sizeof(int32_t) +
+                       (size_t)((c->N_max + 15) & ~15);
+    SEGK_REQUIRE(lds <= 64 * 1024, "N_max too large for the LDS score vector");
+    hipLaunchKernelGGL(k_fbb_segment_map, dim3(m.off[s_n]), dim3(128), lds, (hipStream_t)stream, *c, *bt, m, b, n_slices_max, wip,
+                       time_power_term, score, boundaries, new_tok, n_new, out_logprob, ctx->probe_alpha);
+    SEGK_LAUNCH_CHECK();
+    return SEGK_OK;
+}
+
 int32_t segk_fbb_token_scores(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt,
                               const int32_t *tok_rows, int64_t n, float *ll_mat, int64_t ll_ld, void *stream)
 {
@@ -2548,6 +2826,51 @@ int32_t segk_fbb_assign_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_f
 {
     SEGK_REQUIRE(f && f->cov_type == 1, "the float32 token likelihoods of this entry point are the diagonal (Student-t) ones");
     return fbb_assign_impl(ctx, c, f, bt, s_lo, s_n, b, n_utts, sweep, anneal_temp, new_tok, n_new, nullptr, 0, 1, stream);
+}
+
+int32_t segk_fbb_assign_map(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,
+                            int32_t s_n, int32_t b, const int32_t *n_utts, uint64_t sweep, const int32_t *new_tok,
+                            const int32_t *n_new, int32_t f32_terms, void *stream)
+{
+    (void)sweep;                  // no uniforms are consumed
+    SEGK_REQUIRE(ctx, "context");
+    SEGK_REQUIRE(!ctx->probe_ll || ctx->probe_ll_ld >= f->K_max, "probe leading dimension");
+    int rc = check_fbb(c, f, bt);
+    if (rc) return rc;
+    if (f->lm_unigram) {
+        segk_set_error("segk_fbb_assign_map: there is no MAP assignment with a language model (the reference's bigram segmenter "
+                       "has no Viterbi mode)");
+        return SEGK_ERR_UNSUPPORTED;
+    }
+    SEGK_REQUIRE(!f32_terms || f->cov_type == 1, "the float32 token likelihoods are the diagonal (Student-t) ones");
+    FbbMap m;
+    rc = make_map(&m, s_lo, s_n, n_utts, 1);
+    if (rc) return rc;
+    if (m.off[s_n] == 0) return SEGK_OK;
+    // chunks and threads as segk_fbb_assign chooses them without a language model: as many likelihood rows as fit beside the
+    // prior terms (two workgroups per CU); 512 threads and chunks of sixteen tokens where the slots alone would leave most of
+    // 256 idle
+    int rcap = FBB_R;
+    const size_t fixed_b = (size_t)(f->K_max + FBA_R * c->D + FBA_R) * sizeof(double);
+    while (rcap > 1 && fixed_b + (size_t)rcap * f->K_max * sizeof(double) > 80 * 1024) rcap >>= 1;
+    const int nt = (f->K_max <= 128 && rcap == FBB_R) ? 512 : 256;
+    if (nt == 512 && fixed_b + (size_t)FBA_R * f->K_max * sizeof(double) <= 80 * 1024) rcap = FBA_R;
+    const size_t lds = fixed_b + (size_t)rcap * f->K_max * sizeof(double);
+    SEGK_REQUIRE(lds <= 160 * 1024, "K_max too large for the LDS logits buffer");
+#define SEGK_ASSIGN_MAP(COV, F32)                                                                                               \
+    do {                                                                                                                        \
+        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbb_assign_map<XT, COV, F32>, lds));                                        \
+        hipLaunchKernelGGL((k_fbb_assign_map<XT, COV, F32>), dim3(m.off[s_n]), dim3(nt), lds, (hipStream_t)stream, *c, *f, *bt, m, b, \
+                           f->alpha, new_tok, n_new, rcap, ctx->probe_ll, ctx->probe_ll_ld);                                    \
+    } while (0)
+    DISPATCH_XT(c, {
+        if (f->cov_type == 0) SEGK_ASSIGN_MAP(0, 0);
+        else if (f32_terms) SEGK_ASSIGN_MAP(1, 1);
+        else SEGK_ASSIGN_MAP(1, 0);
+    });
+#undef SEGK_ASSIGN_MAP
+    SEGK_LAUNCH_CHECK();
+    return SEGK_OK;
 }
 
 int32_t segk_fbb_step_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,

@@ -1108,10 +1108,17 @@ class FbgmmBatchSweeper(object):
         self.in_batch_state = True
 
     def sweep(self, boundaries, n_slices_min, n_slices_max, wip, time_power_term, anneal_temp_fb=1.0,
-              anneal_temp_am=1.0):
-        """One sweep = n_gibbs_blocks steps, all enqueued on the current stream."""
+              anneal_temp_am=1.0, viterbi=False):
+        """One sweep = n_gibbs_blocks steps, all enqueued on the current stream.
+
+        viterbi: the sweep of fb_type "viterbi" (specification tests/map_batch.py) -- per step the same span scores, then
+        the MAP boundaries (segk_fbb_segment_map) and the MAP slot of every new segment (segk_fbb_assign_map) in place of the
+        draws: no uniform is consumed and the temperatures have no effect.  Always the three calls, never the fused step."""
         torch = _torch()
         df = self.df
+        if viterbi and df.lm is not None:
+            raise SegkError("batch sweeps with fb_type=\"viterbi\" exist without a language model only: the reference's "
+                            "bigram segmenter has no Viterbi mode (fb_type is \"bigram\" or \"unigram\")")
         if not self.in_batch_state:
             self.enter(boundaries)
         L, ctx, cp, fp, bp, st = self._args()
@@ -1120,7 +1127,7 @@ class FbgmmBatchSweeper(object):
             if self.lm_tok is not None:
                 check(L.segk_fbb_lm_apply(ctx, cp, fp, bp, b, -1, st))
             check(L.segk_fbb_prepare(ctx, cp, fp, bp, b, st))
-            if self.score_diag32 and self.lm_tok is None and self._fused is not False:
+            if self.score_diag32 and self.lm_tok is None and self._fused is not False and not viterbi:
                 # span scores, boundaries and slots of the block by ONE launch where the library can (segk_fbb_step_diag32)
                 rc = L.segk_fbb_step_diag32(ctx, cp, fp, bp, self.s_lo, self.s_n, b, self._n_utts[b], sw, int(n_slices_min),
                                             int(n_slices_max), float(wip), float(time_power_term), float(anneal_temp_fb),
@@ -1141,6 +1148,17 @@ class FbgmmBatchSweeper(object):
                 check(L.segk_fbb_score_diag32(ctx, cp, fp, bp, self.s_lo, self.s_n, b, self._n_rows[b], ptr(df.score), st))
             else:
                 check(L.segk_fbb_score(ctx, cp, fp, bp, self.s_lo, self.s_n, b, self._n_rows[b], ptr(df.score), st))
+            if viterbi:
+                check(L.segk_fbb_segment_map(ctx, cp, fp, bp, self.s_lo, self.s_n, b, self._n_utts[b], sw, int(n_slices_min),
+                                             int(n_slices_max), float(wip), float(time_power_term), ptr(df.score),
+                                             ptr(boundaries), ptr(df.new_tok), ptr(df.n_new), ptr(df.out_logprob),
+                                             ptr(df.status), st))
+                # (the fixed-variance tolerance modes take the fp64 quadratic here: the token-likelihood matrix is not formed)
+                check(L.segk_fbb_assign_map(ctx, cp, fp, bp, self.s_lo, self.s_n, b, self._n_utts[b], sw, ptr(df.new_tok),
+                                            ptr(df.n_new), 1 if self.score_diag32 else 0, st))
+                check(L.segk_fbb_partials(ctx, cp, fp, bp, self.s_lo, self.s_n, b, ptr(df.new_tok), ptr(df.n_new), st))
+                self._gather(self.partials, b)
+                continue
             check(L.segk_fbb_segment(ctx, cp, fp, bp, self.s_lo, self.s_n, b, self._n_utts[b], sw, int(n_slices_min),
                                      int(n_slices_max), float(wip), float(time_power_term), float(anneal_temp_fb),
                                      ptr(df.score), ptr(boundaries), ptr(df.new_tok), ptr(df.n_new),

@@ -161,9 +161,11 @@ class UnigramAcousticWordseg(object):
         return self._sweeper
 
     def batch_sweep_async(self, anneal_temp=1, anneal_gibbs_am=False):
-        """Enqueue one batch-synchronous sweep (fb_type "standard" sampling); results stay on the device."""
+        """Enqueue one batch-synchronous sweep -- sampling with fb_type "standard", the MAP boundaries and slots with
+        "viterbi" (the temperatures then have no effect); results stay on the device."""
         self._get_sweeper().sweep(self._dev_bounds, self.n_slices_min, self.n_slices_max, self.wip,
-                                  self.time_power_term, anneal_temp, anneal_temp if anneal_gibbs_am else 1.0)
+                                  self.time_power_term, anneal_temp, anneal_temp if anneal_gibbs_am else 1.0,
+                                  viterbi=self.fb_type == "viterbi")
         self.utterances.mark_device_dirty()
 
     def materialise(self):
@@ -225,7 +227,6 @@ class UnigramAcousticWordseg(object):
                 self.acoustic_model.gibbs_sample(am_n_iter, consider_unassigned=False)
             anneal_temp = next(get_anneal_temp, anneal_end_temp_inv)
             if self.sync == "batch":
-                assert self.fb_type == "standard", "batch mode samples boundaries (fb_type=\"standard\")"
                 self.batch_sweep_async(anneal_temp, anneal_gibbs_am)
                 torch.cuda.synchronize()
                 self._df.check_status()

@@ -1,0 +1,236 @@
+"""Executable SPECIFICATION of the batch sweep with fb_type="viterbi" (the point estimate a sampler run ends with), its
+test corpora and the census of decision margins the parity tests rest on.  Test infrastructure only, like tests/anneal.py
+and tests/fbgmm_long.py: tests/test_map_batch_cpu.py checks, with the oracle alone, that every corpus is one on which exact
+parity of an argmax is defined; tests/test_gpu_map_batch.py runs the device against `MapBatch` on the same corpora.
+
+Definition.  `MapBatch.sweep` is `FbgmmBatch.sweep` (oracle/np_fbgmm_batch.py) with exactly two substitutions; everything
+else -- stats_excluding, derive, the log_marg span scores including `lms`, dur ** time_power_term, + wip, the order of
+application, the partial sums -- is unchanged:
+
+  1. boundaries: no.forward_backward_viterbi(vec, 0.0, N, n_slices_min, n_slices_max, i) in place of no.forward_backward
+     (unigram_acoustic_wordseg.py:759-864).  No uniform is consumed, anneal_temp is ignored (the reference's Viterbi ignores
+     it), the returned log_prob goes to log_probs[i], a total of -inf raises nothing;
+  2. slots: for every new token, in token order, z = log(alpha / K_max + cnt) + loglik(d, x) and k = the first index of
+     max(z) (FBGMM.map_assign_i, fbgmm.py:465-494): no `lms` on the prior term (fbgmm.py:475-479 has none), no temperature,
+     no uniform, no `k > K` clamp (batch slots are slots).  An empty slot scores the prior predictive: all empty slots of a
+     token tie exactly and the first one wins.
+
+The reference takes np.argmax(np.exp(z - logsumexp(z))), and in the DP's backward pass np.argmax(p[::-1]) of the same
+form; exp is monotone, so wherever the candidates are not within rounding of each other these are the argmax of z and
+the argmax over q that prefers the largest s (the shortest span) among equal maxima.  `Census` records, for every decision of
+a sweep, how far apart the candidates were, and whether the reference's softmax form agrees.
+
+A property of the model to know when choosing corpora: the synthetic rows are L2-normalised and the fixed-variance prior has
+mu_0 = 0, so the prior predictive is the same number c for every row.  Wherever spans are scored mostly by the empty slots,
+c d1 + c d2 = c (d1 + d2): segmentations of the same total duration tie up to rounding (decision margins down to 7e-12
+relative with wip = 0, time_power_term = 1; still 2e-9 with wip = -0.2 alone, since moving a cut between two segments keeps
+the tie).  Every fixed-variance exact case therefore runs with FIXED_KW (lms = 0.7, wip = -0.2, time_power_term = 1.2).  The
+diagonal cases need nothing: the Student-t product is not a function of the norm."""
+import numpy as np
+
+from oracle import np_fbgmm_batch as nb
+from oracle import np_oracle as no
+from tests import fbgmm_long
+
+FIXED_KW = dict(lms=0.7, wip=-0.2, time_power_term=1.2)
+MARGIN = 1e-6        # three orders above the 1e-9 the suite holds the device's fp64 log-probabilities to: a condition on the inputs
+
+
+def _case(kind, n_utt, D, K, nmax, B, S, N=None, N_range=None, cseed=200, **kw):
+    c = dict(kind=kind, n_utt=n_utt, D=D, K=K, cseed=cseed, nmax=nmax, B=B, S=S, kw=dict(FIXED_KW if kind == "fixed" else {}))
+    c["kw"].update(kw)
+    if N is not None:
+        c["N"] = N
+    else:
+        c["N_range"] = N_range
+    return c
+
+
+# name -> case of tests/fbgmm_long.py's builders (oracle_of / product_of take the dict); two sweeps each
+LONG_CASES = {
+    "fixed_small": _case("fixed", 24, 8, 10, 5, 3, 4, N_range=(3, 9)),          # one DPP row, K below a wave
+    "diag_K65": _case("diag", 24, 8, 65, 5, 3, 4, N_range=(3, 9)),              # second slot per lane, tie on empty slots
+    "fixed_K300": _case("fixed", 19, 6, 300, 5, 5, 1, N_range=(3, 9)),          # winners that are the first empty slot
+    "fixed_K1025": _case("fixed", 12, 6, 1025, 5, 2, 2, N_range=(3, 9)),        # bank beyond 1024
+    "fixed_w20": _case("fixed", 8, 8, 10, 20, 2, 2, N=24),                      # window beyond one row of sixteen
+    "diag_w20": _case("diag", 8, 8, 10, 20, 2, 2, N=24),
+    "fixed_64_w30": _case("fixed", 8, 8, 10, 30, 2, 2, N=64),                   # the most the triangular kernel takes
+    "ragged_fixed": _case("fixed", 16, 8, 10, 6, 3, 4, N_range=(3, 150)),       # band kernel, short and long utterances
+    "ragged_diag": _case("diag", 16, 8, 10, 6, 3, 4, N_range=(3, 150)),
+    "diag_100_w20": _case("diag", 8, 8, 10, 20, 2, 2, N=100),                   # band, windows over 16 and over 32 lanes
+    "fixed_100_w40": _case("fixed", 8, 8, 10, 40, 2, 2, N=100),
+    "diag_mindur_backtrack": _case("diag", 8, 8, 10, 6, 2, 2, N_range=(60, 200), min_duration=30),      # dead ends
+}
+# (kind, n_utt, D, K, cseed, nmax, B, S) of cases.chain_corpus, as tests/test_gpu_fbgmm_batch.py::_pair builds them; three sweeps
+CHAIN_CASES = {
+    "chain_diag_D70": ("diag", 33, 70, 12, 80, 4, 2, 2),
+    "chain_diag_D256": ("diag", 20, 256, 12, 83, 4, 2, 2),
+}
+# the fixed_small shape on a float64 corpus (cseed: the first the CPU precondition accepts, see test_map_batch_cpu.py)
+F64_CASE = "fixed_small_f64"
+F64_CSEED = 200
+EXACT = list(LONG_CASES) + list(CHAIN_CASES) + [F64_CASE]
+# sampled sweeps, then set_fb_type("viterbi"), then Viterbi sweeps, on one live sweeper
+MIXED = ["fixed_small", "ragged_diag"]
+
+
+def n_sweeps(name):
+    return 3 if name in CHAIN_CASES else 2
+
+
+def _corpus_f64():
+    from segmentalist_amd.synth import make_corpus
+    c = LONG_CASES["fixed_small"]
+    return make_corpus(c["n_utt"], c["D"], c["K"], seed=F64_CSEED, ragged=True, n_slices_max=c["nmax"], N_range=c["N_range"],
+                       dtype=np.float64)
+
+
+def pair(name, product=True, prec="f64", process_group=None, D=None):
+    """(oracle segmenter, MapBatch specification, product segmenter or None) of an exact case, from identical initial states.
+    Both segmenters are built with fb_type="standard" (the builders'); callers switch with set_fb_type.  prec / D: the
+    tolerance-mode variants of a LONG_CASES shape."""
+    if name in CHAIN_CASES:
+        kind, n_utt, Dc, K, cseed, nmax, B, S = CHAIN_CASES[name]
+        from tests.test_gpu_fbgmm_batch import _pair
+        ref, _, seg = _pair(kind, n_utt, Dc, K, cseed, nmax, B, S, product=product)
+        return ref, MapBatch(ref, n_gibbs_blocks=B, n_stat_blocks=S, seed=11), seg
+    c = dict(LONG_CASES["fixed_small" if name == F64_CASE else name])
+    if prec != "f64":
+        c["prec"] = prec
+    if D is not None:
+        c["D"] = D
+    corpus = _corpus_f64() if name == F64_CASE else fbgmm_long.corpus_of(c)
+    ref, _ = fbgmm_long.oracle_of(c, corpus)
+    seg = None
+    if product:
+        kw = {} if process_group is None else dict(process_group=process_group)
+        seg = fbgmm_long.product_of(c, corpus, **kw)
+    return ref, MapBatch(ref, n_gibbs_blocks=c["B"], n_stat_blocks=c["S"], seed=11), seg
+
+
+class Census(object):
+    """What the decisions of MapBatch's Viterbi sweeps looked like (see the module docstring)."""
+
+    def __init__(self):
+        self.dp_margin = np.inf          # smallest relative gap between the two largest finite candidates of a DP step
+        self.slot_margin = np.inf        # smallest relative gap between the maximal logit and the largest smaller one
+        self.dp_steps = self.dead_windows = self.decodes = self.dead_end_starts = self.tokens = 0
+        self.empty_ties = 0              # tokens whose maximum is shared by several (empty) slots
+        self.empty_winners = 0           # tokens whose winner is an empty slot
+        self.tie_on_occupied = 0         # ... shared by a slot that is not empty: never allowed
+        self.softmax_disagrees = 0       # argmax(z) != argmax(exp(z - logsumexp z)), DP or slot
+        self.max_tokens_per_utt = 0
+
+    def dp(self, vec, N, n_max):
+        """every forward step t = 1..N of forward_backward_viterbi on `vec` (t = N is the backward pass' first window)"""
+        self.decodes += 1
+        a = np.ones(N + 1)
+        a[0] = 0.0
+        i = 0
+        for t in range(1, N + 1):
+            q = no._win(vec, t, i, n_max) + (a[:t][-n_max:] if n_max else a[:t])
+            fin = np.sort(q[q != -np.inf])
+            self.dp_steps += 1
+            if len(fin) == 0:
+                self.dead_windows += 1
+                self.dead_end_starts += t == N
+                a[t] = -np.inf
+            else:
+                a[t] = fin[-1]
+                if len(fin) > 1:
+                    self.dp_margin = min(self.dp_margin, (fin[-1] - fin[-2]) / max(1.0, abs(fin[-1])))
+                with np.errstate(invalid="ignore"):
+                    p = np.exp(q[::-1] - no.logsumexp(q))
+                self.softmax_disagrees += int(np.argmax(p)) != int(np.argmax(q[::-1]))
+            i += t
+
+    def slot(self, z, cnt):
+        self.tokens += 1
+        k = int(np.argmax(z))
+        at_max = np.where(z == z[k])[0]
+        if len(at_max) > 1:
+            self.empty_ties += 1
+            self.tie_on_occupied += bool(np.any(cnt[at_max] > 0))
+        self.empty_winners += cnt[k] == 0
+        below = z[z < z[k]]
+        if len(below):
+            self.slot_margin = min(self.slot_margin, (z[k] - below.max()) / max(1.0, abs(z[k])))
+        self.softmax_disagrees += int(np.argmax(np.exp(z - nb._sp_logsumexp(z)))) != k
+
+
+class MapBatch(nb.FbgmmBatch):
+    """FbgmmBatch whose sweep is the Viterbi / MAP one; `sweep(..., viterbi=False)` is FbgmmBatch.sweep on the same state
+    (sampled sweeps, then Viterbi sweeps: the use pattern).  `census`, when set, records the decisions of the Viterbi sweeps."""
+
+    census = None
+
+    def sweep(self, sweep_index, anneal_temp=1.0, anneal_gibbs_am=False, viterbi=True):
+        if not viterbi:
+            return nb.FbgmmBatch.sweep(self, sweep_index, anneal_temp, anneal_gibbs_am)
+        assert self.lm is None, "there is no Viterbi mode with a language model"
+        u = self.seg.utterances
+        log_probs = np.zeros(u.D)
+        for b in range(self.B):
+            self.step(b, log_probs)
+        return log_probs
+
+    def step(self, b, log_probs):
+        """Gibbs step b of FbgmmBatch.sweep with the two substitutions."""
+        seg, u = self.seg, self.seg.utterances
+        cnt, sx, sxx = self.stats_excluding(b)
+        d = self.derive(cnt, sx, sxx)
+        new_state = {}
+        for s in range(self.s_lo, self.s_hi):
+            for i in range(*self.ranges[s][b]):
+                N = u.lengths[i]
+                vec = self.span_vec(d, i)
+                if self.census is not None:
+                    self.census.dp(vec, N, seg.n_slices_max)
+                lp, bnd = no.forward_backward_viterbi(vec, 0.0, N, seg.n_slices_min, seg.n_slices_max, i)
+                new_state[i] = (lp, np.asarray(bnd, dtype=bool), self._tokens(i))
+        for i, (lp, bounds_new, old) in new_state.items():
+            for e in old:
+                self.slot[e] = -1
+        prior = np.log(float(self.alpha) / self.K_max + d["cnt"])          # fbgmm.py:475-479: no lms
+        for i, (lp, bounds_new, old) in new_state.items():
+            N = u.lengths[i]
+            u.boundaries[i, :N] = bounds_new
+            log_probs[i] = lp
+            toks = self._tokens(i)
+            for e in toks:
+                z = prior + self.loglik(d, self.X[e])
+                if self.census is not None:
+                    self.census.slot(z, d["cnt"])
+                self.slot[e] = int(np.argmax(z))
+            if self.census is not None:
+                self.census.max_tokens_per_utt = max(self.census.max_tokens_per_utt, len(toks))
+        mine = {s: self._partial(s, b) for s in range(self.s_lo, self.s_hi)}
+        for part in ([mine] if self.world == 1 else self.ago(mine)):
+            for s, p in part.items():
+                self.P[s][b] = p
+
+    def span_vec(self, d, i):
+        """vec of utterance i under the statistics `d`: FbgmmBatch.sweep's, statement by statement."""
+        seg, u = self.seg, self.seg.utterances
+        N = u.lengths[i]
+        tri = (N * N + N) // 2
+        vec = -np.inf * np.ones(tri)
+        for j in range(tri):
+            e = u.vec_ids[i, j]
+            if e == -1:
+                continue
+            dur = u.durations[i, j]
+            vec[j] = -np.inf if np.isnan(dur) else self.log_marg(d, self.X[e]) * dur ** seg.time_power_term
+        return vec + seg.wip
+
+
+def path_total(vec, bnd, N):
+    """Sum of vec over the segments the boundaries `bnd` select: what forward_backward_viterbi returns for its own
+    boundaries on an utterance without dead ends (a dead end leaves a boundary that no chosen segment accounts for)."""
+    total, s = 0.0, 0
+    for t in range(1, N + 1):
+        if bnd[t - 1]:
+            total += vec[t * (t - 1) // 2 + s]
+            s = t
+    return total
+

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Throughput of the sequential (reference-chain) FBGMM / bigram Gibbs drivers on BASELINE
-config 2 shapes (1 000 utterances, D = 39, K = 100) -- development measurement, not bench.py."""
+"""Throughput of the sequential (reference-chain) and batch FBGMM / bigram Gibbs drivers on BASELINE
+config 2 shapes (1 000 utterances, D = 39, K = 100) -- development measurement, not bench.py.
+--fb-type viterbi: the Viterbi / MAP sweeps of the unigram segmenters, with either --sync (the bigram one has no such mode)."""
 import argparse
 import os
 import random
@@ -23,6 +24,7 @@ def main():
     ap.add_argument("--sync", default="sequential")
     ap.add_argument("--blocks", type=int, default=8)
     ap.add_argument("--precision", default="f64")
+    ap.add_argument("--fb-type", default="standard", choices=["standard", "viterbi"])
     args = ap.parse_args()
     import torch
     from segmentalist_amd import bigram_acoustic_wordseg as baw, fbgmm, unigram_acoustic_wordseg as uaw
@@ -44,15 +46,18 @@ def main():
     pk = dict(score_precision=args.precision) if args.sync == "batch" else {}
     lm = {"type": "smooth", "intrp_lambda": 0.1, "a": 0.5, "b": 0.5}
     for which in args.which.split(","):
+        if which == "bigram" and args.fb_type == "viterbi":
+            print("bigram: no Viterbi mode (fb_type is \"bigram\" or \"unigram\"), skipped", flush=True)
+            continue
         random.seed(0)
         np.random.seed(0)
         t0 = time.perf_counter()
         if which == "diag":
             seg = uaw.UnigramAcousticWordseg(fbgmm.FBGMM, 1.0, K, NIW(*diag), *corpus, covariance_type="diag",
-                                             fb_type="standard", **kw)
+                                             fb_type=args.fb_type, **kw, **pk)
         elif which == "fixed":
             seg = uaw.UnigramAcousticWordseg(fbgmm.FBGMM, 1.0, K, FixedVarPrior(*fixed), *corpus,
-                                             covariance_type="fixed", fb_type="standard", **kw, **pk)
+                                             covariance_type="fixed", fb_type=args.fb_type, **kw, **pk)
         else:
             seg = baw.BigramAcousticWordseg(K, FixedVarPrior(*fixed), lm, *corpus, covariance_type="fixed",
                                             fb_type="unigram", **kw, **pk)
@@ -83,10 +88,10 @@ def main():
         np.random.seed(0)
         if which == "diag":
             ref = no.UnigramAcousticWordseg(no.FBGMM, 1.0, K, no.NIW(*diag), *sub, covariance_type="diag",
-                                            fb_type="standard", **okw)
+                                            fb_type=args.fb_type, **okw)
         elif which == "fixed":
             ref = no.UnigramAcousticWordseg(no.FBGMM, 1.0, K, no.FixedVarPrior(*fixed), *sub,
-                                            covariance_type="fixed", fb_type="standard", **okw)
+                                            covariance_type="fixed", fb_type=args.fb_type, **okw)
         else:
             ref = no.BigramAcousticWordseg(K, no.FixedVarPrior(*fixed), lm, *sub, covariance_type="fixed",
                                            fb_type="unigram", **okw)

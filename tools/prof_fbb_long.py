@@ -1,7 +1,7 @@
 """Cost of the batch sampler's boundary kernels beyond 64 landmarks (k_fbb_segment_band against k_fbb_segment): ten f64
 sweeps of 2 000 utterances, D = 8, K = 10, fixed-variance components, window 6, 8 x 8 blocks.  From the repository root:
 
-    rocprofv3 --kernel-trace --stats -f csv -d OUT -- python tools/prof_fbb_long.py ragged|n150|n64
+    rocprofv3 --kernel-trace --stats -f csv -d OUT -- python tools/prof_fbb_long.py ragged|n150|n64 [standard|viterbi]
 
 ragged: 3..150 landmarks (the corpus family of tests/fbgmm_long.py); n150 / n64: every utterance that long.  The kernels'
 rows of OUT/.../*_kernel_stats.csv are the figures of profiles/README.md (80 launches of 250 utterances each)."""
@@ -15,6 +15,7 @@ from segmentalist_amd.synth import make_corpus
 from tests.golden import cases
 
 which = sys.argv[1]
+fb_type = sys.argv[2] if len(sys.argv) > 2 else "standard"      # viterbi: k_fbb_segment_map(_band) / k_fbb_assign_map
 D, K, W, U = 8, 10, 6, 2000
 t0 = time.time()
 if which == "ragged":
@@ -23,7 +24,7 @@ else:
     corpus = make_corpus(U, D, K, seed=110, N=150 if which == "n150" else 64, n_slices_max=W)
 random.seed(5); np.random.seed(5)
 seg = uaw.UnigramAcousticWordseg(fbgmm.FBGMM, 1.0, K, FixedVarPrior(*cases.fixed_prior_params(D)), *corpus, covariance_type="fixed",
-                                 fb_type="standard", n_slices_min=0, n_slices_max=W, p_boundary_init=0.5, beta_sent_boundary=-1,
+                                 fb_type=fb_type, n_slices_min=0, n_slices_max=W, p_boundary_init=0.5, beta_sent_boundary=-1,
                                  lms=1.0, wip=0.0, init_am_assignments="rand", time_power_term=1.0, sync="batch",
                                  n_gibbs_blocks=8, n_stat_blocks=8, batch_seed=11, score_precision="f64")
 print(which, "built in %.1f s, N_max %d" % (time.time() - t0, seg._corpus.N_max), flush=True)
