@@ -279,6 +279,120 @@ __global__ __launch_bounds__(256) void k_kmeans_segment_w8(segk_corpus c, segk_k
     SEGK_TSTAMP_MAX(0, 3);
 }
 
+// k_kmeans_segment_w8 for utterances of at most 32 landmarks: TWO utterances per wave, lanes 0-31 and lanes 32-63 (seg_w8_uniform_x2).
+// With one utterance per wave the headline sweep's 10 000 waves do not fit on the chip at once (7 waves per SIMD: 7 168) and
+// half of every wave's lanes idle; 5 000 waves do.  Each half has the LDS arrays of k_kmeans_segment_w8 to itself (wave_bytes
+// per half).  An odd utterance count: the last wave's second half repeats the first half's utterance on its own arrays and
+// stores nothing.
+__global__ __launch_bounds__(256, 7) void k_kmeans_segment_w8x2(segk_corpus c, segk_kmeans m, const int32_t *utts, int utt0, int n_utts,
+                                    int n_max, double wip, segk_cand cand, uint8_t *boundaries, int32_t *old_tok,
+                                    int32_t *new_tok, int32_t *new_k, int32_t *n_old, int32_t *n_new, int32_t *n_flag,
+                                    double *out_total, int32_t *status, int band_cap, int wave_bytes)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, h = lane >> 5, hl = lane & 31;
+    const int first = 2 * (blockIdx.x * (blockDim.x >> 6) + wv);
+    SEGK_TSTAMP(0, 0);
+    if (first >= n_utts) return;
+    const bool live = first + h < n_utts;
+    const int slot = live ? first + h : first;
+    const int u = utts ? utts[slot] : utt0 + slot;
+    const int N = c.lengths[u];
+    const int W = (n_max > 0 && n_max < N) ? n_max : N;          // <= 8 (host checks n_max <= 8)
+    const int64_t triMax = (int64_t)c.N_max * (c.N_max + 1) / 2;
+    const int32_t *vid = c.vec_ids + (int64_t)u * triMax;
+    const double *dur = c.durations + (int64_t)u * triMax;
+    const bool band = c.band_ids != nullptr && c.band_W == W && W > 0;
+    const int32_t *bandi = band ? c.band_ids + (int64_t)u * c.N_max * c.band_W : nullptr;
+    const double *bandd = band ? c.band_dur + (int64_t)u * c.N_max * c.band_W : nullptr;
+    uint8_t *gbnd = boundaries + (int64_t)u * c.N_max;
+    const int Nm = max(__builtin_amdgcn_readlane(N, 0), __builtin_amdgcn_readlane(N, 32));      // the longer of the two
+
+    char *base_w = smem + (size_t)wv * 2 * wave_bytes;
+    char *base = base_w + (size_t)h * wave_bytes;
+    double *bvec = (double *)base;                    // the layout of k_kmeans_segment_w8, per half
+    double *gam = bvec + c.N_max * 8;
+    int32_t *bk = (int32_t *)(gam + c.N_max + 12);
+    int32_t *bid = bk + band_cap;
+    int32_t *l_old = bid + band_cap;
+    int32_t *l_new = l_old + c.N_max;
+    int32_t *l_newk = l_new + c.N_max;
+    int32_t *l_cnt = l_newk + c.N_max;
+
+    // the band: lane (r, w) of a half takes entry (r + 1, w), 16 span ends per half and batch; rows up to the longer utterance's
+    // end are written (-inf past this one's: the forward pass runs that far in both halves)
+    {
+        const int w = hl & 7;
+        for (int z0 = 0; z0 < Nm; z0 += 16) {
+            int id[4], kq[4];
+            double dd[4], sc[4];
+#pragma unroll
+            for (int z = 0; z < 4; z++) {
+                const int r = z0 + 4 * z + (hl >> 3), t = r + 1, sp = t - 1 - w;
+                id[z] = -1;
+                dd[z] = 0.0;
+                if (r < N && w < W && sp >= 0) {
+                    const int j = t * (t - 1) / 2 + sp;
+                    id[z] = band ? bandi[r * W + w] : vid[j];
+                    dd[z] = band ? bandd[r * W + w] : dur[j];
+                }
+            }
+#pragma unroll
+            for (int z = 0; z < 4; z++) {
+                kq[z] = -1;
+                sc[z] = 0.0;
+                if (id[z] >= 0) {
+                    kq[z] = cand.k[id[z]];
+                    sc[z] = cand.s[id[z]];
+                }
+            }
+#pragma unroll
+            for (int z = 0; z < 4; z++) {
+                const int r = z0 + 4 * z + (hl >> 3);
+                if (r < Nm) {
+                    double v = NEG_INF_D;
+                    if (id[z] >= 0) v = isnan(dd[z]) ? NEG_INF_D : sc[z] * dd[z];      // :346-349
+                    if (r < N && w < W) {
+                        bid[r * W + w] = id[z];
+                        bk[r * W + w] = kq[z];
+                    }
+                    bvec[r * 8 + w] = v + wip;                                          // :351
+                }
+            }
+        }
+    }
+    const unsigned int oldb = (unsigned int)(__ballot(hl < N && gbnd[hl < N ? hl : 0] != 0) >> (32 * h));
+    WAVE_SYNC();
+    SEGK_TSTAMP(0, 1);
+    {
+        const int no_ = seg_old_tokens_half(bid, vid, N, W, oldb, l_old, hl, h);
+        if (hl == 0) l_cnt[0] = no_;
+    }
+    double total;
+    seg_w8_uniform_x2(bvec, gam, bid, bk, N, W, *m.K, l_new, l_newk, l_cnt, &total, hl, h, (const double *)base_w, wave_bytes / 8);
+    WAVE_SYNC();
+    SEGK_TSTAMP(0, 2);
+    if (hl == 0 && live) {
+        out_total[u] = total;
+        n_old[u] = l_cnt[0];
+        n_new[u] = l_cnt[1];
+        if (n_flag) n_flag[u] = l_cnt[4];
+        if (l_cnt[5]) atomicOr(status, 1);
+    }
+    WAVE_SYNC();
+    if (!live) return;
+    const int no = l_cnt[0], nn = l_cnt[1];
+    const unsigned int newb = (unsigned int)l_cnt[2];
+    if (hl < N) gbnd[hl] = (uint8_t)((newb >> hl) & 1u);
+    if (hl < no) old_tok[(int64_t)u * c.N_max + hl] = l_old[hl];
+    // slots beyond the utterance's tokens carry k = -1: the batch statistics scan new_k as it stands
+    if (hl < c.N_max) {
+        if (hl < nn) new_tok[(int64_t)u * c.N_max + hl] = l_new[hl];
+        new_k[(int64_t)u * c.N_max + hl] = hl < nn ? l_newk[hl] : -1;
+    }
+    SEGK_TSTAMP_MAX(0, 3);
+}
+
 // ======================================================================================
 // Function-level DPs on caller-supplied vectors (drop-in for the module functions
 // forward_backward_kmeans_viterbi / forward_backward / forward_backward_viterbi):
@@ -456,6 +570,16 @@ int32_t segk_kmeans_segment(segk_ctx *ctx, const segk_corpus *c, const segk_kmea
         // four waves per workgroup (10 000 utterances, interleaved on one box: 1, 2, 4 and 8 waves within 0.2 % of each other,
         // 16 waves 0.6 % of the sweep behind)
         int w8w = 4;
+        if (c->N_max <= 32) {
+            // two utterances per wave: half the waves, one round of them at the headline shape (7 per SIMD)
+            while (w8w > 1 && w8w * 2 * w8_bytes > 64 * 1024) w8w >>= 1;
+            const int n_waves = (n_utts + 1) / 2;
+            hipLaunchKernelGGL(k_kmeans_segment_w8x2, dim3((n_waves + w8w - 1) / w8w), dim3(64 * w8w), w8w * 2 * w8_bytes, st, *c, *m,
+                               utts, utt0, n_utts, n_slices_max, wip, *cand, boundaries, old_tok, new_tok, new_k, n_old, n_new, n_flag,
+                               out_total, status, band_cap, (int)w8_bytes);
+            SEGK_LAUNCH_CHECK();
+            return SEGK_OK;
+        }
         while (w8w > 1 && w8w * w8_bytes > 64 * 1024) w8w >>= 1;
         hipLaunchKernelGGL(k_kmeans_segment_w8, dim3((n_utts + w8w - 1) / w8w), dim3(64 * w8w), w8w * w8_bytes, st, *c, *m, utts, utt0,
                            n_utts, n_slices_max, wip, *cand, boundaries, old_tok, new_tok, new_k, n_old, n_new, n_flag,

@@ -216,3 +216,144 @@ __device__ __forceinline__ void seg_w8_uniform(const double *bvec8, double *gamp
 #undef SEG_U_STAMP
 }
 
+// ---- seg_w8_uniform_x2: seg_w8_uniform for TWO utterances of at most 32 landmarks in one wave, lanes 0-31 the first and lanes
+// 32-63 the second (k_kmeans_segment_w8x2: the batch sweep's one-wave-per-utterance launch left half of every wave idle and did
+// not fit on the chip in one round).  Every array pointer and N, W are the lane's half's own; `hl` is the lane within its half,
+// `h` the half.  The forward recurrence is seg_forward_uniform as it stands, run to the longer of the two utterances over the
+// wider of the two windows (rows past an utterance's end and candidates past its window hold -inf: the caller's band fetch);
+// the backward walk is the same scalar walk, one half after the other; ballots are split per half.  Same values, decisions and
+// outputs per utterance as seg_w8_uniform (l_new, l_newk, l_cnt[1..5], the total).
+//   bvec8_w / half_doubles: the wave-uniform address of half 0's bvec8 and the distance to half 1's, for the walk's one LDS read
+__device__ __forceinline__ int seg_old_tokens_half(const int32_t *bid, const int32_t *vid, int N, int W, unsigned int oldb,
+                                                   int32_t *l_old, int hl, int h)
+{
+    const bool bit = hl < N && ((oldb >> hl) & 1u);
+    const unsigned int below = oldb & ((1u << hl) - 1u);
+    const int jp = below ? 32 - __clz((int)below) : 0;
+    int id = -1;
+    if (bit) {
+        const int t = hl + 1, w = hl - jp;
+        id = w < W ? bid[(t - 1) * W + w] : vid[t * (t - 1) / 2 + jp];
+    }
+    const unsigned int keep = (unsigned int)(__ballot(bit && id >= 0) >> (32 * h));
+    if (bit && id >= 0) l_old[__popc(keep & ((1u << hl) - 1u))] = id;
+    return __popc(keep);
+}
+// A8 backward for the half whose lanes start at l0: N and bvec8 wave-uniform (the half's own), kbv / cv the lanes' decisions
+__device__ __forceinline__ void seg_walk_half(int kbv, double cv, int N, int l0, const double *bvec8, unsigned int &newb_out,
+                                              double &total_out)
+{
+    unsigned int newb = 1u << (N - 1);
+    int t = N;
+    double total = 0.0;
+    bool blocked = false;
+    for (;;) {                                         // the walk as long as every span end on it has a finite candidate
+        const int kb = __builtin_amdgcn_readlane(kbv, l0 + t - 1);
+        if (kb == 0) {
+            blocked = true;
+            break;
+        }
+        total += seg_readlane_f64(cv, l0 + t - 1);
+        t = t - kb;
+        if (t < 1) break;
+        newb |= 1u << (t - 1);
+    }
+    if (blocked)
+        for (;;) {                                     // ... and from the first span end whose candidates are all -inf on (:516-530)
+            int kb = __builtin_amdgcn_readlane(kbv, l0 + t - 1);
+            if (kb == 0) {
+                do {
+                    t = t - 1;
+                    if (t == 0) break;
+                    kb = __builtin_amdgcn_readlane(kbv, l0 + t - 1);
+                } while (kb == 0);
+                if (t == 0) {                          // python vec[-1]: the last span [N-1, N)
+                    newb |= 1u << (N - 1);
+                    total += bvec8[(size_t)(N - 1) * 8];
+                    break;
+                }
+                newb |= 1u << (t - 1);
+            }
+            total += seg_readlane_f64(cv, l0 + t - 1);
+            t = t - kb;
+            if (t < 1) break;
+            newb |= 1u << (t - 1);
+        }
+    newb_out = newb;
+    total_out = total;
+}
+__device__ __forceinline__ void seg_w8_uniform_x2(const double *bvec8, double *gamp, const int32_t *bid, const int32_t *bk, int N, int W,
+                                                  int Kact, int32_t *l_new, int32_t *l_newk, int32_t *l_cnt, double *total_out, int hl,
+                                                  int h, const double *bvec8_w, int half_doubles)
+{
+    const int N0 = __builtin_amdgcn_readlane(N, 0), N1 = __builtin_amdgcn_readlane(N, 32);
+    const int W0 = __builtin_amdgcn_readlane(W, 0), W1 = __builtin_amdgcn_readlane(W, 32);
+    const int Nm = N0 > N1 ? N0 : N1, Wm = W0 > W1 ? W0 : W1;
+    // ---- A8 forward (kmeans_acoustic_wordseg.py:494-506)
+    if (hl < 8) gamp[hl] = NEG_INF_D;
+    if (hl == 0) gamp[8] = 0.0;
+    if (Wm <= 2) seg_forward_uniform<2>(bvec8, gamp, Nm, hl);
+    else if (Wm <= 4) seg_forward_uniform<4>(bvec8, gamp, Nm, hl);
+    else if (Wm <= 6) seg_forward_uniform<6>(bvec8, gamp, Nm, hl);
+    else seg_forward_uniform<8>(bvec8, gamp, Nm, hl);
+    WAVE_SYNC();
+    // ---- the decision of every span end at once (lane hl = t - 1 of its half), as in seg_w8_uniform
+    int kbv = 0;
+    double cv = 0.0;
+    if (hl < N) {
+        const double mx = gamp[8 + hl + 1];
+        double v[8], g[8];
+        const double2 *src = reinterpret_cast<const double2 *>(bvec8 + (size_t)hl * 8);
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const double2 d = src[q];
+            v[2 * q] = d.x;
+            v[2 * q + 1] = d.y;
+        }
+#pragma unroll
+        for (int w = 0; w < 8; w++) g[w] = gamp[8 + hl - w];
+        if (mx != NEG_INF_D) {
+#pragma unroll
+            for (int w = 7; w >= 0; w--)
+                if (v[w] + g[w] == mx) {
+                    kbv = w + 1;
+                    cv = v[w];
+                }
+        }
+    }
+    // ---- A8 backward (:510-553): the two halves' walks, one after the other
+    unsigned int nb0, nb1;
+    double tt0, tt1;
+    seg_walk_half(kbv, cv, N0, 0, bvec8_w, nb0, tt0);
+    seg_walk_half(kbv, cv, N1, 32, bvec8_w + half_doubles, nb1, tt1);
+    const unsigned int newb = h ? nb1 : nb0;
+    // ---- new tokens + their best components (:312-313)
+    {
+        const bool bit = hl < N && ((newb >> hl) & 1u);
+        const unsigned int below = newb & ((1u << hl) - 1u);
+        const int jp = below ? 32 - __clz((int)below) : 0;
+        const int w = hl - jp;
+        int id = -1, kk = -1;
+        if (bit && w < W) {
+            id = bid[hl * W + w];
+            kk = bk[hl * W + w];
+        }
+        const bool valid = bit && id >= 0;
+        const unsigned int keep = (unsigned int)(__ballot(valid) >> (32 * h)), badm = (unsigned int)(__ballot(bit && !valid) >> (32 * h)),
+                           fl = (unsigned int)(__ballot(valid && kk >= Kact) >> (32 * h));
+        if (valid) {
+            const int r = __popc(keep & ((1u << hl) - 1u));
+            l_new[r] = id;
+            l_newk[r] = kk;
+        }
+        if (hl == 0) {
+            l_cnt[1] = __popc(keep);
+            l_cnt[2] = (int32_t)newb;
+            l_cnt[3] = 0;
+            l_cnt[4] = __popc(fl);
+            l_cnt[5] = badm != 0u;
+        }
+    }
+    *total_out = h ? tt1 : tt0;
+}
+
