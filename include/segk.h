@@ -56,8 +56,9 @@ const char *segk_last_error(void);
  *   8 round 4: segk_fbb_step_diag32
  *   9 segk_fbatch.centre (the reduced-precision FBGMM kernels work in coordinates centred on it), segk_fbatch.tab32
  *  10 segk_kmeans_delta_stats
- *  11 segk_fbb_segment_map, segk_fbb_assign_map (batch sweeps with fb_type "viterbi")                                       */
-#define SEGK_ABI_VERSION 11
+ *  11 segk_fbb_segment_map, segk_fbb_assign_map (batch sweeps with fb_type "viterbi")
+ *  12 segk_fbgmm.cov_type 2 "full": the existing fields at other shapes (below); status bits 32 and 64                       */
+#define SEGK_ABI_VERSION 12
 int32_t segk_abi_version(void);
 
 /* Timing of the MAIN launch of the MFMA score kernel (k_kmeans_score<..., 0>) with HIP events
@@ -425,6 +426,22 @@ int32_t segk_kmeans_sum_neg_sqrd_norm(segk_ctx *ctx, const segk_corpus *c, const
  *   cov_type 1 "diag":  prior_a = S_0, prior_b = m_0, (prior_c unused), k_0, v_0;
  *        stat_a = m_N_numerators, stat_b = S_N_partials, log_prod = log_prod_vars,
  *        pred = inv_vars
+ *   cov_type 2 "full":  device image of `GaussianComponents` (gaussian_components.py:75-126), D <= 64, no language
+ *        model.  prior_a = S_0 [D, D], prior_b = m_0 [D], k_0, v_0;
+ *        stat_a = m_N_numerators [K_max, D], stat_b = S_N_partials [K_max, D, D] (row-major, symmetric),
+ *        log_prod = logdet_covars [K_max], kconst as for the other types.
+ *        pred [K_max, D, D] holds, where the reference keeps inv_covars, the lower Cholesky factor L of
+ *        covar = (k_N + 1) / (k_N (v_N - D + 1)) (S_N_partial - k_N m_N m_N') (:319-331), recomputed from the
+ *        statistics after every add and delete: pred[k][j * D + d] = L[d][j] for d >= j, 0 above the diagonal --
+ *        column j of L is contiguous, it is what step j of a forward substitution reads.  logdet = 2 sum log L_dd,
+ *        the Mahalanobis term of the Student-t (:334-344) is |L^-1 delta|^2.
+ *        prior_c [D * D + n_emb + 1] is WRITTEN by segk_fbgmm_init_stats: the factor of the prior's covar
+ *        (:207-214) in the same layout, `cached_log_prior` of every row (:125-127), and one int32 status word
+ *        (in the first four bytes of the last double) for the calls that take no status argument: bit 32 = a
+ *        factorisation met a non-positive or non-finite pivot (the component kept its previous factor), bit 64 =
+ *        add_item / del_component named a component beyond K (nothing was done).
+ *        Accepted by segk_fbgmm_init_stats, _update (ops 1, 2, 4), _score, _pred_vector, _assign, _gibbs_items;
+ *        every other entry point that takes a segk_fbgmm returns SEGK_ERR_UNSUPPORTED.
  * ------------------------------------------------------------------------------------- */
 typedef struct segk_fbgmm {
     int32_t cov_type;
@@ -432,13 +449,13 @@ typedef struct segk_fbgmm {
     double alpha;              /* Dirichlet concentration (fbgmm.py:59)                       */
     double lms;                /* language-model scaling factor (fbgmm.py:62)                 */
     double k_0, v_0;           /* NIW scalars (diag only)                                     */
-    const double *prior_a;     /* [dev] [D]                                                   */
+    const double *prior_a;     /* [dev] [D]            (full: [D, D])                         */
     const double *prior_b;     /* [dev] [D]                                                   */
-    const double *prior_c;     /* [dev] [D]                                                   */
+    const double *prior_c;     /* [dev] [D]            (full: [D * D + n_emb + 1], derived)   */
     double *stat_a;            /* [dev] [K_max, D]                                            */
-    double *stat_b;            /* [dev] [K_max, D]                                            */
+    double *stat_b;            /* [dev] [K_max, D]     (full: [K_max, D, D])                  */
     double *log_prod;          /* [dev] [K_max]                                               */
-    double *pred;              /* [dev] [K_max, D]                                            */
+    double *pred;              /* [dev] [K_max, D]     (full: [K_max, D, D])                  */
     int64_t *counts;           /* [dev] [K_max]                                               */
     int32_t *assignments;      /* [dev] [n_emb]                                               */
     int32_t *K;                /* [dev] [1]                                                   */

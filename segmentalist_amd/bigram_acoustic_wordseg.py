@@ -51,6 +51,9 @@ class BigramAcousticWordseg(object):
         """Same arguments as the reference (bigram_acoustic_wordseg.py:129-136) plus the execution
         mode of UnigramAcousticWordseg (sync="batch": oracle/np_fbgmm_batch.py)."""
         logger.info("Initializing")
+        if covariance_type == "full":
+            raise NotImplementedError("full-covariance components (segmentalist_amd.gaussian_components) are supported by "
+                                      "the stand-alone FBGMM only; the segmenters take covariance_type 'fixed' or 'diag'")
         assert sync in ("sequential", "batch")
         self.sync = sync
         self._batch_args = (n_gibbs_blocks, n_stat_blocks, batch_seed, process_group, score_precision)

@@ -13,6 +13,9 @@ class BigramFBGMM(object):
     """bigram_fbgmm.py:19-100."""
 
     def __init__(self, X, prior, K, assignments="rand", covariance_type="full", lms=1.0, lm=None, _corpus=None):
+        if covariance_type == "full":       # before any device call
+            raise NotImplementedError("full-covariance components (segmentalist_amd.gaussian_components) are supported by "
+                                      "the stand-alone FBGMM only; BigramFBGMM takes covariance_type 'fixed' or 'diag'")
         self.prior = prior
         self.covariance_type = covariance_type
         self.lms = lms
@@ -37,8 +40,7 @@ class BigramFBGMM(object):
         elif self.covariance_type == "fixed":
             self.components = GaussianComponentsFixedVar(X, self.prior, assignments, K_max=K, lm=lm, **kw)
         elif self.covariance_type == "full":
-            raise NotImplementedError(
-                "full-covariance components are outside the accelerated hot path (SURVEY.md section 2, #8)")
+            raise NotImplementedError("full-covariance components are supported by the stand-alone FBGMM only")
         else:
             assert False, "Invalid covariance type."
 

@@ -815,3 +815,60 @@ static __device__ double fb_dp_sample(const double *vec, double *a, double *w, d
 {
     return fb_dp_sample_on(FbTriVec{vec, tri}, a, w, pr, N, n_max, viterbi, log_p_continue, anneal_temp, bnd, lane, usrc, fast);
 }
+
+// ---------------------------------------------------------------------------------------
+// component draw of the FBGMM item loops (segk_fbgmm.hip, segk_fullcov.hip)
+// ---------------------------------------------------------------------------------------
+// softmax of the logits in z (scipy logsumexp order: max-shift, sum, log), optional annealing
+// (fbgmm.py:446-449), then utils.draw in forward order with one uniform of the stream -- or the
+// first maximum when map_assign -- and the `k > K -> K` clamp (:459-460).  Result in *sh_k.
+static __device__ void fb_draw_component(const segk_fbgmm &f, double *z, double *red, int map_assign, double anneal_temp,
+                                  const double *ustream, int64_t *ucursor, int64_t ucap, int32_t *status, int shK,
+                                  int *sh_k_out, int64_t ubase = 0)      // ustream[0] is value `ubase` of the stream
+{
+    // scipy logsumexp: max-shift, sum, log
+    double mx = NEG_INF_D;
+    for (int k = threadIdx.x; k < f.K_max; k += blockDim.x) mx = z[k] > mx ? z[k] : mx;
+    mx = block_max(mx, red);
+    double s = 0.0;
+    for (int k = threadIdx.x; k < f.K_max; k += blockDim.x) s += exp(z[k] - mx);
+    s = block_sum(s, red);
+    double lse = log(s) + mx;
+    if (!map_assign && anneal_temp != 1.0) {     // :446-449
+        for (int k = threadIdx.x; k < f.K_max; k += blockDim.x) z[k] = (1. / anneal_temp) * (z[k] - lse);
+        __syncthreads();
+        double mx2 = NEG_INF_D;
+        for (int k = threadIdx.x; k < f.K_max; k += blockDim.x) mx2 = z[k] > mx2 ? z[k] : mx2;
+        mx2 = block_max(mx2, red);
+        double s2 = 0.0;
+        for (int k = threadIdx.x; k < f.K_max; k += blockDim.x) s2 += exp(z[k] - mx2);
+        s2 = block_sum(s2, red);
+        lse = log(s2) + mx2;
+    }
+    for (int k = threadIdx.x; k < f.K_max; k += blockDim.x) z[k] = exp(z[k] - lse);      // prob_z
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        int k;
+        if (map_assign) {                         // np.argmax(prob_z): first maximum
+            double bm = z[0];
+            k = 0;
+            for (int q = threadIdx.x; q < f.K_max; q += 64)
+                if (z[q] > bm) { bm = z[q]; k = q; }
+            for (int o = 32; o > 0; o >>= 1) {
+                const double om = __shfl_xor(bm, o);
+                const int ok = __shfl_xor(k, o);
+                if (om > bm || (om == bm && ok < k)) { bm = om; k = ok; }
+            }
+        } else {                                  // utils.draw (utils.py:10-21), forward order
+            const int64_t cur = *ucursor;
+            const double uu = (cur < ucap) ? ustream[cur - ubase] : 0.5;
+            k = fb_draw_seq(z, f.K_max, uu);
+            if (threadIdx.x == 0) {
+                if (cur >= ucap) atomicOr(status, 8);
+                *ucursor = cur + 1;
+            }
+        }
+        if (k > shK) k = shK;                     // :459-460
+        if (threadIdx.x == 0) *sh_k_out = k;
+    }
+}

@@ -2379,6 +2379,7 @@ __global__ void k_fbb_rows16(segk_fbgmm f, segk_fbatch bt, int D, double prior_a
 static int check_fbb(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt)
 {
     SEGK_REQUIRE(c && f && bt, "NULL corpus / fbgmm / batch state");
+    SEGK_REFUSE_FULLCOV(f, "segk_fbb_*");
     SEGK_REQUIRE(f->cov_type == 0 || f->cov_type == 1, "cov_type must be 0 (fixed) or 1 (diag)");
     SEGK_REQUIRE(c->D > 0 && c->D <= 64 * FBB_MAXCH, "batch mode supports D <= 256");
     SEGK_REQUIRE(c->N_max > 0, "corpus without landmarks");       // (more than 64 per utterance: check_fbb_long)
@@ -2526,6 +2527,7 @@ int32_t segk_fbb_prior_rows(segk_ctx *ctx, const segk_corpus *c, const segk_fbgm
 {
     (void)ctx;
     SEGK_REQUIRE(c && f && out, "null argument");
+    SEGK_REFUSE_FULLCOV(f, "segk_fbb_prior_rows");
     SEGK_REQUIRE(c->x_dtype == SEGK_F32 || c->x_dtype == SEGK_F64, "unsupported dtype");
     if (c->n_emb == 0) return SEGK_OK;
     const unsigned grid = (unsigned)((c->n_emb + 3) / 4);
@@ -2824,6 +2826,7 @@ int32_t segk_fbb_assign_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_f
                                int32_t s_n, int32_t b, const int32_t *n_utts, uint64_t sweep, double anneal_temp,
                                const int32_t *new_tok, const int32_t *n_new, void *stream)
 {
+    SEGK_REFUSE_FULLCOV(f, "segk_fbb_assign_diag32");
     SEGK_REQUIRE(f && f->cov_type == 1, "the float32 token likelihoods of this entry point are the diagonal (Student-t) ones");
     return fbb_assign_impl(ctx, c, f, bt, s_lo, s_n, b, n_utts, sweep, anneal_temp, new_tok, n_new, nullptr, 0, 1, stream);
 }

@@ -9,6 +9,8 @@
 //   k_fbgmm_assign      A10  gibbs_sample_inside_loop_i / map_assign_i for the new segments of one
 //                            utterance, sequentially, statistics updated between segments
 //
+// Full-covariance components (cov_type 2): the entry points at the end of this file route them to segk_fullcov.hip.
+//
 // Tolerance contract (BASELINE north_star): log-likelihoods within 1e-4 relative of the
 // reference; everything here is fp64 with device libm, which lands at ~1e-15.
 #include <stdlib.h>
@@ -553,59 +555,7 @@ __global__ __launch_bounds__(128) void k_unigram_segment(segk_corpus c, int utt,
     n_new[utt] = nn >= 0 ? nn : fb_collect_tokens(vid, bnd, N, new_tok + (int64_t)utt * c.N_max);
 }
 
-// softmax of the logits in z (scipy logsumexp order: max-shift, sum, log), optional annealing
-// (fbgmm.py:446-449), then utils.draw in forward order with one uniform of the stream -- or the
-// first maximum when map_assign -- and the `k > K -> K` clamp (:459-460).  Result in *sh_k.
-__device__ void fb_draw_component(const segk_fbgmm &f, double *z, double *red, int map_assign, double anneal_temp,
-                                  const double *ustream, int64_t *ucursor, int64_t ucap, int32_t *status, int shK,
-                                  int *sh_k_out, int64_t ubase = 0)      // ustream[0] is value `ubase` of the stream
-{
-    // scipy logsumexp: max-shift, sum, log
-    double mx = NEG_INF_D;
-    for (int k = threadIdx.x; k < f.K_max; k += blockDim.x) mx = z[k] > mx ? z[k] : mx;
-    mx = block_max(mx, red);
-    double s = 0.0;
-    for (int k = threadIdx.x; k < f.K_max; k += blockDim.x) s += exp(z[k] - mx);
-    s = block_sum(s, red);
-    double lse = log(s) + mx;
-    if (!map_assign && anneal_temp != 1.0) {     // :446-449
-        for (int k = threadIdx.x; k < f.K_max; k += blockDim.x) z[k] = (1. / anneal_temp) * (z[k] - lse);
-        __syncthreads();
-        double mx2 = NEG_INF_D;
-        for (int k = threadIdx.x; k < f.K_max; k += blockDim.x) mx2 = z[k] > mx2 ? z[k] : mx2;
-        mx2 = block_max(mx2, red);
-        double s2 = 0.0;
-        for (int k = threadIdx.x; k < f.K_max; k += blockDim.x) s2 += exp(z[k] - mx2);
-        s2 = block_sum(s2, red);
-        lse = log(s2) + mx2;
-    }
-    for (int k = threadIdx.x; k < f.K_max; k += blockDim.x) z[k] = exp(z[k] - lse);      // prob_z
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        int k;
-        if (map_assign) {                         // np.argmax(prob_z): first maximum
-            double bm = z[0];
-            k = 0;
-            for (int q = threadIdx.x; q < f.K_max; q += 64)
-                if (z[q] > bm) { bm = z[q]; k = q; }
-            for (int o = 32; o > 0; o >>= 1) {
-                const double om = __shfl_xor(bm, o);
-                const int ok = __shfl_xor(k, o);
-                if (om > bm || (om == bm && ok < k)) { bm = om; k = ok; }
-            }
-        } else {                                  // utils.draw (utils.py:10-21), forward order
-            const int64_t cur = *ucursor;
-            const double uu = (cur < ucap) ? ustream[cur - ubase] : 0.5;
-            k = fb_draw_seq(z, f.K_max, uu);
-            if (threadIdx.x == 0) {
-                if (cur >= ucap) atomicOr(status, 8);
-                *ucursor = cur + 1;
-            }
-        }
-        if (k > shK) k = shK;                     // :459-460
-        if (threadIdx.x == 0) *sh_k_out = k;
-    }
-}
+// (fb_draw_component: segk_fb_common.h, shared with segk_fullcov.hip)
 
 // ---------------------------------------------------------------------------------------
 // A10 for the new segments of one utterance, in order (fbgmm.py:422-494).  One workgroup.
@@ -1247,12 +1197,15 @@ __global__ void k_fbgmm_init_stats(segk_corpus c, segk_fbgmm f, const int32_t *b
         }                                           \
     } while (0)
 
-static int check_fb(const segk_corpus *c, const segk_fbgmm *f)
+// full_ok: the entry point `who` has a full-covariance form (cov_type 2, segk_fullcov.hip); the others refuse it
+static int check_fb(const segk_corpus *c, const segk_fbgmm *f, const char *who, bool full_ok = false)
 {
     SEGK_REQUIRE(c && f, "NULL corpus / fbgmm");
-    SEGK_REQUIRE(f->cov_type == 0 || f->cov_type == 1, "cov_type must be 0 (fixed) or 1 (diag)");
+    if (!full_ok) SEGK_REFUSE_FULLCOV(f, who);
+    SEGK_REQUIRE(f->cov_type == 0 || f->cov_type == 1 || f->cov_type == 2, "cov_type must be 0 (fixed), 1 (diag) or 2 (full)");
     SEGK_REQUIRE(f->K_max > 0 && c->D > 0, "sizes");
     SEGK_REQUIRE(f->kconst != NULL, "kconst buffer missing");
+    if (f->cov_type == 2) return segk_fc_check(c, f, who);
     return SEGK_OK;
 }
 
@@ -1270,9 +1223,10 @@ int32_t segk_fbgmm_update(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *f, in
                           int64_t item, int32_t k, const uint8_t *boundaries, void *stream)
 {
     (void)ctx;
-    int rc = check_fb(c, f);
-    if (rc) return rc;
     SEGK_REQUIRE(op == 0 || op == 1 || op == 2 || op == 4 || op == 5 || op == 6, "op");
+    int rc = check_fb(c, f, "segk_fbgmm_update ops 0, 5 and 6", op == 1 || op == 2 || op == 4);
+    if (rc) return rc;
+    if (f->cov_type == 2) return segk_fc_update(c, f, op, item, k, stream);
     DISPATCH_XT(c, hipLaunchKernelGGL(k_fbgmm_update<XT>, dim3(1), dim3(fb_nt(f)), 0, (hipStream_t)stream, *c, *f, op, utt,
                                        item, k, boundaries););
     SEGK_LAUNCH_CHECK();
@@ -1282,8 +1236,9 @@ int32_t segk_fbgmm_update(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *f, in
 int32_t segk_fbgmm_init_stats(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *f, void *stream)
 {
     SEGK_REQUIRE(ctx, "ctx");
-    int rc = check_fb(c, f);
+    int rc = check_fb(c, f, "segk_fbgmm_init_stats", true);
     if (rc) return rc;
+    if (f->cov_type == 2) return segk_fc_init_stats(ctx, c, f, stream);
     hipStream_t st = (hipStream_t)stream;
     SEGK_CHECK_HIP(hipMemsetAsync(f->K, 0, sizeof(int32_t), st));
     const int32_t *blk_lo = nullptr, *sorted = nullptr, *koff = nullptr;
@@ -1301,9 +1256,10 @@ int32_t segk_fbgmm_score(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *
                          int64_t row0, int64_t n, double *out, void *stream)
 {
     (void)ctx;
-    int rc = check_fb(c, f);
+    int rc = check_fb(c, f, "segk_fbgmm_score", true);
     if (rc) return rc;
     if (n <= 0) return SEGK_OK;
+    if (f->cov_type == 2) return segk_fc_score(c, f, ids, row0, n, out, stream);
     const int nt = fb_nt(f);
     size_t lds = fb_lds(c, f, nt);
     SEGK_REQUIRE(lds <= 160 * 1024, "K_max too large for the LDS logits buffer");
@@ -1322,9 +1278,10 @@ int32_t segk_fbgmm_pred_vector(segk_ctx *ctx, const segk_corpus *c, const segk_f
                                double *out, void *stream)
 {
     (void)ctx;
-    int rc = check_fb(c, f);
+    int rc = check_fb(c, f, "segk_fbgmm_pred_vector", true);
     if (rc) return rc;
     SEGK_REQUIRE(row >= 0 && row < c->n_emb, "row out of range");
+    if (f->cov_type == 2) return segk_fc_pred_vector(c, f, row, out, stream);
     DISPATCH_XT(c, hipLaunchKernelGGL(k_fbgmm_pred_vector<XT>, dim3((f->K_max + 1 + 127) / 128), dim3(128), 0,
                                        (hipStream_t)stream, *c, *f, row, out););
     SEGK_LAUNCH_CHECK();
@@ -1358,8 +1315,10 @@ int32_t segk_fbgmm_assign(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *f, in
                           const double *ustream, int64_t *ucursor, int64_t ucap, int32_t *status, void *stream)
 {
     (void)ctx;
-    int rc = check_fb(c, f);
+    int rc = check_fb(c, f, "segk_fbgmm_assign", true);
     if (rc) return rc;
+    if (f->cov_type == 2)
+        return segk_fc_assign(c, f, utt, map_assign, anneal_temp, new_tok, n_new, ustream, ucursor, ucap, status, stream);
     const int nt = fb_nt(f);
     size_t lds = fb_lds(c, f, nt);
     SEGK_REQUIRE(lds <= 160 * 1024, "K_max too large for the LDS logits buffer");
@@ -1386,7 +1345,7 @@ int32_t segk_fbgmm_sequential_sweep(segk_ctx *ctx, const segk_corpus *c, segk_fb
                                     double *out_logprob, int32_t *status, void *stream)
 {
     SEGK_REQUIRE(ctx, "ctx");
-    int rc = check_fb(c, f);
+    int rc = check_fb(c, f, "segk_fbgmm_sequential_sweep");
     if (rc) return rc;
     SEGK_REQUIRE(order && n_order >= 0 && row_start && score && ustream && ucursor && boundaries && new_tok && n_new && out_logprob && status,
                  "sequential sweep operands");
@@ -1605,11 +1564,13 @@ int32_t segk_fbgmm_gibbs_items(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *
                                int64_t *ucursor, int64_t ucap, int32_t *status, void *stream)
 {
     (void)ctx;
-    int rc = check_fb(c, f);
+    int rc = check_fb(c, f, "segk_fbgmm_gibbs_items", true);
     if (rc) return rc;
     SEGK_REQUIRE(f->lm_unigram == NULL, "FBGMM.gibbs_sample has no language-model variant in the reference");
     SEGK_REQUIRE(ids != NULL || n <= c->n_emb, "n exceeds the number of rows");
     if (n <= 0) return SEGK_OK;
+    if (f->cov_type == 2)
+        return segk_fc_gibbs_items(c, f, ids, n, consider_unassigned, anneal_temp, ustream, ucursor, ucap, status, stream);
     const int nt = fb_nt(f);
     size_t lds = fb_lds(c, f, nt) + (size_t)3 * c->D * sizeof(double);
     SEGK_REQUIRE(lds <= 160 * 1024, "K_max too large for the LDS logits buffer");

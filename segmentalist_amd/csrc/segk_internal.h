@@ -159,6 +159,26 @@ int segk_rows_by_label(segk_ctx *ctx, const int32_t *labels, int64_t n, int K_ma
 
 #define SEGK_LAUNCH_CHECK() SEGK_CHECK_HIP(hipGetLastError())
 
+// Full-covariance components (segk_fbgmm.cov_type 2, segk_fullcov.hip) exist behind the stand-alone FBGMM entry points only
+// (init_stats, update ops 1 / 2 / 4, score, pred_vector, assign, gibbs_items); every other one refuses them by name.
+#define SEGK_REFUSE_FULLCOV(f, who)                                                                                 \
+    do {                                                                                                            \
+        if ((f) && (f)->cov_type == 2) {                                                                            \
+            segk_set_error("%s: full-covariance components (cov_type 2) are not supported by this entry point", who); \
+            return SEGK_ERR_UNSUPPORTED;                                                                            \
+        }                                                                                                           \
+    } while (0)
+// segk_fullcov.hip: the cov_type 2 forms of the segk_fbgmm_* entry points (arguments already checked by the caller)
+int segk_fc_check(const segk_corpus *c, const segk_fbgmm *f, const char *who);
+int segk_fc_init_stats(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *f, void *stream);
+int segk_fc_update(const segk_corpus *c, segk_fbgmm *f, int op, int64_t item, int k, void *stream);
+int segk_fc_score(const segk_corpus *c, const segk_fbgmm *f, const int32_t *ids, int64_t row0, int64_t n, double *out, void *stream);
+int segk_fc_pred_vector(const segk_corpus *c, const segk_fbgmm *f, int64_t row, double *out, void *stream);
+int segk_fc_assign(const segk_corpus *c, segk_fbgmm *f, int utt, int map_assign, double anneal_temp, const int32_t *new_tok,
+                   const int32_t *n_new, const double *ustream, int64_t *ucursor, int64_t ucap, int32_t *status, void *stream);
+int segk_fc_gibbs_items(const segk_corpus *c, segk_fbgmm *f, const int32_t *ids, int64_t n, int consider_unassigned,
+                        double anneal_temp, const double *ustream, int64_t *ucursor, int64_t ucap, int32_t *status, void *stream);
+
 // A workspace the context owns, grown on demand: *buf replaced by a fresh allocation of `bytes`.  Refuses during a graph capture
 // (workspaces must exist before it), waits for `st` first (work in flight may still use the old block), frees the old block.
 // The contents are gone.  On failure *buf is NULL.

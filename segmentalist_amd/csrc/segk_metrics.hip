@@ -198,6 +198,7 @@ int32_t segk_fbgmm_record_metrics(segk_ctx *ctx, const segk_corpus *c, const seg
                                   double *out, void *stream)
 {
     SEGK_REQUIRE(ctx && c && f && out, "arguments");
+    SEGK_REFUSE_FULLCOV(f, "segk_fbgmm_record_metrics");
     SEGK_REQUIRE(f->cov_type == 0 || f->cov_type == 1, "cov_type");
     SEGK_REQUIRE(f->K_max <= 8192, "K_max <= 8192");
     hipStream_t st = (hipStream_t)stream;

@@ -729,7 +729,7 @@ class KMeansBatchSweeper(object):
 
 
 class DeviceFbgmm(object):
-    """Device image of FBGMM + its Gaussian components (fixed-variance or diagonal), see
+    """Device image of FBGMM + its Gaussian components (fixed-variance, diagonal or full covariance), see
     include/segk.h `segk_fbgmm`."""
 
     def __init__(self, corpus, cov_type, K_max, alpha, lms, prior_a, prior_b, prior_c, k_0, v_0, assignments,
@@ -743,11 +743,19 @@ class DeviceFbgmm(object):
         f64 = torch.float64
         self.prior_a = to_dev(prior_a, np.float64)
         self.prior_b = to_dev(prior_b, np.float64)
-        self.prior_c = to_dev(prior_c if prior_c is not None else np.zeros(c.D), np.float64)
+        if self.cov_type == 2:
+            # full covariance: D x D statistics and factors per component; prior_c is derived by the library (the prior's
+            # factor, the prior predictive of every row, one status word)
+            assert lm is None and tuple(self.prior_a.shape) == (c.D, c.D)
+            self.prior_c = torch.zeros(c.D * c.D + c.n_emb + 1, dtype=f64, device=dev)
+            mat = (self.K_max, c.D, c.D)
+        else:
+            self.prior_c = to_dev(prior_c if prior_c is not None else np.zeros(c.D), np.float64)
+            mat = (self.K_max, c.D)
         self.stat_a = torch.zeros((self.K_max, c.D), dtype=f64, device=dev)
-        self.stat_b = torch.zeros((self.K_max, c.D), dtype=f64, device=dev)
+        self.stat_b = torch.zeros(mat, dtype=f64, device=dev)
         self.log_prod = torch.zeros(self.K_max, dtype=f64, device=dev)
-        self.pred = torch.zeros((self.K_max, c.D), dtype=f64, device=dev)
+        self.pred = torch.zeros(mat, dtype=f64, device=dev)
         self.kconst = torch.zeros(self.K_max + 1, dtype=f64, device=dev)
         self.counts = torch.zeros(self.K_max, dtype=torch.int64, device=dev)
         self.assignments = to_dev(assignments, np.int32)
@@ -913,10 +921,17 @@ class DeviceFbgmm(object):
 
     def check_status(self):
         st = int(self.status[0].item())
+        if self.cov_type == 2:      # the calls without a status argument (init_stats, update) report in prior_c's last word
+            st |= int(self.prior_c[-1:].view(_torch().int32)[0].item())
         if st & 8:
             raise SegkError("uniform stream exhausted")
         if st & 16:
             raise AssertionError("forward_backward: log_prob == -inf (unigram_acoustic_wordseg.py:753)")
+        if st & 32:
+            raise SegkError("full-covariance component: the covariance matrix of a component is not positive definite "
+                            "(a non-positive or non-finite Cholesky pivot); the component kept its previous factor")
+        if st & 64:
+            raise SegkError("full-covariance component: add_item / del_component named a component beyond K")
 
 
 class FbgmmBatchSweeper(object):

@@ -8,6 +8,7 @@ import time
 import numpy as np
 from scipy.special import gammaln
 
+from .gaussian_components import GaussianComponents
 from .gaussian_components_diag import GaussianComponentsDiag
 from .gaussian_components_fixedvar import GaussianComponentsFixedVar
 from .kmeans import _consecutive
@@ -41,8 +42,10 @@ class FBGMM(object):
         elif self.covariance_type == "fixed":
             self.components = GaussianComponentsFixedVar(X, self.prior, assignments, K_max=K, **kw)
         elif self.covariance_type == "full":
-            raise NotImplementedError(
-                "full-covariance components are outside the accelerated hot path (SURVEY.md section 2, #8)")
+            # (the reference would die on a prior without S_0 with an AttributeError further down)
+            if np.asarray(getattr(self.prior, "S_0", None)).shape != (D, D):
+                raise NotImplementedError("full covariance needs a NIW prior with a D×D S_0")
+            self.components = GaussianComponents(X, self.prior, assignments, K_max=K, **kw)
         else:
             assert False, "Invalid covariance type."
 

@@ -46,6 +46,9 @@ class UnigramAcousticWordseg(object):
         components "f32" evaluates the Student-t terms in float32 with the hardware logarithm (same
         tolerance); "f64" reproduces the specification to the last draw."""
         logger.info("Initializing")
+        if covariance_type == "full":
+            raise NotImplementedError("full-covariance components (segmentalist_amd.gaussian_components) are supported by "
+                                      "the stand-alone FBGMM only; the segmenters take covariance_type 'fixed' or 'diag'")
         assert sync in ("sequential", "batch")
         self.sync = sync
         self._batch_args = (n_gibbs_blocks, n_stat_blocks, batch_seed, process_group, score_precision)
