@@ -13,8 +13,8 @@
 //   k_fbb_score     log_marg_i of every candidate span of the block: R rows x all slots per
 //                   workgroup, online logsumexp per row                         (fp64 VALU)
 //   k_fbb_segment   one workgroup per utterance: score vector, DP, backward sampling with the
-//                   counter-based uniforms, new token list (corpora with an utterance of more than 64
-//                   landmarks: k_fbb_segment_band, the span tables as a band of n_slices_max columns)
+//                   counter-based uniforms (or the max-plus DP, fb_type "viterbi"), new token list (corpora with
+//                   an utterance of more than 64 landmarks: the span tables as a band of n_slices_max columns)
 //   k_fbb_assign    one workgroup per utterance: logits -> softmax -> draw for each new token
 //                   (with a language model: the bigram prior of the previous token's slot)
 //   k_fbb_partials  the block's partial sums from its new tokens (token order per slot)
@@ -1242,9 +1242,26 @@ __global__ __launch_bounds__(256) void k_vlog_calibrate(int iters, float seed, f
 }
 
 // ---------------------------------------------------------------------------------------
-// boundaries of one utterance per workgroup (128 threads; wave 0 runs the DP)
+// Boundaries of one utterance per workgroup (128 threads; wave 0 runs the DP).  One kernel with two axes:
+//   BAND  how the span tables sit in LDS.  false: triangles (N_max <= 64).  true: corpora with an utterance of more than 64
+//         landmarks -- the scores and the span ids are held as a BAND, [N][W], W = n_slices_max <= 64, the corpus' band layout,
+//         so LDS grows with N_max * W and not with N_max^2; the DP addresses the band (its register path: lane w reads entry
+//         (t, w)) and the token lists are taken 64 flags at a time.  Every utterance of such a corpus runs there, short ones
+//         too: an utterance of N <= W landmarks reads the rows t <= N of the corpus' band, whose entries w >= t are -1.
+//   MAP   the DP.  false: forward filtering / backward sampling with the counter-based uniforms (fb_dp_sample_on).  true: the
+//         MAP boundaries (fb_type "viterbi": unigram_acoustic_wordseg.py:759-864) by the max-plus DP (fb_dp_viterbi_on): no
+//         uniforms, no temperature -- sweep, anneal_temp and status are ignored; the backpointers live in the scratch row `w`.
+//         A total of -inf sets no status bit (the serial kernel raises it only when it samples).
+// (`n_max` sits in the padding between `b` and the 8-byte `sweep`: every later argument keeps the offset it has without it, and
+// the sampling instantiations' scalar-register allocation with it -- profiles/segment_template_resource_usage.txt.)
+// LDS, `cells` = N_max W (band) or N_max (N_max + 1) / 2 (triangle) -- fbb_seg_lds is its size on the host:
+//   vec [cells], a [N_max], w [N_max + 1], pr [N_max + 1] (double); old [N_max], ids [cells] (int32); bnd [N_max] (bytes)
+// The span ids and the boundary flags are staged in LDS: the token lists before and after the DP are then taken from LDS -- from
+// memory each was two dependent round trips, the second one behind the DP's own stores of the flags -- and the flags go back
+// to memory once, at the end (the workgroup is a chain of round trips: 19 of its 25 us).
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(128) void k_fbb_segment(segk_corpus c, segk_fbatch bt, FbbMap map, int b, uint64_t sweep, int n_max, double wip,
+template <bool BAND, bool MAP>
+__global__ __launch_bounds__(128) void k_fbb_segment(segk_corpus c, segk_fbatch bt, FbbMap map, int b, int n_max, uint64_t sweep, double wip,
                               double time_power_term, double anneal_temp, const double *score, uint8_t *boundaries,
                               int32_t *new_tok, int32_t *n_new, double *out_logprob, int32_t *status, double *probe_alpha)
 {
@@ -1253,207 +1270,67 @@ __global__ __launch_bounds__(128) void k_fbb_segment(segk_corpus c, segk_fbatch 
     if (!fbb_locate(map, blockIdx.x, &s, &idx)) return;
     const int slice = map.lo[s];
     const int utt = bt.utt_range[(slice * bt.n_blocks + b) * 2] + idx;
-    const int N = c.lengths[utt];
+    const int N = c.lengths[utt], NM = c.N_max;        // (triangle: N <= 64)
+    [[maybe_unused]] const int W = c.band_W;           // the band's columns (BAND only)
     const int tri = N * (N + 1) / 2;
-    const int64_t triMax = (int64_t)c.N_max * (c.N_max + 1) / 2;
-    const FbSpanTab tab = fb_span_tab(c, utt, N, n_max);
-    const int32_t *vid = tab.vid;
-    double *vec = (double *)smem;           // [tri]
-    double *a = vec + triMax;               // [N]
-    double *w = a + c.N_max;                // [N+1]
-    double *pr = w + c.N_max + 1;           // [N+1]
-    int32_t *old = (int32_t *)(pr + c.N_max + 1);      // [N_max]
-    // The span ids (triangular) and the boundary flags staged in LDS: the token lists before and after the DP are then taken from
-    // LDS -- from memory each was two dependent round trips, the second one behind the DP's own stores of the flags -- and the
-    // flags go back to memory once, at the end (the workgroup is a chain of round trips: 19 of its 25 us)
-    int32_t *vid_l = old + c.N_max;                    // [triMax]
-    uint8_t *bnd_l = (uint8_t *)(vid_l + triMax);      // [N_max]
-    uint8_t *bnd_g = boundaries + (int64_t)utt * c.N_max;
-    for (int j = threadIdx.x; j < N; j += blockDim.x) bnd_l[j] = bnd_g[j];
-    if (tab.band) {
-        for (int j = threadIdx.x; j < tri; j += blockDim.x) vid_l[j] = -1;
-        __syncthreads();
-        const int W = tab.W;
-        for (int i = threadIdx.x; i < N * W; i += blockDim.x) {
-            const int t = i / W + 1, s2 = t - 1 - (i - (t - 1) * W);
-            if (s2 >= 0) vid_l[t * (t - 1) / 2 + s2] = tab.bandi[i];
-        }
-    } else {
-        for (int j = threadIdx.x; j < tri; j += blockDim.x) vid_l[j] = vid[j];
-    }
-    fb_fill_vec(tab, N, tri, [&](int id) { return score[id]; }, time_power_term, wip, vec, threadIdx.x, blockDim.x);
-    __syncthreads();
-    if (threadIdx.x >= 64) return;
-    const int lane = threadIdx.x;
-    uint8_t *bnd = bnd_l;
-    vid = vid_l;
-    const int n_old = N <= 64 ? fb_collect_tokens_wave(vid, bnd, N, old, lane)
-                              : __shfl(lane == 0 ? fb_collect_tokens(vid, bnd, N, old) : 0, 0);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    CounterUniforms usrc = {bt.seed, sweep, (uint64_t)utt, 0};
-    const double total = fb_dp_sample(vec, a, w, pr, N, tri, n_max, 0, 0.0, anneal_temp, bnd, lane, usrc, bt.fast_dp);
-    if (probe_alpha)            // segk_fbb_set_probe: the forward filter's values (the backward pass only reads them)
-        for (int j = lane; j < N; j += 64) probe_alpha[(int64_t)utt * c.N_max + j] = a[j];
-    for (int j = lane; j < n_old; j += 64) bt.slot[old[j]] = -1;
-    // (the boundary flags were written by lane 0 of this wave)
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const int nn = N <= 64 ? fb_collect_tokens_wave(vid, bnd, N, new_tok + (int64_t)utt * c.N_max, lane) : -1;
-    for (int j = lane; j < N; j += 64) bnd_g[j] = bnd_l[j];
-    if (lane != 0) return;
-    if (total == NEG_INF_D) atomicOr(status, 16);
-    out_logprob[utt] = total;
-    n_new[utt] = nn >= 0 ? nn : fb_collect_tokens(vid, bnd, N, new_tok + (int64_t)utt * c.N_max);
-}
-
-// ---------------------------------------------------------------------------------------
-// The same for corpora with utterances of more than 64 landmarks (N_max > 64): the scores and the span ids of
-// the utterance are held as a BAND -- [N][W], W = n_slices_max <= 64, the corpus' band layout -- instead of triangles, so LDS
-// grows with N_max * W and not with N_max^2.  The DP is fb_dp_sample_on with the band's addressing (its register path: lane w
-// reads entry (t, w)); the token lists are taken 64 flags at a time.  Every utterance of such a corpus runs here, short ones
-// too: an utterance of N <= W landmarks reads the rows t <= N of the corpus' band, whose entries w >= t are -1.
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(128) void k_fbb_segment_band(segk_corpus c, segk_fbatch bt, FbbMap map, int b, uint64_t sweep, double wip,
-                              double time_power_term, double anneal_temp, const double *score, uint8_t *boundaries,
-                              int32_t *new_tok, int32_t *n_new, double *out_logprob, int32_t *status, double *probe_alpha)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    int s, idx;
-    if (!fbb_locate(map, blockIdx.x, &s, &idx)) return;
-    const int slice = map.lo[s];
-    const int utt = bt.utt_range[(slice * bt.n_blocks + b) * 2] + idx;
-    const int N = c.lengths[utt], NM = c.N_max, W = c.band_W;
-    double *vec = (double *)smem;                      // [N_max W]
-    double *a = vec + (int64_t)NM * W;                 // [N_max]
+    const int64_t cells = BAND ? (int64_t)NM * W : (int64_t)NM * (NM + 1) / 2;
+    double *vec = (double *)smem;                      // [cells]
+    double *a = vec + cells;                           // [N_max]
     double *w = a + NM;                                // [N_max + 1]
     double *pr = w + NM + 1;                           // [N_max + 1]
     int32_t *old = (int32_t *)(pr + NM + 1);           // [N_max]
-    int32_t *bid_l = old + NM;                         // [N_max W]
-    uint8_t *bnd_l = (uint8_t *)(bid_l + (int64_t)NM * W);      // [N_max]
+    int32_t *ids = old + NM;                           // [cells]
+    uint8_t *bnd = (uint8_t *)(ids + cells);           // [N_max]
     uint8_t *bnd_g = boundaries + (int64_t)utt * NM;
-    for (int j = threadIdx.x; j < N; j += blockDim.x) bnd_l[j] = bnd_g[j];
-    fb_fill_vec_band(c.band_ids + (int64_t)utt * NM * W, c.band_dur + (int64_t)utt * NM * W, N, W, [&](int id) { return score[id]; },
-                     time_power_term, wip, vec, bid_l, threadIdx.x, blockDim.x);
-    __syncthreads();
-    if (threadIdx.x >= 64) return;
-    const int lane = threadIdx.x;
-    const int n_old = fb_collect_tokens_wave_band(bid_l, W, bnd_l, N, old, lane);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    CounterUniforms usrc = {bt.seed, sweep, (uint64_t)utt, 0};
-    // (the tolerance modes' float32 DP is built for N <= 64: here their hardware exponentials enter the fp64 recurrence)
-    const double total = fb_dp_sample_on(FbBandVec{vec, W, N}, a, w, pr, N, W, 0, 0.0, anneal_temp, bnd_l, lane, usrc, bt.fast_dp);
-    if (probe_alpha)
-        for (int j = lane; j < N; j += 64) probe_alpha[(int64_t)utt * NM + j] = a[j];
-    for (int j = lane; j < n_old; j += 64) bt.slot[old[j]] = -1;
-    // (the boundary flags were written by lane 0 of this wave)
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const int nn = fb_collect_tokens_wave_band(bid_l, W, bnd_l, N, new_tok + (int64_t)utt * NM, lane);
-    for (int j = lane; j < N; j += 64) bnd_g[j] = bnd_l[j];
-    if (lane != 0) return;
-    if (total == NEG_INF_D) atomicOr(status, 16);
-    out_logprob[utt] = total;
-    n_new[utt] = nn;
-}
-
-// ---------------------------------------------------------------------------------------
-// The MAP boundaries (fb_type "viterbi": unigram_acoustic_wordseg.py:759-864) of one utterance per workgroup: k_fbb_segment
-// and k_fbb_segment_band with the max-plus DP (fb_dp_viterbi_on) in place of the sampling one -- the same staging of the span
-// tables and boundary flags in LDS, the same token lists, the same clearing of the old segments' slots, the same probe.  No
-// uniforms, no temperature; the backpointers live where the sampling DP keeps its scratch row `w`.  A total of -inf sets no
-// status bit (the serial kernel raises it only when it samples).
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(128) void k_fbb_segment_map(segk_corpus c, segk_fbatch bt, FbbMap map, int b, int n_max, double wip,
-                              double time_power_term, const double *score, uint8_t *boundaries, int32_t *new_tok,
-                              int32_t *n_new, double *out_logprob, double *probe_alpha)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    int s, idx;
-    if (!fbb_locate(map, blockIdx.x, &s, &idx)) return;
-    const int slice = map.lo[s];
-    const int utt = bt.utt_range[(slice * bt.n_blocks + b) * 2] + idx;
-    const int N = c.lengths[utt];                      // <= 64: corpora with longer utterances take k_fbb_segment_map_band
-    const int tri = N * (N + 1) / 2;
-    const int64_t triMax = (int64_t)c.N_max * (c.N_max + 1) / 2;
-    const FbSpanTab tab = fb_span_tab(c, utt, N, n_max);
-    double *vec = (double *)smem;                      // [tri]
-    double *a = vec + triMax;                          // [N]
-    int32_t *bp = (int32_t *)(a + c.N_max);            // [N+1] (the layout of k_fbb_segment: its w and pr rows)
-    int32_t *old = (int32_t *)(a + 3 * c.N_max + 2);   // [N_max]
-    int32_t *vid_l = old + c.N_max;                    // [triMax]
-    uint8_t *bnd_l = (uint8_t *)(vid_l + triMax);      // [N_max]
-    uint8_t *bnd_g = boundaries + (int64_t)utt * c.N_max;
-    for (int j = threadIdx.x; j < N; j += blockDim.x) bnd_l[j] = bnd_g[j];
-    if (tab.band) {
-        for (int j = threadIdx.x; j < tri; j += blockDim.x) vid_l[j] = -1;
-        __syncthreads();
-        const int W = tab.W;
-        for (int i = threadIdx.x; i < N * W; i += blockDim.x) {
-            const int t = i / W + 1, s2 = t - 1 - (i - (t - 1) * W);
-            if (s2 >= 0) vid_l[t * (t - 1) / 2 + s2] = tab.bandi[i];
-        }
+    for (int j = threadIdx.x; j < N; j += blockDim.x) bnd[j] = bnd_g[j];
+    const auto score_of = [&](int id) { return score[id]; };
+    if constexpr (BAND) {
+        fb_fill_vec_band(c.band_ids + (int64_t)utt * NM * W, c.band_dur + (int64_t)utt * NM * W, N, W, score_of, time_power_term, wip,
+                         vec, ids, threadIdx.x, blockDim.x);
     } else {
-        for (int j = threadIdx.x; j < tri; j += blockDim.x) vid_l[j] = tab.vid[j];
+        const FbSpanTab tab = fb_span_tab(c, utt, N, n_max);
+        if (tab.band) {
+            for (int j = threadIdx.x; j < tri; j += blockDim.x) ids[j] = -1;
+            __syncthreads();
+            const int Wt = tab.W;
+            for (int i = threadIdx.x; i < N * Wt; i += blockDim.x) {
+                const int t = i / Wt + 1, s2 = t - 1 - (i - (t - 1) * Wt);
+                if (s2 >= 0) ids[t * (t - 1) / 2 + s2] = tab.bandi[i];
+            }
+        } else {
+            for (int j = threadIdx.x; j < tri; j += blockDim.x) ids[j] = tab.vid[j];
+        }
+        fb_fill_vec(tab, N, tri, score_of, time_power_term, wip, vec, threadIdx.x, blockDim.x);
     }
-    fb_fill_vec(tab, N, tri, [&](int id) { return score[id]; }, time_power_term, wip, vec, threadIdx.x, blockDim.x);
     __syncthreads();
     if (threadIdx.x >= 64) return;
     const int lane = threadIdx.x;
-    const int n_old = fb_collect_tokens_wave(vid_l, bnd_l, N, old, lane);
+    int n_old;
+    if constexpr (BAND) n_old = fb_collect_tokens_wave_band(ids, W, bnd, N, old, lane);
+    else n_old = fb_collect_tokens_wave(ids, bnd, N, old, lane);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    const double total = fb_dp_viterbi_on(FbTriVec{vec, tri}, a, bp, N, n_max, bnd_l, lane);
-    if (probe_alpha)            // segk_fbb_set_probe: the forward maxima (the backward pass only reads the backpointers)
-        for (int j = lane; j < N; j += 64) probe_alpha[(int64_t)utt * c.N_max + j] = a[j];
-    for (int j = lane; j < n_old; j += 64) bt.slot[old[j]] = -1;
-    // (the boundary flags were written by lane 0 of this wave)
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const int nn = fb_collect_tokens_wave(vid_l, bnd_l, N, new_tok + (int64_t)utt * c.N_max, lane);
-    for (int j = lane; j < N; j += 64) bnd_g[j] = bnd_l[j];
-    if (lane != 0) return;
-    out_logprob[utt] = total;
-    n_new[utt] = nn;
-}
-
-__global__ __launch_bounds__(128) void k_fbb_segment_map_band(segk_corpus c, segk_fbatch bt, FbbMap map, int b, double wip,
-                              double time_power_term, const double *score, uint8_t *boundaries, int32_t *new_tok,
-                              int32_t *n_new, double *out_logprob, double *probe_alpha)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    int s, idx;
-    if (!fbb_locate(map, blockIdx.x, &s, &idx)) return;
-    const int slice = map.lo[s];
-    const int utt = bt.utt_range[(slice * bt.n_blocks + b) * 2] + idx;
-    const int N = c.lengths[utt], NM = c.N_max, W = c.band_W;
-    double *vec = (double *)smem;                      // [N_max W]
-    double *a = vec + (int64_t)NM * W;                 // [N_max]
-    int32_t *bp = (int32_t *)(a + NM);                 // [N_max + 1] (the layout of k_fbb_segment_band: its w and pr rows)
-    int32_t *old = (int32_t *)(a + 3 * NM + 2);        // [N_max]
-    int32_t *bid_l = old + NM;                         // [N_max W]
-    uint8_t *bnd_l = (uint8_t *)(bid_l + (int64_t)NM * W);      // [N_max]
-    uint8_t *bnd_g = boundaries + (int64_t)utt * NM;
-    for (int j = threadIdx.x; j < N; j += blockDim.x) bnd_l[j] = bnd_g[j];
-    fb_fill_vec_band(c.band_ids + (int64_t)utt * NM * W, c.band_dur + (int64_t)utt * NM * W, N, W, [&](int id) { return score[id]; },
-                     time_power_term, wip, vec, bid_l, threadIdx.x, blockDim.x);
-    __syncthreads();
-    if (threadIdx.x >= 64) return;
-    const int lane = threadIdx.x;
-    const int n_old = fb_collect_tokens_wave_band(bid_l, W, bnd_l, N, old, lane);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const double total = fb_dp_viterbi_on(FbBandVec{vec, W, N}, a, bp, N, W, bnd_l, lane);
-    if (probe_alpha)
+    // (the tolerance modes' float32 DP is built for triangles: on the band their hardware exponentials enter the fp64 recurrence.
+    // The triangular sampling form goes through fb_dp_sample, the wrapper k_fbb_step_diag32 calls: with a second route to
+    // fb_dp_sample_on<., FbTriVec> in this unit the fused step's generated code moves)
+    [[maybe_unused]] CounterUniforms usrc = {bt.seed, sweep, (uint64_t)utt, 0};
+    double total;
+    if constexpr (BAND && MAP) total = fb_dp_viterbi_on(FbBandVec{vec, W, N}, a, (int32_t *)w, N, W, bnd, lane);
+    else if constexpr (BAND) total = fb_dp_sample_on(FbBandVec{vec, W, N}, a, w, pr, N, W, 0, 0.0, anneal_temp, bnd, lane, usrc, bt.fast_dp);
+    else if constexpr (MAP) total = fb_dp_viterbi_on(FbTriVec{vec, tri}, a, (int32_t *)w, N, n_max, bnd, lane);
+    else total = fb_dp_sample(vec, a, w, pr, N, tri, n_max, 0, 0.0, anneal_temp, bnd, lane, usrc, bt.fast_dp);
+    if (probe_alpha)            // segk_fbb_set_probe: the forward filter's values / maxima (the backward pass does not change them)
         for (int j = lane; j < N; j += 64) probe_alpha[(int64_t)utt * NM + j] = a[j];
     for (int j = lane; j < n_old; j += 64) bt.slot[old[j]] = -1;
     // (the boundary flags were written by lane 0 of this wave)
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    const int nn = fb_collect_tokens_wave_band(bid_l, W, bnd_l, N, new_tok + (int64_t)utt * NM, lane);
-    for (int j = lane; j < N; j += 64) bnd_g[j] = bnd_l[j];
+    int nn;
+    if constexpr (BAND) nn = fb_collect_tokens_wave_band(ids, W, bnd, N, new_tok + (int64_t)utt * NM, lane);
+    else nn = fb_collect_tokens_wave(ids, bnd, N, new_tok + (int64_t)utt * NM, lane);
+    for (int j = lane; j < N; j += 64) bnd_g[j] = bnd[j];
     if (lane != 0) return;
+    if (!MAP && total == NEG_INF_D) atomicOr(status, 16);
     out_logprob[utt] = total;
     n_new[utt] = nn;
 }
@@ -2389,12 +2266,13 @@ static int check_fbb(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatc
     return SEGK_OK;
 }
 
-// LDS of k_fbb_segment_band: band of scores (double) and of span ids (int32), alpha and the DP's two scratch rows, the old
-// token list, the boundary flags
+// LDS of k_fbb_segment: scores (double) and span ids (int32) of the band or the triangle, alpha and the DP's two scratch rows,
+// the old token list, the boundary flags
 #define FBB_BAND_LDS_MAX (160 * 1024)
-static size_t fbb_band_lds(int64_t NM, int64_t W)
+static size_t fbb_seg_lds(int64_t NM, int64_t W, bool band)
 {
-    return (size_t)(NM * W + 3 * NM + 2) * sizeof(double) + (size_t)(NM + NM * W) * sizeof(int32_t) + (size_t)((NM + 15) & ~15);
+    const int64_t cells = band ? NM * W : NM * (NM + 1) / 2;
+    return (size_t)(cells + 3 * NM + 2) * sizeof(double) + (size_t)(NM + cells) * sizeof(int32_t) + (size_t)((NM + 15) & ~15);
 }
 
 // What a corpus with an utterance of more than 64 landmarks needs from the boundary step (N_max <= 64: nothing).
@@ -2412,7 +2290,7 @@ static int check_fbb_long(const segk_corpus *c, int n_slices_max)
                        "use sync=\"sequential\"", c->N_max, n_slices_max);
         return SEGK_ERR_ARG;
     }
-    const size_t lds = fbb_band_lds(c->N_max, c->band_W);
+    const size_t lds = fbb_seg_lds(c->N_max, c->band_W, true);
     if (lds > FBB_BAND_LDS_MAX) {
         segk_set_error("the banded span table of the longest utterance does not fit in LDS: N_max = %d landmarks, window W = %d: "
                        "12 N_max W + 28 N_max + 16 + (N_max rounded up to 16) = %zu bytes needed, %d available: shorten the "
@@ -2420,6 +2298,25 @@ static int check_fbb_long(const segk_corpus *c, int n_slices_max)
         return SEGK_ERR_ARG;
     }
     return SEGK_OK;
+}
+
+// Chunks and threads of the assignment kernels (k_fbb_assign, k_fbb_assign_map).  Tokens per chunk: as many likelihood rows
+// of K_max doubles as fit beside the `fixed_b` bytes of the rest (two workgroups per CU).  512 threads where the slots alone
+// would leave most of 256 idle and the tokens' draws are independent (no language model): four row groups in the likelihood
+// phase, a wave per token in the draw phase -- and chunks of sixteen tokens where those fit.
+struct FbbChunks {
+    int rcap, threads;
+    size_t lds;
+};
+static FbbChunks fbb_assign_chunks(size_t fixed_b, int K_max, bool lm)
+{
+    const size_t row_b = (size_t)K_max * sizeof(double);
+    FbbChunks ch = {FBB_R, 256, 0};
+    while (ch.rcap > 1 && fixed_b + ch.rcap * row_b > 80 * 1024) ch.rcap >>= 1;
+    if (K_max <= 128 && !lm && ch.rcap == FBB_R) ch.threads = 512;
+    if (ch.threads == 512 && fixed_b + FBA_R * row_b <= 80 * 1024) ch.rcap = FBA_R;
+    ch.lds = fixed_b + ch.rcap * row_b;
+    return ch;
 }
 
 // host copies of the ranges are passed in: counts[s] = work items of local slice s_lo + s
@@ -2613,16 +2510,19 @@ int32_t segk_fbb_score_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_fb
     int64_t rows = 0;
     for (int s = 0; s < s_n; s++) rows += n_rows[s];
     if (prof) SEGK_CHECK_HIP(hipEventRecord(ctx->prof_ev[slot][0], st));
+#define SEGK_SCORE_DIAG32(RPG, TLDS)                                                                                             \
+    do {                                                                                                                        \
+        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbb_score_diag32<XT, RPG, TLDS>, lds));                                     \
+        hipLaunchKernelGGL((k_fbb_score_diag32<XT, RPG, TLDS>), dim3(m.off[s_n]), dim3(256), lds, st, *c, *f, *bt, m, b, alpha, \
+                           score, d32dbg);                                                                                      \
+    } while (0)
     DISPATCH_XT(c, {
-        if (lds > 48 * 1024) {
-            SEGK_CHECK_HIP(hipFuncSetAttribute((const void *)k_fbb_score_diag32<XT, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            SEGK_CHECK_HIP(hipFuncSetAttribute((const void *)k_fbb_score_diag32<XT, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        }
-        if (tlds && two_groups) hipLaunchKernelGGL((k_fbb_score_diag32<XT, 8, true>), dim3(m.off[s_n]), dim3(256), lds, st, *c, *f, *bt, m, b, alpha, score, d32dbg);
-        else if (tlds) hipLaunchKernelGGL((k_fbb_score_diag32<XT, 16, true>), dim3(m.off[s_n]), dim3(256), lds, st, *c, *f, *bt, m, b, alpha, score, d32dbg);
-        else if (two_groups) hipLaunchKernelGGL((k_fbb_score_diag32<XT, 8, false>), dim3(m.off[s_n]), dim3(256), lds, st, *c, *f, *bt, m, b, alpha, score, d32dbg);
-        else hipLaunchKernelGGL((k_fbb_score_diag32<XT, 16, false>), dim3(m.off[s_n]), dim3(256), lds, st, *c, *f, *bt, m, b, alpha, score, d32dbg);
+        if (tlds && two_groups) SEGK_SCORE_DIAG32(8, true);
+        else if (tlds) SEGK_SCORE_DIAG32(16, true);
+        else if (two_groups) SEGK_SCORE_DIAG32(8, false);
+        else SEGK_SCORE_DIAG32(16, false);
     });
+#undef SEGK_SCORE_DIAG32
     if (prof) {
         SEGK_CHECK_HIP(hipEventRecord(ctx->prof_ev[slot][1], st));
         ctx->prof_rows[slot] = rows;
@@ -2660,11 +2560,12 @@ int32_t segk_calibrate_vlog(segk_ctx *ctx, double *out_terms_per_s, void *stream
     return SEGK_OK;
 }
 
-int32_t segk_fbb_segment(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,
-                         int32_t s_n, int32_t b, const int32_t *n_utts, uint64_t sweep, int32_t n_slices_min,
-                         int32_t n_slices_max, double wip, double time_power_term, double anneal_temp,
-                         const double *score, uint8_t *boundaries, int32_t *new_tok, int32_t *n_new,
-                         double *out_logprob, int32_t *status, void *stream)
+// The boundary step of both DPs: the checks, the LDS of the layout the corpus takes, the instantiation
+static int32_t fbb_segment_impl(bool map_dp, segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,
+                                int32_t s_n, int32_t b, const int32_t *n_utts, uint64_t sweep, int32_t n_slices_min,
+                                int32_t n_slices_max, double wip, double time_power_term, double anneal_temp,
+                                const double *score, uint8_t *boundaries, int32_t *new_tok, int32_t *n_new,
+                                double *out_logprob, int32_t *status, void *stream)
 {
     SEGK_REQUIRE(ctx, "context");
     int rc = check_fbb(c, f, bt);
@@ -2676,23 +2577,33 @@ int32_t segk_fbb_segment(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *
     rc = check_fbb_long(c, n_slices_max);
     if (rc) return rc;
     if (m.off[s_n] == 0) return SEGK_OK;
-    if (c->N_max > 64) {
-        const size_t ldsb = fbb_band_lds(c->N_max, c->band_W);
-        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbb_segment_band, ldsb));
-        hipLaunchKernelGGL(k_fbb_segment_band, dim3(m.off[s_n]), dim3(128), ldsb, (hipStream_t)stream, *c, *bt, m, b, sweep, wip,
-                           time_power_term, anneal_temp, score, boundaries, new_tok, n_new, out_logprob, status, ctx->probe_alpha);
-        SEGK_LAUNCH_CHECK();
-        return SEGK_OK;
-    }
-    const int64_t triMax = (int64_t)c->N_max * (c->N_max + 1) / 2;
-    const size_t lds = (size_t)(triMax + 3 * c->N_max + 2) * sizeof(double) + (size_t)(c->N_max + triMax) * sizeof(int32_t) +
-                       (size_t)((c->N_max + 15) & ~15);
-    SEGK_REQUIRE(lds <= 64 * 1024, "N_max too large for the LDS score vector");
-    hipLaunchKernelGGL(k_fbb_segment, dim3(m.off[s_n]), dim3(128), lds, (hipStream_t)stream, *c, *bt, m, b, sweep,
-                       n_slices_max, wip, time_power_term, anneal_temp, score, boundaries, new_tok, n_new, out_logprob,
-                       status, ctx->probe_alpha);
+    const bool band = c->N_max > 64;
+    const size_t lds = fbb_seg_lds(c->N_max, c->band_W, band);
+    SEGK_REQUIRE(band || lds <= 64 * 1024, "N_max too large for the LDS score vector");         // (the band: check_fbb_long)
+#define SEGK_SEGMENT(BAND, MAP)                                                                                                 \
+    do {                                                                                                                        \
+        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbb_segment<BAND, MAP>, lds));                                              \
+        hipLaunchKernelGGL((k_fbb_segment<BAND, MAP>), dim3(m.off[s_n]), dim3(128), lds, (hipStream_t)stream, *c, *bt, m, b,    \
+                           n_slices_max, sweep, wip, time_power_term, anneal_temp, score, boundaries, new_tok, n_new, out_logprob, \
+                           status, ctx->probe_alpha);                                                                           \
+    } while (0)
+    if (band && map_dp) SEGK_SEGMENT(true, true);
+    else if (band) SEGK_SEGMENT(true, false);
+    else if (map_dp) SEGK_SEGMENT(false, true);
+    else SEGK_SEGMENT(false, false);
+#undef SEGK_SEGMENT
     SEGK_LAUNCH_CHECK();
     return SEGK_OK;
+}
+
+int32_t segk_fbb_segment(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,
+                         int32_t s_n, int32_t b, const int32_t *n_utts, uint64_t sweep, int32_t n_slices_min,
+                         int32_t n_slices_max, double wip, double time_power_term, double anneal_temp,
+                         const double *score, uint8_t *boundaries, int32_t *new_tok, int32_t *n_new,
+                         double *out_logprob, int32_t *status, void *stream)
+{
+    return fbb_segment_impl(false, ctx, c, f, bt, s_lo, s_n, b, n_utts, sweep, n_slices_min, n_slices_max, wip, time_power_term,
+                            anneal_temp, score, boundaries, new_tok, n_new, out_logprob, status, stream);
 }
 
 int32_t segk_fbb_segment_map(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,
@@ -2701,34 +2612,10 @@ int32_t segk_fbb_segment_map(segk_ctx *ctx, const segk_corpus *c, const segk_fbg
                              uint8_t *boundaries, int32_t *new_tok, int32_t *n_new, double *out_logprob, int32_t *status,
                              void *stream)
 {
-    (void)sweep;                  // no uniforms are consumed
-    (void)status;                 // (a total of -inf raises nothing: the serial kernel sets bit 16 only when it samples)
-    SEGK_REQUIRE(ctx, "context");
-    int rc = check_fbb(c, f, bt);
-    if (rc) return rc;
-    SEGK_REQUIRE(n_slices_min == 0 || n_slices_min == 1, "n_slices_min must be 0 or 1");
-    FbbMap m;
-    rc = make_map(&m, s_lo, s_n, n_utts, 1);
-    if (rc) return rc;
-    rc = check_fbb_long(c, n_slices_max);
-    if (rc) return rc;
-    if (m.off[s_n] == 0) return SEGK_OK;
-    if (c->N_max > 64) {
-        const size_t ldsb = fbb_band_lds(c->N_max, c->band_W);
-        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbb_segment_map_band, ldsb));
-        hipLaunchKernelGGL(k_fbb_segment_map_band, dim3(m.off[s_n]), dim3(128), ldsb, (hipStream_t)stream, *c, *bt, m, b, wip,
-                           time_power_term, score, boundaries, new_tok, n_new, out_logprob, ctx->probe_alpha);
-        SEGK_LAUNCH_CHECK();
-        return SEGK_OK;
-    }
-    const int64_t triMax = (int64_t)c->N_max * (c->N_max + 1) / 2;
-    const size_t lds = (size_t)(triMax + 3 * c->N_max + 2) * sizeof(double) + (size_t)(c->N_max + triMax) * sizeof(int32_t) +
-                       (size_t)((c->N_max + 15) & ~15);
-    SEGK_REQUIRE(lds <= 64 * 1024, "N_max too large for the LDS score vector");
-    hipLaunchKernelGGL(k_fbb_segment_map, dim3(m.off[s_n]), dim3(128), lds, (hipStream_t)stream, *c, *bt, m, b, n_slices_max, wip,
-                       time_power_term, score, boundaries, new_tok, n_new, out_logprob, ctx->probe_alpha);
-    SEGK_LAUNCH_CHECK();
-    return SEGK_OK;
+    // no uniforms are consumed: `sweep` is not passed on; nor is `status` (a total of -inf raises nothing: the serial kernel sets
+    // bit 16 only when it samples)
+    return fbb_segment_impl(true, ctx, c, f, bt, s_lo, s_n, b, n_utts, 0, n_slices_min, n_slices_max, wip, time_power_term, 1.0,
+                            score, boundaries, new_tok, n_new, out_logprob, nullptr, stream);
 }
 
 int32_t segk_fbb_token_scores(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt,
@@ -2762,24 +2649,16 @@ static int32_t fbb_assign_impl(segk_ctx *ctx, const segk_corpus *c, const segk_f
     const double alpha = f->lm_unigram ? f->lm_a : f->alpha;
     // timing-only ablation knob (development): 1 = one dimension, 2 = one token, 4 = no draw
     const int dbg = segk_dev_env("SEGK_FBB_DBG");       // -DSEGK_DEV builds only
-    // tokens per chunk: as many likelihood rows as fit beside the logits (two workgroups per CU)
-    int rcap = FBB_R;
-    const size_t fixed_b = (size_t)(f->K_max + FBA_R * c->D + FBA_R + 16) * sizeof(double);
-    while (rcap > 1 && fixed_b + (size_t)rcap * f->K_max * sizeof(double) > 80 * 1024) rcap >>= 1;
-    // 512 threads where the slots alone would leave most of 256 idle and the tokens' draws are independent (no language
-    // model): four row groups in the likelihood phase, a wave per token in the draw phase -- and chunks of sixteen tokens
-    const int nt_assign = (f->K_max <= 128 && !f->lm_unigram && rcap == FBB_R) ? 512 : 256;
-    if (nt_assign == 512 && fixed_b + (size_t)FBA_R * f->K_max * sizeof(double) <= 80 * 1024) rcap = FBA_R;
-    const size_t lds = fixed_b + (size_t)rcap * f->K_max * sizeof(double);
-    SEGK_REQUIRE(lds <= 160 * 1024, "K_max too large for the LDS logits buffer");
+    // (the fixed part: the logits z, the token rows xs, their prior predictive lpr, the sixteen doubles of red)
+    const FbbChunks ch = fbb_assign_chunks((size_t)(f->K_max + FBA_R * c->D + FBA_R + 16) * sizeof(double), f->K_max, f->lm_unigram != nullptr);
+    SEGK_REQUIRE(ch.lds <= 160 * 1024, "K_max too large for the LDS logits buffer");
     // language model + matrix-core likelihoods: one wave per utterance (SEGK_FBB_ASSIGN_WAVE=0: the block-wide form)
     if (f->lm_unigram && ll_mat && dbg == 0 && segk_env_int("SEGK_FBB_ASSIGN_WAVE", 1) != 0 && 4 * (size_t)f->K_max * sizeof(double) <= 146 * 1024) {
         const size_t ldsw = 4 * (size_t)f->K_max * sizeof(double) + sizeof(int) * (size_t)(f->K_max + 2);
         const int n_items = m.off[s_n];
 #define SEGK_LM_WAVE(PP)                                                                                                        \
     do {                                                                                                                        \
-        if (ldsw > 48 * 1024)                                                                                                   \
-            SEGK_CHECK_HIP(hipFuncSetAttribute((const void *)k_fbb_assign_lm_wave<PP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw)); \
+        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbb_assign_lm_wave<PP>, ldsw));                                             \
         hipLaunchKernelGGL((k_fbb_assign_lm_wave<PP>), dim3((n_items + 3) / 4), dim3(256), ldsw, (hipStream_t)stream, *c, *f, *bt, m, b, \
                            sweep, alpha, anneal_temp, new_tok, n_new, ll_mat, ll_ld, n_items, ctx->probe_ll, ctx->probe_ll_ld);  \
     } while (0)
@@ -2789,28 +2668,19 @@ static int32_t fbb_assign_impl(segk_ctx *ctx, const segk_corpus *c, const segk_f
         SEGK_LAUNCH_CHECK();
         return SEGK_OK;
     }
+#define SEGK_ASSIGN(COV, F32)                                                                                                   \
+    do {                                                                                                                        \
+        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbb_assign<XT, COV, F32>, ch.lds));                                         \
+        hipLaunchKernelGGL((k_fbb_assign<XT, COV, F32>), dim3(m.off[s_n]), dim3(ch.threads), ch.lds, (hipStream_t)stream, *c, *f, *bt, \
+                           m, b, sweep, alpha, anneal_temp, new_tok, n_new, ch.rcap, dbg, ll_mat, ll_ld, ctx->probe_ll,          \
+                           ctx->probe_ll_ld);                                                                                   \
+    } while (0)
     DISPATCH_XT(c, {
-        if (f->cov_type == 0) {
-            if (lds > 48 * 1024)
-                SEGK_CHECK_HIP(hipFuncSetAttribute((const void *)k_fbb_assign<XT, 0>,
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((k_fbb_assign<XT, 0>), dim3(m.off[s_n]), dim3(nt_assign), lds, (hipStream_t)stream, *c, *f, *bt, m,
-                               b, sweep, alpha, anneal_temp, new_tok, n_new, rcap, dbg, ll_mat, ll_ld, ctx->probe_ll, ctx->probe_ll_ld);
-        } else {
-            if (lds > 48 * 1024)
-                SEGK_CHECK_HIP(hipFuncSetAttribute((const void *)k_fbb_assign<XT, 1>,
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            if (f32) {
-                if (lds > 48 * 1024)
-                    SEGK_CHECK_HIP(hipFuncSetAttribute((const void *)k_fbb_assign<XT, 1, 1>,
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL((k_fbb_assign<XT, 1, 1>), dim3(m.off[s_n]), dim3(nt_assign), lds, (hipStream_t)stream, *c, *f, *bt, m,
-                                   b, sweep, alpha, anneal_temp, new_tok, n_new, rcap, dbg, ll_mat, ll_ld, ctx->probe_ll, ctx->probe_ll_ld);
-            } else
-            hipLaunchKernelGGL((k_fbb_assign<XT, 1>), dim3(m.off[s_n]), dim3(nt_assign), lds, (hipStream_t)stream, *c, *f, *bt, m,
-                               b, sweep, alpha, anneal_temp, new_tok, n_new, rcap, dbg, ll_mat, ll_ld, ctx->probe_ll, ctx->probe_ll_ld);
-        }
+        if (f->cov_type == 0) SEGK_ASSIGN(0, 0);
+        else if (f32) SEGK_ASSIGN(1, 1);
+        else SEGK_ASSIGN(1, 0);
     });
+#undef SEGK_ASSIGN
     SEGK_LAUNCH_CHECK();
     return SEGK_OK;
 }
@@ -2850,21 +2720,14 @@ int32_t segk_fbb_assign_map(segk_ctx *ctx, const segk_corpus *c, const segk_fbgm
     rc = make_map(&m, s_lo, s_n, n_utts, 1);
     if (rc) return rc;
     if (m.off[s_n] == 0) return SEGK_OK;
-    // chunks and threads as segk_fbb_assign chooses them without a language model: as many likelihood rows as fit beside the
-    // prior terms (two workgroups per CU); 512 threads and chunks of sixteen tokens where the slots alone would leave most of
-    // 256 idle
-    int rcap = FBB_R;
-    const size_t fixed_b = (size_t)(f->K_max + FBA_R * c->D + FBA_R) * sizeof(double);
-    while (rcap > 1 && fixed_b + (size_t)rcap * f->K_max * sizeof(double) > 80 * 1024) rcap >>= 1;
-    const int nt = (f->K_max <= 128 && rcap == FBB_R) ? 512 : 256;
-    if (nt == 512 && fixed_b + (size_t)FBA_R * f->K_max * sizeof(double) <= 80 * 1024) rcap = FBA_R;
-    const size_t lds = fixed_b + (size_t)rcap * f->K_max * sizeof(double);
-    SEGK_REQUIRE(lds <= 160 * 1024, "K_max too large for the LDS logits buffer");
+    // (the fixed part: the prior terms pz, the token rows xs, their prior predictive lpr -- no red)
+    const FbbChunks ch = fbb_assign_chunks((size_t)(f->K_max + FBA_R * c->D + FBA_R) * sizeof(double), f->K_max, false);
+    SEGK_REQUIRE(ch.lds <= 160 * 1024, "K_max too large for the LDS logits buffer");
 #define SEGK_ASSIGN_MAP(COV, F32)                                                                                               \
     do {                                                                                                                        \
-        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbb_assign_map<XT, COV, F32>, lds));                                        \
-        hipLaunchKernelGGL((k_fbb_assign_map<XT, COV, F32>), dim3(m.off[s_n]), dim3(nt), lds, (hipStream_t)stream, *c, *f, *bt, m, b, \
-                           f->alpha, new_tok, n_new, rcap, ctx->probe_ll, ctx->probe_ll_ld);                                    \
+        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbb_assign_map<XT, COV, F32>, ch.lds));                                     \
+        hipLaunchKernelGGL((k_fbb_assign_map<XT, COV, F32>), dim3(m.off[s_n]), dim3(ch.threads), ch.lds, (hipStream_t)stream, *c, *f, \
+                           *bt, m, b, f->alpha, new_tok, n_new, ch.rcap, ctx->probe_ll, ctx->probe_ll_ld);                       \
     } while (0)
     DISPATCH_XT(c, {
         if (f->cov_type == 0) SEGK_ASSIGN_MAP(0, 0);

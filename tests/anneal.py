@@ -71,12 +71,12 @@ EXACT = {
     "wide_diag_w20": _chain("diag", 8, 8, 10, 93, 20, 2, 2, 2.0, True, "k_fbb_segment, window 20", n_landmarks=24, **TP0),
     "wide_fixed_w30_n64": _chain("fixed", 8, 8, 10, 93, 30, 2, 2, 2.0, False, "k_fbb_segment, window 30 at 64 landmarks",
                                  n_landmarks=64, **TP0),
-    # k_fbb_segment_band (N_max > 64): the LDS path with FbBandVec addressing
-    "long_ragged_fixed": _long("ragged_fixed", 10.0, True, "k_fbb_segment_band", **TP0),
-    "long_ragged_fixed_T05": _long("ragged_fixed", 0.5, True, "k_fbb_segment_band, T < 1", **TP0),
-    "long_ragged_diag": _long("ragged_diag", 0.5, True, "k_fbb_segment_band, T < 1", **TP0),
-    "long_ragged_bigram": _long("ragged_bigram", 0.5, True, "k_fbb_segment_band, T < 1; block-wide draw", **TP0),
-    "long_diag_100_w20": _long("diag_100_w20", 2.0, True, "k_fbb_segment_band, window 20", **TP0),
+    # k_fbb_segment<BAND> (N_max > 64): the LDS path with FbBandVec addressing
+    "long_ragged_fixed": _long("ragged_fixed", 10.0, True, "k_fbb_segment<BAND>", **TP0),
+    "long_ragged_fixed_T05": _long("ragged_fixed", 0.5, True, "k_fbb_segment<BAND>, T < 1", **TP0),
+    "long_ragged_diag": _long("ragged_diag", 0.5, True, "k_fbb_segment<BAND>, T < 1", **TP0),
+    "long_ragged_bigram": _long("ragged_bigram", 0.5, True, "k_fbb_segment<BAND>, T < 1; block-wide draw", **TP0),
+    "long_diag_100_w20": _long("diag_100_w20", 2.0, True, "k_fbb_segment<BAND>, window 20", **TP0),
     # k_fbb_assign by bank size.  The large banks' log-marginals sit near +52 (D = 100) and +285 (D = 256) per span: the word
     # insertion penalty takes that off, or the segmentation with the most segments wins at every temperature
     "K300_am": _chain("fixed", 19, 6, 300, 81, 5, 5, 1, 10.0, True, "k_fbb_assign, 256 threads (K_max > 128)", **TP0),
@@ -116,7 +116,7 @@ TOLERANCE = {
                                **TP0),
     # more than 64 landmarks: the fp64 recurrence with the hardware exponential and logarithm (fb_logsumexp_wave_fast,
     # fb_exp_fast) on the LDS path, band addressing
-    "long_fixed_f32": _long("fixed_f32", 10.0, True, "k_fbb_segment_band with fast_dp", **TP0),
+    "long_fixed_f32": _long("fixed_f32", 10.0, True, "k_fbb_segment<BAND> with fast_dp", **TP0),
 }
 
 

@@ -22,6 +22,9 @@ CASES = {
     "short_fixed": dict(kind="fixed", n_utt=16, D=8, K=10, cseed=101, N_range=(3, 64), nmax=6, B=3, S=4),
     "short_diag": dict(kind="diag", n_utt=16, D=8, K=10, cseed=102, N_range=(3, 64), nmax=6, B=3, S=4),
     "short_bigram": dict(kind="bigram", n_utt=16, D=8, K=10, cseed=103, N_range=(3, 64), nmax=5, B=3, S=4),
+    # the smallest band corpus, N_max = 65: the token lists' second chunk of 64 flags holds a single landmark, and an utterance
+    # of two landmarks, shorter than the window, reads only the band's -1 padded rows
+    "diag_65": dict(kind="diag", n_utt=12, D=8, K=10, cseed=168, N_range=(2, 65), nmax=6, B=2, S=2),
     # the stated upper end
     "fixed_256": dict(kind="fixed", n_utt=6, D=8, K=10, cseed=104, N=256, nmax=6, B=2, S=2),
     # windows beyond one DPP row of sixteen lanes and beyond 32 lanes

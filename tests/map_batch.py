@@ -57,6 +57,7 @@ LONG_CASES = {
     "fixed_64_w30": _case("fixed", 8, 8, 10, 30, 2, 2, N=64),                   # the most the triangular kernel takes
     "ragged_fixed": _case("fixed", 16, 8, 10, 6, 3, 4, N_range=(3, 150)),       # band kernel, short and long utterances
     "ragged_diag": _case("diag", 16, 8, 10, 6, 3, 4, N_range=(3, 150)),
+    "diag_65": _case("diag", 12, 8, 10, 6, 2, 2, N_range=(2, 65), cseed=168),   # the smallest band corpus (tests/fbgmm_long.py)
     "diag_100_w20": _case("diag", 8, 8, 10, 20, 2, 2, N=100),                   # band, windows over 16 and over 32 lanes
     "fixed_100_w40": _case("fixed", 8, 8, 10, 40, 2, 2, N=100),
     "diag_mindur_backtrack": _case("diag", 8, 8, 10, 6, 2, 2, N_range=(60, 200), min_duration=30),      # dead ends

@@ -1,9 +1,9 @@
 """The batch-synchronous FBGMM / bigram sampler (sync="batch") at temperatures other than 1, which no other GPU test passes:
 
   * score_precision="f64": the specification's chain (oracle/np_fbgmm_batch.py::FbgmmBatch.sweep(sweep, T, am)) bit for bit,
-    per kernel form -- k_fbb_segment / k_fbb_segment_band (fb_dp_sample_on leaves its register path for the LDS path whenever
-    T != 1), k_fbb_assign's wave-per-token and block-wide draws at every chunk size --, through gibbs_sample's schedule and on
-    two ranks;
+    per kernel form -- k_fbb_segment on triangles and on the band (fb_dp_sample_on leaves its register path for the LDS path
+    whenever T != 1), k_fbb_assign's wave-per-token and block-wide draws at every chunk size --, through gibbs_sample's
+    schedule and on two ranks;
   * score_precision "f32" / "f16": every boundary draw and every slot draw of one sweep, value by value, against the fp64
     probabilities of the device's own span scores, alphas and token likelihoods (segk_fbb_set_probe) -- fb_dp_sample_fast32's
     float32 re-normalisation, k_fbb_assign_lm_wave's two forms, k_fbb_step_diag32's float32 inverse temperature on base-2

@@ -1,7 +1,7 @@
 """The batch-synchronous FBGMM / bigram sampler on corpora whose longest utterance has more than 64 landmarks (up to 256):
 bit for bit the specification oracle/np_fbgmm_batch.py with score_precision="f64" -- boundaries, slots, bigram table;
 log-probabilities to 1e-9 relative --, the 1e-4 contract in the tolerance modes, the same bits on two ranks, and the
-refusals that remain.  Such corpora run the banded boundary kernel (k_fbb_segment_band) and the chunked partial sums;
+refusals that remain.  Such corpora run the banded boundary kernel (k_fbb_segment<BAND>) and the chunked partial sums;
 corpora of at most 64 landmarks keep the triangular kernel.  The corpora and what each is there for: tests/fbgmm_long.py;
 that they do exercise it is checked with the oracle in tests/test_fbgmm_batch_long_cpu.py and again here, before the device
 runs."""
@@ -40,6 +40,8 @@ def _specification(name, sweeps=2):
         assert fl.longest(ref) <= 64
     else:
         assert fl.longest(ref) > 64
+    if name == "diag_65":
+        assert fl.longest(ref) == 65 and min(ref.utterances.lengths) < fl.CASES[name]["nmax"]
     if name == "fixed_150_w1":
         assert max(fl.tokens_per_utterance(ref)) > 64
     if name == "diag_mindur":

@@ -1,4 +1,4 @@
-"""Cost of the batch sampler's boundary kernels beyond 64 landmarks (k_fbb_segment_band against k_fbb_segment): ten f64
+"""Cost of the batch sampler's boundary kernels beyond 64 landmarks (k_fbb_segment on the band against the triangle): ten f64
 sweeps of 2 000 utterances, D = 8, K = 10, fixed-variance components, window 6, 8 x 8 blocks.  From the repository root:
 
     rocprofv3 --kernel-trace --stats -f csv -d OUT -- python tools/prof_fbb_long.py ragged|n150|n64 [standard|viterbi]
@@ -15,7 +15,7 @@ from segmentalist_amd.synth import make_corpus
 from tests.golden import cases
 
 which = sys.argv[1]
-fb_type = sys.argv[2] if len(sys.argv) > 2 else "standard"      # viterbi: k_fbb_segment_map(_band) / k_fbb_assign_map
+fb_type = sys.argv[2] if len(sys.argv) > 2 else "standard"      # viterbi: k_fbb_segment<BAND, true> / k_fbb_assign_map
 D, K, W, U = 8, 10, 6, 2000
 t0 = time.time()
 if which == "ragged":
