@@ -57,8 +57,10 @@ const char *segk_last_error(void);
  *   9 segk_fbatch.centre (the reduced-precision FBGMM kernels work in coordinates centred on it), segk_fbatch.tab32
  *  10 segk_kmeans_delta_stats
  *  11 segk_fbb_segment_map, segk_fbb_assign_map (batch sweeps with fb_type "viterbi")
- *  12 segk_fbgmm.cov_type 2 "full": the existing fields at other shapes (below); status bits 32 and 64                       */
-#define SEGK_ABI_VERSION 12
+ *  12 segk_fbgmm.cov_type 2 "full": the existing fields at other shapes (below); status bits 32 and 64
+ *  13 cov_type 2 in the unigram segmenter's serial chain: segk_fbgmm_update op 0 and segk_fbgmm_record_metrics (urn = 0)
+ *     accept it on a corpus with utterances                                                                               */
+#define SEGK_ABI_VERSION 13
 int32_t segk_abi_version(void);
 
 /* Timing of the MAIN launch of the MFMA score kernel (k_kmeans_score<..., 0>) with HIP events
@@ -440,8 +442,15 @@ int32_t segk_kmeans_sum_neg_sqrd_norm(segk_ctx *ctx, const segk_corpus *c, const
  *        (in the first four bytes of the last double) for the calls that take no status argument: bit 32 = a
  *        factorisation met a non-positive or non-finite pivot (the component kept its previous factor), bit 64 =
  *        add_item / del_component named a component beyond K (nothing was done).
- *        Accepted by segk_fbgmm_init_stats, _update (ops 1, 2, 4), _score, _pred_vector, _assign, _gibbs_items;
- *        every other entry point that takes a segk_fbgmm returns SEGK_ERR_UNSUPPORTED.
+ *        Accepted by segk_fbgmm_init_stats, _update (ops 0, 1, 2, 4), _score, _pred_vector, _assign, _gibbs_items and
+ *        _record_metrics (urn = 0) on a corpus that carries utterances (op 0 and the record are the segmenter's: on a
+ *        corpus of rows alone they refuse as in ABI 12) -- with segk_unigram_segment, which never looks at the components, the launches
+ *        per utterance of the unigram segmenter's serial chain.  segk_fbgmm_score evaluates lists of 16 rows or more
+ *        (an utterance's triangle) a lane per row against factors staged in LDS, through a [rows, K_max] buffer of
+ *        the context; shorter lists a workgroup per row.  Every other entry point that takes a segk_fbgmm returns
+ *        SEGK_ERR_UNSUPPORTED: segk_fbgmm_sequential_sweep (the persistent chain kernel holds the model in LDS, and
+ *        K_max D^2 doubles do not fit; the caller falls back to the launches per utterance), _update ops 5 and 6,
+ *        _record_metrics with urn = 1 or on a corpus without utterances, and all of segk_fbb_* (the batch sampler).
  * ------------------------------------------------------------------------------------- */
 typedef struct segk_fbgmm {
     int32_t cov_type;
@@ -478,8 +487,9 @@ typedef struct segk_fbgmm {
  *                         lm.a: the reference's loop never advances j_prev, so it is the Polya-urn probability of
  *                         the tokens under the smoothed unigram model -- a function of the counts);
  *   log_prob_X_given_z    components.log_marg(): gaussian_components_fixedvar.py:261-296 (sums of x and x^2 per
- *                         component in the dtype of X, rows ascending, as numpy's axis-0 reduction) or
- *                         gaussian_components_diag.py:271-303.
+ *                         component in the dtype of X, rows ascending, as numpy's axis-0 reduction),
+ *                         gaussian_components_diag.py:271-303, or gaussian_components.py:253-303 (cov_type 2, urn = 0
+ *                         only: log|S_N| and log|S_0| from the log-determinants of the factors already held).
  * Values agree with the reference's to ~1e-12 relative (contract for record values: 1e-8); workspace: the context's. */
 int32_t segk_fbgmm_record_metrics(segk_ctx *ctx, const segk_corpus *c, const struct segk_fbgmm *f,
                                   int32_t urn, double urn_a, double *out, void *stream);
@@ -490,7 +500,8 @@ int32_t segk_fbgmm_init_stats(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *f
 
 /* A11 for FBGMM components, reference order and arithmetic, one workgroup:
  *   op 0: del_item for every segment of the CURRENT segmentation of utterance `utt`
- *         (unigram_acoustic_wordseg.py:270-273; boundaries [dev] uint8 [n_utt, N_max])
+ *         (unigram_acoustic_wordseg.py:270-273; boundaries [dev] uint8 [n_utt, N_max]); cov_type 2: gaussian_components.py
+ *         :171-205, every delete with its refresh of the component's factor
  *   op 1: add_item(item, k)  (fixedvar:153-170 / diag:162-177)
  *   op 2: del_item(item)     (fixedvar:172-188 / diag:179-194; deletes the component when it
  *         empties: del_component fixedvar:190-221 / diag:196-213, swap-last compaction)
@@ -553,7 +564,8 @@ int32_t segk_fbgmm_assign(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *f, in
  * keeps its own copy of the bigram counts (K_max^2 int64 in global memory, owned by the context).
  * row_start [dev] int32 [n_utt + 1]: first row of every utterance (an utterance's rows are contiguous);
  * score [dev] double [n_emb] scratch.  Returns SEGK_ERR_UNSUPPORTED, with nothing enqueued, where the kernel does not apply
- * (more than 64 landmarks, 3 K_max D doubles beyond a workgroup's LDS, an utterance listed twice, SEGK_FB_CHAIN=0): the
+ * (more than 64 landmarks, 3 K_max D doubles beyond a workgroup's LDS, an utterance listed twice, SEGK_FB_CHAIN=0,
+ * full-covariance components -- cov_type 2: K_max D^2 doubles of factors do not fit a workgroup's LDS): the
  * caller then makes the calls per utterance.  SYNCHRONISES the stream after every launch.                                  */
 int32_t segk_fbgmm_sequential_sweep(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *f, const int32_t *order, int32_t n_order,
                                     const int32_t *row_start, int32_t viterbi, int32_t map_assign, int32_t n_slices_min,

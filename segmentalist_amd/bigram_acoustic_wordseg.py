@@ -53,7 +53,8 @@ class BigramAcousticWordseg(object):
         logger.info("Initializing")
         if covariance_type == "full":
             raise NotImplementedError("full-covariance components (segmentalist_amd.gaussian_components) are supported by "
-                                      "the stand-alone FBGMM only; the segmenters take covariance_type 'fixed' or 'diag'")
+                                      "the stand-alone FBGMM and the unigram segmenter's serial chain only; the bigram "
+                                      "segmenter takes covariance_type 'fixed' or 'diag'")
         assert sync in ("sequential", "batch")
         self.sync = sync
         self._batch_args = (n_gibbs_blocks, n_stat_blocks, batch_seed, process_group, score_precision)

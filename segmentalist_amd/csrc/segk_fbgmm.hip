@@ -1224,9 +1224,9 @@ int32_t segk_fbgmm_update(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *f, in
 {
     (void)ctx;
     SEGK_REQUIRE(op == 0 || op == 1 || op == 2 || op == 4 || op == 5 || op == 6, "op");
-    int rc = check_fb(c, f, "segk_fbgmm_update ops 0, 5 and 6", op == 1 || op == 2 || op == 4);
+    int rc = check_fb(c, f, "segk_fbgmm_update ops 5 and 6", op == 0 || op == 1 || op == 2 || op == 4);
     if (rc) return rc;
-    if (f->cov_type == 2) return segk_fc_update(c, f, op, item, k, stream);
+    if (f->cov_type == 2) return segk_fc_update(c, f, op, utt, item, k, boundaries, stream);
     DISPATCH_XT(c, hipLaunchKernelGGL(k_fbgmm_update<XT>, dim3(1), dim3(fb_nt(f)), 0, (hipStream_t)stream, *c, *f, op, utt,
                                        item, k, boundaries););
     SEGK_LAUNCH_CHECK();
@@ -1255,11 +1255,10 @@ int32_t segk_fbgmm_init_stats(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *f
 int32_t segk_fbgmm_score(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const int32_t *ids,
                          int64_t row0, int64_t n, double *out, void *stream)
 {
-    (void)ctx;
     int rc = check_fb(c, f, "segk_fbgmm_score", true);
     if (rc) return rc;
     if (n <= 0) return SEGK_OK;
-    if (f->cov_type == 2) return segk_fc_score(c, f, ids, row0, n, out, stream);
+    if (f->cov_type == 2) return segk_fc_score(ctx, c, f, ids, row0, n, out, stream);
     const int nt = fb_nt(f);
     size_t lds = fb_lds(c, f, nt);
     SEGK_REQUIRE(lds <= 160 * 1024, "K_max too large for the LDS logits buffer");
@@ -1335,7 +1334,9 @@ int32_t segk_fbgmm_assign(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *f, in
 
 // gibbs_sample_i (unigram_acoustic_wordseg.py:252-360) for every utterance of `order` in turn by the persistent kernel
 // k_fb_chain.  SEGK_ERR_UNSUPPORTED (nothing enqueued) where it does not apply: a language model, a model that does
-// not fit a workgroup's LDS, more than 64 landmarks, an utterance listed twice, assignments_only.  The call SYNCHRONISES the
+// not fit a workgroup's LDS, more than 64 landmarks, an utterance listed twice, assignments_only, full-covariance components
+// (cov_type 2: the kernel holds the model in LDS, and K_max D^2 doubles do not fit; the caller walks the utterances with the
+// launches per utterance, which take them).  The call SYNCHRONISES the
 // stream after every launch (it reads how far the kernel got: a launch ends early when a component empties).
 int32_t segk_fbgmm_sequential_sweep(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *f, const int32_t *order, int32_t n_order,
                                     const int32_t *row_start, int32_t viterbi, int32_t map_assign, int32_t n_slices_min,

@@ -16,7 +16,9 @@
 //
 //   k_fc_init / k_fc_prior_rows   __init__ (:95-127)
 //   k_fc_update                   add_item / del_item / del_component (:154-205)
-//   k_fc_score                    FBGMM.log_marg_i (fbgmm.py:256-285)
+//   k_fc_del_utt                  del_item over an utterance's segments (unigram_acoustic_wordseg.py:270-273)
+//   k_fc_score                    FBGMM.log_marg_i (fbgmm.py:256-285), a workgroup per row
+//   k_fc_span_terms / _span_lse   the same for a long list of rows (an utterance's triangle), a lane per row
 //   k_fc_pred_vector              log_post_pred / log_prior (:207-251)
 //   k_fc_assign                   gibbs_sample_inside_loop_i / map_assign_i (fbgmm.py:422-494)
 //   k_fc_gibbs_items              the inner loop of FBGMM.gibbs_sample (fbgmm.py:352-405)
@@ -472,6 +474,122 @@ __global__ __launch_bounds__(FC_NT) void k_fc_update(segk_corpus c, segk_fbgmm f
     if (threadIdx.x == 0) *f.K = shK;
 }
 
+// op 0: del_item for every segment of the current segmentation of utterance `utt`, in the reference's order
+// (unigram_acoustic_wordseg.py:270-273); one workgroup, every delete with its own refresh (the factor after the last
+// delete of a component is a function of its statistics alone, so deferring the refreshes would give the same bits:
+// not done, the bookkeeping across swap-last moves has not been shown to pay)
+template <typename XT>
+__global__ __launch_bounds__(FC_NT) void k_fc_del_utt(segk_corpus c, segk_fbgmm f, int utt, const uint8_t *boundaries)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char *end;
+    const FcLds S = fc_carve(smem, f.K_max, c.D, &end);
+    int &shK = S.ctl[FC_SHK];
+    int *sh_i = S.ctl + FC_SHI;
+    if (threadIdx.x == 0) shK = *f.K;
+    __syncthreads();
+    const int N = c.lengths[utt];
+    const int64_t triMax = (int64_t)c.N_max * (c.N_max + 1) / 2;
+    const int32_t *vid = c.vec_ids + (int64_t)utt * triMax;
+    const uint8_t *bnd = boundaries + (int64_t)utt * c.N_max;
+    int jp = 0;
+    for (int j = 0; j < N; j++) {
+        if (bnd[j]) {                                       // uniform: every thread reads the same byte
+            const int64_t id = vid[(j + 1) * j / 2 + jp];
+            jp = j + 1;
+            if (id >= 0 && id < c.n_emb) {
+                fc_load_row<XT>(c, id, S);
+                fc_del_item<XT>(c, f, id, &shK, sh_i, S);
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) *f.K = shK;
+}
+
+// ---------------------------------------------------------------------------------------
+// Span scores of many rows at once (the triangle of an utterance): a lane per row, a wave per (component, 64 rows).
+// k_fc_score above spends, per (row, component), D dependent steps of lane reads on one useful multiply-add per lane;
+// here the row's delta vector sits in the lane's registers, the component's factor (lower triangle, the diagonal slots
+// holding the reciprocal pivots) and mean are staged once per workgroup in LDS and read as same-address broadcasts,
+// and the substitution has no cross-lane traffic:  y_j = delta_j r_j,  s += y_j^2,  delta_d -= L_dj y_j (d > j),
+// j ascending as in fc_mahalanobis.  DB: D rounded up to a multiple of 8 (compile-time bounds keep delta in registers;
+// the padding is zeros).  The waves of a workgroup share the component and take consecutive chunks of 64 rows.
+//   terms[q * K_max + k] = log_post_pred_k(row q of the list), k < K
+// ---------------------------------------------------------------------------------------
+#define FC_SPAN_NT 256
+template <typename XT, int DB>
+__global__ __launch_bounds__(FC_SPAN_NT) void k_fc_span_terms(segk_corpus c, segk_fbgmm f, const int32_t *ids, int64_t row0, int64_t n,
+                                                             double *terms)
+{
+    constexpr int TRI = DB * (DB + 1) / 2;
+    __shared__ double Ls[TRI];                              // column j at j * DB - j (j - 1) / 2: entries d = j .. DB - 1
+    __shared__ double mu[DB];
+    const int k = blockIdx.y, D = c.D, tid = threadIdx.x, nt = blockDim.x;
+    if (k >= *f.K) return;                                  // (workgroup-uniform)
+    const double cnt = (double)f.counts[k];
+    const double k_N = f.k_0 + cnt, v = f.v_0 + cnt - (double)D + 1.;
+    const double *Lt = f.pred + (int64_t)k * D * D;
+    for (int i = tid; i < DB * DB; i += nt) {
+        const int j = i / DB, d = i - j * DB;
+        if (d < j) continue;
+        double l = (d < D) ? Lt[j * D + d] : 0.0;           // (d >= j: d < D implies j < D)
+        if (d == j) l = (j < D) ? 1. / l : 0.0;
+        Ls[j * DB - j * (j - 1) / 2 + (d - j)] = l;
+    }
+    for (int d = tid; d < DB; d += nt) mu[d] = d < D ? f.stat_a[(int64_t)k * D + d] / k_N : 0.0;
+    __syncthreads();
+    const int64_t q = (int64_t)blockIdx.x * nt + tid;
+    if (q >= n) return;
+    const int64_t e = ids ? (int64_t)ids[q] : row0 + q;
+    if (e < 0 || e >= c.n_emb) return;
+    const XT *x = (const XT *)c.X + e * c.ldx;
+    double delta[DB];
+#pragma unroll
+    for (int d = 0; d < DB; d++) delta[d] = d < D ? (double)x[d] - mu[d] : 0.0;
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < DB; j++) {
+        if (j < D) {                                        // (uniform)
+            const double *col = Ls + (j * DB - j * (j - 1) / 2);
+            const double y = delta[j] * col[0];
+            s += y * y;
+#pragma unroll
+            for (int d = j + 1; d < DB; d++) delta[d] -= col[d - j] * y;
+        }
+    }
+    terms[q * f.K_max + k] = f.kconst[k] - 0.5 * f.log_prod[k] - (v + (double)D) / 2. * log(1. + 1. / v * s);
+}
+
+// ... then per row (a wave each): the assignment prior of fbgmm.py:268-272, the row's cached_log_prior in the slots
+// k >= K, and the max-shift log-sum-exp (_cython_utils.logsumexp) into out[row].  The logits overwrite the row of `terms`.
+__global__ __launch_bounds__(256) void k_fc_span_lse(segk_corpus c, segk_fbgmm f, const int32_t *ids, int64_t row0, int64_t n,
+                                                     double *terms, double *out)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t q = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (q >= n) return;
+    const int64_t e = ids ? (int64_t)ids[q] : row0 + q;
+    if (e < 0 || e >= c.n_emb) return;
+    const int KM = f.K_max, K = *f.K;
+    double tot = 0.0;
+    for (int k = lane; k < KM; k += 64) tot += (double)f.counts[k];
+    tot = fb_wave_sum(tot);                                 // exact: integer-valued
+    const double lt = log(tot + f.alpha), lprior = fc_prior_rows(c, f)[e];
+    double *z = terms + q * KM;
+    double mx = NEG_INF_D;
+    for (int k = lane; k < KM; k += 64) {
+        const double zk = f.lms * (log(f.alpha / (double)KM + (double)f.counts[k]) - lt) + (k < K ? z[k] : lprior);
+        z[k] = zk;                                          // (read back by the same lane below)
+        mx = zk > mx ? zk : mx;
+    }
+    mx = fb_wave_max(mx, false);
+    double s = 0.0;
+    for (int k = lane; k < KM; k += 64) s += exp(z[k] - mx);
+    s = fb_wave_sum(s);
+    if (lane == 0) out[e] = log(s) + mx;
+}
+
 // A4: out[row] = log_marg_i(row) (fbgmm.py:256-285); one workgroup per row
 template <typename XT>
 __global__ __launch_bounds__(FC_NT) void k_fc_score(segk_corpus c, segk_fbgmm f, const int32_t *ids, int64_t row0, double *out)
@@ -656,8 +774,19 @@ int segk_fc_init_stats(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *f, void 
     return SEGK_OK;
 }
 
-int segk_fc_update(const segk_corpus *c, segk_fbgmm *f, int op, int64_t item, int k, void *stream)
+int segk_fc_update(const segk_corpus *c, segk_fbgmm *f, int op, int utt, int64_t item, int k, const uint8_t *boundaries, void *stream)
 {
+    if (op == 0) {
+        SEGK_REQUIRE(c->vec_ids && c->lengths && boundaries, "cov_type 2, op 0 needs the corpus's utterances and the boundaries");
+        SEGK_REQUIRE(utt >= 0 && utt < c->n_utt, "utterance out of range");
+        const size_t lds0 = fc_lds_bytes(f->K_max, c->D);
+        FC_DISPATCH_XT(c, {
+            SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fc_del_utt<XT>, lds0));
+            hipLaunchKernelGGL(k_fc_del_utt<XT>, dim3(1), dim3(FC_NT), lds0, (hipStream_t)stream, *c, *f, utt, boundaries);
+        });
+        SEGK_LAUNCH_CHECK();
+        return SEGK_OK;
+    }
     SEGK_REQUIRE(op == 4 || (item >= 0 && item < c->n_emb), "item out of range");
     SEGK_REQUIRE(op == 2 || (k >= 0 && k < f->K_max), "component out of range");
     const size_t lds = fc_lds_bytes(f->K_max, c->D);
@@ -669,9 +798,53 @@ int segk_fc_update(const segk_corpus *c, segk_fbgmm *f, int op, int64_t item, in
     return SEGK_OK;
 }
 
-int segk_fc_score(const segk_corpus *c, const segk_fbgmm *f, const int32_t *ids, int64_t row0, int64_t n, double *out, void *stream)
+// Lists of at least FC_SPAN_MIN rows go through k_fc_span_terms + k_fc_span_lse, shorter ones (log_marg_i, a few ids)
+// stay on k_fc_score: two launches and a workgroup per component do not pay for a handful of rows (profiles/README.md
+// "Full-covariance segmenter").  SEGK_FC_SPAN_MIN overrides the threshold (a launch-plan switch for measurements: the
+// two paths sum |L^-1 delta|^2 and the logits in different orders and agree to the last bits only).
+#define FC_SPAN_MIN 16
+
+template <typename XT>
+static int fc_span_launch(const segk_corpus *c, const segk_fbgmm *f, const int32_t *ids, int64_t row0, int64_t n, double *terms,
+                          hipStream_t st)
+{
+    const int chunks = (int)((n + 63) / 64);
+    const int nt = 64 * (chunks < FC_SPAN_NT / 64 ? chunks : FC_SPAN_NT / 64);
+    const dim3 grid((unsigned)((n + nt - 1) / nt), (unsigned)f->K_max);
+#define FC_SPAN_CASE(DB)                                                                                              \
+    case DB:                                                                                                          \
+        hipLaunchKernelGGL((k_fc_span_terms<XT, DB>), grid, dim3(nt), 0, st, *c, *f, ids, row0, n, terms);             \
+        break;
+    switch ((c->D + 7) & ~7) {
+        FC_SPAN_CASE(8) FC_SPAN_CASE(16) FC_SPAN_CASE(24) FC_SPAN_CASE(32) FC_SPAN_CASE(40) FC_SPAN_CASE(48) FC_SPAN_CASE(56)
+        FC_SPAN_CASE(64)
+    default:
+        segk_set_error("cov_type 2: no span-score kernel for D = %d", c->D);
+        return SEGK_ERR_UNSUPPORTED;
+    }
+#undef FC_SPAN_CASE
+    SEGK_LAUNCH_CHECK();
+    return SEGK_OK;
+}
+
+int segk_fc_score(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const int32_t *ids, int64_t row0, int64_t n, double *out,
+                  void *stream)
 {
     SEGK_REQUIRE(ids != NULL || (row0 >= 0 && row0 + n <= c->n_emb), "rows out of range");
+    if (n >= segk_env_int("SEGK_FC_SPAN_MIN", FC_SPAN_MIN) && f->K_max <= 65535) {
+        SEGK_REQUIRE(ctx, "ctx");
+        hipStream_t st = (hipStream_t)stream;
+        // (sized for the longest utterance's triangle at once: the buffer is not replaced from one utterance to the next)
+        const int64_t tri = (int64_t)c->N_max * (c->N_max + 1) / 2;
+        const int64_t need = (n > tri ? n : tri) * f->K_max;
+        if (int rc = segk_ws_grow(ctx, &ctx->fc_terms, &ctx->fc_terms_n, need, (size_t)need * sizeof(double), st)) return rc;
+        int rc;
+        FC_DISPATCH_XT(c, rc = fc_span_launch<XT>(c, f, ids, row0, n, ctx->fc_terms, st););
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_fc_span_lse, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, *c, *f, ids, row0, n, ctx->fc_terms, out);
+        SEGK_LAUNCH_CHECK();
+        return SEGK_OK;
+    }
     const size_t lds = fc_lds_bytes(f->K_max, c->D);
     FC_DISPATCH_XT(c, {
         SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fc_score<XT>, lds));

@@ -66,6 +66,8 @@ struct segk_ctx {
     int rb_K;
     int32_t *rb_misc;            // blk_lo [68], dummy K, flags; then doubles (part_tot, scalars, terms)
     double *rb_term;             // [rb_K] per-component terms of the record metrics
+    double *fc_terms;            // full-covariance span scores (segk_fullcov.hip k_fc_span_terms): [rows][K_max] Student-t logits
+    int64_t fc_terms_n;          // ... doubles allocated
     // hinted score path (segk_score_hint.hip): the filter's partial top-2 per (range, row), then the hint waves' result per row
     void *hint_part;
     size_t hint_part_bytes;
@@ -159,8 +161,9 @@ int segk_rows_by_label(segk_ctx *ctx, const int32_t *labels, int64_t n, int K_ma
 
 #define SEGK_LAUNCH_CHECK() SEGK_CHECK_HIP(hipGetLastError())
 
-// Full-covariance components (segk_fbgmm.cov_type 2, segk_fullcov.hip) exist behind the stand-alone FBGMM entry points only
-// (init_stats, update ops 1 / 2 / 4, score, pred_vector, assign, gibbs_items); every other one refuses them by name.
+// Full-covariance components (segk_fbgmm.cov_type 2, segk_fullcov.hip) exist behind the entry points of the stand-alone FBGMM
+// and of the unigram segmenter's launches per utterance (init_stats, update ops 0 / 1 / 2 / 4, score, pred_vector, assign,
+// gibbs_items, record_metrics with urn = 0); every other one refuses them by name.
 #define SEGK_REFUSE_FULLCOV(f, who)                                                                                 \
     do {                                                                                                            \
         if ((f) && (f)->cov_type == 2) {                                                                            \
@@ -171,8 +174,9 @@ int segk_rows_by_label(segk_ctx *ctx, const int32_t *labels, int64_t n, int K_ma
 // segk_fullcov.hip: the cov_type 2 forms of the segk_fbgmm_* entry points (arguments already checked by the caller)
 int segk_fc_check(const segk_corpus *c, const segk_fbgmm *f, const char *who);
 int segk_fc_init_stats(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *f, void *stream);
-int segk_fc_update(const segk_corpus *c, segk_fbgmm *f, int op, int64_t item, int k, void *stream);
-int segk_fc_score(const segk_corpus *c, const segk_fbgmm *f, const int32_t *ids, int64_t row0, int64_t n, double *out, void *stream);
+int segk_fc_update(const segk_corpus *c, segk_fbgmm *f, int op, int utt, int64_t item, int k, const uint8_t *boundaries, void *stream);
+int segk_fc_score(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const int32_t *ids, int64_t row0, int64_t n, double *out,
+                  void *stream);
 int segk_fc_pred_vector(const segk_corpus *c, const segk_fbgmm *f, int64_t row, double *out, void *stream);
 int segk_fc_assign(const segk_corpus *c, segk_fbgmm *f, int utt, int map_assign, double anneal_temp, const int32_t *new_tok,
                    const int32_t *n_new, const double *ustream, int64_t *ucursor, int64_t ucap, int32_t *status, void *stream);

@@ -3,6 +3,7 @@
 //   BigramAcousticWordseg.log_prob_z           bigram_acoustic_wordseg.py:287-305
 //   GaussianComponentsFixedVar.log_marg        gaussian_components_fixedvar.py:261-296
 //   GaussianComponentsDiag.log_marg            gaussian_components_diag.py:271-303
+//   GaussianComponents.log_marg                gaussian_components.py:253-303 (cov_type 2, urn = 0)
 // Before, these were numpy on host snapshots (4 MB of assignments, a stable sort of a million labels, for the
 // bigram driver a Python loop over 80 000 tokens): three orders of magnitude more than the sweep they record.
 //
@@ -87,6 +88,25 @@ __global__ __launch_bounds__(256) void k_metric_log_marg(segk_corpus c, segk_fbg
         }
         for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
         if (lane == 0) term[k] = s;
+    } else if (f.cov_type == 2) {
+        // gaussian_components.py:253-276.  Neither determinant is factored again: log_prod[k] is logdet of
+        // covar = (k_N + 1) / (k_N (v_N - D + 1)) S_N, so log|S_N| = log_prod[k] + D log(k_N (v_N - D + 1) / (k_N + 1)), and
+        // log|S_0| comes the same way from the prior's factor in prior_c (its diagonal at [d * D + d]); D <= 64: a lane per
+        // dimension; lgamma where the reference reads its table
+        const double k_N = f.k_0 + N, v_N = f.v_0 + N;
+        double ld0 = 0.0, lg = 0.0;
+        if (lane < D) {
+            ld0 = 2. * log(f.prior_c[(int64_t)lane * D + lane]);
+            lg = lgamma((v_N - (double)lane) / 2.) - lgamma((f.v_0 - (double)lane) / 2.);      // (v + 1 - j) / 2, j = lane + 1
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            ld0 += __shfl_xor(ld0, o);
+            lg += __shfl_xor(lg, o);
+        }
+        const double lS0 = ld0 + D * log(f.k_0 * (f.v_0 - (double)D + 1.) / (f.k_0 + 1.));
+        const double lSN = f.log_prod[k] + D * log(k_N * (v_N - (double)D + 1.) / (k_N + 1.));
+        if (lane == 0)
+            term[k] = -N * D / 2. * 1.1447298858494002 + D / 2. * log(f.k_0) - D / 2. * log(k_N) + f.v_0 / 2. * lS0 - v_N / 2. * lSN + lg;
     } else {
         // gaussian_components_diag.py:271-290
         const double k_N = f.k_0 + N, v_N = f.v_0 + N;
@@ -198,8 +218,12 @@ int32_t segk_fbgmm_record_metrics(segk_ctx *ctx, const segk_corpus *c, const seg
                                   double *out, void *stream)
 {
     SEGK_REQUIRE(ctx && c && f && out, "arguments");
-    SEGK_REFUSE_FULLCOV(f, "segk_fbgmm_record_metrics");
-    SEGK_REQUIRE(f->cov_type == 0 || f->cov_type == 1, "cov_type");
+    // cov_type 2: the record of a segmenter's sweep only (urn = 0, a corpus with utterances); the stand-alone FBGMM keeps its
+    // host expressions, and without utterances the call refuses as it did before the segmenter took cov_type 2
+    if (urn || c->n_utt <= 0 || !c->vec_ids) SEGK_REFUSE_FULLCOV(f, "segk_fbgmm_record_metrics with urn = 1 or a corpus without utterances");
+    SEGK_REQUIRE(f->cov_type == 0 || f->cov_type == 1 || f->cov_type == 2, "cov_type");
+    if (f->cov_type == 2)
+        if (int rc = segk_fc_check(c, f, "segk_fbgmm_record_metrics")) return rc;
     SEGK_REQUIRE(f->K_max <= 8192, "K_max <= 8192");
     hipStream_t st = (hipStream_t)stream;
     const int32_t *blk_lo = nullptr, *sorted = nullptr, *koff = nullptr;

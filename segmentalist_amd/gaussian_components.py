@@ -4,8 +4,9 @@ components, statistics resident in HBM (`segk_fbgmm`, cov_type 2).
 
 Where the reference keeps `inv_covars`, the device keeps the lower Cholesky factor of each
 component's Student-t covariance matrix (include/segk.h); `inv_covars` is formed from a snapshot of
-the factors on request.  Supported by the stand-alone `FBGMM` only: D <= 64, no language model; the
-segmenters and the batch sampler refuse covariance_type="full".
+the factors on request.  Supported by the stand-alone `FBGMM` and by `UnigramAcousticWordseg` with
+sync="sequential": D <= 64, no language model; the batch sampler and the bigram classes refuse
+covariance_type="full".
 """
 import math
 

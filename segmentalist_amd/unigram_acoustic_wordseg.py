@@ -44,12 +44,21 @@ class UnigramAcousticWordseg(object):
         scores on the matrix cores (fp32 MFMA, or two-way fp16 splits of the fp32 operands on the
         16-bit pipe) -- within the 1e-4 tolerance of the path, 5x / 10x faster; with diagonal
         components "f32" evaluates the Student-t terms in float32 with the hardware logarithm (same
-        tolerance); "f64" reproduces the specification to the last draw."""
+        tolerance); "f64" reproduces the specification to the last draw.
+        covariance_type="full" (D <= 64) runs with sync="sequential" and beta_sent_boundary=-1 only: the launches per utterance, the span
+        scores of an utterance's triangle a lane per row (segk_fullcov.hip); the batch sampler has no
+        full-covariance form."""
         logger.info("Initializing")
-        if covariance_type == "full":
-            raise NotImplementedError("full-covariance components (segmentalist_amd.gaussian_components) are supported by "
-                                      "the stand-alone FBGMM only; the segmenters take covariance_type 'fixed' or 'diag'")
         assert sync in ("sequential", "batch")
+        if covariance_type == "full" and sync == "batch":
+            raise NotImplementedError("the batch sampler (sync='batch') has no full-covariance form: its partial sums would be "
+                                      "K_max * D^2 per (block, slice); use sync='sequential' with covariance_type='full'")
+        if covariance_type == "full" and beta_sent_boundary != -1:
+            # (calc_p_continue asserts for any other value, here and in the reference: no sweep could run.  The other
+            # covariance types keep the reference's behaviour -- construct, then fail at the first sweep --; for the
+            # type this package added later the unusable configuration is refused where it is made.)
+            raise NotImplementedError("full-covariance components in the unigram segmenter need beta_sent_boundary=-1: "
+                                      "calc_p_continue supports no other value (unigram_acoustic_wordseg.py:513-531)")
         self.sync = sync
         self._batch_args = (n_gibbs_blocks, n_stat_blocks, batch_seed, process_group, score_precision)
         self._sweeper = None
