@@ -59,8 +59,11 @@ const char *segk_last_error(void);
  *  11 segk_fbb_segment_map, segk_fbb_assign_map (batch sweeps with fb_type "viterbi")
  *  12 segk_fbgmm.cov_type 2 "full": the existing fields at other shapes (below); status bits 32 and 64
  *  13 cov_type 2 in the unigram segmenter's serial chain: segk_fbgmm_update op 0 and segk_fbgmm_record_metrics (urn = 0)
- *     accept it on a corpus with utterances                                                                               */
-#define SEGK_ABI_VERSION 13
+ *     accept it on a corpus with utterances
+ *  14 cov_type 2 in the batch sampler (unigram, fp64 scores, D <= 64, K_max <= 1024, one process): segk_fbatch.partials /
+ *     mean_t / q_t at other shapes (below), no structure grows; segk_fbb_prior_rows, _partials, _prepare, _score, _segment,
+ *     _segment_map, _assign, _assign_map, _canonical accept it, every other segk_fbb_* entry point keeps refusing it      */
+#define SEGK_ABI_VERSION 14
 int32_t segk_abi_version(void);
 
 /* Timing of the MAIN launch of the MFMA score kernel (k_kmeans_score<..., 0>) with HIP events
@@ -593,6 +596,13 @@ int32_t segk_fbgmm_gibbs_items(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *
  * Gibbs step b resamples block b of every slice in parallel conditioned on all other blocks.
  * Component labels are "slots" 0..K_max-1 that are not renumbered during a sweep (count 0 = empty
  * component = prior predictive); segk_fbb_canonical gives the reference's contiguous labelling.
+ * Full-covariance components (cov_type 2; specification tests/fullcov_batch.py): the calls of a unigram step with fp64
+ * scores -- segk_fbb_prior_rows, _partials (needs ctx), _prepare, _score, _segment / _segment_map, _assign (ll_mat NULL) /
+ * _assign_map (f32_terms 0), _canonical, with segk_fbb_collect -- take them, D <= 64, K_max <= 1024, no language model,
+ * with segk_fbatch's fields at the shapes given below; _score_f32, _score_diag32, _assign_diag32, _step_diag32,
+ * _token_scores, _lm_apply and _lm_fill return SEGK_ERR_UNSUPPORTED with a message that names cov_type 2, and so does any
+ * call with a language model attached or D > 64.  The serial view (stat_a / stat_b / pred / log_prod / kconst / K) is not
+ * written: segk_fbgmm_init_stats rebuilds it from the assignments segk_fbb_canonical leaves.
  * ------------------------------------------------------------------------------------- */
 typedef struct {
     int32_t n_slices, n_blocks;   /* S (<= 16), B (>= 2)                                          */
@@ -637,6 +647,17 @@ typedef struct {
     /* optional: [dev] [2, D, K_max] floats, written by segk_fbb_prepare when non-NULL: float(mean - centre) and float(q) of
      * every slot, the tables the diagonal float32 kernels stage (each of their workgroups converted the fp64 ones itself)  */
     float *tab32;
+    /* Full-covariance components (segk_fbgmm.cov_type 2): the existing fields at other shapes, as in segk_fbgmm.
+     *   partials  the record of a (block, slice) cell is K_max (1 + D + D (D + 1) / 2) doubles: counts [K_max], sum x
+     *             [K_max, D], the lower triangle of sum outer(x, x) per slot, packed [K_max, D (D + 1) / 2] -- entry (a, b),
+     *             a >= b, at b D - b (b - 1) / 2 + (a - b); the products are rounded in the dtype of X
+     *             (gaussian_components.py:116-118)
+     *   mean_t    [K_max, D]     the mean m_N of every slot, slot-major
+     *   q_t       [K_max, D, D]  the lower Cholesky factor of covar as segk_fbgmm.pred stores it: q_t[k][j D + d] = L[d][j]
+     *   lconst    the Student-t constant of v = v_N - D + 1 degrees of freedom - logdet / 2;  half = (v + D) / 2;
+     *             zconst, cnt, scal as for the other types
+     * prior_rows is required; y / tiles32 / the fp16x2 buffers / centre / tab32 / lm_tok are not used.  segk_fbb_prepare sets
+     * status bit 32 in the last word of segk_fbgmm.prior_c at a pivot that is not a positive finite number.             */
 } segk_fbatch;
 
 /* token lists of all utterances from the boundaries: new_tok [n_utt, N_max], n_new [n_utt]     */

@@ -1,0 +1,91 @@
+// segk_fbb_dev.h -- what the batch sampler's translation units share (segk_fbbatch.hip; segk_fullcov.hip for the
+// full-covariance forms of its kernels): the record of a (block, slice) cell, the workgroup -> (slice, index) map of a
+// launch, the specification's balanced tree.  Not part of the ABI.
+#pragma once
+#include "segk_internal.h"
+
+// doubles of the partial sums of one (block, slice) cell: counts [K_max], sum x [K_max, D], then sum x^2 [K_max, D] or, with
+// full-covariance components (cov_type 2), the lower triangle of sum outer(x, x) per slot, packed [K_max, D (D + 1) / 2] --
+// entry (a, b), a >= b, at fbb_tri_index(D, a, b): the products are symmetric bit for bit
+static __host__ __device__ __forceinline__ int fbb_tri(int D) { return D * (D + 1) / 2; }
+static __host__ __device__ __forceinline__ int fbb_tri_index(int D, int a, int b) { return b * D - b * (b - 1) / 2 + (a - b); }
+static __host__ __device__ __forceinline__ int64_t fbb_rec(const segk_fbgmm &f, int D)
+{
+    return f.cov_type == 2 ? (int64_t)f.K_max * (1 + D + fbb_tri(D)) : (int64_t)f.K_max * (2 * D + 1);
+}
+
+// which (slice, local index) a workgroup works on: `off` is the prefix of the per-slice counts
+struct FbbMap {
+    int n;
+    int lo[16];
+    int off[17];
+};
+
+static __device__ __forceinline__ bool fbb_locate(const FbbMap &m, int wg, int *slice, int *idx)
+{
+    for (int s = 0; s < m.n; s++)
+        if (wg < m.off[s + 1]) {
+            *slice = s;
+            *idx = wg - m.off[s];
+            return true;
+        }
+    return false;
+}
+
+// the pairing of oracle tree_sum: [(0+1), (2+3), ...], odd element carried
+static __device__ __forceinline__ double fbb_tree(double *p, int n, int stride)
+{
+    while (n > 1) {
+        const int h = n >> 1;
+        for (int j = 0; j < h; j++) p[j * stride] = p[2 * j * stride] + p[(2 * j + 1) * stride];
+        if (n & 1) p[h * stride] = p[(n - 1) * stride];
+        n = (n + 1) >> 1;
+    }
+    return p[0];
+}
+
+// my[s * stride] = sum over the blocks bp != b of partials[(bp * S + s) * rec + off], in block order, for every slice s: the
+// loads of eight slices x eight blocks are in flight together (k_fbb_prepare's own form of this is its `sum_slices`)
+static __device__ __forceinline__ void fbb_sum_slices(const segk_fbatch &bt, int64_t rec, int64_t off, int b, double *my, int stride)
+{
+    const int S = bt.n_slices, B = bt.n_blocks;
+    for (int s0 = 0; s0 < S; s0 += 8) {
+        double a[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) a[i] = 0.0;
+        for (int bp0 = 0; bp0 < B; bp0 += 8) {
+            double v[8][8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const int sidx = s0 + i < S ? s0 + i : S - 1;
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    const int bp = bp0 + j < B ? bp0 + j : B - 1;
+                    v[i][j] = bt.partials[((int64_t)bp * S + sidx) * rec + off];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 8; i++)
+#pragma unroll
+                for (int j = 0; j < 8; j++)
+                    if (bp0 + j < B && bp0 + j != b) a[i] += v[i][j];
+        }
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            if (s0 + i < S) my[(s0 + i) * stride] = a[i];
+    }
+}
+
+// segk_fullcov.hip: the cov_type 2 forms of the segk_fbb_* entry points a unigram step uses (arguments checked by the callers
+// in segk_fbbatch.hip, which also bucket the block's tokens by slot -- k_fbb_sort -- for the partial sums)
+int segk_fcb_check(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, const char *who);
+int segk_fcb_partials(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int s_lo, int s_n, int b,
+                      const int32_t *sorted, int64_t sorted_stride, const int32_t *koff, void *stream);
+int segk_fcb_prepare(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int b, void *stream);
+int segk_fcb_score(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int s_lo, int s_n, int b, const int32_t *n_rows,
+                   double *score, void *stream);
+// token likelihoods of the block's new segments into a table the context owns: row (local slice * *u_cap + utterance of the
+// cell) * N_max + token, [K_max] each, the row's prior predictive in the empty slots (k_fbb_assign / _assign_map read it)
+int segk_fcb_token_ll(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int s_lo, int s_n, int b,
+                      const int32_t *n_utts, const int32_t *new_tok, const int32_t *n_new, const double **ll, int *u_cap,
+                      void *stream);

@@ -24,12 +24,11 @@
 
 #include <type_traits>
 #include "segk_fb_common.h"
+#include "segk_fbb_dev.h"
 
 #define FBB_R 8            // rows per workgroup of the score kernel
 #define FBA_R 16           // token rows of the assignment kernel's LDS image (chunks of 16 tokens with four row groups, else <= FBB_R)
 #define FBB_MAXCH 4        // dimension chunks of 64 lanes held in registers (D <= 256)
-
-static __device__ __forceinline__ int64_t fbb_rec(const segk_fbgmm &f, int D) { return (int64_t)f.K_max * (2 * D + 1); }
 
 template <typename XT>
 static __device__ __forceinline__ double fbb_sq(XT x)      // np.square(X) in the dtype of X (diag:125)
@@ -38,30 +37,12 @@ static __device__ __forceinline__ double fbb_sq(XT x)      // np.square(X) in th
     return (double)q;
 }
 
-// which (slice, local index) a workgroup works on: `off` is the prefix of the per-slice counts
-struct FbbMap {
-    int n;
-    int lo[16];
-    int off[17];
-};
-
 // Column maps of the packed fp16x2 image (written by k_fbb_rows16), behind the constants: [K_max] column of slot k (-1: empty), [K_max] the
 // pseudo-component's (= the number of occupied slots), [K_max + 1] tiles in use, then [K_max + 1] the slot of column c.  The
 // token-likelihood matrix has the image's columns.
 static __host__ __device__ __forceinline__ int32_t *fbb_cmap(const segk_fbatch *bt, int KM)
 {
     return reinterpret_cast<int32_t *>(bt->consts16 + KM + 2);
-}
-
-static __device__ __forceinline__ bool fbb_locate(const FbbMap &m, int wg, int *slice, int *idx)
-{
-    for (int s = 0; s < m.n; s++)
-        if (wg < m.off[s + 1]) {
-            *slice = s;
-            *idx = wg - m.off[s];
-            return true;
-        }
-    return false;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -333,18 +314,6 @@ __global__ void k_fbb_partials_sorted(segk_corpus c, segk_fbgmm f, segk_fbatch b
             rec[f.K_max + (int64_t)f.K_max * D + (int64_t)k * D + d] = axx[q];
         }
     }
-}
-
-// the pairing of oracle tree_sum: [(0+1), (2+3), ...], odd element carried
-static __device__ __forceinline__ double fbb_tree(double *p, int n, int stride)
-{
-    while (n > 1) {
-        const int h = n >> 1;
-        for (int j = 0; j < h; j++) p[j * stride] = p[2 * j * stride] + p[(2 * j + 1) * stride];
-        if (n & 1) p[h * stride] = p[(n - 1) * stride];
-        n = (n + 1) >> 1;
-    }
-    return p[0];
 }
 
 // dimension d of the vector the float32 kernels subtract from both x and the slot means before rounding them
@@ -1341,7 +1310,8 @@ __global__ __launch_bounds__(128) void k_fbb_segment(segk_corpus c, segk_fbatch 
 template <typename XT, int COV, int F32 = 0>
 __global__ __launch_bounds__(512) void k_fbb_assign(segk_corpus c, segk_fbgmm f, segk_fbatch bt, FbbMap map, int b, uint64_t sweep,
                              double prior_alpha, double anneal_temp, const int32_t *new_tok, const int32_t *n_new,
-                             int rcap, int dbg, const float *llmat, int64_t ll_ld, double *probe_ll, int64_t probe_ld)
+                             int rcap, int dbg, const float *llmat, int64_t ll_ld, double *probe_ll, int64_t probe_ld,
+                             const double *fc_ll, int fc_ucap)
 {
     // The likelihood part of the logits does not depend on the previous segment's slot, so it is
     // evaluated for up to `rcap` (<= FBB_R) tokens of the utterance at once -- the component
@@ -1383,6 +1353,11 @@ __global__ __launch_bounds__(512) void k_fbb_assign(segk_corpus c, segk_fbgmm f,
                                                                          : (double)mrow[pc] * LN2 - zc_empty - log(n_empty) + norm;
                 }
             }
+        } else if constexpr (COV == 2) {
+            // full covariance: the block's token likelihoods were formed by k_fcb_token_ll (the row's prior predictive in the
+            // empty slots)
+            const double *tab = fc_ll + (((int64_t)s * fc_ucap + idx) * c.N_max + t0) * KM;
+            for (int j = tid; j < nr * KM; j += nt) ll[j] = tab[j];
         } else {
         for (int j = tid; j < (rcap > FBB_R ? rcap : FBB_R) * D; j += nt) {
             const int r = j / D, d = j - r * D;
@@ -1591,7 +1566,8 @@ static __device__ __forceinline__ int fbb_wave_min_i32(int v)       // minimum o
 
 template <typename XT, int COV, int F32 = 0>
 __global__ __launch_bounds__(512) void k_fbb_assign_map(segk_corpus c, segk_fbgmm f, segk_fbatch bt, FbbMap map, int b, double prior_alpha,
-                                 const int32_t *new_tok, const int32_t *n_new, int rcap, double *probe_ll, int64_t probe_ld)
+                                 const int32_t *new_tok, const int32_t *n_new, int rcap, double *probe_ll, int64_t probe_ld,
+                                 const double *fc_ll, int fc_ucap)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int D = c.D, KM = f.K_max, tid = threadIdx.x, nt = blockDim.x;
@@ -1610,6 +1586,11 @@ __global__ __launch_bounds__(512) void k_fbb_assign_map(segk_corpus c, segk_fbgm
     for (int t0 = 0; t0 < nn; t0 += rcap) {
         const int nr = nn - t0 < rcap ? nn - t0 : rcap;
         __syncthreads();
+        if constexpr (COV == 2) {
+            // full covariance: the block's token likelihoods were formed by k_fcb_token_ll (k_fbb_assign)
+            const double *tab = fc_ll + (((int64_t)s * fc_ucap + idx) * c.N_max + t0) * KM;
+            for (int j = tid; j < nr * KM; j += nt) ll[j] = tab[j];
+        } else {
         for (int j = tid; j < (rcap > FBB_R ? rcap : FBB_R) * D; j += nt) {
             const int r = j / D, d = j - r * D;
             xs[j] = r < nr ? (double)X[(int64_t)new_tok[(int64_t)utt * c.N_max + t0 + r] * c.ldx + d] : 0.0;
@@ -1680,6 +1661,7 @@ __global__ __launch_bounds__(512) void k_fbb_assign_map(segk_corpus c, segk_fbgm
                 for (int r = 0; r < FBB_R; r++)
                     if (r < nr) ll[(int64_t)r * KM + k] = lpr[r];
             }
+        }
         }
         __syncthreads();
         if (probe_ll)           // segk_fbb_set_probe: the likelihood part of the logits, as the argmax below uses it
@@ -2253,11 +2235,14 @@ __global__ void k_fbb_rows16(segk_fbgmm f, segk_fbatch bt, int D, double prior_a
         }                                           \
     } while (0)
 
-static int check_fbb(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt)
+// fc_who: the entry point's name where it has a full-covariance form (cov_type 2: the unigram step's calls); NULL refuses it
+static int check_fbb(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, const char *fc_who = nullptr)
 {
     SEGK_REQUIRE(c && f && bt, "NULL corpus / fbgmm / batch state");
-    SEGK_REFUSE_FULLCOV(f, "segk_fbb_*");
-    SEGK_REQUIRE(f->cov_type == 0 || f->cov_type == 1, "cov_type must be 0 (fixed) or 1 (diag)");
+    if (!fc_who) SEGK_REFUSE_FULLCOV(f, "segk_fbb_*");
+    SEGK_REQUIRE(f->cov_type >= 0 && f->cov_type <= 2, "cov_type must be 0 (fixed), 1 (diag) or 2 (full)");
+    if (f->cov_type == 2)
+        if (int rc = segk_fcb_check(c, f, bt, fc_who)) return rc;
     SEGK_REQUIRE(c->D > 0 && c->D <= 64 * FBB_MAXCH, "batch mode supports D <= 256");
     SEGK_REQUIRE(c->N_max > 0, "corpus without landmarks");       // (more than 64 per utterance: check_fbb_long)
     SEGK_REQUIRE(bt->n_slices >= 1 && bt->n_slices <= 16, "n_slices must be in 1..16");
@@ -2349,14 +2334,17 @@ int32_t segk_fbb_partials(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm 
                           int32_t s_lo, int32_t s_n, int32_t b, const int32_t *new_tok, const int32_t *n_new,
                           void *stream)
 {
-    int rc = check_fbb(c, f, bt);
+    int rc = check_fbb(c, f, bt, "segk_fbb_partials");
     if (rc) return rc;
     SEGK_REQUIRE(s_lo >= 0 && s_n >= 1 && s_lo + s_n <= bt->n_slices && b >= 0 && b < bt->n_blocks, "slice / block range");
+    SEGK_REQUIRE(f->cov_type != 2 || ctx, "cov_type 2: segk_fbb_partials needs the context (the tokens are bucketed by slot)");
     const int64_t waves = (int64_t)s_n * f->K_max;
     // many slots: bucket the tokens by slot first (k_fbb_sort), then every slot sums its own list; SEGK_FBB_SORT=0: the
     // one-step kernel.  LDS of the sort: 16 waves x K_max counters.
     const size_t lds_sort = ((size_t)FBS_WAVES * f->K_max + FBS_WAVES + 1) * sizeof(int32_t);
-    if (ctx && f->K_max >= 256 && f->K_max <= 1024 && lds_sort <= 150 * 1024 && segk_env_int("SEGK_FBB_SORT", 1) != 0) {
+    // (full-covariance components: always -- a thread per triangle entry then walks the slot's own list)
+    if (f->cov_type == 2 ||
+        (ctx && f->K_max >= 256 && f->K_max <= 1024 && lds_sort <= 150 * 1024 && segk_env_int("SEGK_FBB_SORT", 1) != 0)) {
         const int64_t stride = (int64_t)c->n_utt * c->N_max;             // more than any (slice, block) can hold
         const size_t need = ((size_t)s_n * stride + (size_t)s_n * (f->K_max + 1)) * sizeof(int32_t);
         if (ctx->fbs_bytes < need) {
@@ -2370,6 +2358,11 @@ int32_t segk_fbb_partials(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm 
         SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbb_sort, lds_sort));
         hipLaunchKernelGGL(k_fbb_sort, dim3(s_n), dim3(FBS_THREADS), lds_sort, (hipStream_t)stream, *c, *f, *bt, s_lo, b, new_tok, n_new,
                            sorted, stride, koff);
+        if (f->cov_type == 2) {
+            SEGK_LAUNCH_CHECK();
+            rc = segk_fcb_partials(c, f, bt, s_lo, s_n, b, sorted, stride, koff, stream);
+            if (rc) return rc;
+        } else
         DISPATCH_XT(c, hipLaunchKernelGGL(k_fbb_partials_sorted<XT>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0,
                                            (hipStream_t)stream, *c, *f, *bt, s_lo, s_n, b, sorted, stride, koff););
         SEGK_LAUNCH_CHECK();
@@ -2391,7 +2384,7 @@ int32_t segk_fbb_partials(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm 
 int32_t segk_fbb_prepare(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t b,
                          void *stream)
 {
-    int rc = check_fbb(c, f, bt);
+    int rc = check_fbb(c, f, bt, "segk_fbb_prepare");
     if (rc) return rc;
     SEGK_REQUIRE(b >= -1 && b < bt->n_blocks, "block");
     hipStream_t st = (hipStream_t)stream;
@@ -2399,6 +2392,7 @@ int32_t segk_fbb_prepare(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *
     if (!ctx || ctx->fbb_scal_zeroed != (const void *)bt->scal || ctx->fbb_scal_stream != stream)
         SEGK_CHECK_HIP(hipMemsetAsync(bt->scal, 0, 2 * sizeof(double), st));
     if (ctx) { ctx->fbb_scal_zeroed = nullptr; ctx->fbb_scal_stream = nullptr; }
+    if (f->cov_type == 2) return segk_fcb_prepare(c, f, bt, b, stream);
     const double alpha = f->lm_unigram ? f->lm_a : f->alpha;
     hipLaunchKernelGGL(k_fbb_prepare, dim3(f->K_max), dim3(192), 0, st, *f, *bt, c->D, b, alpha);
     if (bt->tiles16 && bt->y16 && f->cov_type == 0) {
@@ -2424,9 +2418,15 @@ int32_t segk_fbb_prior_rows(segk_ctx *ctx, const segk_corpus *c, const segk_fbgm
 {
     (void)ctx;
     SEGK_REQUIRE(c && f && out, "null argument");
-    SEGK_REFUSE_FULLCOV(f, "segk_fbb_prior_rows");
     SEGK_REQUIRE(c->x_dtype == SEGK_F32 || c->x_dtype == SEGK_F64, "unsupported dtype");
     if (c->n_emb == 0) return SEGK_OK;
+    if (f->cov_type == 2) {
+        // `cached_log_prior` of every row: segk_fbgmm_init_stats left it behind the prior's factor in prior_c
+        SEGK_REQUIRE(f->prior_c != NULL, "cov_type 2: prior_c must point to D * D + n_emb + 1 doubles");
+        SEGK_CHECK_HIP(hipMemcpyAsync(out, f->prior_c + (int64_t)c->D * c->D, (size_t)c->n_emb * sizeof(double), hipMemcpyDeviceToDevice,
+                                      (hipStream_t)stream));
+        return SEGK_OK;
+    }
     const unsigned grid = (unsigned)((c->n_emb + 3) / 4);
     DISPATCH_XT(c, { hipLaunchKernelGGL(k_fbb_prior_rows<XT>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *c, *f, out); });
     SEGK_LAUNCH_CHECK();
@@ -2467,8 +2467,10 @@ int32_t segk_fbb_score(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f,
                        int32_t s_n, int32_t b, const int32_t *n_rows, double *score, void *stream)
 {
     (void)ctx;
-    int rc = check_fbb(c, f, bt);
+    int rc = check_fbb(c, f, bt, "segk_fbb_score");
     if (rc) return rc;
+    SEGK_REQUIRE(s_lo >= 0 && s_n >= 1 && s_lo + s_n <= bt->n_slices && b >= 0 && b < bt->n_blocks, "slice / block range");
+    if (f->cov_type == 2) return segk_fcb_score(c, f, bt, s_lo, s_n, b, n_rows, score, stream);
     FbbMap m;
     rc = make_map(&m, s_lo, s_n, n_rows, FBB_R);
     if (rc) return rc;
@@ -2568,7 +2570,7 @@ static int32_t fbb_segment_impl(bool map_dp, segk_ctx *ctx, const segk_corpus *c
                                 double *out_logprob, int32_t *status, void *stream)
 {
     SEGK_REQUIRE(ctx, "context");
-    int rc = check_fbb(c, f, bt);
+    int rc = check_fbb(c, f, bt, map_dp ? "segk_fbb_segment_map" : "segk_fbb_segment");      // (the kernel reads scores only)
     if (rc) return rc;
     SEGK_REQUIRE(n_slices_min == 0 || n_slices_min == 1, "n_slices_min must be 0 or 1");
     FbbMap m;
@@ -2640,12 +2642,19 @@ static int32_t fbb_assign_impl(segk_ctx *ctx, const segk_corpus *c, const segk_f
 {
     SEGK_REQUIRE(ctx, "context");
     SEGK_REQUIRE(!ctx->probe_ll || ctx->probe_ll_ld >= f->K_max, "probe leading dimension");
-    int rc = check_fbb(c, f, bt);
+    int rc = check_fbb(c, f, bt, f32 ? nullptr : "segk_fbb_assign");
     if (rc) return rc;
     FbbMap m;
     rc = make_map(&m, s_lo, s_n, n_utts, 1);
     if (rc) return rc;
     if (m.off[s_n] == 0) return SEGK_OK;
+    const double *fc_ll = nullptr;
+    int fc_ucap = 0;
+    if (f->cov_type == 2) {
+        SEGK_REQUIRE(!ll_mat, "cov_type 2: the token likelihoods are the library's own (ll_mat must be NULL)");
+        rc = segk_fcb_token_ll(ctx, c, f, bt, s_lo, s_n, b, n_utts, new_tok, n_new, &fc_ll, &fc_ucap, stream);
+        if (rc) return rc;
+    }
     const double alpha = f->lm_unigram ? f->lm_a : f->alpha;
     // timing-only ablation knob (development): 1 = one dimension, 2 = one token, 4 = no draw
     const int dbg = segk_dev_env("SEGK_FBB_DBG");       // -DSEGK_DEV builds only
@@ -2673,10 +2682,11 @@ static int32_t fbb_assign_impl(segk_ctx *ctx, const segk_corpus *c, const segk_f
         SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbb_assign<XT, COV, F32>, ch.lds));                                         \
         hipLaunchKernelGGL((k_fbb_assign<XT, COV, F32>), dim3(m.off[s_n]), dim3(ch.threads), ch.lds, (hipStream_t)stream, *c, *f, *bt, \
                            m, b, sweep, alpha, anneal_temp, new_tok, n_new, ch.rcap, dbg, ll_mat, ll_ld, ctx->probe_ll,          \
-                           ctx->probe_ll_ld);                                                                                   \
+                           ctx->probe_ll_ld, fc_ll, fc_ucap);                                                                   \
     } while (0)
     DISPATCH_XT(c, {
         if (f->cov_type == 0) SEGK_ASSIGN(0, 0);
+        else if (f->cov_type == 2) SEGK_ASSIGN(2, 0);
         else if (f32) SEGK_ASSIGN(1, 1);
         else SEGK_ASSIGN(1, 0);
     });
@@ -2708,7 +2718,7 @@ int32_t segk_fbb_assign_map(segk_ctx *ctx, const segk_corpus *c, const segk_fbgm
     (void)sweep;                  // no uniforms are consumed
     SEGK_REQUIRE(ctx, "context");
     SEGK_REQUIRE(!ctx->probe_ll || ctx->probe_ll_ld >= f->K_max, "probe leading dimension");
-    int rc = check_fbb(c, f, bt);
+    int rc = check_fbb(c, f, bt, f32_terms ? nullptr : "segk_fbb_assign_map");
     if (rc) return rc;
     if (f->lm_unigram) {
         segk_set_error("segk_fbb_assign_map: there is no MAP assignment with a language model (the reference's bigram segmenter "
@@ -2720,6 +2730,12 @@ int32_t segk_fbb_assign_map(segk_ctx *ctx, const segk_corpus *c, const segk_fbgm
     rc = make_map(&m, s_lo, s_n, n_utts, 1);
     if (rc) return rc;
     if (m.off[s_n] == 0) return SEGK_OK;
+    const double *fc_ll = nullptr;
+    int fc_ucap = 0;
+    if (f->cov_type == 2) {
+        rc = segk_fcb_token_ll(ctx, c, f, bt, s_lo, s_n, b, n_utts, new_tok, n_new, &fc_ll, &fc_ucap, stream);
+        if (rc) return rc;
+    }
     // (the fixed part: the prior terms pz, the token rows xs, their prior predictive lpr -- no red)
     const FbbChunks ch = fbb_assign_chunks((size_t)(f->K_max + FBA_R * c->D + FBA_R) * sizeof(double), f->K_max, false);
     SEGK_REQUIRE(ch.lds <= 160 * 1024, "K_max too large for the LDS logits buffer");
@@ -2727,10 +2743,11 @@ int32_t segk_fbb_assign_map(segk_ctx *ctx, const segk_corpus *c, const segk_fbgm
     do {                                                                                                                        \
         SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbb_assign_map<XT, COV, F32>, ch.lds));                                     \
         hipLaunchKernelGGL((k_fbb_assign_map<XT, COV, F32>), dim3(m.off[s_n]), dim3(ch.threads), ch.lds, (hipStream_t)stream, *c, *f, \
-                           *bt, m, b, f->alpha, new_tok, n_new, ch.rcap, ctx->probe_ll, ctx->probe_ll_ld);                       \
+                           *bt, m, b, f->alpha, new_tok, n_new, ch.rcap, ctx->probe_ll, ctx->probe_ll_ld, fc_ll, fc_ucap);       \
     } while (0)
     DISPATCH_XT(c, {
         if (f->cov_type == 0) SEGK_ASSIGN_MAP(0, 0);
+        else if (f->cov_type == 2) SEGK_ASSIGN_MAP(2, 0);
         else if (f32_terms) SEGK_ASSIGN_MAP(1, 1);
         else SEGK_ASSIGN_MAP(1, 0);
     });
@@ -2855,7 +2872,7 @@ int32_t segk_fbb_canonical(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *f, c
                            void *stream)
 {
     (void)ctx;
-    int rc = check_fbb(c, f, bt);
+    int rc = check_fbb(c, f, bt, "segk_fbb_canonical");
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_fbb_remap, dim3(1), dim3(64), 0, st, *f, *bt, remap);

@@ -27,6 +27,7 @@
 // dimension in the substitution, a D x D fp64 matrix in LDS for the factorisation).
 #include "segk_internal.h"
 #include "segk_fb_common.h"
+#include "segk_fbb_dev.h"
 
 #define FC_DMAX 64
 #define FC_NT 512                      // threads of every kernel of this unit
@@ -518,6 +519,40 @@ __global__ __launch_bounds__(FC_NT) void k_fc_del_utt(segk_corpus c, segk_fbgmm 
 //   terms[q * K_max + k] = log_post_pred_k(row q of the list), k < K
 // ---------------------------------------------------------------------------------------
 #define FC_SPAN_NT 256
+// The factor Lt (column j at Lt[j * D], as `pred` stores it) as the packed lower triangle the substitution reads: column j at
+// Ls[j * DB - j (j - 1) / 2], entries d = j .. DB - 1, the diagonal slots holding the reciprocal pivots, zeros in the padding.
+// By the whole workgroup; the caller's barrier follows.
+template <int DB>
+static __device__ __forceinline__ void fc_stage_tri(double *Ls, const double *Lt, int D, int tid, int nt)
+{
+    for (int i = tid; i < DB * DB; i += nt) {
+        const int j = i / DB, d = i - j * DB;
+        if (d < j) continue;
+        double l = (d < D) ? Lt[j * D + d] : 0.0;           // (d >= j: d < D implies j < D)
+        if (d == j) l = (j < D) ? 1. / l : 0.0;
+        Ls[j * DB - j * (j - 1) / 2 + (d - j)] = l;
+    }
+}
+// |L^-1 delta|^2 of the lane's own row, delta in registers (destroyed), the staged triangle read as same-address broadcasts:
+// y_j = delta_j r_j,  s += y_j^2,  delta_d -= L_dj y_j (d > j),  j ascending.  The one copy the serial span kernel and the
+// batch kernels (k_fcb_score, k_fcb_token_ll) share.
+template <int DB>
+static __device__ __forceinline__ double fc_subst(const double *Ls, double (&delta)[DB], int D)
+{
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < DB; j++) {
+        if (j < D) {                                        // (uniform)
+            const double *col = Ls + (j * DB - j * (j - 1) / 2);
+            const double y = delta[j] * col[0];
+            s += y * y;
+#pragma unroll
+            for (int d = j + 1; d < DB; d++) delta[d] -= col[d - j] * y;
+        }
+    }
+    return s;
+}
+
 template <typename XT, int DB>
 __global__ __launch_bounds__(FC_SPAN_NT) void k_fc_span_terms(segk_corpus c, segk_fbgmm f, const int32_t *ids, int64_t row0, int64_t n,
                                                              double *terms)
@@ -530,13 +565,7 @@ __global__ __launch_bounds__(FC_SPAN_NT) void k_fc_span_terms(segk_corpus c, seg
     const double cnt = (double)f.counts[k];
     const double k_N = f.k_0 + cnt, v = f.v_0 + cnt - (double)D + 1.;
     const double *Lt = f.pred + (int64_t)k * D * D;
-    for (int i = tid; i < DB * DB; i += nt) {
-        const int j = i / DB, d = i - j * DB;
-        if (d < j) continue;
-        double l = (d < D) ? Lt[j * D + d] : 0.0;           // (d >= j: d < D implies j < D)
-        if (d == j) l = (j < D) ? 1. / l : 0.0;
-        Ls[j * DB - j * (j - 1) / 2 + (d - j)] = l;
-    }
+    fc_stage_tri<DB>(Ls, Lt, D, tid, nt);
     for (int d = tid; d < DB; d += nt) mu[d] = d < D ? f.stat_a[(int64_t)k * D + d] / k_N : 0.0;
     __syncthreads();
     const int64_t q = (int64_t)blockIdx.x * nt + tid;
@@ -547,17 +576,7 @@ __global__ __launch_bounds__(FC_SPAN_NT) void k_fc_span_terms(segk_corpus c, seg
     double delta[DB];
 #pragma unroll
     for (int d = 0; d < DB; d++) delta[d] = d < D ? (double)x[d] - mu[d] : 0.0;
-    double s = 0.0;
-#pragma unroll
-    for (int j = 0; j < DB; j++) {
-        if (j < D) {                                        // (uniform)
-            const double *col = Ls + (j * DB - j * (j - 1) / 2);
-            const double y = delta[j] * col[0];
-            s += y * y;
-#pragma unroll
-            for (int d = j + 1; d < DB; d++) delta[d] -= col[d - j] * y;
-        }
-    }
+    const double s = fc_subst<DB>(Ls, delta, D);
     terms[q * f.K_max + k] = f.kconst[k] - 0.5 * f.log_prod[k] - (v + (double)D) / 2. * log(1. + 1. / v * s);
 }
 
@@ -885,4 +904,339 @@ int segk_fc_gibbs_items(const segk_corpus *c, segk_fbgmm *f, const int32_t *ids,
     });
     SEGK_LAUNCH_CHECK();
     return SEGK_OK;
+}
+
+// ======================================================================================
+// Batch sampler (segk_fbbatch.hip, specification tests/fullcov_batch.py on oracle/np_fbgmm_batch.py): the cov_type 2 forms
+// of the kernels of one Gibbs step.  State is the batch's own (segk_fbatch, cov_type 2 shapes): nothing here writes the serial view
+// (stat_a / stat_b / pred / log_prod / kconst / K), which segk_fbgmm_init_stats rebuilds when the batch state is materialised.
+//   k_fcb_partials    counts, sum x and the packed triangle of sum outer(x, x) of a (block, slice) cell: a workgroup per
+//                     (slice, slot), a thread per triangle entry, the slot's tokens (k_fbb_sort's list) walked in order
+//   k_fcb_prepare     a workgroup per slot: every entry of the record summed without block b in the specification's order,
+//                     covar formed in LDS and factored, the slot's tables written
+//   k_fcb_score       span scores of the block's rows: a workgroup of 256 rows (a lane per row) walks the occupied slots,
+//                     staging each factor's triangle in LDS, an online log-sum-exp per lane -- no (rows x K_max) buffer
+//   k_fcb_token_ll    token likelihoods of the block's new segments into a table of the context, same substitution body
+// ======================================================================================
+template <typename XT>
+__global__ __launch_bounds__(FC_NT) void k_fcb_partials(segk_corpus c, segk_fbgmm f, segk_fbatch bt, int s_lo, int b,
+                                                       const int32_t *sorted, int64_t sorted_stride, const int32_t *koff)
+{
+    const int tid = threadIdx.x, nt = blockDim.x, D = c.D, KM = f.K_max;
+    // (the step's totals are cleared here, as by the other types' kernels: see k_fbb_partials)
+    if (blockIdx.x == 0 && tid < 2) bt.scal[tid] = 0.0;
+    const int si = blockIdx.x / KM, s = s_lo + si, k = blockIdx.x - si * KM;
+    const int32_t *list = sorted + (int64_t)si * sorted_stride;
+    const int q0 = koff[(int64_t)si * (KM + 1) + k], q1 = koff[(int64_t)si * (KM + 1) + k + 1];
+    const XT *X = (const XT *)c.X;
+    // every thread owns the entries tid, tid + nt, ... of the D x D square that lie in the lower triangle and, below D, one
+    // of sum x; the tokens are walked in order by all of them (k_fc_init)
+    constexpr int PER = FC_DMAX * FC_DMAX / FC_NT;
+    double acc[PER], am = 0.0;
+    int ia[PER], ib[PER];
+    bool own[PER];
+#pragma unroll
+    for (int q = 0; q < PER; q++) {
+        const int i = tid + q * nt;
+        acc[q] = 0.0;
+        ib[q] = i / D;                                      // column
+        ia[q] = i - ib[q] * D;                              // row
+        own[q] = i < D * D && ia[q] >= ib[q];
+        if (!own[q]) ia[q] = ib[q] = 0;
+    }
+    for (int t = q0; t < q1; t++) {
+        const int64_t e = list[t];
+        if (e < 0 || e >= c.n_emb) continue;                // (uniform)
+        const XT *x = X + e * c.ldx;
+#pragma unroll
+        for (int r = 0; r < PER; r++)
+            if (own[r]) acc[r] += fc_xprod<XT>(x[ia[r]], x[ib[r]]);
+        if (tid < D) am += (double)x[tid];
+    }
+    double *rec = bt.partials + ((int64_t)b * bt.n_slices + s) * fbb_rec(f, D);
+    if (tid == 0) rec[k] = (double)(q1 - q0);
+    if (tid < D) rec[KM + (int64_t)k * D + tid] = am;
+    double *tri = rec + KM + (int64_t)KM * D + (int64_t)k * fbb_tri(D);
+#pragma unroll
+    for (int q = 0; q < PER; q++)
+        if (own[q]) tri[fbb_tri_index(D, ia[q], ib[q])] = acc[q];
+}
+
+#define FCB_PREP_NT 256
+static size_t fcb_prepare_lds(int D) { return (size_t)(16 * FCB_PREP_NT + D * D + 3 * D + 16 + 2) * sizeof(double); }
+
+__global__ __launch_bounds__(FCB_PREP_NT) void k_fcb_prepare(segk_corpus c, segk_fbgmm f, segk_fbatch bt, int b, double prior_alpha)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, nt = blockDim.x, D = c.D, KM = f.K_max, k = blockIdx.x, S = bt.n_slices;
+    double *scr = (double *)smem;                           // [16 slices][nt]
+    double *A = scr + 16 * FCB_PREP_NT;                     // [D * D] column j contiguous
+    double *diag = A + D * D;                               // [D]
+    double *mN = diag + D;                                  // [D]
+    double *sxs = mN + D;                                   // [D]
+    double *red = sxs + D;                                  // [16]
+    double *shn = red + 16;                                 // [1]
+    const int64_t rec = fbb_rec(f, D);
+    const int T = fbb_tri(D);
+    double *my = scr + tid;
+    // every entry of the slot's record without block b: blocks ascending inside a slice, the slices by the tree
+    if (tid == 0) {
+        fbb_sum_slices(bt, rec, k, b, my, FCB_PREP_NT);
+        shn[0] = fbb_tree(my, S, FCB_PREP_NT);
+    } else if (tid >= 64 && tid < 64 + D) {
+        const int d = tid - 64;
+        fbb_sum_slices(bt, rec, KM + (int64_t)k * D + d, b, my, FCB_PREP_NT);
+        sxs[d] = fbb_tree(my, S, FCB_PREP_NT);
+    }
+    const int64_t tri0 = KM + (int64_t)KM * D + (int64_t)k * T;
+    for (int i = tid; i < D * D; i += nt) {
+        const int j = i / D, d = i - j * D;
+        if (d < j) continue;
+        fbb_sum_slices(bt, rec, tri0 + fbb_tri_index(D, d, j), b, my, FCB_PREP_NT);
+        const double sxx = fbb_tree(my, S, FCB_PREP_NT);
+        // S = (S_0 + k_0 m_0 m_0') + sxx: the prior term first (add_item of a new component, then the tokens)
+        A[i] = (f.prior_a[d * D + j] + f.k_0 * (f.prior_b[d] * f.prior_b[j])) + sxx;
+    }
+    __syncthreads();
+    const double n = shn[0];
+    const double k_N = f.k_0 + n, v_N = f.v_0 + n, v = v_N - (double)D + 1.;
+    if (tid < D) mN[tid] = (f.k_0 * f.prior_b[tid] + sxs[tid]) / k_N;
+    __syncthreads();
+    double lconst = 0.0;
+    if (n > 0.0) {                                          // (uniform)
+        const double scale = (k_N + 1.) / (k_N * (v_N - (double)D + 1.));
+        for (int i = tid; i < D * D; i += nt) {
+            const int j = i / D, d = i - j * D;
+            if (d >= j) A[i] = scale * (A[i] - k_N * (mN[d] * mN[j]));
+        }
+        const bool ok = fc_cholesky(A, diag, D);
+        if (!ok) {
+            // (no previous factor to keep in batch mode: the sweep's status check raises)
+            if (tid == 0) atomicOr(fc_status(c, f), FC_STATUS_PIVOT);
+        } else {
+            double *pp = bt.q_t + (int64_t)k * D * D;
+            for (int i = tid; i < D * D; i += nt) {
+                const int j = i / D, d = i - j * D;
+                pp[i] = d > j ? A[i] : (d == j ? diag[j] : 0.0);
+            }
+            const double tot = block_sum(tid < D ? log(diag[tid]) : 0.0, red);
+            lconst = fc_const(D, v) - 0.5 * (2. * tot);
+        }
+    }
+    if (tid < D) bt.mean_t[(int64_t)k * D + tid] = mN[tid];
+    if (tid == 0) {
+        bt.cnt[k] = n;
+        bt.lconst[k] = lconst;
+        bt.zconst[k] = f.lms * log(prior_alpha / (double)KM + n) + (n > 0.0 ? lconst : 0.0);
+        bt.half[k] = (v + (double)D) / 2.;
+        atomicAdd(&bt.scal[0], n);                          // integer valued: exact in any order
+        if (n > 0.0) atomicAdd(&bt.scal[1], 1.0);
+    }
+}
+
+#define FCB_NT 256
+#define FCB_KMAX 1024                  // slots of the batch form (the occupancy flags of k_fcb_score, k_fbb_sort's one thread per slot)
+template <typename XT, int DB>
+__global__ __launch_bounds__(FCB_NT) void k_fcb_score(segk_corpus c, segk_fbgmm f, segk_fbatch bt, FbbMap map, int b, double prior_alpha,
+                                                     double *score)
+{
+    constexpr int TRI = DB * (DB + 1) / 2;
+    __shared__ double Ls[TRI];
+    __shared__ double mu[DB];
+    __shared__ uint8_t occ[FCB_KMAX];
+    const int D = c.D, KM = f.K_max, tid = threadIdx.x, nt = blockDim.x;
+    int s, idx;
+    if (!fbb_locate(map, blockIdx.x, &s, &idx)) return;     // (workgroup-uniform)
+    const int slice = map.lo[s];
+    const int64_t r_lo = bt.row_range[(slice * bt.n_blocks + b) * 2], r_hi = bt.row_range[(slice * bt.n_blocks + b) * 2 + 1];
+    const int64_t row = r_lo + (int64_t)idx * FCB_NT + tid;
+    const bool valid = row < r_hi && row >= 0 && row < c.n_emb;
+    const XT *x = (const XT *)c.X + (valid ? row : 0) * c.ldx;
+    for (int k = tid; k < KM; k += nt) occ[k] = bt.cnt[k] > 0.0;
+    double mx = NEG_INF_D, sm = 0.0;
+    for (int k = 0; k < KM; k++) {
+        __syncthreads();                                    // the flags are written; the previous slot's triangle has been read
+        if (!occ[k]) continue;                              // (uniform)
+        fc_stage_tri<DB>(Ls, bt.q_t + (int64_t)k * D * D, D, tid, nt);
+        for (int d = tid; d < DB; d += nt) mu[d] = d < D ? bt.mean_t[(int64_t)k * D + d] : 0.0;
+        __syncthreads();
+        if (valid) {
+            double delta[DB];
+#pragma unroll
+            for (int d = 0; d < DB; d++) delta[d] = d < D ? (double)x[d] - mu[d] : 0.0;
+            const double sq = fc_subst<DB>(Ls, delta, D);
+            const double v = f.v_0 + bt.cnt[k] - (double)D + 1.;
+            const double z = bt.zconst[k] - bt.half[k] * log(1. + 1. / v * sq);
+            if (z > mx) {
+                sm = sm * exp(mx - z) + 1.0;                // exp(-inf) = 0 on the first value
+                mx = z;
+            } else {
+                sm += exp(z - mx);
+            }
+        }
+    }
+    if (!valid) return;
+    // the empty slots share one value: lms log(alpha / K_max) + the row's prior predictive
+    const double n_empty = (double)KM - bt.scal[1];
+    if (n_empty > 0.0) {
+        const double z = f.lms * log(prior_alpha / (double)KM) + bt.prior_rows[row];
+        if (z > mx) {
+            sm = sm * exp(mx - z) + n_empty;
+            mx = z;
+        } else {
+            sm += n_empty * exp(z - mx);
+        }
+    }
+    score[row] = log(sm) + mx - f.lms * log(bt.scal[0] + prior_alpha);
+}
+
+template <typename XT, int DB>
+__global__ __launch_bounds__(FCB_NT) void k_fcb_token_ll(segk_corpus c, segk_fbgmm f, segk_fbatch bt, int s_lo, int b,
+                                                        const int32_t *new_tok, const int32_t *n_new, double *ll, int u_cap)
+{
+    constexpr int TRI = DB * (DB + 1) / 2;
+    __shared__ double Ls[TRI];
+    __shared__ double mu[DB];
+    const int D = c.D, KM = f.K_max, NM = c.N_max, tid = threadIdx.x, nt = blockDim.x;
+    const int k = blockIdx.y, si = blockIdx.z, slice = s_lo + si;
+    const int u0 = bt.utt_range[(slice * bt.n_blocks + b) * 2], u1 = bt.utt_range[(slice * bt.n_blocks + b) * 2 + 1];
+    if ((int64_t)blockIdx.x * nt >= (int64_t)(u1 - u0) * NM) return;     // (workgroup-uniform)
+    const bool occupied = bt.cnt[k] > 0.0;                  // (uniform)
+    if (occupied) {
+        fc_stage_tri<DB>(Ls, bt.q_t + (int64_t)k * D * D, D, tid, nt);
+        for (int d = tid; d < DB; d += nt) mu[d] = d < D ? bt.mean_t[(int64_t)k * D + d] : 0.0;
+    }
+    __syncthreads();
+    const int64_t p = (int64_t)blockIdx.x * nt + tid;
+    const int ui = (int)(p / NM), t = (int)(p - (int64_t)ui * NM);
+    const int utt = u0 + ui;
+    if (utt >= u1 || ui >= u_cap || t >= n_new[utt]) return;
+    const int64_t e = new_tok[(int64_t)utt * NM + t];
+    if (e < 0 || e >= c.n_emb) return;
+    const int64_t r = ((int64_t)si * u_cap + ui) * NM + t;  // (< local slices * u_cap * N_max rows: the launcher's allocation)
+    double v = bt.prior_rows[e];
+    if (occupied) {
+        const XT *x = (const XT *)c.X + e * c.ldx;
+        double delta[DB];
+#pragma unroll
+        for (int d = 0; d < DB; d++) delta[d] = d < D ? (double)x[d] - mu[d] : 0.0;
+        const double sq = fc_subst<DB>(Ls, delta, D);
+        const double dof = f.v_0 + bt.cnt[k] - (double)D + 1.;
+        v = bt.lconst[k] - bt.half[k] * log(1. + 1. / dof * sq);
+    }
+    ll[r * KM + k] = v;
+}
+
+int segk_fcb_check(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, const char *who)
+{
+    if (c->D > FC_DMAX) {
+        segk_set_error("%s: full-covariance components (cov_type 2) support D <= %d, got %d", who, FC_DMAX, c->D);
+        return SEGK_ERR_UNSUPPORTED;
+    }
+    if (f->lm_unigram) {
+        segk_set_error("%s: full-covariance components (cov_type 2) take no language model", who);
+        return SEGK_ERR_UNSUPPORTED;
+    }
+    if (f->K_max > FCB_KMAX) {
+        segk_set_error("%s: the batch sampler takes full-covariance components (cov_type 2) with K_max <= %d, got %d", who, FCB_KMAX,
+                       f->K_max);
+        return SEGK_ERR_UNSUPPORTED;
+    }
+    SEGK_REQUIRE(f->prior_c != NULL, "cov_type 2: prior_c must point to D * D + n_emb + 1 doubles");
+    SEGK_REQUIRE(bt->mean_t && bt->q_t && bt->prior_rows, "cov_type 2: mean_t [K_max, D] / q_t [K_max, D, D] / prior_rows missing");
+    return SEGK_OK;
+}
+
+int segk_fcb_partials(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int s_lo, int s_n, int b,
+                      const int32_t *sorted, int64_t sorted_stride, const int32_t *koff, void *stream)
+{
+    FC_DISPATCH_XT(c, hipLaunchKernelGGL(k_fcb_partials<XT>, dim3((unsigned)(s_n * f->K_max)), dim3(FC_NT), 0, (hipStream_t)stream, *c, *f,
+                                          *bt, s_lo, b, sorted, sorted_stride, koff););
+    SEGK_LAUNCH_CHECK();
+    return SEGK_OK;
+}
+
+int segk_fcb_prepare(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int b, void *stream)
+{
+    const size_t lds = fcb_prepare_lds(c->D);
+    SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fcb_prepare, lds));
+    hipLaunchKernelGGL(k_fcb_prepare, dim3((unsigned)f->K_max), dim3(FCB_PREP_NT), lds, (hipStream_t)stream, *c, *f, *bt, b, f->alpha);
+    SEGK_LAUNCH_CHECK();
+    return SEGK_OK;
+}
+
+#define FCB_DB_SWITCH(D, CASE)                                                                        \
+    switch (((D) + 7) & ~7) {                                                                         \
+        CASE(8) CASE(16) CASE(24) CASE(32) CASE(40) CASE(48) CASE(56) CASE(64)                        \
+    default:                                                                                          \
+        segk_set_error("cov_type 2: no batch kernel for D = %d", (D));                                \
+        return SEGK_ERR_UNSUPPORTED;                                                                  \
+    }
+
+template <typename XT>
+static int fcb_score_launch(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, const FbbMap &m, int n_wg, int b,
+                            double *score, hipStream_t st)
+{
+#define FCB_CASE(DB)                                                                                                              \
+    case DB:                                                                                                                      \
+        hipLaunchKernelGGL((k_fcb_score<XT, DB>), dim3((unsigned)n_wg), dim3(FCB_NT), 0, st, *c, *f, *bt, m, b, f->alpha, score);   \
+        break;
+    FCB_DB_SWITCH(c->D, FCB_CASE)
+#undef FCB_CASE
+    SEGK_LAUNCH_CHECK();
+    return SEGK_OK;
+}
+
+int segk_fcb_score(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int s_lo, int s_n, int b, const int32_t *n_rows,
+                   double *score, void *stream)
+{
+    SEGK_REQUIRE(s_n >= 1 && s_n <= 16, "at most 16 local slices");
+    // (256 rows per workgroup at every block size: a wave of 64 rows per workgroup, tried for blocks that leave compute units
+    // idle, was slower -- profiles/README.md "Full-covariance batch sampler")
+    const int nt = FCB_NT;
+    FbbMap m;
+    m.n = s_n;
+    m.off[0] = 0;
+    for (int s = 0; s < s_n; s++) {
+        m.lo[s] = s_lo + s;
+        m.off[s + 1] = m.off[s] + (n_rows[s] + nt - 1) / nt;
+    }
+    if (m.off[s_n] == 0) return SEGK_OK;
+    int rc;
+    FC_DISPATCH_XT(c, rc = fcb_score_launch<XT>(c, f, bt, m, m.off[s_n], b, score, (hipStream_t)stream););
+    return rc;
+}
+
+template <typename XT>
+static int fcb_token_launch(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, dim3 grid, int s_lo, int b,
+                            const int32_t *new_tok, const int32_t *n_new, double *ll, int u_cap, hipStream_t st)
+{
+#define FCB_CASE(DB)                                                                                                              \
+    case DB:                                                                                                                      \
+        hipLaunchKernelGGL((k_fcb_token_ll<XT, DB>), grid, dim3(FCB_NT), 0, st, *c, *f, *bt, s_lo, b, new_tok, n_new, ll, u_cap);  \
+        break;
+    FCB_DB_SWITCH(c->D, FCB_CASE)
+#undef FCB_CASE
+    SEGK_LAUNCH_CHECK();
+    return SEGK_OK;
+}
+
+int segk_fcb_token_ll(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int s_lo, int s_n, int b,
+                      const int32_t *n_utts, const int32_t *new_tok, const int32_t *n_new, const double **ll, int *u_cap,
+                      void *stream)
+{
+    SEGK_REQUIRE(ctx, "context");
+    int u_most = 0;
+    for (int s = 0; s < s_n; s++) u_most = n_utts[s] > u_most ? n_utts[s] : u_most;
+    *u_cap = u_most;
+    *ll = nullptr;
+    if (u_most == 0) return SEGK_OK;
+    // (bounded by the token positions of one block of the local slices)
+    const int64_t need = (int64_t)s_n * u_most * c->N_max * f->K_max;
+    if (int rc = segk_ws_grow(ctx, &ctx->fcb_ll, &ctx->fcb_ll_n, need, (size_t)need * sizeof(double), (hipStream_t)stream)) return rc;
+    *ll = ctx->fcb_ll;
+    const dim3 grid((unsigned)(((int64_t)u_most * c->N_max + FCB_NT - 1) / FCB_NT), (unsigned)f->K_max, (unsigned)s_n);
+    int rc;
+    FC_DISPATCH_XT(c, rc = fcb_token_launch<XT>(c, f, bt, grid, s_lo, b, new_tok, n_new, ctx->fcb_ll, u_most, (hipStream_t)stream););
+    return rc;
 }

@@ -950,6 +950,19 @@ class FbgmmBatchSweeper(object):
         dev = _dev()
         self.df, self.comm = df, get_comm(group)
         assert score_precision in ("f64", "f32", "f16")
+        self.fullcov = df.cov_type == 2
+        if self.fullcov:
+            # full-covariance components: fp64 scores, no language model, one process
+            if score_precision != "f64":
+                raise SegkError("the batch sampler takes full-covariance components with score_precision='f64' only "
+                                "(got %r): there is no reduced-precision form of the triangular solves" % (score_precision,))
+            if df.lm is not None:
+                raise SegkError("the batch sampler takes full-covariance components without a language model only")
+            if self.comm.world > 1:
+                raise SegkError("the batch sampler takes full-covariance components in one process only (%d ranks): the "
+                                "exchange of their partial sums between ranks is not covered by any test" % self.comm.world)
+            if df.corpus.D > 64:
+                raise SegkError("full-covariance components (cov_type 2) support D <= 64, got %d" % df.corpus.D)
         if score_precision == "f16" and df.cov_type != 0:
             raise SegkError("score_precision='f16' (matrix-core span score) exists for fixed-variance components only")
         if score_precision == "f16" and 2 * df.corpus.D > 208:
@@ -983,12 +996,15 @@ class FbgmmBatchSweeper(object):
         self.utt_range_np, self.row_range_np = ur, rr
         self.utt_range, self.row_range = to_dev(ur), to_dev(rr)
         K, D = df.K_max, c.D
-        self.rec = K * (2 * D + 1)
+        # doubles of a (block, slice) cell's record: counts, sum x, then sum x^2 or the packed triangle of sum outer(x, x)
+        self.rec = K * (1 + D + D * (D + 1) // 2) if self.fullcov else K * (2 * D + 1)
         f64 = torch.float64
         self.partials = torch.zeros((self.B, self.S, self.rec), dtype=f64, device=dev)
         self.cnt = torch.zeros(K, dtype=f64, device=dev)
-        self.mean_t = torch.zeros((D, K), dtype=f64, device=dev)
-        self.q_t = torch.zeros((D, K), dtype=f64, device=dev)
+        # (full covariance: the mean of every slot, slot-major, and the Cholesky factor of its covar as DeviceFbgmm.pred
+        # stores it -- include/segk.h, segk_fbatch)
+        self.mean_t = torch.zeros((K, D) if self.fullcov else (D, K), dtype=f64, device=dev)
+        self.q_t = torch.zeros((K, D, D) if self.fullcov else (D, K), dtype=f64, device=dev)
         self.lconst = torch.zeros(K, dtype=f64, device=dev)
         self.zconst = torch.zeros(K, dtype=f64, device=dev)
         self.half = torch.zeros(K, dtype=f64, device=dev)
@@ -1199,6 +1215,21 @@ class FbgmmBatchSweeper(object):
             check(L.segk_fbb_partials(ctx, cp, fp, bp, self.s_lo, self.s_n, b, ptr(df.new_tok), ptr(df.n_new), st))
             self._gather(self.partials, b)
         self.sweep_index += 1
+
+    def cell_partials(self, b, s):
+        """(counts [K], sum x [K, D], sum x^2 [K, D] -- full covariance: sum outer(x, x) [K, D, D], the packed triangle
+        unfolded --) of the (block b, slice s) cell, as numpy float64."""
+        K, D = self.df.K_max, self.df.corpus.D
+        r = self.partials[b, s].cpu().numpy()
+        cnt, sx = r[:K].copy(), r[K:K + K * D].reshape(K, D).copy()
+        if not self.fullcov:
+            return cnt, sx, r[K + K * D:].reshape(K, D).copy()
+        tri = r[K + K * D:].reshape(K, D * (D + 1) // 2)
+        sxx = np.zeros((K, D, D))
+        cols, rows = np.triu_indices(D)                      # column-major lower triangle: (b, a), a >= b, b ascending
+        sxx[:, rows, cols] = tri
+        sxx[:, cols, rows] = tri
+        return cnt, sx, sxx
 
     def utt_values(self, t):
         """numpy copy of a per-utterance device vector with every rank's own utterances filled in."""

@@ -45,14 +45,17 @@ class UnigramAcousticWordseg(object):
         16-bit pipe) -- within the 1e-4 tolerance of the path, 5x / 10x faster; with diagonal
         components "f32" evaluates the Student-t terms in float32 with the hardware logarithm (same
         tolerance); "f64" reproduces the specification to the last draw.
-        covariance_type="full" (D <= 64) runs with sync="sequential" and beta_sent_boundary=-1 only: the launches per utterance, the span
-        scores of an utterance's triangle a lane per row (segk_fullcov.hip); the batch sampler has no
-        full-covariance form."""
+        covariance_type="full" (D <= 64) is constructed with sync="sequential" and beta_sent_boundary=-1 only.  Its serial
+        chain is the launches per utterance, the span scores of an utterance's triangle a lane per row (segk_fullcov.hip).
+        Its batch sweeps (fp64 scores, one process) are reached from such an object: pass n_gibbs_blocks / n_stat_blocks /
+        batch_seed here, then batch_sweep_async() / materialise(), or gibbs_sample(..., sync="batch")."""
         logger.info("Initializing")
         assert sync in ("sequential", "batch")
         if covariance_type == "full" and sync == "batch":
-            raise NotImplementedError("the batch sampler (sync='batch') has no full-covariance form: its partial sums would be "
-                                      "K_max * D^2 per (block, slice); use sync='sequential' with covariance_type='full'")
+            raise NotImplementedError("the batch sampler is not reached through the constructor's sync='batch' with "
+                                      "covariance_type='full': construct with sync='sequential' (and n_gibbs_blocks, "
+                                      "n_stat_blocks, batch_seed), then call gibbs_sample(..., sync='batch') or "
+                                      "batch_sweep_async() / materialise()")
         if covariance_type == "full" and beta_sent_boundary != -1:
             # (calc_p_continue asserts for any other value, here and in the reference: no sweep could run.  The other
             # covariance types keep the reference's behaviour -- construct, then fail at the first sweep --; for the
@@ -212,9 +215,13 @@ class UnigramAcousticWordseg(object):
 
     # ------------------------------------------------------------------ sweeps
     def gibbs_sample(self, n_iter, am_n_iter=0, anneal_schedule=None, anneal_start_temp_inv=0.1,
-                     anneal_end_temp_inv=1, n_anneal_steps=-1, anneal_gibbs_am=False):
-        """unigram_acoustic_wordseg.py:362-472; same record keys."""
+                     anneal_end_temp_inv=1, n_anneal_steps=-1, anneal_gibbs_am=False, sync=None):
+        """unigram_acoustic_wordseg.py:362-472; same record keys.  sync: None = the mode the object was built with; "batch" /
+        "sequential" = the sweeps of this call in that mode (the two modes mix freely: every switch rebuilds the state the
+        other one reads)."""
         import torch
+        assert sync in (None, "sequential", "batch")
+        sync = self.sync if sync is None else sync
         if anneal_schedule is None:
             get_anneal_temp = iter([])
         elif anneal_schedule == "linear":
@@ -238,7 +245,7 @@ class UnigramAcousticWordseg(object):
                 self._leave_batch()
                 self.acoustic_model.gibbs_sample(am_n_iter, consider_unassigned=False)
             anneal_temp = next(get_anneal_temp, anneal_end_temp_inv)
-            if self.sync == "batch":
+            if sync == "batch":
                 self.batch_sweep_async(anneal_temp, anneal_gibbs_am)
                 torch.cuda.synchronize()
                 self._df.check_status()

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Throughput of the sequential (reference-chain) and batch FBGMM / bigram Gibbs drivers on BASELINE
 config 2 shapes (1 000 utterances, D = 39, K = 100) -- development measurement, not bench.py.
---fb-type viterbi: the Viterbi / MAP sweeps of the unigram segmenters, with either --sync (the bigram one has no such mode)."""
+--fb-type viterbi: the Viterbi / MAP sweeps of the unigram segmenters, with either --sync (the bigram one has no such mode).
+--cov full: the unigram segmenter with full-covariance components in place of --which (D <= 64): --sync sequential its
+serial chain (four launches per utterance), --sync batch its batch sweeps (profiles/README.md "Full-covariance batch
+sampler"); no oracle timing."""
 import argparse
 import os
 import random
@@ -25,7 +28,11 @@ def main():
     ap.add_argument("--blocks", type=int, default=8)
     ap.add_argument("--precision", default="f64")
     ap.add_argument("--fb-type", default="standard", choices=["standard", "viterbi"])
+    ap.add_argument("--cov", default=None, choices=["full"])
+    ap.add_argument("--slices", type=int, default=8)
     args = ap.parse_args()
+    if args.cov == "full":
+        args.which = "full"
     import torch
     from segmentalist_amd import bigram_acoustic_wordseg as baw, fbgmm, unigram_acoustic_wordseg as uaw
     from segmentalist_amd.gaussian_components_fixedvar import FixedVarPrior
@@ -41,8 +48,9 @@ def main():
     kw = dict(n_slices_min=0, n_slices_max=6, p_boundary_init=0.5, beta_sent_boundary=-1, lms=1.0, wip=0.0,
               init_am_assignments="rand", time_power_term=1.0)
     okw = dict(kw)
+    full = (np.zeros(D), 0.05, D + 3, 0.002 * (D + 3) * np.eye(D))
     if args.sync == "batch":
-        kw.update(sync="batch", n_gibbs_blocks=args.blocks)
+        kw.update(sync="batch", n_gibbs_blocks=args.blocks, n_stat_blocks=args.slices)
     pk = dict(score_precision=args.precision) if args.sync == "batch" else {}
     lm = {"type": "smooth", "intrp_lambda": 0.1, "a": 0.5, "b": 0.5}
     for which in args.which.split(","):
@@ -52,7 +60,11 @@ def main():
         random.seed(0)
         np.random.seed(0)
         t0 = time.perf_counter()
-        if which == "diag":
+        if which == "full":
+            # (the constructor takes "full" with sync="sequential" only; the batch sweeps are enqueued below all the same)
+            seg = uaw.UnigramAcousticWordseg(fbgmm.FBGMM, 1.0, K, NIW(*full), *corpus, covariance_type="full",
+                                             fb_type=args.fb_type, **dict(kw, sync="sequential"), **pk)
+        elif which == "diag":
             seg = uaw.UnigramAcousticWordseg(fbgmm.FBGMM, 1.0, K, NIW(*diag), *corpus, covariance_type="diag",
                                              fb_type=args.fb_type, **kw, **pk)
         elif which == "fixed":
@@ -82,7 +94,7 @@ def main():
               % (which, t_init, ["%.3f" % x for x in st], 1.0 / min(st), 1e6 * min(st) / args.utts,
                  rec["components"][-1]), flush=True)
         # oracle on a bounded sample (--cpu-utts 0: device timings only)
-        if not keys:
+        if not keys or which == "full":
             continue
         random.seed(0)
         np.random.seed(0)
