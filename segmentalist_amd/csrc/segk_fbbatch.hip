@@ -430,43 +430,9 @@ __global__ __launch_bounds__(192) void k_fbb_prepare(segk_fbgmm f, segk_fbatch b
     }
 }
 
-// acc[r] += sum_d term(mean[d, k], q[d, k], xs[r][d]) for the FBB_R rows in LDS; the parameters of
-// four dimensions are fetched ahead of their use (the loads are independent, the compiler keeps
-// them in flight together), dimensions in increasing order.
-template <int COV>
-static __device__ __forceinline__ void fbb_accumulate(const segk_fbatch &bt, int KM, int k, int D, const double *xs,
-                                                      double *acc)
-{
-    int d = 0;
-    for (; d + 4 <= D; d += 4) {
-        double m[4], q[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            m[j] = bt.mean_t[(int64_t)(d + j) * KM + k];
-            q[j] = bt.q_t[(int64_t)(d + j) * KM + k];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-#pragma unroll
-            for (int r = 0; r < FBB_R; r++) {
-                const double delta = m[j] - xs[r * D + d + j];
-                if (COV == 0) acc[r] += (delta * delta) * q[j];
-                else acc[r] += log(1. + (delta * delta) * q[j]);
-            }
-        }
-    }
-    for (; d < D; d++) {
-        const double m = bt.mean_t[(int64_t)d * KM + k], q = bt.q_t[(int64_t)d * KM + k];
-#pragma unroll
-        for (int r = 0; r < FBB_R; r++) {
-            const double delta = m - xs[r * D + d];
-            if (COV == 0) acc[r] += (delta * delta) * q;
-            else acc[r] += log(1. + (delta * delta) * q);
-        }
-    }
-}
-
-// the same for NR rows starting at xs (a row group of k_fbb_assign): per (row, slot) the identical sequence of operations
+// acc[r] += sum_d term(mean[d, k], q[d, k], xs[r][d]) for NR rows in LDS starting at xs (FBB_R rows of k_fbb_score, a row
+// group of the assignment kernels); the parameters of four dimensions are fetched ahead of their use (the loads are
+// independent, the compiler keeps them in flight together), dimensions in increasing order.
 template <int COV, int NR>
 static __device__ __forceinline__ void fbb_accumulate_rows(const segk_fbatch &bt, int KM, int k, int D, const double *xs, double *acc)
 {
@@ -500,49 +466,37 @@ static __device__ __forceinline__ void fbb_accumulate_rows(const segk_fbatch &bt
 }
 
 // the diagonal (Student-t) terms of NR rows in float32 with the hardware logarithm (log2; the caller multiplies by ln 2):
-// the arithmetic of k_fbb_score_diag32, for the token likelihoods of the assignment step (`score_precision="f32"`)
+// the arithmetic of k_fbb_score_diag32, for the token likelihoods of the assignment step (`score_precision="f32"`).
+// fbb_terms32: the dimensions d .. d + NB - 1, their parameters in flight together
+template <int NR, int NB>
+static __device__ __forceinline__ void fbb_terms32(const segk_fbatch &bt, int KM, int k, int D, int d, const double *xs, float *acc)
+{
+    float m[NB], q[NB];
+    double cj[NB];
+#pragma unroll
+    for (int j = 0; j < NB; j++) {
+        cj[j] = fbb_centre(bt, d + j);
+        m[j] = (float)(bt.mean_t[(int64_t)(d + j) * KM + k] - cj[j]);
+        q[j] = (float)bt.q_t[(int64_t)(d + j) * KM + k];
+    }
+#pragma unroll
+    for (int j = 0; j < NB; j++) {
+#pragma unroll
+        for (int r = 0; r < NR; r++) {
+            const float delta = m[j] - (float)(xs[r * D + d + j] - cj[j]);
+            acc[r] += __builtin_amdgcn_logf(1.f + (delta * delta) * q[j]);
+        }
+    }
+}
+
 template <int NR>
 static __device__ __forceinline__ void fbb_accumulate_rows32(const segk_fbatch &bt, int KM, int k, int D, const double *xs, float *acc)
 {
     int d = 0;
-    // sixteen dimensions' parameters in flight (four at a time were ten dependent round trips for D = 39); the terms in the
-    // same order
-    for (; d + 16 <= D; d += 16) {
-        float m[16], q[16];
-        double cj[16];
-#pragma unroll
-        for (int j = 0; j < 16; j++) {
-            cj[j] = fbb_centre(bt, d + j);
-            m[j] = (float)(bt.mean_t[(int64_t)(d + j) * KM + k] - cj[j]);
-            q[j] = (float)bt.q_t[(int64_t)(d + j) * KM + k];
-        }
-#pragma unroll
-        for (int j = 0; j < 16; j++) {
-#pragma unroll
-            for (int r = 0; r < NR; r++) {
-                const float delta = m[j] - (float)(xs[r * D + d + j] - cj[j]);
-                acc[r] += __builtin_amdgcn_logf(1.f + (delta * delta) * q[j]);
-            }
-        }
-    }
-    for (; d + 4 <= D; d += 4) {
-        float m[4], q[4];
-        double cj[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            cj[j] = fbb_centre(bt, d + j);
-            m[j] = (float)(bt.mean_t[(int64_t)(d + j) * KM + k] - cj[j]);
-            q[j] = (float)bt.q_t[(int64_t)(d + j) * KM + k];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-#pragma unroll
-            for (int r = 0; r < NR; r++) {
-                const float delta = m[j] - (float)(xs[r * D + d + j] - cj[j]);
-                acc[r] += __builtin_amdgcn_logf(1.f + (delta * delta) * q[j]);
-            }
-        }
-    }
+    // sixteen dimensions' parameters in flight (four at a time were ten dependent round trips for D = 39), then four; the terms
+    // in the same order
+    for (; d + 16 <= D; d += 16) fbb_terms32<NR, 16>(bt, KM, k, D, d, xs, acc);
+    for (; d + 4 <= D; d += 4) fbb_terms32<NR, 4>(bt, KM, k, D, d, xs, acc);
     for (; d < D; d++) {
         const double cd = fbb_centre(bt, d);
         const float m = (float)(bt.mean_t[(int64_t)d * KM + k] - cd), q = (float)bt.q_t[(int64_t)d * KM + k];
@@ -654,7 +608,7 @@ __global__ __launch_bounds__(256) void k_fbb_score(segk_corpus c, segk_fbgmm f, 
             double acc[FBB_R];
 #pragma unroll
             for (int r = 0; r < FBB_R; r++) acc[r] = 0.0;
-            fbb_accumulate<COV>(bt, KM, k, D, xs, acc);
+            fbb_accumulate_rows<COV, FBB_R>(bt, KM, k, D, xs, acc);
             const double zc = bt.zconst[k], h = bt.half[k];
 #pragma unroll
             for (int r = 0; r < FBB_R; r++) z[r] = zc - h * acc[r];
@@ -1305,6 +1259,79 @@ __global__ __launch_bounds__(128) void k_fbb_segment(segk_corpus c, segk_fbatch 
 }
 
 // ---------------------------------------------------------------------------------------
+// The diagonal / fixed-variance token likelihoods of one chunk of an utterance's new tokens, shared by k_fbb_assign (sampled
+// slots) and k_fbb_assign_map (MAP slots): ll[r][k] = lconst_k - half_k * sum_d term(row r, slot k, d) for an occupied slot,
+// the row's prior predictive for an empty one.
+//
+// fbb_slot_ll: slot k against a group of NR rows, the first `nr` of them tokens; xr, lpr and ll point at the group's first row.
+// F32: the terms in float32 on the hardware logarithm (fbb_accumulate_rows32), else fp64 (fbb_accumulate_rows).  Dt: the
+// dimensions walked (D; the sampled kernel's development ablation walks one).
+// ---------------------------------------------------------------------------------------
+template <int COV, int F32, int NR>
+static __device__ __forceinline__ void fbb_slot_ll(const segk_fbatch &bt, int KM, int k, int Dt, const double *xr, const double *lpr,
+                                                   int nr, double *ll)
+{
+    if (bt.cnt[k] > 0.0) {
+        double acc[NR];
+#pragma unroll
+        for (int r = 0; r < NR; r++) acc[r] = 0.0;
+        if (F32) {
+            float a32[NR];
+#pragma unroll
+            for (int r = 0; r < NR; r++) a32[r] = 0.f;
+            fbb_accumulate_rows32<NR>(bt, KM, k, Dt, xr, a32);
+#pragma unroll
+            for (int r = 0; r < NR; r++) acc[r] = 0.6931471805599453 * (double)a32[r];
+        } else
+            fbb_accumulate_rows<COV, NR>(bt, KM, k, Dt, xr, acc);
+        const double lc = bt.lconst[k], h = bt.half[k];
+#pragma unroll
+        for (int r = 0; r < NR; r++)
+            if (r < nr) ll[(int64_t)r * KM + k] = lc - h * acc[r];
+    } else {
+#pragma unroll
+        for (int r = 0; r < NR; r++)
+            if (r < nr) ll[(int64_t)r * KM + k] = lpr[r];
+    }
+}
+
+// The whole phase for the tokens t0 .. t0 + nr - 1 of utterance `utt` (nr <= rcap): their rows into xs, the rows' prior
+// predictive by one wave each into lpr, then the slots.  Two thread layouts:
+//   * 512 threads and K_max <= 128: four groups of 128 threads take four rows each of a chunk of FBA_R = 16 (with one thread
+//     per slot 100 of 256 threads each walked D x 8 software logarithms; an utterance with nine tokens paid a chunk of eight
+//     twice).  fbb_assign_chunks launches 512 threads with rcap == FBA_R only;
+//   * else one thread per slot over the chunk's (at most FBB_R) rows.
+// Per (row, slot) the sequence of operations is the same in both.  Ends without a barrier: the caller's follows.
+template <typename XT, int COV, int F32>
+static __device__ __forceinline__ void fbb_token_ll(const segk_corpus &c, const segk_fbgmm &f, const segk_fbatch &bt, int utt, int t0,
+                                                    int nr, int rcap, int Dt, const int32_t *new_tok, double *xs, double *lpr,
+                                                    double *ll)
+{
+    const int D = c.D, KM = f.K_max, tid = threadIdx.x, nt = blockDim.x;
+    const XT *X = (const XT *)c.X;
+    for (int j = tid; j < (rcap > FBB_R ? rcap : FBB_R) * D; j += nt) {
+        const int r = j / D, d = j - r * D;
+        xs[j] = r < nr ? (double)X[(int64_t)new_tok[(int64_t)utt * c.N_max + t0 + r] * c.ldx + d] : 0.0;
+    }
+    __syncthreads();
+    {
+        const int w = tid >> 6, lane = tid & 63, nw = nt >> 6;
+        for (int r = w; r < nr; r += nw) {
+            const double v = bt.prior_rows ? bt.prior_rows[new_tok[(int64_t)utt * c.N_max + t0 + r]]
+                                           : fbb_prior_row<XT>(f, D, xs + r * D, lane);
+            if (lane == 0) lpr[r] = v;
+        }
+    }
+    __syncthreads();
+    if (nt >= 4 * 128 && KM <= 128) {
+        const int k = tid & 127, r0 = 4 * (tid >> 7);
+        if (k < KM && r0 < nr) fbb_slot_ll<COV, F32, 4>(bt, KM, k, Dt, xs + r0 * D, lpr + r0, nr - r0, ll + (int64_t)r0 * KM);
+    } else {
+        for (int k = tid; k < KM; k += nt) fbb_slot_ll<COV, F32, FBB_R>(bt, KM, k, Dt, xs, lpr, nr, ll);
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // slots of the new tokens of one utterance per workgroup
 // ---------------------------------------------------------------------------------------
 template <typename XT, int COV, int F32 = 0>
@@ -1314,7 +1341,7 @@ __global__ __launch_bounds__(512) void k_fbb_assign(segk_corpus c, segk_fbgmm f,
                              const double *fc_ll, int fc_ucap)
 {
     // The likelihood part of the logits does not depend on the previous segment's slot, so it is
-    // evaluated for up to `rcap` (<= FBB_R) tokens of the utterance at once -- the component
+    // evaluated for up to `rcap` (<= FBA_R) tokens of the utterance at once (fbb_token_ll) -- the component
     // parameters are streamed once per chunk -- and kept in LDS; the draws then run in token order
     // (with a language model each needs the slot of the one before).
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1329,7 +1356,6 @@ __global__ __launch_bounds__(512) void k_fbb_assign(segk_corpus c, segk_fbgmm f,
     if (!fbb_locate(map, blockIdx.x, &s, &idx)) return;
     const int slice = map.lo[s];
     const int utt = bt.utt_range[(slice * bt.n_blocks + b) * 2] + idx;
-    const XT *X = (const XT *)c.X;
     const int nn = n_new[utt];
     const double zc_empty = f.lms * log(prior_alpha / (double)KM);
     const double tot = bt.scal[0];
@@ -1359,79 +1385,7 @@ __global__ __launch_bounds__(512) void k_fbb_assign(segk_corpus c, segk_fbgmm f,
             const double *tab = fc_ll + (((int64_t)s * fc_ucap + idx) * c.N_max + t0) * KM;
             for (int j = tid; j < nr * KM; j += nt) ll[j] = tab[j];
         } else {
-        for (int j = tid; j < (rcap > FBB_R ? rcap : FBB_R) * D; j += nt) {
-            const int r = j / D, d = j - r * D;
-            xs[j] = r < nr ? (double)X[(int64_t)new_tok[(int64_t)utt * c.N_max + t0 + r] * c.ldx + d] : 0.0;
-        }
-        __syncthreads();
-        {
-            const int w = tid >> 6, lane = tid & 63, nw = nt >> 6;
-            for (int r = w; r < nr; r += nw) {
-                const double v = bt.prior_rows ? bt.prior_rows[new_tok[(int64_t)utt * c.N_max + t0 + r]]
-                                               : fbb_prior_row<XT>(f, D, xs + r * D, lane);
-                if (lane == 0) lpr[r] = v;
-            }
-        }
-        __syncthreads();
-        if (nt >= 4 * 128 && KM <= 128) {
-            // few slots: four groups of threads take two rows each (the per-(row, slot) arithmetic is unchanged; with one
-            // thread per slot 100 of 256 threads each walked D x 8 software logarithms) -- four rows each when the chunk
-            // holds sixteen tokens (an utterance with nine tokens paid the whole chunk twice)
-            auto rows_of_group = [&](auto NRC) {
-                constexpr int NR = decltype(NRC)::value;
-                const int k = tid & 127, r0 = NR * (tid >> 7);
-                if (k < KM && r0 < nr) {
-                    if (bt.cnt[k] > 0.0) {
-                        double acc[NR];
-#pragma unroll
-                        for (int r = 0; r < NR; r++) acc[r] = 0.0;
-                        if (F32) {
-                            float a32[NR];
-#pragma unroll
-                            for (int r = 0; r < NR; r++) a32[r] = 0.f;
-                            fbb_accumulate_rows32<NR>(bt, KM, k, (dbg & 1) ? 1 : D, xs + r0 * D, a32);
-#pragma unroll
-                            for (int r = 0; r < NR; r++) acc[r] = 0.6931471805599453 * (double)a32[r];
-                        } else
-                        fbb_accumulate_rows<COV, NR>(bt, KM, k, (dbg & 1) ? 1 : D, xs + r0 * D, acc);
-                        const double lc = bt.lconst[k], h = bt.half[k];
-#pragma unroll
-                        for (int r = 0; r < NR; r++)
-                            if (r0 + r < nr) ll[(int64_t)(r0 + r) * KM + k] = lc - h * acc[r];
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < NR; r++)
-                            if (r0 + r < nr) ll[(int64_t)(r0 + r) * KM + k] = lpr[r0 + r];
-                    }
-                }
-            };
-            if (rcap > FBB_R) rows_of_group(std::integral_constant<int, 4>());
-            else rows_of_group(std::integral_constant<int, 2>());
-        } else
-        for (int k = tid; k < KM; k += nt) {
-            if (bt.cnt[k] > 0.0) {
-                double acc[FBB_R];
-#pragma unroll
-                for (int r = 0; r < FBB_R; r++) acc[r] = 0.0;
-                if (F32) {
-                    float a32[FBB_R];
-#pragma unroll
-                    for (int r = 0; r < FBB_R; r++) a32[r] = 0.f;
-                    fbb_accumulate_rows32<FBB_R>(bt, KM, k, (dbg & 1) ? 1 : D, xs, a32);
-#pragma unroll
-                    for (int r = 0; r < FBB_R; r++) acc[r] = 0.6931471805599453 * (double)a32[r];
-                } else
-                fbb_accumulate<COV>(bt, KM, k, (dbg & 1) ? 1 : D, xs, acc);
-                const double lc = bt.lconst[k], h = bt.half[k];
-#pragma unroll
-                for (int r = 0; r < FBB_R; r++)
-                    if (r < nr) ll[(int64_t)r * KM + k] = lc - h * acc[r];
-            } else {
-#pragma unroll
-                for (int r = 0; r < FBB_R; r++)
-                    if (r < nr) ll[(int64_t)r * KM + k] = lpr[r];
-            }
-        }
+            fbb_token_ll<XT, COV, F32>(c, f, bt, utt, t0, nr, rcap, (dbg & 1) ? 1 : D, new_tok, xs, lpr, ll);
         }
         __syncthreads();
         if (probe_ll) {         // segk_fbb_set_probe: the likelihood part of the logits, as the draws below use it
@@ -1541,8 +1495,8 @@ __global__ __launch_bounds__(512) void k_fbb_assign(segk_corpus c, segk_fbgmm f,
 // z_k = log(alpha / K_max + n_k) + loglik_k(x) -- no `lms` on the prior term (fbgmm.py:475-479 has none), no temperature, no
 // uniform, no softmax (the reference's argmax(exp(z - logsumexp z)) is the argmax of z: tests/test_map_batch_cpu.py holds
 // that on every token of the test corpora).  k_fbb_assign without a language model with the draw replaced: one workgroup per
-// utterance; the prior terms once per workgroup into LDS; the likelihoods of a chunk of tokens by the same accumulation
-// (fbb_accumulate / fbb_accumulate_rows / fbb_accumulate_rows32, the same row groups) into LDS; then one WAVE per token: a
+// utterance; the prior terms once per workgroup into LDS; the likelihoods of a chunk of tokens by the same code (fbb_token_ll:
+// the same staging, row groups and accumulation, with Dt = D) into LDS; then one WAVE per token: a
 // per-lane (value, index) over k = lane, lane + 64, ... with strict >, the wave's maximum by DPP and the lowest index among
 // the lanes that hold it.  All empty slots of a token carry one value, so the first of them wins a tie among them without
 // being treated apart.  Never reads ll_mat: in the fixed-variance tolerance modes the token likelihood is the fp64 quadratic
@@ -1579,7 +1533,6 @@ __global__ __launch_bounds__(512) void k_fbb_assign_map(segk_corpus c, segk_fbgm
     if (!fbb_locate(map, blockIdx.x, &s, &idx)) return;
     const int slice = map.lo[s];
     const int utt = bt.utt_range[(slice * bt.n_blocks + b) * 2] + idx;
-    const XT *X = (const XT *)c.X;
     const int nn = n_new[utt];
     if (nn == 0) return;
     for (int k = tid; k < KM; k += nt) pz[k] = log(prior_alpha / (double)KM + bt.cnt[k]);      // fbgmm.py:475-479
@@ -1591,77 +1544,7 @@ __global__ __launch_bounds__(512) void k_fbb_assign_map(segk_corpus c, segk_fbgm
             const double *tab = fc_ll + (((int64_t)s * fc_ucap + idx) * c.N_max + t0) * KM;
             for (int j = tid; j < nr * KM; j += nt) ll[j] = tab[j];
         } else {
-        for (int j = tid; j < (rcap > FBB_R ? rcap : FBB_R) * D; j += nt) {
-            const int r = j / D, d = j - r * D;
-            xs[j] = r < nr ? (double)X[(int64_t)new_tok[(int64_t)utt * c.N_max + t0 + r] * c.ldx + d] : 0.0;
-        }
-        __syncthreads();
-        {
-            const int w = tid >> 6, lane = tid & 63, nw = nt >> 6;
-            for (int r = w; r < nr; r += nw) {
-                const double v = bt.prior_rows ? bt.prior_rows[new_tok[(int64_t)utt * c.N_max + t0 + r]]
-                                               : fbb_prior_row<XT>(f, D, xs + r * D, lane);
-                if (lane == 0) lpr[r] = v;
-            }
-        }
-        __syncthreads();
-        if (nt >= 4 * 128 && KM <= 128) {
-            // few slots: four groups of threads take two rows each, four when the chunk holds sixteen tokens (k_fbb_assign)
-            auto rows_of_group = [&](auto NRC) {
-                constexpr int NR = decltype(NRC)::value;
-                const int k = tid & 127, r0 = NR * (tid >> 7);
-                if (k < KM && r0 < nr) {
-                    if (bt.cnt[k] > 0.0) {
-                        double acc[NR];
-#pragma unroll
-                        for (int r = 0; r < NR; r++) acc[r] = 0.0;
-                        if (F32) {
-                            float a32[NR];
-#pragma unroll
-                            for (int r = 0; r < NR; r++) a32[r] = 0.f;
-                            fbb_accumulate_rows32<NR>(bt, KM, k, D, xs + r0 * D, a32);
-#pragma unroll
-                            for (int r = 0; r < NR; r++) acc[r] = 0.6931471805599453 * (double)a32[r];
-                        } else
-                        fbb_accumulate_rows<COV, NR>(bt, KM, k, D, xs + r0 * D, acc);
-                        const double lc = bt.lconst[k], h = bt.half[k];
-#pragma unroll
-                        for (int r = 0; r < NR; r++)
-                            if (r0 + r < nr) ll[(int64_t)(r0 + r) * KM + k] = lc - h * acc[r];
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < NR; r++)
-                            if (r0 + r < nr) ll[(int64_t)(r0 + r) * KM + k] = lpr[r0 + r];
-                    }
-                }
-            };
-            if (rcap > FBB_R) rows_of_group(std::integral_constant<int, 4>());
-            else rows_of_group(std::integral_constant<int, 2>());
-        } else
-        for (int k = tid; k < KM; k += nt) {
-            if (bt.cnt[k] > 0.0) {
-                double acc[FBB_R];
-#pragma unroll
-                for (int r = 0; r < FBB_R; r++) acc[r] = 0.0;
-                if (F32) {
-                    float a32[FBB_R];
-#pragma unroll
-                    for (int r = 0; r < FBB_R; r++) a32[r] = 0.f;
-                    fbb_accumulate_rows32<FBB_R>(bt, KM, k, D, xs, a32);
-#pragma unroll
-                    for (int r = 0; r < FBB_R; r++) acc[r] = 0.6931471805599453 * (double)a32[r];
-                } else
-                fbb_accumulate<COV>(bt, KM, k, D, xs, acc);
-                const double lc = bt.lconst[k], h = bt.half[k];
-#pragma unroll
-                for (int r = 0; r < FBB_R; r++)
-                    if (r < nr) ll[(int64_t)r * KM + k] = lc - h * acc[r];
-            } else {
-#pragma unroll
-                for (int r = 0; r < FBB_R; r++)
-                    if (r < nr) ll[(int64_t)r * KM + k] = lpr[r];
-            }
-        }
+            fbb_token_ll<XT, COV, F32>(c, f, bt, utt, t0, nr, rcap, D, new_tok, xs, lpr, ll);
         }
         __syncthreads();
         if (probe_ll)           // segk_fbb_set_probe: the likelihood part of the logits, as the argmax below uses it
@@ -2287,8 +2170,11 @@ static int check_fbb_long(const segk_corpus *c, int n_slices_max)
 
 // Chunks and threads of the assignment kernels (k_fbb_assign, k_fbb_assign_map).  Tokens per chunk: as many likelihood rows
 // of K_max doubles as fit beside the `fixed_b` bytes of the rest (two workgroups per CU).  512 threads where the slots alone
-// would leave most of 256 idle and the tokens' draws are independent (no language model): four row groups in the likelihood
-// phase, a wave per token in the draw phase -- and chunks of sixteen tokens where those fit.
+// would leave most of 256 idle and the tokens' draws are independent (no language model): four row groups of four rows in
+// the likelihood phase (fbb_token_ll), a wave per token in the draw phase.  512 threads come with chunks of FBA_R = 16 tokens
+// only -- the row groups are written for that chunk.  Sixteen rows always fit where K_max <= 128: fixed_b is at most
+// (K_max + 16 D + 32) doubles and check_fbb caps D at 256, so fixed_b + 16 rows <= 8 (17 * 128 + 16 * 256 + 32) = 50 432
+// bytes of the 80 KiB.  Should a later D limit break that, the shape falls back to 256 threads and chunks of FBB_R or fewer.
 struct FbbChunks {
     int rcap, threads;
     size_t lds;
@@ -2297,9 +2183,8 @@ static FbbChunks fbb_assign_chunks(size_t fixed_b, int K_max, bool lm)
 {
     const size_t row_b = (size_t)K_max * sizeof(double);
     FbbChunks ch = {FBB_R, 256, 0};
+    if (K_max <= 128 && !lm && fixed_b + FBA_R * row_b <= 80 * 1024) ch = {FBA_R, 512, 0};
     while (ch.rcap > 1 && fixed_b + ch.rcap * row_b > 80 * 1024) ch.rcap >>= 1;
-    if (K_max <= 128 && !lm && ch.rcap == FBB_R) ch.threads = 512;
-    if (ch.threads == 512 && fixed_b + FBA_R * row_b <= 80 * 1024) ch.rcap = FBA_R;
     ch.lds = fixed_b + ch.rcap * row_b;
     return ch;
 }
@@ -2635,32 +2520,62 @@ int32_t segk_fbb_token_scores(segk_ctx *ctx, const segk_corpus *c, const segk_fb
                                     stream, fbb_cmap(bt, f->K_max) + f->K_max + 1, tiles_hint);
 }
 
+// What the slot entry points do before they launch: the arguments checked, the step's utterances mapped to workgroups
+// (p->m.off[s_n] == 0: nothing to launch), with cov_type 2 the token table of segk_fcb_token_ll formed, chunks and threads
+// chosen.  map_slots: segk_fbb_assign_map -- no language model, and no `red` in the fixed part of the kernel's LDS.
+struct FbbAssignPlan {
+    FbbMap m;
+    FbbChunks ch;
+    const double *fc_ll;
+    int fc_ucap;
+};
+static int32_t fbb_assign_plan(FbbAssignPlan *p, bool map_slots, segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f,
+                               const segk_fbatch *bt, int32_t s_lo, int32_t s_n, int32_t b, const int32_t *n_utts,
+                               const int32_t *new_tok, const int32_t *n_new, const float *ll_mat, int f32, void *stream)
+{
+    SEGK_REQUIRE(ctx, "context");
+    SEGK_REQUIRE(!ctx->probe_ll || ctx->probe_ll_ld >= f->K_max, "probe leading dimension");
+    int rc = check_fbb(c, f, bt, f32 ? nullptr : map_slots ? "segk_fbb_assign_map" : "segk_fbb_assign");
+    if (rc) return rc;
+    if (map_slots) {
+        if (f->lm_unigram) {
+            segk_set_error("segk_fbb_assign_map: there is no MAP assignment with a language model (the reference's bigram segmenter "
+                           "has no Viterbi mode)");
+            return SEGK_ERR_UNSUPPORTED;
+        }
+        SEGK_REQUIRE(!f32 || f->cov_type == 1, "the float32 token likelihoods are the diagonal (Student-t) ones");
+    }
+    p->ch = {};
+    p->fc_ll = nullptr;
+    p->fc_ucap = 0;
+    rc = make_map(&p->m, s_lo, s_n, n_utts, 1);
+    if (rc || p->m.off[s_n] == 0) return rc;
+    if (f->cov_type == 2) {
+        SEGK_REQUIRE(!ll_mat, "cov_type 2: the token likelihoods are the library's own (ll_mat must be NULL)");
+        rc = segk_fcb_token_ll(ctx, c, f, bt, s_lo, s_n, b, n_utts, new_tok, n_new, &p->fc_ll, &p->fc_ucap, stream);
+        if (rc) return rc;
+    }
+    // (the fixed part: the logits z or the prior terms pz, the token rows xs, their prior predictive lpr, the sixteen doubles of
+    // the sampled kernel's red)
+    p->ch = fbb_assign_chunks((size_t)(f->K_max + FBA_R * c->D + FBA_R + (map_slots ? 0 : 16)) * sizeof(double), f->K_max,
+                              f->lm_unigram != nullptr);
+    SEGK_REQUIRE(p->ch.lds <= 160 * 1024, "K_max too large for the LDS logits buffer");
+    return SEGK_OK;
+}
+
 static int32_t fbb_assign_impl(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,
                                int32_t s_n, int32_t b, const int32_t *n_utts, uint64_t sweep, double anneal_temp,
                                const int32_t *new_tok, const int32_t *n_new, const float *ll_mat, int64_t ll_ld, int f32,
                                void *stream)
 {
-    SEGK_REQUIRE(ctx, "context");
-    SEGK_REQUIRE(!ctx->probe_ll || ctx->probe_ll_ld >= f->K_max, "probe leading dimension");
-    int rc = check_fbb(c, f, bt, f32 ? nullptr : "segk_fbb_assign");
-    if (rc) return rc;
-    FbbMap m;
-    rc = make_map(&m, s_lo, s_n, n_utts, 1);
-    if (rc) return rc;
-    if (m.off[s_n] == 0) return SEGK_OK;
-    const double *fc_ll = nullptr;
-    int fc_ucap = 0;
-    if (f->cov_type == 2) {
-        SEGK_REQUIRE(!ll_mat, "cov_type 2: the token likelihoods are the library's own (ll_mat must be NULL)");
-        rc = segk_fcb_token_ll(ctx, c, f, bt, s_lo, s_n, b, n_utts, new_tok, n_new, &fc_ll, &fc_ucap, stream);
-        if (rc) return rc;
-    }
+    FbbAssignPlan p;
+    const int rc = fbb_assign_plan(&p, false, ctx, c, f, bt, s_lo, s_n, b, n_utts, new_tok, n_new, ll_mat, f32, stream);
+    if (rc || p.m.off[s_n] == 0) return rc;
+    const FbbMap &m = p.m;
+    const FbbChunks &ch = p.ch;
     const double alpha = f->lm_unigram ? f->lm_a : f->alpha;
     // timing-only ablation knob (development): 1 = one dimension, 2 = one token, 4 = no draw
     const int dbg = segk_dev_env("SEGK_FBB_DBG");       // -DSEGK_DEV builds only
-    // (the fixed part: the logits z, the token rows xs, their prior predictive lpr, the sixteen doubles of red)
-    const FbbChunks ch = fbb_assign_chunks((size_t)(f->K_max + FBA_R * c->D + FBA_R + 16) * sizeof(double), f->K_max, f->lm_unigram != nullptr);
-    SEGK_REQUIRE(ch.lds <= 160 * 1024, "K_max too large for the LDS logits buffer");
     // language model + matrix-core likelihoods: one wave per utterance (SEGK_FBB_ASSIGN_WAVE=0: the block-wide form)
     if (f->lm_unigram && ll_mat && dbg == 0 && segk_env_int("SEGK_FBB_ASSIGN_WAVE", 1) != 0 && 4 * (size_t)f->K_max * sizeof(double) <= 146 * 1024) {
         const size_t ldsw = 4 * (size_t)f->K_max * sizeof(double) + sizeof(int) * (size_t)(f->K_max + 2);
@@ -2682,7 +2597,7 @@ static int32_t fbb_assign_impl(segk_ctx *ctx, const segk_corpus *c, const segk_f
         SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbb_assign<XT, COV, F32>, ch.lds));                                         \
         hipLaunchKernelGGL((k_fbb_assign<XT, COV, F32>), dim3(m.off[s_n]), dim3(ch.threads), ch.lds, (hipStream_t)stream, *c, *f, *bt, \
                            m, b, sweep, alpha, anneal_temp, new_tok, n_new, ch.rcap, dbg, ll_mat, ll_ld, ctx->probe_ll,          \
-                           ctx->probe_ll_ld, fc_ll, fc_ucap);                                                                   \
+                           ctx->probe_ll_ld, p.fc_ll, p.fc_ucap);                                                               \
     } while (0)
     DISPATCH_XT(c, {
         if (f->cov_type == 0) SEGK_ASSIGN(0, 0);
@@ -2716,34 +2631,16 @@ int32_t segk_fbb_assign_map(segk_ctx *ctx, const segk_corpus *c, const segk_fbgm
                             const int32_t *n_new, int32_t f32_terms, void *stream)
 {
     (void)sweep;                  // no uniforms are consumed
-    SEGK_REQUIRE(ctx, "context");
-    SEGK_REQUIRE(!ctx->probe_ll || ctx->probe_ll_ld >= f->K_max, "probe leading dimension");
-    int rc = check_fbb(c, f, bt, f32_terms ? nullptr : "segk_fbb_assign_map");
-    if (rc) return rc;
-    if (f->lm_unigram) {
-        segk_set_error("segk_fbb_assign_map: there is no MAP assignment with a language model (the reference's bigram segmenter "
-                       "has no Viterbi mode)");
-        return SEGK_ERR_UNSUPPORTED;
-    }
-    SEGK_REQUIRE(!f32_terms || f->cov_type == 1, "the float32 token likelihoods are the diagonal (Student-t) ones");
-    FbbMap m;
-    rc = make_map(&m, s_lo, s_n, n_utts, 1);
-    if (rc) return rc;
-    if (m.off[s_n] == 0) return SEGK_OK;
-    const double *fc_ll = nullptr;
-    int fc_ucap = 0;
-    if (f->cov_type == 2) {
-        rc = segk_fcb_token_ll(ctx, c, f, bt, s_lo, s_n, b, n_utts, new_tok, n_new, &fc_ll, &fc_ucap, stream);
-        if (rc) return rc;
-    }
-    // (the fixed part: the prior terms pz, the token rows xs, their prior predictive lpr -- no red)
-    const FbbChunks ch = fbb_assign_chunks((size_t)(f->K_max + FBA_R * c->D + FBA_R) * sizeof(double), f->K_max, false);
-    SEGK_REQUIRE(ch.lds <= 160 * 1024, "K_max too large for the LDS logits buffer");
+    FbbAssignPlan p;
+    const int rc = fbb_assign_plan(&p, true, ctx, c, f, bt, s_lo, s_n, b, n_utts, new_tok, n_new, nullptr, f32_terms, stream);
+    if (rc || p.m.off[s_n] == 0) return rc;
+    const FbbMap &m = p.m;
+    const FbbChunks &ch = p.ch;
 #define SEGK_ASSIGN_MAP(COV, F32)                                                                                               \
     do {                                                                                                                        \
         SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbb_assign_map<XT, COV, F32>, ch.lds));                                     \
         hipLaunchKernelGGL((k_fbb_assign_map<XT, COV, F32>), dim3(m.off[s_n]), dim3(ch.threads), ch.lds, (hipStream_t)stream, *c, *f, \
-                           *bt, m, b, f->alpha, new_tok, n_new, ch.rcap, ctx->probe_ll, ctx->probe_ll_ld, fc_ll, fc_ucap);       \
+                           *bt, m, b, f->alpha, new_tok, n_new, ch.rcap, ctx->probe_ll, ctx->probe_ll_ld, p.fc_ll, p.fc_ucap);   \
     } while (0)
     DISPATCH_XT(c, {
         if (f->cov_type == 0) SEGK_ASSIGN_MAP(0, 0);

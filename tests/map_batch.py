@@ -50,6 +50,8 @@ def _case(kind, n_utt, D, K, nmax, B, S, N=None, N_range=None, cseed=200, **kw):
 LONG_CASES = {
     "fixed_small": _case("fixed", 24, 8, 10, 5, 3, 4, N_range=(3, 9)),          # one DPP row, K below a wave
     "diag_K65": _case("diag", 24, 8, 65, 5, 3, 4, N_range=(3, 9)),              # second slot per lane, tie on empty slots
+    # one thread per slot (K > 128) on diagonal terms, a chunk of eight tokens then a remainder; D = 16 + 4 + 3
+    "diag_K130": _case("diag", 24, 23, 130, 5, 3, 4, N_range=(3, 9)),
     "fixed_K300": _case("fixed", 19, 6, 300, 5, 5, 1, N_range=(3, 9)),          # winners that are the first empty slot
     "fixed_K1025": _case("fixed", 12, 6, 1025, 5, 2, 2, N_range=(3, 9)),        # bank beyond 1024
     "fixed_w20": _case("fixed", 8, 8, 10, 20, 2, 2, N=24),                      # window beyond one row of sixteen

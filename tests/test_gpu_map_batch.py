@@ -171,7 +171,7 @@ def _one_map_step(sw, seg, b):
     df.check_status()
 
 
-TOLERANCE = [("diag_K65", "f32", None), ("ragged_diag", "f32", None), ("fixed_small", "f32", None), ("fixed_small", "f16", 12)]
+TOLERANCE = [("diag_K65", "f32", None), ("diag_K130", "f32", None), ("ragged_diag", "f32", None), ("fixed_small", "f32", None), ("fixed_small", "f16", 12)]
 
 
 @pytest.mark.parametrize("name,prec,D", TOLERANCE, ids=["%s_%s" % (c[0], c[1]) for c in TOLERANCE])

@@ -135,6 +135,7 @@ CASES = [
     ("diag", "f32", 48, 39, 100, None),            # configs[1] shape: float32 Student-t token likelihoods, fast_dp
     ("diag", "f32", 48, 39, 100, "fused"),         # ... the Gibbs step as one launch (segk_fbb_step_diag32)
     ("diag", "f32", 40, 20, 160, "fused"),         # ... with three chunks of 64 slots
+    ("diag", "f32", 48, 39, 130, None),            # the first row beyond 128 slots: segk_fbb_assign_diag32 with one thread per slot
     ("fixed", "f16", 48, 39, 100, None),           # fp16x2 token likelihoods, block-wide draw kernel, fast_dp
     ("fixed", "f32", 48, 39, 100, None),           # fp32 MFMA span scores, fp64 token likelihoods, fast_dp
     ("bigram", "f16", 48, 100, 1000, None),        # configs[4] shape: one wave per utterance, hardware log / exp

@@ -11,6 +11,7 @@ Where the 1e-6 comes from: the suite holds the device's fp64 log-probabilities t
 device: if a seed fails it after some later change to the corpus generator, change the seed, never the threshold.
 
 Measured (smallest DP margin / smallest slot margin, corpus seed 200): fixed_small 3.6e-3 / 1.0e-2, diag_K65 1.1e-2 / 2.7e-1,
+diag_K130 3.0e-4 / 8.9e-3 (no tie on an occupied slot, 29 ties among empty slots, 16 occupied slots, 115 tokens in two sweeps),
 fixed_K300 3.2e-3 / 6.1e-2, fixed_K1025 2.3e-2 / 4.7e-2, fixed_w20 3.8e-4 / 5.0e-2, diag_w20 5.2e-4 / 3.2e-2, fixed_64_w30
 3.6e-5 / 2.6e-3, ragged_fixed 2.9e-6 / 4.3e-5, ragged_diag 2.7e-5 / 4.2e-4, diag_65 (corpus seed 168) 3.6e-5 / 1.1e-2,
 diag_100_w20 3.2e-6 / 2.1e-2, fixed_100_w40 1.7e-5 / 5.1e-2, diag_mindur_backtrack 3.4e-5 / 1.1e-3, chain_diag_D70
