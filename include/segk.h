@@ -62,8 +62,10 @@ const char *segk_last_error(void);
  *     accept it on a corpus with utterances
  *  14 cov_type 2 in the batch sampler (unigram, fp64 scores, D <= 64, K_max <= 1024, one process): segk_fbatch.partials /
  *     mean_t / q_t at other shapes (below), no structure grows; segk_fbb_prior_rows, _partials, _prepare, _score, _segment,
- *     _segment_map, _assign, _assign_map, _canonical accept it, every other segk_fbb_* entry point keeps refusing it      */
-#define SEGK_ABI_VERSION 14
+ * *     _segment_map, _assign, _assign_map, _canonical accept it, every other segk_fbb_* entry point keeps refusing it
+ *  15 segk_fbi_assign: the item step of the stand-alone FBGMM's batch sweeps; segk_fbb_partials / _prepare / _canonical accept
+ *     a corpus of items (no span tables, N_max = 1) with n_blocks = 1                                                       */
+#define SEGK_ABI_VERSION 15
 int32_t segk_abi_version(void);
 
 /* Timing of the MAIN launch of the MFMA score kernel (k_kmeans_score<..., 0>) with HIP events
@@ -803,6 +805,29 @@ int32_t segk_fbb_token_scores(segk_ctx *ctx, const segk_corpus *c, const segk_fb
  *     ll_out[(utt * N_max + t) * ll_ld + k]                                 (ll_out [dev] double [n_utt * N_max, ll_ld]).
  * NULL pointers (the default) switch a probe off.                                                                  */
 int32_t segk_fbb_set_probe(segk_ctx *ctx, double *alpha_out, double *ll_out, int64_t ll_ld);
+/* Batch Gibbs sweeps of the STAND-ALONE mixture model (ABI 15; FBGMM.gibbs_sample, fbgmm.py:288-463, as the blocked sampler
+ * above with "utterance" read as "item"; specification tests/fbgmm_items.py).  The items are presented as a corpus of
+ * one-landmark utterances: segk_corpus with n_utt = n_emb, N_max = 1 and NO span tables (vec_ids, durations, lengths,
+ * band_* NULL), new_tok[i] = i, n_new[i] = 1 where item i holds a slot and 0 where it does not; bt->utt_range holds the item
+ * ranges of the (slice, block) cells (bt->row_range the same numbers), bt->prior_rows is required.  The statistics are the
+ * segmenter's: segk_fbb_partials, segk_fbb_prepare(b), and segk_fbb_prepare(-1) + segk_fbb_canonical + segk_fbgmm_init_stats
+ * for the reference's view; on such a corpus they also take n_blocks = 1 (every item against the prior).
+ * This call is step b's item half, after segk_fbb_prepare(b) and before segk_fbb_partials(b): every considered item i of block
+ * b of the local slices [s_lo, s_lo + s_n) -- bt->slot[i] >= 0, or every item when consider_unassigned -- forms
+ * z_k = lms log(alpha / K_max + n_k) + log predictive_k(X[i]) over all K_max slots (fbgmm.py:436-440; an empty slot: the prior
+ * predictive), anneals it when anneal_temp != 1 (fbgmm.py:446-449), and draws its slot by the batch sampler's inverse-CDF walk
+ * on u01(bt->seed, sweep, i, 1) -- counter N_max + t of a one-landmark utterance, so the draws are those of segk_fbb_assign on
+ * the same rows as utterances.  bt->slot[i] and n_new[i] = 1 are written; an item not considered keeps -1 and 0.
+ * n_items [host] [s_n]: items of block b per local slice (the widths of bt->utt_range).  cov_type 0, 1 (D <= 256) and 2
+ * (D <= 64, K_max <= 1024; the likelihoods by the token-likelihood kernel of segk_fbb_assign); X float32 or float64; fp64
+ * arithmetic.  A language model (f->lm_unigram) is SEGK_ERR_UNSUPPORTED.  probe_ll (NULL in production) receives the likelihood
+ * part of the logits, probe_ll[i * probe_ld + k], k < K_max <= probe_ld, of every item of the block's tiles -- the role
+ * segk_fbb_set_probe plays for the segmenter.  One launch per 64 items x all slots; the logits of a tile live in LDS or, beyond
+ * a workgroup's budget, in a workspace of the context bounded by 64 MiB (a block of more tiles is walked in several launches).  */
+int32_t segk_fbi_assign(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt,
+                        int32_t s_lo, int32_t s_n, int32_t b, const int32_t *n_items, uint64_t sweep,
+                        double anneal_temp, int32_t consider_unassigned, const int32_t *new_tok,
+                        int32_t *n_new, double *probe_ll, int64_t probe_ld, void *stream);
 /* bigram table += sign * (transcripts of block b, all slices) from bt->lm_tok                  */
 int32_t segk_fbb_lm_apply(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f,
                           const segk_fbatch *bt, int32_t b, int32_t sign, void *stream);

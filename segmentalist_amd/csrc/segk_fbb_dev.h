@@ -1,8 +1,10 @@
 // segk_fbb_dev.h -- what the batch sampler's translation units share (segk_fbbatch.hip; segk_fullcov.hip for the
-// full-covariance forms of its kernels): the record of a (block, slice) cell, the workgroup -> (slice, index) map of a
-// launch, the specification's balanced tree.  Not part of the ABI.
+// full-covariance forms of its kernels; segk_fbitems.hip for the stand-alone model's item step): the record of a (block,
+// slice) cell, the workgroup -> (slice, index) map of a launch, the specification's balanced tree, the draw of one token's
+// slot.  Not part of the ABI.
 #pragma once
 #include "segk_internal.h"
+#include "segk_fb_common.h"
 
 // doubles of the partial sums of one (block, slice) cell: counts [K_max], sum x [K_max, D], then sum x^2 [K_max, D] or, with
 // full-covariance components (cov_type 2), the lower triangle of sum outer(x, x) per slot, packed [K_max, D (D + 1) / 2] --
@@ -74,6 +76,51 @@ static __device__ __forceinline__ void fbb_sum_slices(const segk_fbatch &bt, int
         for (int i = 0; i < 8; i++)
             if (s0 + i < S) my[(s0 + i) * stride] = a[i];
     }
+}
+
+// The slot of one token without a language model, by one wave: zr[k] holds the likelihood part of the logits of all K_max slots
+// (LDS or memory; overwritten).  The prior's term lms log(alpha / K_max + n_k) (fbgmm.py:436-440), the softmax, the annealing
+// (fbgmm.py:446-449) and the inverse-CDF walk on u01(seed, sweep, utt, j).  The sums keep the association of the block-wide
+// form at 256 threads (per wave of 64 consecutive slots a butterfly, the waves' results added in order), so the
+// probabilities -- and the draws -- are the bits of k_fbb_assign's wave-per-token branch (segk_fbbatch.hip), whose statements
+// these are: called from there instead, the function changed that kernel's generated code (instruction order), so the kernel
+// keeps its own copy and k_fbi_assign (a wave per item of a tile) calls this one.  Keep the two alike.  Result in all lanes.
+static __device__ __forceinline__ int fbb_draw_row(const segk_fbgmm &f, const segk_fbatch &bt, int KM, double prior_alpha, double zc_empty,
+                                                   double anneal_temp, double *zr, uint64_t sweep, uint64_t utt, uint64_t j, int lane)
+{
+    double mx = NEG_INF_D;
+    for (int k = lane; k < KM; k += 64) {
+        const double n = bt.cnt[k];
+        const double v = (n > 0.0 ? f.lms * log(prior_alpha / (double)KM + n) : zc_empty) + zr[k];      // fbgmm.py:436-440
+        zr[k] = v;
+        mx = v > mx ? v : mx;
+    }
+    mx = fb_wave_max(mx, false);
+    auto sum_exp = [&](double shift) -> double {       // sum_k exp(zr[k] - shift) in the order of block_sum at 256 threads
+        double tot = 0.0;
+        for (int cw = 0; cw < 4 && cw * 64 < KM; cw++) {
+            double sv = 0.0;
+            for (int k = cw * 64 + lane; k < KM; k += 256) sv += exp(zr[k] - shift);
+            sv = fb_wave_sum(sv);
+            tot = cw == 0 ? sv : tot + sv;
+        }
+        return tot;
+    };
+    double lse = log(sum_exp(mx)) + mx;
+    if (anneal_temp != 1.0) {                           // fbgmm.py:446-449
+        double mx2 = NEG_INF_D;
+        for (int k = lane; k < KM; k += 64) {
+            const double v = (1. / anneal_temp) * (zr[k] - lse);
+            zr[k] = v;
+            mx2 = v > mx2 ? v : mx2;
+        }
+        mx2 = fb_wave_max(mx2, false);
+        lse = log(sum_exp(mx2)) + mx2;
+    }
+    for (int k = lane; k < KM; k += 64) zr[k] = exp(zr[k] - lse);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    return fb_draw_chunked(zr, KM, segk_u01(bt.seed, sweep, utt, j), lane);
 }
 
 // segk_fullcov.hip: the cov_type 2 forms of the segk_fbb_* entry points a unigram step uses (arguments checked by the callers

@@ -1403,6 +1403,7 @@ __global__ __launch_bounds__(512) void k_fbb_assign(segk_corpus c, segk_fbgmm f,
             const int w = tid >> 6, lane = tid & 63, nw = nt >> 6;
             for (int r = w; r < ((dbg & 2) ? 1 : nr); r += nw) {
                 const int64_t e = new_tok[(int64_t)utt * c.N_max + t0 + r];
+                // (fbb_draw_row of segk_fbb_dev.h restates the statements from here to the draw for k_fbi_assign: keep the two alike)
                 double *zr = ll + (int64_t)r * KM;
                 double mx = NEG_INF_D;
                 for (int k = lane; k < KM; k += 64) {
@@ -2129,7 +2130,10 @@ static int check_fbb(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatc
     SEGK_REQUIRE(c->D > 0 && c->D <= 64 * FBB_MAXCH, "batch mode supports D <= 256");
     SEGK_REQUIRE(c->N_max > 0, "corpus without landmarks");       // (more than 64 per utterance: check_fbb_long)
     SEGK_REQUIRE(bt->n_slices >= 1 && bt->n_slices <= 16, "n_slices must be in 1..16");
-    SEGK_REQUIRE(bt->n_blocks >= 2, "n_blocks must be >= 2 (with one block nothing is conditioned on)");
+    // (a corpus of items -- no span tables: the stand-alone batch sweep, segk_fbi_assign -- may have one block: its specification
+    // defines that sweep, every item against the prior)
+    SEGK_REQUIRE(bt->n_blocks >= 2 || (bt->n_blocks == 1 && !c->vec_ids && !c->band_ids),
+                 "n_blocks must be >= 2 (with one block nothing is conditioned on)");
     SEGK_REQUIRE(f->kconst != NULL, "kconst buffer missing");
     return SEGK_OK;
 }
@@ -2227,9 +2231,12 @@ int32_t segk_fbb_partials(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm 
     // many slots: bucket the tokens by slot first (k_fbb_sort), then every slot sums its own list; SEGK_FBB_SORT=0: the
     // one-step kernel.  LDS of the sort: 16 waves x K_max counters.
     const size_t lds_sort = ((size_t)FBS_WAVES * f->K_max + FBS_WAVES + 1) * sizeof(int32_t);
-    // (full-covariance components: always -- a thread per triangle entry then walks the slot's own list)
+    // (full-covariance components: always -- a thread per triangle entry then walks the slot's own list.  A corpus of items --
+    // no span tables, one landmark: the stand-alone batch sweep -- at every K_max <= 1024: a block is thousands of one-token
+    // "utterances", which the one-step kernel walks four at a time per (slice, slot) wave)
+    const bool items = !c->vec_ids && !c->band_ids && c->N_max == 1;
     if (f->cov_type == 2 ||
-        (ctx && f->K_max >= 256 && f->K_max <= 1024 && lds_sort <= 150 * 1024 && segk_env_int("SEGK_FBB_SORT", 1) != 0)) {
+        (ctx && (f->K_max >= 256 || items) && f->K_max <= 1024 && lds_sort <= 150 * 1024 && segk_env_int("SEGK_FBB_SORT", 1) != 0)) {
         const int64_t stride = (int64_t)c->n_utt * c->N_max;             // more than any (slice, block) can hold
         const size_t need = ((size_t)s_n * stride + (size_t)s_n * (f->K_max + 1)) * sizeof(int32_t);
         if (ctx->fbs_bytes < need) {

@@ -1282,3 +1282,130 @@ class FbgmmBatchSweeper(object):
             df.lm._unigram.zero_()
             df.lm._unigram[:K] = self.cnt[occ].round().long()
         check(L.segk_fbgmm_init_stats(ctx, cp, C.byref(df.f), st))
+
+
+class FbgmmItemSweeper(object):
+    """Batch-synchronous sweeps of the STAND-ALONE mixture model (FBGMM.gibbs_sample(sync="batch")): FbgmmBatchSweeper with
+    "utterance" read as "item" -- specification tests/fbgmm_items.py, C ABI `segk_fbi_assign` (include/segk.h).
+
+    The items 0..N-1 are cut into `n_stat_blocks` slices x `n_gibbs_blocks` blocks.  Step b: segk_fbb_prepare(b) (the
+    statistics of all other blocks), segk_fbi_assign (logits and draw of every considered item of block b),
+    segk_fbb_partials(b).  The statistics kernels see the items as a corpus of one-landmark utterances: new_tok[i] = i,
+    n_new[i] = does item i hold a slot.  One process, fp64 scores, no language model."""
+
+    def __init__(self, df, n_gibbs_blocks=8, n_stat_blocks=8, seed=0, group=None):
+        torch = _torch()
+        c = df.corpus
+        if c.n_utt:
+            raise SegkError("this mixture model is the acoustic model of a segmenter (its corpus carries utterances): batch "
+                            "sweeps of its tokens are the segmenter's gibbs_sample(sync=\"batch\")")
+        world = get_comm(group).world
+        if world > 1:
+            raise SegkError("the stand-alone mixture model's batch sweeps run in one process only (%d ranks)" % world)
+        if df.lm is not None:
+            raise SegkError("the stand-alone mixture model's batch sweeps take no language model")
+        self.fullcov = df.cov_type == 2
+        if self.fullcov and c.D > 64:
+            raise SegkError("full-covariance components (cov_type 2) support D <= 64, got %d" % c.D)
+        if self.fullcov and df.K_max > 1024:
+            raise SegkError("the batch sampler takes full-covariance components (cov_type 2) with K_max <= 1024, got %d"
+                            % df.K_max)
+        self.S, self.B = int(n_stat_blocks), int(n_gibbs_blocks)
+        if not (1 <= self.S <= 16 and self.B >= 1):
+            raise SegkError("n_stat_blocks must be in 1..16 and n_gibbs_blocks >= 1 (got %d, %d)" % (self.S, self.B))
+        dev = _dev()
+        self.df = df
+        N, K, D = c.n_emb, df.K_max, c.D
+        self.N = N
+        # the items as one-landmark utterances: the corpus structure with n_utt = N, N_max = 1 and no span tables
+        self.c = _abi.Corpus.from_buffer_copy(c.c)
+        self.c.n_utt, self.c.N_max = N, 1
+        sb = [(s * N) // self.S for s in range(self.S + 1)]
+        ur = np.zeros((self.S, self.B, 2), np.int32)
+        for s in range(self.S):
+            n_s = sb[s + 1] - sb[s]
+            for b in range(self.B):
+                ur[s, b] = (sb[s] + (b * n_s) // self.B, sb[s] + ((b + 1) * n_s) // self.B)
+        self.utt_range_np = ur
+        self.utt_range = to_dev(ur)
+        self.rec = K * (1 + D + D * (D + 1) // 2) if self.fullcov else K * (2 * D + 1)
+        f64 = torch.float64
+        self.partials = torch.zeros((self.B, self.S, self.rec), dtype=f64, device=dev)
+        self.cnt = torch.zeros(K, dtype=f64, device=dev)
+        self.mean_t = torch.zeros((K, D) if self.fullcov else (D, K), dtype=f64, device=dev)
+        self.q_t = torch.zeros((K, D, D) if self.fullcov else (D, K), dtype=f64, device=dev)
+        self.lconst = torch.zeros(K, dtype=f64, device=dev)
+        self.zconst = torch.zeros(K, dtype=f64, device=dev)
+        self.half = torch.zeros(K, dtype=f64, device=dev)
+        self.scal = torch.zeros(2, dtype=f64, device=dev)
+        self.slot = torch.zeros(N, dtype=torch.int32, device=dev)
+        self.remap = torch.zeros(K, dtype=torch.int32, device=dev)
+        self.new_tok = torch.arange(N, dtype=torch.int32, device=dev)
+        self.n_new = torch.zeros(N, dtype=torch.int32, device=dev)
+        self.f = _abi.FbgmmDev.from_buffer_copy(df.f)
+        self.prior_rows = torch.zeros(N, dtype=f64, device=dev)
+        check(df._L.segk_fbb_prior_rows(df._ctx, C.byref(self.c), C.byref(self.f), self.prior_rows.data_ptr(), _abi.stream()))
+        self.bt = _abi.FbatchDev(
+            prior_rows=self.prior_rows.data_ptr(), n_slices=self.S, n_blocks=self.B, u_max=0, fast_dp=0,
+            utt_range=self.utt_range.data_ptr(), row_range=self.utt_range.data_ptr(), partials=self.partials.data_ptr(),
+            cnt=self.cnt.data_ptr(), mean_t=self.mean_t.data_ptr(), q_t=self.q_t.data_ptr(), lconst=self.lconst.data_ptr(),
+            zconst=self.zconst.data_ptr(), half=self.half.data_ptr(), scal=self.scal.data_ptr(), slot=self.slot.data_ptr(),
+            seed=int(seed) & (2 ** 64 - 1))
+        I32 = C.c_int32 * self.S
+        self._n_items = [I32(*[int(ur[s, b, 1] - ur[s, b, 0]) for s in range(self.S)]) for b in range(self.B)]
+        self.probe_ll = None             # a [N, K_max] float64 device tensor: the likelihood part of the logits (tests)
+        self.in_batch_state = False
+        self.sweep_index = 0
+
+    def _args(self):
+        df = self.df
+        self.f.alpha, self.f.lms = df.f.alpha, df.f.lms
+        return df._L, df._ctx, C.byref(self.c), C.byref(self.f), C.byref(self.bt), _abi.stream()
+
+    def enter(self):
+        """Build the batch state (slots, all partial sums) from the sequential-mode assignments."""
+        torch = _torch()
+        L, ctx, cp, fp, bp, st = self._args()
+        self.slot.copy_(self.df.assignments)
+        self.n_new.copy_((self.slot >= 0).to(torch.int32))
+        for b in range(self.B):
+            check(L.segk_fbb_partials(ctx, cp, fp, bp, 0, self.S, b, ptr(self.new_tok), ptr(self.n_new), st))
+        self.in_batch_state = True
+
+    def sweep(self, anneal_temp=1.0, consider_unassigned=True):
+        """One sweep = n_gibbs_blocks steps, all enqueued on the current stream."""
+        if not self.in_batch_state:
+            self.enter()
+        L, ctx, cp, fp, bp, st = self._args()
+        pl = self.probe_ll
+        for b in range(self.B):
+            check(L.segk_fbb_prepare(ctx, cp, fp, bp, b, st))
+            check(L.segk_fbi_assign(ctx, cp, fp, bp, 0, self.S, b, self._n_items[b], self.sweep_index, float(anneal_temp),
+                                    1 if consider_unassigned else 0, ptr(self.new_tok), ptr(self.n_new), ptr(pl),
+                                    pl.shape[1] if pl is not None else 0, st))
+            check(L.segk_fbb_partials(ctx, cp, fp, bp, 0, self.S, b, ptr(self.new_tok), ptr(self.n_new), st))
+        self.sweep_index += 1
+
+    cell_partials = FbgmmBatchSweeper.cell_partials
+
+    def totals(self):
+        """(counts per slot as float64 numpy, total, occupied) of the current state."""
+        L, ctx, cp, fp, bp, st = self._args()
+        check(L.segk_fbb_prepare(ctx, cp, fp, bp, -1, st))
+        sc = self.scal.cpu().numpy()
+        return self.cnt.cpu().numpy(), float(sc[0]), int(sc[1])
+
+    def invalidate(self):
+        """The sequential-mode state was mutated: rebuild the batch state before the next sweep."""
+        self.in_batch_state = False
+
+    def materialise(self):
+        """The reference's view of the current batch state, without touching it: contiguous component labels in
+        `assignments` / K and the sequential-mode statistics rebuilt from them (Components.__init__ order)."""
+        if not self.in_batch_state:
+            return
+        df = self.df
+        L, ctx, cp, fp, bp, st = self._args()
+        check(L.segk_fbb_prepare(ctx, cp, fp, bp, -1, st))
+        check(L.segk_fbb_canonical(ctx, cp, C.byref(df.f), bp, ptr(self.remap), st))
+        check(L.segk_fbgmm_init_stats(ctx, df._cp(), C.byref(df.f), st))

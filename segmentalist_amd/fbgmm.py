@@ -17,7 +17,19 @@ logger = logging.getLogger(__name__)
 
 
 class FBGMM(object):
-    def __init__(self, X, prior, alpha, K, assignments="rand", covariance_type="full", lms=1.0, _corpus=None):
+    def __init__(self, X, prior, alpha, K, assignments="rand", covariance_type="full", lms=1.0, _corpus=None,
+                 sync="sequential", n_gibbs_blocks=8, n_stat_blocks=8, batch_seed=0):
+        """fbgmm.py:43-91.  sync: the mode of gibbs_sample -- "sequential" is the reference's serial chain over the items
+        (draw for draw); "batch" the batch-synchronous blocked Gibbs sampler specified in tests/fbgmm_items.py (the items cut
+        into n_stat_blocks slices x n_gibbs_blocks blocks, every block resampled in parallel against the statistics of all
+        other blocks, uniforms from the counter-based stream of batch_seed).  The two modes mix freely: gibbs_sample(...,
+        sync=...) chooses per call, batch_sweep_async() / materialise() are the asynchronous form.  Direct calls of
+        components.add_item / del_item between batch sweeps are not intercepted: call materialise() first; the next batch
+        sweep then has to re-enter from the serial state (`_leave_batch()`)."""
+        assert sync in ("sequential", "batch")
+        self.sync = sync
+        self._batch_args = (n_gibbs_blocks, n_stat_blocks, batch_seed)
+        self._sweeper = None
         self.alpha = alpha
         self.prior = prior
         self.covariance_type = covariance_type
@@ -27,6 +39,8 @@ class FBGMM(object):
 
     def setup_components(self, K, assignments="rand", X=None):
         """fbgmm.py:93-137."""
+        self._leave_batch()
+        self._sweeper = None                # (bound to the components it was built from)
         if X is None:
             assert hasattr(self, "components")
             X = self.components.X
@@ -63,25 +77,59 @@ class FBGMM(object):
     def log_marg(self):
         return self.log_prob_z() + self.log_prob_X_given_z()
 
+    # batch mode ------------------------------------------------------------------------------------
+    def _get_sweeper(self):
+        if self._sweeper is None:
+            from .device import FbgmmItemSweeper
+            B, S, seed = self._batch_args
+            self._sweeper = FbgmmItemSweeper(self.components.dev, B, S, seed)
+        return self._sweeper
+
+    def batch_sweep_async(self, anneal_temp=1, consider_unassigned=True):
+        """Enqueue one batch-synchronous sweep over the items; results stay on the device (materialise() brings
+        `components` up to date)."""
+        self._get_sweeper().sweep(float(anneal_temp), consider_unassigned)
+
+    def materialise(self):
+        """Bring the reference's view (components.K / assignments / statistics) up to date with the batch state."""
+        if self._sweeper is not None:
+            self._sweeper.materialise()
+
+    def _leave_batch(self):
+        if getattr(self, "_sweeper", None) is not None and self._sweeper.in_batch_state:
+            self.materialise()
+            self._sweeper.invalidate()
+
     # hot path --------------------------------------------------------------------------------------
     def log_marg_i(self, i):
         """fbgmm.py:256-285 (A4), on the device."""
         assert i != -1
+        self._leave_batch()
         return float(self.components.dev.log_marg_rows([i])[0])
 
     def gibbs_sample_inside_loop_i(self, i, anneal_temp=1):
         """fbgmm.py:422-463 (A10); consumes one random.random() like the reference."""
+        self._leave_batch()
         self.components.dev.assign_item(i, random.random(), anneal_temp, map_assign=False)
 
     def map_assign_i(self, i):
         """fbgmm.py:465-494."""
+        self._leave_batch()
         self.components.dev.assign_item(i, 0.0, 1.0, map_assign=True)
 
     def gibbs_sample(self, n_iter, consider_unassigned=True, anneal_schedule=None, anneal_start_temp_inv=0.1,
-                     anneal_end_temp_inv=1, n_anneal_steps=-1):
+                     anneal_end_temp_inv=1, n_anneal_steps=-1, sync=None):
         """fbgmm.py:288-420 on the device: per iteration one kernel walks the items in index order
         (cache statistics, del_item, logits, draw, restore or add_item); the uniforms are the
-        `random.random()` values the reference would consume -- one per considered item."""
+        `random.random()` values the reference would consume -- one per considered item.
+        sync: None = the mode the object was built with; "batch" = the sweeps of this call as batch-synchronous sweeps
+        (no random.random() is consumed), the record taken from the reference's view after every sweep."""
+        assert sync in (None, "sequential", "batch")
+        sync = self.sync if sync is None else sync
+        if sync == "batch":
+            self._get_sweeper()             # (the refusals, before anything runs)
+        else:
+            self._leave_batch()
         record_dict = {k: [] for k in ["sample_time", "log_marg", "log_prob_z", "log_prob_X_given_z",
                                        "anneal_temp", "components"]}
         start_time = time.time()
@@ -102,10 +150,15 @@ class FBGMM(object):
         dev = c.dev
         for i_iter in range(n_iter):
             anneal_temp = next(get_anneal_temp, anneal_end_temp_inv)
-            n_draws = c.N if consider_unassigned else int(np.count_nonzero(c.assignments != -1))
-            used = dev.gibbs_items([random.random() for _ in range(n_draws)], consider_unassigned, anneal_temp)
-            dev.check_status()
-            assert used == n_draws
+            if sync == "batch":
+                self.batch_sweep_async(anneal_temp, consider_unassigned)
+                self.materialise()              # the record reads the reference's view
+                dev.check_status()
+            else:
+                n_draws = c.N if consider_unassigned else int(np.count_nonzero(c.assignments != -1))
+                used = dev.gibbs_items([random.random() for _ in range(n_draws)], consider_unassigned, anneal_temp)
+                dev.check_status()
+                assert used == n_draws
             record_dict["sample_time"].append(time.time() - start_time)
             start_time = time.time()
             record_dict["log_marg"].append(self.log_marg())
