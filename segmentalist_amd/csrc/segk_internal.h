@@ -92,6 +92,19 @@ struct segk_ctx {
     int delta_valid;             // the state in delta_buf / hint_part is that of the call delta_key describes
     const void *delta_key[6];    // row image, float32 rows, tile image, means, cand.k, cand.s
     int64_t delta_key_n[5];      // row0, n, n_emb, K_max, D
+    // A pending prep: segk_kmeans_batch_finalize has run the delta prep for the NEXT hinted call inside k_batch_post, for the
+    // tuple in delta_key and with what is recorded here; the hinted call that matches all of it skips its k_delta_prep launch.
+    // The first hinted call after it consumes it, used or not: one that cannot take it over but has valid state repeats the prep
+    // as a launch of its own (`redo`: k_batch_post's has refreshed the means' snapshot and moved the counters on; it left what
+    // it found in spare control words).  Dropped (segk_delta_pending_drop) by every entry that can write
+    // `means`, the tile images, K, cand or the delta buffer behind its back:
+    //   segk_kmeans_prepare, segk_kmeans_mark_duplicates, segk_kmeans_init_stats, segk_kmeans_update_utt,
+    //   segk_kmeans_sequential_sweep, segk_kmeans_add_item, segk_kmeans_del_item, segk_kmeans_clean_components,
+    //   segk_kmeans_del_component, another segk_kmeans_batch_finalize, any score call but the hinted one (segk_kmeans_filter),
+    //   a reallocation of the delta buffer or of hint_part (launch_delta_prep).
+    int delta_pending;           // 1: as above; 2: dropped after k_batch_post ran it -- the next prep on this state repeats it
+    const void *delta_pending_remap, *delta_pending_K, *delta_pending_stream;
+    int delta_pending_cap, delta_pending_budget, delta_pending_seq;
     volatile int32_t *delta_host;    // host-mapped [4]: last call's mode, changed columns, packed tiles, positions the hint waves skipped
     int32_t *delta_host_dev;
     void *hint_fb;               // per-XCD shares and wave lifetimes of the matrix kernel's last launches, [3][8] floats + [3][8] uint32

@@ -48,6 +48,7 @@ int32_t segk_kmeans_filter(segk_ctx *ctx, const segk_corpus *c, const segk_kmean
     if (rc) return rc;
     if (n <= 0) return SEGK_OK;
     ctx->delta_valid = 0;                              // any score call but the hinted one drops the delta pass's state
+    segk_delta_pending_drop(ctx);
     hipStream_t st = (hipStream_t)stream;
     // 4-wave workgroups, two per CU: the two waves sharing a SIMD belong to DIFFERENT workgroups
     // and drift apart, covering each other's barrier/staging gaps.  (Measured: an 8-wave
@@ -139,6 +140,7 @@ int32_t segk_kmeans_sequential_sweep(segk_ctx *ctx, const segk_corpus *c, segk_k
     SEGK_REQUIRE(order && n_order >= 0 && cand && cand->k && cand->s && keys_scratch, "sequential sweep operands");
     SEGK_REQUIRE(c->vec_ids && c->lengths && c->n_utt > 0, "corpus without utterances");
     ctx->delta_valid = 0;
+    segk_delta_pending_drop(ctx);
     if (c->x_dtype != SEGK_F32) {
         segk_set_error("segk_kmeans_sequential_sweep: float32 data only (use the per-utterance calls for float64)");
         return SEGK_ERR_UNSUPPORTED;

@@ -793,6 +793,181 @@ static inline bool segk_hint_plan(int K_max, int ks, int n_tiles, HintPlan *p)
     return p->n_ranges <= SEGK_HINT_MAX_RANGES;
 }
 int segk_dispatch_score_hint(segk_ctx *ctx, const ScoreArgs &A, const int32_t *remap, const int32_t *K_dev, int64_t n_emb, int ks, hipStream_t st);
+
+// ---- delta score pass: what changed since the base pass (segk_score_hint.hip; the control words: there) ----------------------
+// The prep in front of K1, as a kernel of its own (k_delta_prep) or inside k_batch_post (segk_stats.hip), which has just
+// finished the images and follows the kernel that wrote `means`: the same three bodies.
+#define SEGK_DELTA_MODE 1            /* K1 multiplies the packed changed columns only */
+#define SEGK_DELTA_SKIP 2            /* hint_out and snap_means32 are the previous call's, the relabelling is the identity */
+#define SEGK_PREP_THREADS 256
+#define SEGK_PREP_COLS 4            /* at most 32 * SEGK_PREP_COLS tiles (four LDS ranges of 32) */
+struct DeltaPrepArgs {
+    const float *tiles_hdr;         // tiles_b3 (header, then the tiles)
+    int n_tiles, stride;            // stride: floats per tile of the global image
+    int K_max, D;
+    const float *means32;
+    const int32_t *remap;
+    const int32_t *K_dev;           // [1] active components (NULL: all K_max)
+    int valid;                      // the state (snapshot, part_base, lab_base) belongs to this call's tuple
+    int hint_valid;                 // hint_out and snap_means32 are the previous call's on the same tuple
+    int cap;                        // packed tiles at most
+    int budget;                     // packed tiles multiplied since the base at most
+    int seq;                        // number of this launch on the context (the parity of the means-changed counters)
+    int redo;                       // this prep repeats the one k_batch_post ran (same seq), which the call could not take over
+    int32_t *ctl, *colchg, *meanchg;    // (ctl NULL in k_batch_post's arguments: no prep in that launch)
+    float *snap_img;                // [4 floats: image exponent][n_tiles][KS * 256 + 32]
+    float *packed;                  // [n_tiles][stride]
+    float *snap_means;              // [K_max][D]
+};
+struct DeltaPrepLds { int chg[32], slot[32], nonid, last, n_chg, n_nonid, old[5]; };
+
+// Workgroup `wg` of `n_wg` (SEGK_PREP_THREADS threads): the rows of the float32 `means` against their copy of the previous call
+// (a wave per row), for the hint waves, and the copy refreshed.  (redo: the copy is already that of the prep this one repeats;
+// a row has changed since the previous call if that prep found so or this one does.)
+static __device__ __forceinline__ void delta_prep_means_rows(const DeltaPrepArgs &P, int wg, int n_wg)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr int NWV = SEGK_PREP_THREADS / 64;
+    for (int k = wg * NWV + wave; k < P.K_max; k += n_wg * NWV) {
+        const int *cur = (const int *)(P.means32 + (int64_t)k * P.D);
+        int *snap = (int *)(P.snap_means + (int64_t)k * P.D);
+        bool chg = false;
+        for (int d = lane; d < P.D; d += 64) {
+            const int c = cur[d];
+            chg |= c != snap[d];
+            snap[d] = c;
+        }
+        const bool any = __any(chg);
+        if (lane == 0) {
+            const bool before = P.redo && P.meanchg[k] != 0;
+            P.meanchg[k] = (any || before || !P.hint_valid) ? 1 : 0;
+            if (any) atomicAdd(P.ctl + 5 + (P.seq & 1), 1);
+        }
+    }
+}
+
+// A workgroup per tile `t` (a lane per (lane half, column), the KS k-steps over the four waves): every column of the image K1
+// multiplies against the snapshot of the base pass, bit for bit, and the tile's 32 entries of the relabelling table against
+// the identity.  ONE returning atomic per workgroup (ctl[16..17] as a 64-bit word: changed columns so far | tickets << 32 |
+// workgroups with a relabelled entry << 48) hands out the tile's packed slots, tells the workgroup that arrives last that it
+// is the last, and gives it both totals: no fence, no second round trip -- what the workgroups store is read by the next
+// kernel only.  The changed columns are copied to their slots at once (a call that turns out FULL never reads them).
+// e_cur: the exponent of the image as it is NOW -- the caller's to know: inside k_batch_post header word 0 may be rewritten by
+// tile 0's workgroup in the same launch.  -> this workgroup arrived last: delta_prep_mode is its to run.
+static __device__ __forceinline__ bool delta_prep_tile(const DeltaPrepArgs &P, const int KS, const int t, const int e_cur, DeltaPrepLds &S)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr int NWV = SEGK_PREP_THREADS / 64;
+    const int TL = KS * 256 + 32, c_off = KS * 512;
+    const int c = lane & 31;
+    const float *g = P.tiles_hdr + 1024 + (int64_t)t * P.stride;
+    const float *q = P.snap_img + 4 + (int64_t)t * TL;
+    // (redo: the prep this one repeats may have moved the snapshot's exponent on; it left the one it found in ctl[18])
+    const bool all = !P.valid || e_cur != (P.redo ? P.ctl[18] : ((const int *)P.snap_img)[0]);
+    if (tid < 32) S.chg[tid] = 0;
+    if (tid == 0) S.nonid = 0;
+    __syncthreads();
+    if (!all) {
+        bool chg = false;
+        for (int ks = wave; ks < KS; ks += NWV) {
+            const int4 a = *reinterpret_cast<const int4 *>(g + ks * 512 + lane * 4);
+            const int4 b = *reinterpret_cast<const int4 *>(q + ks * 256 + lane * 4);
+            chg |= a.x != b.x || a.y != b.y || a.z != b.z || a.w != b.w;
+        }
+        if (tid < 32) chg |= __float_as_int(g[c_off + c]) != __float_as_int(q[KS * 256 + c]);
+        if (chg) atomicOr(&S.chg[c], 1);
+    }
+    if (P.remap && tid >= SEGK_PREP_THREADS - 32) {
+        // the labels rows can carry: below the number of active components at the previous call, or now (the batch finalize
+        // rewrites the table's entries beyond as it compacts freshly emptied rows: no row names those)
+        int K_lab = P.K_dev ? *P.K_dev : P.K_max;
+        const int K_prev = P.ctl[P.redo ? 15 : 8];
+        if (K_lab < K_prev) K_lab = K_prev;
+        if (K_lab > P.K_max || !P.valid) K_lab = P.K_max;
+        const int k = t * 32 + c;
+        if (k < K_lab && P.remap[k] != k) S.nonid = 1;
+    }
+    __syncthreads();
+    if (wave == 0) {
+        const bool chg = lane < 32 && (all || S.chg[lane] != 0);
+        if (lane < 32) P.colchg[t * 32 + lane] = chg ? 1 : 0;
+        const unsigned long long mask = __ballot(chg);
+        unsigned int base = 0;
+        if (lane == 0) {
+            // what the previous call left, for the last workgroup (read in front of the ticket: these words are written by the
+            // last workgroup alone, behind every ticket; redo: as the prep this one repeats found them)
+            S.old[0] = P.ctl[P.redo ? 12 : 5 + ((P.seq + 1) & 1)];
+            S.old[1] = P.ctl[P.redo ? 13 : 4];
+            S.old[2] = P.ctl[P.redo ? 14 : 7];
+            S.old[3] = P.ctl[P.redo ? 15 : 8];
+            S.old[4] = P.redo ? P.ctl[18] : ((const int *)P.snap_img)[0];
+            const int n_own = __popcll(mask), nonid = S.nonid != 0 ? 1 : 0;
+            const unsigned long long old = atomicAdd(reinterpret_cast<unsigned long long *>(P.ctl + 16),
+                                                     (unsigned long long)n_own | (1ull << 32) | ((unsigned long long)nonid << 48));
+            base = (unsigned int)old;
+            S.last = (int)((old >> 32) & 0xffffull) == P.n_tiles - 1 ? 1 : 0;
+            S.n_chg = (int)base + n_own;
+            S.n_nonid = (int)(old >> 48) + nonid;
+        }
+        base = __shfl(base, 0);
+        if (lane < 32) S.slot[lane] = chg ? (int)base + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0)) : -1;
+    }
+    __syncthreads();
+    {
+        const int sl = S.slot[c];
+        if (P.valid && sl >= 0 && sl < P.cap * 32) {
+            float *o = P.packed + (int64_t)(sl >> 5) * P.stride;
+            const int l2 = (lane & 32) + (sl & 31);
+            for (int ks = wave; ks < KS; ks += NWV)
+                *reinterpret_cast<int4 *>(o + ks * 512 + l2 * 4) = *reinterpret_cast<const int4 *>(g + ks * 512 + lane * 4);
+            if (tid < 32) o[c_off + (sl & 31)] = g[c_off + c];
+        }
+    }
+    return S.last != 0;
+}
+
+// The tile workgroup that arrived last (both totals in S): the mode word that says which parameter set K1's launch takes, and
+// the counters -- with what it found in ctl[12..15] and [18], for a prep that has to repeat this one (redo).
+static __device__ __forceinline__ void delta_prep_mode(const DeltaPrepArgs &P, const int KS, const int e_cur, DeltaPrepLds &S)
+{
+    const int tid = threadIdx.x, c_off = KS * 512;
+    const int n_chg = S.n_chg, n_packed = (n_chg + 31) >> 5;
+    const bool nonid = S.n_nonid != 0;
+    // (moved_prev: the counter of the previous call's parity -- complete, that launch is over; this launch's row workgroups
+    // use the other)
+    const int moved_prev = S.old[0], acc = S.old[1], chg_prev = S.old[2];
+    const bool at_rest = n_chg > 0 && n_chg == chg_prev && moved_prev == 0;
+    const bool delta = P.valid && !nonid && n_packed <= P.cap && !at_rest && acc + n_packed <= P.budget;
+    if (tid == 0) {
+        P.ctl[12] = moved_prev; P.ctl[13] = acc; P.ctl[14] = chg_prev; P.ctl[15] = S.old[3]; P.ctl[18] = S.old[4];
+        P.ctl[4] = delta ? acc + n_packed : 0;
+        P.ctl[5 + ((P.seq + 1) & 1)] = 0;
+        P.ctl[7] = delta ? n_chg : 0;
+        P.ctl[8] = P.K_dev ? *P.K_dev : P.K_max;
+        P.ctl[0] = (delta ? SEGK_DELTA_MODE : 0) | ((P.hint_valid && !nonid) ? SEGK_DELTA_SKIP : 0);
+        P.ctl[1] = n_chg;
+        P.ctl[2] = delta ? n_packed : 0;
+        P.ctl[3] = 0;
+        P.ctl[16] = 0;
+        P.ctl[17] = 0;
+        if (!delta) ((int *)P.snap_img)[0] = e_cur;
+    }
+    // the free slots of the last packed tile: absent (their operands are whatever finite column was there before, or zero)
+    if (delta && tid < 32 && n_chg + tid < n_packed * 32) {
+        const int sl = n_chg + tid;
+        P.packed[(int64_t)(sl >> 5) * P.stride + c_off + (sl & 31)] = -3.0e38f;
+    }
+}
+// workgroups of delta_prep_means_rows in a launch
+static inline int segk_delta_prep_row_blocks(int K_max) { return (K_max + 7) / 8 < 128 ? (K_max + 7) / 8 : 128; }
+// segk_kmeans_batch_finalize asks: may k_batch_post run the prep of the next hinted call?  true: *P is filled as that call's
+// launch_delta_prep would fill it and the context holds a pending prep (segk_internal.h); false: P->ctl == NULL.
+bool segk_delta_prep_fold(segk_ctx *ctx, const segk_corpus *c, const segk_kmeans *m, const int32_t *remap, hipStream_t st, DeltaPrepArgs *P);
+// every entry that writes what a pending prep has compared (the list: segk_internal.h, at the field)
+static inline void segk_delta_pending_drop(segk_ctx *ctx)
+{
+    if (ctx && ctx->delta_pending == 1) ctx->delta_pending = 2;
+}
 // segk_score_band.hip: the hinted path's undecided rows -- candidates inside the band of the filter's maximum, exact scores
 bool segk_band_applies(const ScoreArgs &A);
 int segk_launch_band(segk_ctx *ctx, const ScoreArgs &A, const float *thr, int64_t call_rows, int32_t *lab_last, int ks, hipStream_t st);

@@ -220,6 +220,7 @@ int segk_kmeans_prepare_impl(segk_ctx *ctx, const segk_corpus *c, segk_kmeans *m
     int rc = check_corpus(c);
     if (rc) return rc;
     SEGK_REQUIRE(m && m->tiles && m->mnorm_max, "kmeans tiles/mnorm_max");
+    segk_delta_pending_drop(ctx);
     hipStream_t st = (hipStream_t)stream;
     // value hashes of the rows, for segk_kmeans_mark_duplicates (context-owned, K_max <= 2048 only)
     unsigned long long *row_hash = nullptr;
@@ -248,6 +249,7 @@ int32_t segk_kmeans_mark_duplicates(segk_ctx *ctx, const segk_corpus *c, const s
     int rc = check_corpus(c);
     if (rc) return rc;
     SEGK_REQUIRE(m && m->tiles && m->means, "kmeans tiles / means");
+    segk_delta_pending_drop(ctx);
     // needs the row hashes of the segk_kmeans_prepare that built these images (same context, same means buffer)
     if (!ctx || m->K_max > 2048 || !ctx->row_hash || ctx->row_hash_means != m->means) return SEGK_OK;
     hipStream_t st = (hipStream_t)stream;

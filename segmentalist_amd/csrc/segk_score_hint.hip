@@ -143,9 +143,9 @@ struct HintArgs {
 // ctl[0] mode word (SEGK_DELTA_*), [1] columns of the image that differ from the base pass's snapshot, [2] tiles of the packed
 // delta image (0 in full mode), [3] positions the hint waves skipped (cleared by k_delta_prep, added to by K1), [4] packed tiles
 // multiplied since the base pass, [5 + parity] rows of `means` that changed during the call of that parity, [7] ctl[1] of the
-// previous call, [8] the number of active components at the previous call
-#define SEGK_DELTA_MODE 1            /* K1 multiplies the packed changed columns only */
-#define SEGK_DELTA_SKIP 2            /* hint_out and snap_means32 are the previous call's, the relabelling is the identity */
+// previous call, [8] the number of active components at the previous call, [12..15] and [18] what a prep found in [5 + other
+// parity], [4], [7], [8] and in the snapshot's exponent (for a prep that repeats it), [16..17] a 64-bit word: the prep's
+// changed-column count, tickets and relabelled tiles (delta_prep_tile, segk_kmeans_dev.h; zero between launches)
 #define SEGK_MEANCHG_BIT 0x40000000  /* in the hint waves' label map: the float32 mean of this component changed since the previous call */
 
 // ---- K1 ---------------------------------------------------------------------------------------------------------------
@@ -728,137 +728,21 @@ __global__ __launch_bounds__(128 * SEGK_K1_NW, 1) void k_kmeans_top2_rs(HintArgs
 // add up to a whole table (the delta passes have then cost what the new base costs).
 // The workgroups behind the tiles': the rows of the float32 `means` against their copy of the previous call (a wave per row),
 // for the hint waves, and the copy refreshed.
-struct DeltaPrepArgs {
-    const float *tiles_hdr;         // tiles_b3 (header, then the tiles)
-    int n_tiles, stride;            // stride: floats per tile of the global image
-    int K_max, D;
-    const float *means32;
-    const int32_t *remap;
-    const int32_t *K_dev;           // [1] active components (NULL: all K_max)
-    int valid;                      // the state (snapshot, part_base, lab_base) belongs to this call's tuple
-    int hint_valid;                 // hint_out and snap_means32 are the previous call's on the same tuple
-    int cap;                        // packed tiles at most
-    int budget;                     // packed tiles multiplied since the base at most
-    int seq;                        // number of this launch on the context (the parity of the means-changed counters)
-    int32_t *ctl, *colchg, *meanchg;
-    float *snap_img;                // [4 floats: image exponent][n_tiles][KS * 256 + 32]
-    float *packed;                  // [n_tiles][stride]
-    float *snap_means;              // [K_max][D]
-};
-
-#define SEGK_PREP_THREADS 256
-#define SEGK_PREP_COLS 4            /* at most 32 * SEGK_PREP_COLS tiles (four LDS ranges of 32) */
-// Workgroups 0 .. n_tiles - 1: one tile each (a lane per (lane half, column), the k-steps over the four waves); the changed
-// columns take their packed slots by one atomic per tile and are copied there at once (a call that turns out FULL never reads
-// them); the workgroup that finishes last knows the count and writes the mode.  The snapshot itself is refreshed by K1's full
-// launch, which has every tile in LDS anyway.  The workgroups behind: the rows of `means`.
+// (DeltaPrepArgs and the three bodies -- delta_prep_tile, delta_prep_means_rows, delta_prep_mode -- are in segk_kmeans_dev.h:
+// k_batch_post runs them too, for the hinted call that follows a batch finalize.)
+// Workgroups 0 .. n_tiles - 1: one tile each; the workgroup that finishes last knows the count and writes the mode.  The
+// snapshot itself is refreshed by K1's full launch, which has every tile in LDS anyway.  The workgroups behind: the rows of
+// `means`.  This launch is the path of every hinted call that has no pending prep (launch_delta_prep).
 template <int KS>
 __global__ __launch_bounds__(SEGK_PREP_THREADS) void k_delta_prep(DeltaPrepArgs P)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    constexpr int NWV = SEGK_PREP_THREADS / 64;
     if ((int)blockIdx.x >= P.n_tiles) {
-        const int n_w = (gridDim.x - P.n_tiles) * NWV;
-        for (int k = (blockIdx.x - P.n_tiles) * NWV + wave; k < P.K_max; k += n_w) {
-            const int *cur = (const int *)(P.means32 + (int64_t)k * P.D);
-            int *snap = (int *)(P.snap_means + (int64_t)k * P.D);
-            bool chg = false;
-            for (int d = lane; d < P.D; d += 64) {
-                const int c = cur[d];
-                chg |= c != snap[d];
-                snap[d] = c;
-            }
-            const bool any = __any(chg);
-            if (lane == 0) {
-                P.meanchg[k] = (any || !P.hint_valid) ? 1 : 0;
-                if (any) atomicAdd(P.ctl + 5 + (P.seq & 1), 1);
-            }
-        }
+        delta_prep_means_rows(P, (int)blockIdx.x - P.n_tiles, (int)gridDim.x - P.n_tiles);
         return;
     }
-    __shared__ int s_chg[32], s_slot[32], s_last, s_nonid;
-    constexpr int TL = KS * 256 + 32, c_off = KS * 512;
-    const int t = blockIdx.x, c = lane & 31;
-    const float *g = P.tiles_hdr + 1024 + (int64_t)t * P.stride;
-    const float *q = P.snap_img + 4 + (int64_t)t * TL;
+    __shared__ DeltaPrepLds S;
     const int e_cur = ((const int *)P.tiles_hdr)[0];
-    const bool all = !P.valid || e_cur != ((const int *)P.snap_img)[0];
-    if (tid < 32) s_chg[tid] = 0;
-    if (tid == 0) s_nonid = 0;
-    __syncthreads();
-    if (!all) {
-        bool chg = false;
-        for (int ks = wave; ks < KS; ks += NWV) {
-            const int4 a = *reinterpret_cast<const int4 *>(g + ks * 512 + lane * 4);
-            const int4 b = *reinterpret_cast<const int4 *>(q + ks * 256 + lane * 4);
-            chg |= a.x != b.x || a.y != b.y || a.z != b.z || a.w != b.w;
-        }
-        if (tid < 32) chg |= __float_as_int(g[c_off + c]) != __float_as_int(q[KS * 256 + c]);
-        if (chg) atomicOr(&s_chg[c], 1);
-    }
-    __syncthreads();
-    if (wave == 0) {
-        const bool chg = lane < 32 && (all || s_chg[lane] != 0);
-        if (lane < 32) P.colchg[t * 32 + lane] = chg ? 1 : 0;
-        const unsigned long long mask = __ballot(chg);
-        int base = 0;
-        if (lane == 0 && mask != 0ull) base = atomicAdd(P.ctl + 9, __popcll(mask));
-        base = __shfl(base, 0);
-        if (lane < 32) s_slot[lane] = chg ? base + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0)) : -1;
-    }
-    __syncthreads();
-    {
-        const int sl = s_slot[c];
-        if (P.valid && sl >= 0 && sl < P.cap * 32) {
-            float *o = P.packed + (int64_t)(sl >> 5) * P.stride;
-            const int l2 = (lane & 32) + (sl & 31);
-            for (int ks = wave; ks < KS; ks += NWV)
-                *reinterpret_cast<int4 *>(o + ks * 512 + l2 * 4) = *reinterpret_cast<const int4 *>(g + ks * 512 + lane * 4);
-            if (tid < 32) o[c_off + (sl & 31)] = g[c_off + c];
-        }
-    }
-    // the workgroup that finishes last: the count is complete
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) s_last = atomicAdd(P.ctl + 10, 1) == P.n_tiles - 1 ? 1 : 0;
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-    if (P.remap) {
-        // the labels rows can carry: below the number of active components at the previous call, or now (the batch finalize
-        // rewrites the table's entries beyond as it compacts freshly emptied rows: no row names those)
-        int K_lab = P.K_dev ? *P.K_dev : P.K_max;
-        if (K_lab < P.ctl[8]) K_lab = P.ctl[8];
-        if (K_lab > P.K_max || !P.valid) K_lab = P.K_max;
-        bool bad = false;
-        for (int k = tid; k < K_lab; k += SEGK_PREP_THREADS) bad |= P.remap[k] != k;
-        if (bad) s_nonid = 1;
-    }
-    __syncthreads();
-    const int n_chg = atomicAdd(P.ctl + 9, 0), n_packed = (n_chg + 31) >> 5;
-    // (the counter of the previous call's parity: complete, that launch is over; this launch's other workgroups use the other)
-    const int moved_prev = P.ctl[5 + ((P.seq + 1) & 1)], acc = P.ctl[4], chg_prev = P.ctl[7];
-    const bool at_rest = n_chg > 0 && n_chg == chg_prev && moved_prev == 0;
-    const bool delta = P.valid && !s_nonid && n_packed <= P.cap && !at_rest && acc + n_packed <= P.budget;
-    __syncthreads();
-    if (tid == 0) {
-        P.ctl[4] = delta ? acc + n_packed : 0;
-        P.ctl[5 + ((P.seq + 1) & 1)] = 0;
-        P.ctl[7] = delta ? n_chg : 0;
-        P.ctl[8] = P.K_dev ? *P.K_dev : P.K_max;
-        P.ctl[0] = (delta ? SEGK_DELTA_MODE : 0) | ((P.hint_valid && !s_nonid) ? SEGK_DELTA_SKIP : 0);
-        P.ctl[1] = n_chg;
-        P.ctl[2] = delta ? n_packed : 0;
-        P.ctl[3] = 0;
-        P.ctl[9] = 0;
-        P.ctl[10] = 0;
-        if (!delta) ((int *)P.snap_img)[0] = e_cur;
-    }
-    // the free slots of the last packed tile: absent (their operands are whatever finite column was there before, or zero)
-    if (delta && tid < 32 && n_chg + tid < n_packed * 32) {
-        const int sl = n_chg + tid;
-        P.packed[(int64_t)(sl >> 5) * P.stride + c_off + (sl & 31)] = -3.0e38f;
-    }
+    if (delta_prep_tile(P, KS, (int)blockIdx.x, e_cur, S)) delta_prep_mode(P, KS, e_cur, S);
 }
 
 struct HintMergeArgs {
@@ -1184,14 +1068,71 @@ static size_t delta_layout(unsigned char *b, int n_tiles, int K_max, int D, int6
     return off;
 }
 
-// k_delta_prep in front of K1 where the delta pass applies (SEGK_SCORE_DELTA=0: never); B->ctl == NULL where it does not.
-// *cap: packed tiles a delta launch takes at most.
+// packed tiles a delta launch takes at most: a full launch's range (measured on the headline corpus against 2, 4, 8, 12 and 20
+// tiles: profiles/README.md), never more than fit in K1's LDS; and the packed tiles multiplied since the base at most
+static int delta_cap(const HintPlan &lds)
+{
+    int cap = segk_env_int("SEGK_DELTA_CAP", lds.tpr);
+    if (cap > lds.max_tiles) cap = lds.max_tiles;
+    return cap < 1 ? 1 : cap;
+}
+static int delta_budget(int n_tiles) { return segk_env_int("SEGK_DELTA_BUDGET", n_tiles); }
+
+// the prep's arguments for a table on the buffer B; consumes a launch number of the context unless it repeats launch redo_seq
+static DeltaPrepArgs delta_prep_args(segk_ctx *ctx, const DeltaBuf &B, const float *tiles, int n_tiles, int stride, int K_max, int D,
+                                     const float *means32, const int32_t *remap, const int32_t *K_dev, bool valid, int cap, int budget,
+                                     int redo_seq = -1)
+{
+    DeltaPrepArgs P{};
+    P.tiles_hdr = tiles; P.n_tiles = n_tiles; P.stride = stride;
+    P.K_max = K_max; P.D = D; P.means32 = means32; P.remap = remap; P.K_dev = K_dev;
+    P.valid = valid ? 1 : 0; P.hint_valid = valid ? 1 : 0; P.cap = cap;
+    P.budget = budget;
+    P.redo = redo_seq >= 0 ? 1 : 0;
+    P.seq = redo_seq >= 0 ? redo_seq : (int)(ctx->delta_seq++ & 1u);
+    P.ctl = B.ctl; P.colchg = B.colchg; P.meanchg = B.meanchg;
+    P.snap_img = B.snap_img; P.packed = B.packed; P.snap_means = B.snap_means;
+    return P;
+}
+
+// segk_kmeans_batch_finalize: k_batch_post has just finished the images and follows the kernel that wrote `means` -- it runs
+// the prep of the next hinted call on this table if the context holds valid delta state for it: the previous hinted call was
+// on this table over all rows (its key), the buffer is that call's, nothing is pending.  The arguments are those the call's
+// own launch_delta_prep would make (state valid); it takes the prep over if it finds them so, and has no valid state if not.
+// SEGK_DELTA_PREP_FOLD=0: never (same results).
+bool segk_delta_prep_fold(segk_ctx *ctx, const segk_corpus *c, const segk_kmeans *m, const int32_t *remap, hipStream_t st, DeltaPrepArgs *P)
+{
+    *P = DeltaPrepArgs{};
+    if (!ctx || ctx->delta_pending != 0 || !ctx->delta_valid || ctx->capturing || !ctx->delta_buf) return false;
+    if (segk_env_int("SEGK_DELTA_PREP_FOLD", 1) == 0 || segk_env_int("SEGK_SCORE_DELTA", 1) == 0) return false;
+    const void *key[4] = {c->Xb3, c->X32, m->tiles_b3, m->means};
+    const int64_t key_n[5] = {0, c->n_emb, c->n_emb, m->K_max, c->D};
+    if (memcmp(key, ctx->delta_key, sizeof(key)) != 0 || memcmp(key_n, ctx->delta_key_n, sizeof(key_n)) != 0) return false;
+    const int n_tiles = segk_n_tiles(m->K_max), stride_sp = segk_sp_tile_stride(c->D, 2);
+    HintPlan lds;
+    if (n_tiles > 32 * SEGK_PREP_COLS || !segk_hint_plan(m->K_max, segk_b3_kp(c->D) / 16, n_tiles, &lds)) return false;
+    DeltaBuf B{};
+    if (ctx->delta_bytes != delta_layout(nullptr, n_tiles, m->K_max, c->D, c->n_emb, stride_sp, &B)) return false;
+    delta_layout((unsigned char *)ctx->delta_buf, n_tiles, m->K_max, c->D, c->n_emb, stride_sp, &B);
+    const int cap = delta_cap(lds), budget = delta_budget(n_tiles);
+    *P = delta_prep_args(ctx, B, m->tiles_b3, n_tiles, stride_sp, m->K_max, c->D, (const float *)m->means, remap, m->K, true, cap, budget);
+    ctx->delta_pending = 1;
+    ctx->delta_pending_remap = remap; ctx->delta_pending_K = m->K; ctx->delta_pending_stream = (const void *)st;
+    ctx->delta_pending_cap = cap; ctx->delta_pending_budget = budget; ctx->delta_pending_seq = P->seq;
+    return true;
+}
+
+// The prep in front of K1 where the delta pass applies (SEGK_SCORE_DELTA=0: never); B->ctl == NULL where it does not.  A launch
+// of k_delta_prep, unless k_batch_post has run this very prep (the context's pending prep).  *cap: packed tiles a delta launch
+// takes at most.
 template <int KS>
 static int launch_delta_prep(segk_ctx *ctx, const ScoreArgs &A, const int32_t *remap, const int32_t *K_dev, int64_t n_emb,
                              const HintLaunch &L, hipStream_t st, DeltaBuf *B, int *cap)
 {
     *B = DeltaBuf{};
     *cap = 0;
+    const int pending = ctx->delta_pending;                  // consumed by the first hinted call after it, used or not
+    ctx->delta_pending = 0;
     const bool delta_on = segk_env_int("SEGK_SCORE_DELTA", 1) != 0 && L.band && A.ids == nullptr && A.n_tiles <= 32 * SEGK_PREP_COLS;
     const void *key[6] = {A.X32, A.xrows32, A.tiles, A.means32, A.cand.k, A.cand.s};
     const int64_t key_n[5] = {A.row0, A.n, n_emb, A.K_max, A.D};
@@ -1210,21 +1151,20 @@ static int launch_delta_prep(segk_ctx *ctx, const ScoreArgs &A, const int32_t *r
         SEGK_CHECK_HIP(hipMemsetAsync(ctx->delta_buf, 0, B->zero_bytes, st));
     }
     delta_layout((unsigned char *)ctx->delta_buf, A.n_tiles, A.K_max, A.D, A.n, stride_sp, B);
-    // packed tiles at most: a full launch's range (measured on the headline corpus against 2, 4, 8, 12 and 20 tiles:
-    // profiles/README.md), never more than fit in K1's LDS
-    *cap = segk_env_int("SEGK_DELTA_CAP", L.lds.tpr);
-    if (*cap > L.lds.max_tiles) *cap = L.lds.max_tiles;
-    if (*cap < 1) *cap = 1;
-    DeltaPrepArgs P{};
-    P.tiles_hdr = A.tiles; P.n_tiles = A.n_tiles; P.stride = stride_sp;
-    P.K_max = A.K_max; P.D = A.D; P.means32 = A.means32; P.remap = remap; P.K_dev = K_dev;
-    P.valid = state_valid ? 1 : 0; P.hint_valid = state_valid ? 1 : 0; P.cap = *cap;
-    P.budget = segk_env_int("SEGK_DELTA_BUDGET", A.n_tiles);
-    P.seq = (int)(ctx->delta_seq++ & 1u);
-    P.ctl = B->ctl; P.colchg = B->colchg; P.meanchg = B->meanchg;
-    P.snap_img = B->snap_img; P.packed = B->packed; P.snap_means = B->snap_means;
-    const int rows_blocks = (A.K_max + 7) / 8 < 128 ? (A.K_max + 7) / 8 : 128;
-    hipLaunchKernelGGL(k_delta_prep<KS>, dim3(A.n_tiles + rows_blocks), dim3(SEGK_PREP_THREADS), 0, st, P);
+    *cap = delta_cap(L.lds);
+    const int budget = delta_budget(A.n_tiles);
+    // the pending prep is this call's: made for this tuple (state_valid: the key it was made from), this relabelling table and
+    // component count, this stream, these limits.  One that is not -- or was dropped after it ran -- has refreshed the means'
+    // snapshot and moved the counters on all the same: on valid state (its own: only the hinted call of the key sets one up,
+    // and every hinted call consumes it) the launch repeats it.  Without valid state k_delta_prep resets every control word.
+    const bool folded = pending == 1 && state_valid && remap == ctx->delta_pending_remap && K_dev == ctx->delta_pending_K &&
+                        (const void *)st == ctx->delta_pending_stream && *cap == ctx->delta_pending_cap &&
+                        budget == ctx->delta_pending_budget;
+    if (!folded) {
+        const DeltaPrepArgs P = delta_prep_args(ctx, *B, A.tiles, A.n_tiles, stride_sp, A.K_max, A.D, A.means32, remap, K_dev, state_valid,
+                                                *cap, budget, pending != 0 && state_valid ? ctx->delta_pending_seq : -1);
+        hipLaunchKernelGGL(k_delta_prep<KS>, dim3(A.n_tiles + segk_delta_prep_row_blocks(A.K_max)), dim3(SEGK_PREP_THREADS), 0, st, P);
+    }
     memcpy(ctx->delta_key, key, sizeof(key));
     memcpy(ctx->delta_key_n, key_n, sizeof(key_n));
     ctx->delta_valid = 1;

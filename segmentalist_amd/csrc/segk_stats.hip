@@ -1601,15 +1601,25 @@ __global__ __launch_bounds__(256) void k_batch_finalize(
     SEGK_TSTAMP(3, 6);
 }
 
-// final labels of the local tokens + (tile workgroups) split-precision image (SP) and duplicate marking
+// final labels of the local tokens + (tile workgroups) split-precision image (SP) and duplicate marking.  With DP.ctl (SP only):
+// the delta prep of the hinted score call that follows (segk_kmeans_dev.h) -- a tile workgroup compares its own tile once the
+// image, the constants and the "absent" marks are final, the workgroups behind the relabelling ones compare the rows of `means`.
 template <typename XT, bool SP>
 __global__ __launch_bounds__(256) void k_batch_post(segk_corpus c, segk_kmeans m, int lo, int hi, int32_t *new_k, const int32_t *remap,
                                                     int n_tiles, int stride32, int G, float *tiles_sp, int stride_sp, int sp_const_off,
-                                                    const unsigned long long *row_hash)
+                                                    const unsigned long long *row_hash, DeltaPrepArgs DP, int dp_ks)
 {
+    static_assert(SEGK_PREP_THREADS == 256, "the prep's bodies run in this kernel's workgroups");
     if ((int)blockIdx.x >= n_tiles) {
         const int64_t idx = (int64_t)(blockIdx.x - n_tiles) * blockDim.x + threadIdx.x;
         const int64_t p0 = (int64_t)lo * c.N_max, tot = (int64_t)(hi - lo) * c.N_max;
+        if constexpr (SP) {
+            const int n_rel = (int)((tot + 255) / 256);
+            if (DP.ctl && (int)blockIdx.x >= n_tiles + n_rel) {                // (only such a launch has workgroups there)
+                delta_prep_means_rows(DP, (int)blockIdx.x - n_tiles - n_rel, (int)gridDim.x - n_tiles - n_rel);
+                return;
+            }
+        }
         if (idx < tot) {
             const int k = new_k[p0 + idx];
             if (k >= 0) new_k[p0 + idx] = remap[k];
@@ -1619,11 +1629,12 @@ __global__ __launch_bounds__(256) void k_batch_post(segk_corpus c, segk_kmeans m
     }
     const int tile = blockIdx.x;
     SEGK_TSTAMP(4, 0);
+    int eb_new = 0;
     if constexpr (SP) {
         if (tiles_sp) {
             // the finalize kernel has written the image with the exponent of the previous one (its sp_spec path); when
             // the exponent of the new means is the same there is nothing to build (workgroup-uniform)
-            const int eb_new = sp_exponent((float)(sqrt(*m.mnorm_max) * (1.0 + 1e-6)));
+            eb_new = sp_exponent((float)(sqrt(*m.mnorm_max) * (1.0 + 1e-6)));
             const bool built = eb_new == ((const int *)tiles_sp)[3];    // (word 3: no workgroup of this kernel writes it)
             if (!built)
                 dev_prepare_sp_tile((const float *)m.means, m.K_max, c.D, tiles_sp, m.mnorm_max, (const unsigned char *)c.Xb3,
@@ -1635,7 +1646,23 @@ __global__ __launch_bounds__(256) void k_batch_post(segk_corpus c, segk_kmeans m
         }
     }
     SEGK_TSTAMP(4, 1);
-    if (!row_hash) return;
+    // The delta prep of this workgroup's tile.  Its image is final: built here or by the finalize kernel, the marks below stored
+    // by this workgroup -- behind a fence and a barrier, other threads wrote those words.  The image's exponent is eb_new, built
+    // or not (header word 0 is tile 0's workgroup's to rewrite in this launch: not read here).
+    __shared__ DeltaPrepLds dps;
+    auto delta_prep = [&]() {
+        if constexpr (SP) {
+            if (DP.ctl) {
+                __threadfence();
+                __syncthreads();
+                if (delta_prep_tile(DP, dp_ks, tile, eb_new, dps)) delta_prep_mode(DP, dp_ks, eb_new, dps);
+            }
+        }
+    };
+    if (!row_hash) {
+        delta_prep();
+        return;
+    }
     // clean_components leaves exact copies behind (the moved rows, the inactive rows): a duplicate with the higher
     // index can never be np.argmax, but every embedding near the pair is a tie for the full scan -- its accumulator
     // seed becomes the "absent" constant in both images (k_kmeans_mark_dups, one tile per workgroup here)
@@ -1663,6 +1690,7 @@ __global__ __launch_bounds__(256) void k_batch_post(segk_corpus c, segk_kmeans m
         m.tiles[(int64_t)tile * stride32 + G * 128 + (k & 31)] = -3.0e38f;
         if (tiles_sp) tiles_sp[1024 + (int64_t)tile * stride_sp + sp_const_off + (k & 31)] = -3.0e38f;
     }
+    delta_prep();
     SEGK_TSTAMP_MAX(4, 3);
 }
 
@@ -1854,6 +1882,7 @@ int32_t segk_kmeans_update_utt(segk_ctx *ctx, const segk_corpus *c, segk_kmeans 
 {
     int rc = check_corpus(c);
     if (rc) return rc;
+    segk_delta_pending_drop(ctx);
     SEGK_REQUIRE(utt >= 0 && utt < c->n_utt, "utt out of range");
     rc = launch_update(c, m, 0, utt, 0, 0, old_tok, new_tok, new_k, n_old, n_new, status, (hipStream_t)stream);
     if (rc) return rc;
@@ -1865,6 +1894,7 @@ int32_t segk_kmeans_add_item(segk_ctx *ctx, const segk_corpus *c, segk_kmeans *m
 {
     int rc = check_corpus(c);
     if (rc) return rc;
+    segk_delta_pending_drop(ctx);
     SEGK_REQUIRE(i >= 0 && i < c->n_emb, "item out of range");
     SEGK_REQUIRE(k >= 0, "k");
     rc = launch_update(c, m, 1, 0, i, k, nullptr, nullptr, nullptr, nullptr, nullptr, status, (hipStream_t)stream);
@@ -1877,6 +1907,7 @@ int32_t segk_kmeans_del_item(segk_ctx *ctx, const segk_corpus *c, segk_kmeans *m
 {
     int rc = check_corpus(c);
     if (rc) return rc;
+    segk_delta_pending_drop(ctx);
     SEGK_REQUIRE(i >= 0 && i < c->n_emb, "item out of range");
     rc = launch_update(c, m, 2, 0, i, 0, nullptr, nullptr, nullptr, nullptr, nullptr, status, (hipStream_t)stream);
     if (rc) return rc;
@@ -1888,6 +1919,7 @@ int32_t segk_kmeans_clean_components(segk_ctx *ctx, const segk_corpus *c, segk_k
 {
     int rc = check_corpus(c);
     if (rc) return rc;
+    segk_delta_pending_drop(ctx);
     rc = launch_update(c, m, 3, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, status, (hipStream_t)stream);
     if (rc) return rc;
     return segk_kmeans_prepare(ctx, c, m, stream);
@@ -1898,6 +1930,7 @@ int32_t segk_kmeans_del_component(segk_ctx *ctx, const segk_corpus *c, segk_kmea
 {
     int rc = check_corpus(c);
     if (rc) return rc;
+    segk_delta_pending_drop(ctx);
     SEGK_REQUIRE(k >= 0 && k < m->K_max, "k out of range");
     rc = launch_update(c, m, 4, 0, 0, k, nullptr, nullptr, nullptr, nullptr, nullptr, status, (hipStream_t)stream);
     if (rc) return rc;
@@ -1981,6 +2014,7 @@ int32_t segk_kmeans_batch_finalize(segk_ctx *ctx, const segk_corpus *c, segk_kme
     SEGK_REQUIRE(records && new_k && remap_scratch && out_scalars && status && m->tiles && m->mnorm_max, "batch_finalize operands");
     SEGK_REQUIRE(0 <= utt_lo && utt_lo <= utt_hi && utt_hi <= c->n_utt, "utterance range");
     hipStream_t st = (hipStream_t)stream;
+    segk_delta_pending_drop(ctx);
     // value hashes of the rows, for the duplicate marking (context-owned, K_max <= 2048 only; SEGK_MARK_DUPS=0: leave
     // the duplicates in the filters' images)
     unsigned long long *row_hash = nullptr;
@@ -2026,12 +2060,17 @@ int32_t segk_kmeans_batch_finalize(segk_ctx *ctx, const segk_corpus *c, segk_kme
     const int kp = segk_b3_kp(c->D);
     const int stride32 = segk_tile_stride(c->D), G = segk_gmax(c->D);
     const int stride_sp = sp ? segk_sp_tile_stride(c->D, 2) : 0, sp_off = sp ? (kp / 16) * 2 * 256 : 0;
+    // the delta prep of the hinted score call that follows, where the context has valid state for it (segk_delta_prep_fold):
+    // its row workgroups behind the relabelling ones
+    DeltaPrepArgs dp{};
+    const bool fold = sp && segk_delta_prep_fold(ctx, c, m, remap_scratch, st, &dp);
     if (sp)
-        hipLaunchKernelGGL((k_batch_post<float, true>), dim3(grid), dim3(256), 0, st, *c, *m, utt_lo, utt_hi, new_k, remap_scratch,
-                           n_tiles, stride32, G, m->tiles_b3, stride_sp, sp_off, row_hash);
+        hipLaunchKernelGGL((k_batch_post<float, true>), dim3(grid + (fold ? segk_delta_prep_row_blocks(m->K_max) : 0)), dim3(256), 0, st,
+                           *c, *m, utt_lo, utt_hi, new_k, remap_scratch, n_tiles, stride32, G, m->tiles_b3, stride_sp, sp_off, row_hash,
+                           dp, kp / 16);
     else
         DISPATCH_XT(c, hipLaunchKernelGGL((k_batch_post<XT, false>), dim3(grid), dim3(256), 0, st, *c, *m, utt_lo, utt_hi, new_k,
-                                           remap_scratch, n_tiles, stride32, G, (float *)nullptr, 0, 0, row_hash););
+                                           remap_scratch, n_tiles, stride32, G, (float *)nullptr, 0, 0, row_hash, dp, 0););
     SEGK_LAUNCH_CHECK();
     return SEGK_OK;
 }
@@ -2091,6 +2130,7 @@ int32_t segk_kmeans_init_stats(segk_ctx *ctx, const segk_corpus *c, segk_kmeans 
 {
     int rc = check_corpus(c);
     if (rc) return rc;
+    segk_delta_pending_drop(ctx);
     hipStream_t st = (hipStream_t)stream;
     SEGK_CHECK_HIP(hipMemsetAsync(m->K, 0, sizeof(int32_t), st));
     int64_t grid = ((int64_t)m->K_max + 3) / 4;
