@@ -64,7 +64,11 @@ const char *segk_last_error(void);
  *     mean_t / q_t at other shapes (below), no structure grows; segk_fbb_prior_rows, _partials, _prepare, _score, _segment,
  * *     _segment_map, _assign, _assign_map, _canonical accept it, every other segk_fbb_* entry point keeps refusing it
  *  15 segk_fbi_assign: the item step of the stand-alone FBGMM's batch sweeps; segk_fbb_partials / _prepare / _canonical accept
- *     a corpus of items (no span tables, N_max = 1) with n_blocks = 1                                                       */
+ *     a corpus of items (no span tables, N_max = 1) with n_blocks = 1
+ *  15 (no bump) segk_fbt_assign: the token step of the unigram segmenter's acoustic-model batch sweeps.  The rule above concerns
+ *     changed signatures and structures: this adds one entry point, changes none and grows no structure, so a binding written
+ *     against 15 keeps working with this library; segk_fbb_partials / _prepare accept n_blocks = 1 on a segmenter's corpus too
+ *     (every token against the prior), the span-score, boundary and slot entry points keep refusing it                       */
 #define SEGK_ABI_VERSION 15
 int32_t segk_abi_version(void);
 
@@ -828,6 +832,30 @@ int32_t segk_fbi_assign(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f
                         int32_t s_lo, int32_t s_n, int32_t b, const int32_t *n_items, uint64_t sweep,
                         double anneal_temp, int32_t consider_unassigned, const int32_t *new_tok,
                         int32_t *n_new, double *probe_ll, int64_t probe_ld, void *stream);
+/* Acoustic-model batch sweeps of the unigram segmenter (added at ABI 15 without a bump; the inner sweeps of
+ * UnigramAcousticWordseg.gibbs_sample(n, am_n_iter=m), unigram_acoustic_wordseg.py:440-443 -- FBGMM.gibbs_sample(m,
+ * consider_unassigned=False) over the currently assigned tokens -- as a blocked sampler on the segmenter's batch state;
+ * specification tests/am_batch.py).  A sweep is the sweep of segk_fbb_* above with the span scores and the boundary step left
+ * out: per block b segk_fbb_prepare(b), this call, segk_fbb_partials(b).  This call is step b's token half on a corpus WITH
+ * utterances (span tables present, any N_max, band corpora included): every current token (i, t) of the utterances of block b
+ * of the local slices [s_lo, s_lo + s_n) -- row new_tok[i * N_max + t], t < n_new[i] -- forms
+ * z_k = lms log(alpha / K_max + n_k) + log predictive_k(row) over all K_max slots (an empty slot: bt->prior_rows[row]), anneals
+ * it when anneal_temp != 1 (fbgmm.py:446-449) and draws its slot by the inverse-CDF walk on u01(bt->seed, sweep, i, N_max + t):
+ * the uniforms, likelihood bits and draws of segk_fbb_assign on the same token lists and statistics.  Only bt->slot[row] is
+ * written: new_tok, n_new, the boundaries and out_logprob are not.
+ * A first kernel (one workgroup per local slice, an ordered scan of n_new, no atomics) compacts the cell's tokens, in utterance
+ * order, into a workspace of the context; the tile kernel of segk_fbi_assign then takes 64 tokens per workgroup against all
+ * slots.  Nothing is read back: tok_cap [host] [s_n], the landmarks of the cell's utterances (an upper bound on its tokens, at
+ * most n_utts[s] * N_max), sizes the grid, and a tile beyond the device-side count returns at once.  n_utts [host] [s_n]: the
+ * utterances of block b per local slice.  cov_type 0, 1 (D <= 256) and 2 (D <= 64, K_max <= 1024; the likelihoods by the
+ * token-likelihood kernel of segk_fbb_assign); X float32 or float64; fp64 arithmetic; the logits in LDS or the bounded workspace
+ * of segk_fbi_assign (SEGK_FBI_Z_MIB).  A language model (f->lm_unigram) and the cov_type 2 limits are SEGK_ERR_UNSUPPORTED, a
+ * corpus without span tables or D > 256 SEGK_ERR_ARG, all before any launch.  probe_ll (NULL in production) receives the
+ * likelihood part of the logits in the layout of segk_fbb_set_probe's ll_out: probe_ll[(i * N_max + t) * probe_ld + k].        */
+int32_t segk_fbt_assign(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt,
+                        int32_t s_lo, int32_t s_n, int32_t b, const int32_t *n_utts, const int32_t *tok_cap,
+                        uint64_t sweep, double anneal_temp, const int32_t *new_tok, const int32_t *n_new,
+                        double *probe_ll, int64_t probe_ld, void *stream);
 /* bigram table += sign * (transcripts of block b, all slices) from bt->lm_tok                  */
 int32_t segk_fbb_lm_apply(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f,
                           const segk_fbatch *bt, int32_t b, int32_t sign, void *stream);

@@ -2120,7 +2120,9 @@ __global__ void k_fbb_rows16(segk_fbgmm f, segk_fbatch bt, int D, double prior_a
     } while (0)
 
 // fc_who: the entry point's name where it has a full-covariance form (cov_type 2: the unigram step's calls); NULL refuses it
-static int check_fbb(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, const char *fc_who = nullptr)
+// one_block: the statistics entry points (segk_fbb_partials / _prepare) -- the acoustic-model batch sweep (segk_fbt_assign)
+// defines a sweep of one block on a segmenter's corpus, every token against the prior
+static int check_fbb(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, const char *fc_who = nullptr, bool one_block = false)
 {
     SEGK_REQUIRE(c && f && bt, "NULL corpus / fbgmm / batch state");
     if (!fc_who) SEGK_REFUSE_FULLCOV(f, "segk_fbb_*");
@@ -2132,7 +2134,7 @@ static int check_fbb(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatc
     SEGK_REQUIRE(bt->n_slices >= 1 && bt->n_slices <= 16, "n_slices must be in 1..16");
     // (a corpus of items -- no span tables: the stand-alone batch sweep, segk_fbi_assign -- may have one block: its specification
     // defines that sweep, every item against the prior)
-    SEGK_REQUIRE(bt->n_blocks >= 2 || (bt->n_blocks == 1 && !c->vec_ids && !c->band_ids),
+    SEGK_REQUIRE(bt->n_blocks >= 2 || (bt->n_blocks == 1 && (one_block || (!c->vec_ids && !c->band_ids))),
                  "n_blocks must be >= 2 (with one block nothing is conditioned on)");
     SEGK_REQUIRE(f->kconst != NULL, "kconst buffer missing");
     return SEGK_OK;
@@ -2223,7 +2225,7 @@ int32_t segk_fbb_partials(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm 
                           int32_t s_lo, int32_t s_n, int32_t b, const int32_t *new_tok, const int32_t *n_new,
                           void *stream)
 {
-    int rc = check_fbb(c, f, bt, "segk_fbb_partials");
+    int rc = check_fbb(c, f, bt, "segk_fbb_partials", true);
     if (rc) return rc;
     SEGK_REQUIRE(s_lo >= 0 && s_n >= 1 && s_lo + s_n <= bt->n_slices && b >= 0 && b < bt->n_blocks, "slice / block range");
     SEGK_REQUIRE(f->cov_type != 2 || ctx, "cov_type 2: segk_fbb_partials needs the context (the tokens are bucketed by slot)");
@@ -2276,7 +2278,7 @@ int32_t segk_fbb_partials(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm 
 int32_t segk_fbb_prepare(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t b,
                          void *stream)
 {
-    int rc = check_fbb(c, f, bt, "segk_fbb_prepare");
+    int rc = check_fbb(c, f, bt, "segk_fbb_prepare", true);
     if (rc) return rc;
     SEGK_REQUIRE(b >= -1 && b < bt->n_blocks, "block");
     hipStream_t st = (hipStream_t)stream;

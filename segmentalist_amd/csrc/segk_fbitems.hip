@@ -14,6 +14,18 @@
 //   cov_type 2              the likelihoods of the block's items are formed by k_fcb_token_ll (segk_fullcov.hip: one slot's
 //                           packed triangle staged per 256 items) into its context table; k_fbi_assign<XT, 2> is the draw half
 //                           reading that table.
+//
+// The same tile serves the TOKEN step of the unigram segmenter's acoustic-model batch sweep (segk_fbt_assign: the inner sweeps
+// of UnigramAcousticWordseg.gibbs_sample(..., am_n_iter, am_sync="batch"); specification tests/am_batch.py): the boundaries are
+// frozen, every current token of block b is resampled against the statistics of all other blocks.
+//
+//   k_fbt_compact           one workgroup per local slice: an ordered scan of n_new over the cell's utterances writes the cell's
+//                           token list (row, utterance, position) and its length into a workspace of the context -- utterance
+//                           order, then position, the order of the partial sums
+//   k_fbi_assign<.., true>  a tile is 64 consecutive entries of that list (TOK): the rows are gathered through it, the draw of
+//                           token t of utterance i uses u01(seed, sweep, i, N_max + t) as k_fbb_assign does, n_new / new_tok
+//                           are only read.  The grid is sized from the host's bound on the cell's tokens (its landmarks); a
+//                           tile that begins at or beyond the list's length returns at once.
 // No grid barrier, no spin loop, no cooperative launch, no atomics: a plain grid over the tiles.
 #include "segk_fb_common.h"
 #include "segk_fbb_dev.h"
@@ -31,6 +43,49 @@
 
 static __host__ __device__ __forceinline__ size_t fbi_stage_doubles(int D) { return (size_t)FBI_T * D + 2 * (size_t)FBI_KC * D; }
 
+// the token lists of block b of the local slices (k_fbt_compact writes, k_fbi_assign<.., true> reads): local slice s owns the
+// entries off[s] .. off[s + 1] - 1 (the host's bound on its tokens), the first count[s] of them are tokens
+struct FbtList {
+    int32_t *count;             // [16]
+    int32_t *row, *utt, *pos;   // [off[n]] each
+    int off[17];
+};
+
+#define FBT_NT 256
+__global__ __launch_bounds__(FBT_NT) void k_fbt_compact(segk_corpus c, segk_fbatch bt, FbtList L, int s_lo, int b, const int32_t *new_tok,
+                                                       const int32_t *n_new)
+{
+    __shared__ int sc[FBT_NT];
+    const int s = blockIdx.x, slice = s_lo + s, tid = threadIdx.x, NM = c.N_max;
+    const int u0 = bt.utt_range[(slice * bt.n_blocks + b) * 2], u1 = bt.utt_range[(slice * bt.n_blocks + b) * 2 + 1];
+    const int o0 = L.off[s], cap = L.off[s + 1] - o0;
+    int base = 0;                                           // tokens of the utterances before this pass (uniform)
+    for (int c0 = u0; c0 < u1; c0 += FBT_NT) {
+        const int utt = c0 + tid;
+        int n = utt < u1 ? n_new[utt] : 0;
+        n = n < 0 ? 0 : (n > NM ? NM : n);
+        sc[tid] = n;
+        __syncthreads();
+        for (int o = 1; o < FBT_NT; o <<= 1) {              // inclusive scan, utterance order
+            const int v = tid >= o ? sc[tid - o] : 0;
+            __syncthreads();
+            sc[tid] += v;
+            __syncthreads();
+        }
+        const int first = base + sc[tid] - n;
+        for (int t = 0; t < n; t++) {
+            const int j = first + t;
+            if (j >= cap) break;                            // (never: cap counts the cell's landmarks)
+            L.row[o0 + j] = new_tok[(int64_t)utt * NM + t];
+            L.utt[o0 + j] = utt;
+            L.pos[o0 + j] = t;
+        }
+        base += sc[FBT_NT - 1];
+        __syncthreads();
+    }
+    if (tid == 0) L.count[s] = base < cap ? base : cap;
+}
+
 // n_new[i] = 1 for every item of block b of the local slices (consider_unassigned with cov_type 2: k_fcb_token_ll evaluates the
 // tokens n_new names)
 __global__ __launch_bounds__(256) void k_fbi_mark(segk_fbatch bt, int s_lo, int b, int32_t *n_new)
@@ -41,11 +96,12 @@ __global__ __launch_bounds__(256) void k_fbi_mark(segk_fbatch bt, int s_lo, int 
     if (i < u1) n_new[i] = 1;
 }
 
-template <typename XT, int COV>
+// TOK = false: the items of the stand-alone model; TOK = true: the tokens of a segmenter's cell through the lists `L`
+template <typename XT, int COV, bool TOK = false>
 __global__ __launch_bounds__(FBI_NT) void k_fbi_assign(segk_corpus c, segk_fbgmm f, segk_fbatch bt, FbbMap map, int wg0, int b,
                                                       uint64_t sweep, double prior_alpha, double anneal_temp, int consider_unassigned,
                                                       int32_t *n_new, double *zbuf, const double *fc_ll, int fc_ucap,
-                                                      double *probe_ll, int64_t probe_ld)
+                                                      double *probe_ll, int64_t probe_ld, FbtList L)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int D = c.D, KM = f.K_max, tid = threadIdx.x, lane = tid & 63;
@@ -54,12 +110,40 @@ __global__ __launch_bounds__(FBI_NT) void k_fbi_assign(segk_corpus c, segk_fbgmm
     if (!fbb_locate(map, wg0 + blockIdx.x, &s, &idx)) return;
     const int slice = map.lo[s];
     const int u0 = bt.utt_range[(slice * bt.n_blocks + b) * 2], u1 = bt.utt_range[(slice * bt.n_blocks + b) * 2 + 1];
-    const int i0 = u0 + idx * FBI_T;                        // the tile's first item
-    const int nr = u1 - i0 < FBI_T ? u1 - i0 : FBI_T;       // (>= 1: the host counts the tiles from the same ranges)
-    double *ll;                                             // [FBI_T][K_max] likelihood part of the logits, then the probabilities
+    int i0, nr;
+    const int32_t *trow = nullptr, *tutt = nullptr, *tpos = nullptr;    // TOK: the tile's entries of the token lists
+    if constexpr (TOK) {
+        const int n_tok = L.count[s];
+        i0 = idx * FBI_T;                                   // the tile's first token of the cell's list
+        if (i0 >= n_tok) return;                            // (workgroup-uniform: the grid is sized from the host's bound)
+        nr = n_tok - i0 < FBI_T ? n_tok - i0 : FBI_T;
+        trow = L.row + L.off[s] + i0;
+        tutt = L.utt + L.off[s] + i0;
+        tpos = L.pos + L.off[s] + i0;
+    } else {
+        i0 = u0 + idx * FBI_T;                              // the tile's first item
+        nr = u1 - i0 < FBI_T ? u1 - i0 : FBI_T;             // (>= 1: the host counts the tiles from the same ranges)
+    }
+    // the embedding row of the tile's entry r (TOK: -1 where the list names none -- such an entry is left alone)
+    auto row_of = [&](int r) -> int64_t {
+        if constexpr (TOK) {
+            const int64_t e = trow[r];
+            return e >= 0 && e < c.n_emb ? e : -1;
+        } else
+            return i0 + r;
+    };
+    double *ll = nullptr;                                   // [FBI_T][K_max] likelihood part of the logits, then the probabilities
+    // ... of entry r
+    auto row_ll = [&](int r) -> double * {
+        if constexpr (TOK && COV == 2)
+            // k_fcb_token_ll's table: row (local slice * u_cap + utterance of the cell) * N_max + position
+            return const_cast<double *>(fc_ll) + (((int64_t)s * fc_ucap + (tutt[r] - u0)) * c.N_max + tpos[r]) * KM;
+        else
+            return ll + (int64_t)r * KM;
+    };
     if constexpr (COV == 2) {
         // k_fcb_token_ll's table: row (local slice * u_cap + item of the cell), the row's prior predictive in the empty slots
-        ll = const_cast<double *>(fc_ll) + ((int64_t)s * fc_ucap + (int64_t)idx * FBI_T) * KM;
+        if constexpr (!TOK) ll = const_cast<double *>(fc_ll) + ((int64_t)s * fc_ucap + (int64_t)idx * FBI_T) * KM;
     } else {
         double *xs = (double *)smem;                        // [D][FBI_T]: the lanes' rows side by side
         double *pm = xs + (size_t)FBI_T * D;                // [FBI_KC][D][2]: (mean, q) of the staged slots
@@ -67,10 +151,12 @@ __global__ __launch_bounds__(FBI_NT) void k_fbi_assign(segk_corpus c, segk_fbgmm
         const XT *X = (const XT *)c.X;
         for (int j = tid; j < FBI_T * D; j += FBI_NT) {
             const int r = j / D, d = j - r * D;
-            xs[d * FBI_T + r] = r < nr ? (double)X[(int64_t)(i0 + r) * c.ldx + d] : 0.0;
+            const int64_t e = r < nr ? row_of(r) : -1;
+            xs[d * FBI_T + r] = e >= 0 ? (double)X[e * c.ldx + d] : 0.0;
         }
-        const bool valid = lane < nr;
-        const double lp = valid ? bt.prior_rows[i0 + lane] : 0.0;       // an empty slot's likelihood: the row's prior predictive
+        const int64_t e_lane = lane < nr ? row_of(lane) : -1;
+        const bool valid = e_lane >= 0;
+        const double lp = valid ? bt.prior_rows[e_lane] : 0.0;          // an empty slot's likelihood: the row's prior predictive
         for (int k0 = 0; k0 < KM; k0 += FBI_KC) {
             __syncthreads();                                // (the rows are staged; the previous pass has read its parameters)
             for (int j = tid; j < FBI_KC * D; j += FBI_NT) {
@@ -117,12 +203,23 @@ __global__ __launch_bounds__(FBI_NT) void k_fbi_assign(segk_corpus c, segk_fbgmm
     if (probe_ll) {             // the likelihood part of the logits, as the draws below use it
         for (int j = tid; j < nr * KM; j += FBI_NT) {
             const int r = j / KM, k = j - r * KM;
-            probe_ll[(int64_t)(i0 + r) * probe_ld + k] = ll[(int64_t)r * KM + k];
+            if constexpr (TOK) {
+                if (row_of(r) >= 0) probe_ll[((int64_t)tutt[r] * c.N_max + tpos[r]) * probe_ld + k] = row_ll(r)[k];
+            } else
+                probe_ll[(int64_t)(i0 + r) * probe_ld + k] = ll[(int64_t)r * KM + k];
         }
         __syncthreads();
     }
     const double zc_empty = f.lms * log(prior_alpha / (double)KM);
     for (int r = w; r < nr; r += FBI_NT / 64) {             // a wave per item
+        if constexpr (TOK) {
+            const int64_t e = row_of(r);                    // (wave-uniform)
+            if (e < 0) continue;
+            const int k = fbb_draw_row(f, bt, KM, prior_alpha, zc_empty, anneal_temp, row_ll(r), sweep, (uint64_t)tutt[r],
+                                       (uint64_t)(c.N_max + tpos[r]), lane);
+            if (lane == 0) bt.slot[e] = k;
+            continue;
+        }
         const int i = i0 + r;
         if (!consider_unassigned && bt.slot[i] < 0) continue;           // (wave-uniform) keeps -1 and contributes to nothing
         const int k = fbb_draw_row(f, bt, KM, prior_alpha, zc_empty, anneal_temp, ll + (int64_t)r * KM, sweep, (uint64_t)i, 1ull, lane);
@@ -131,6 +228,72 @@ __global__ __launch_bounds__(FBI_NT) void k_fbi_assign(segk_corpus c, segk_fbgmm
             n_new[i] = 1;
         }
     }
+}
+
+// What both entry points do once their arguments are checked: the tiles of block b mapped to workgroups (m: FBI_T entries
+// each), with cov_type 2 the token-likelihood table formed, the logits placed (LDS, or the bounded workspace and several
+// launches), the launches.  tok: the lists of segk_fbt_assign (NULL: items).
+static int32_t fbi_launch(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, const FbbMap &m, int32_t s_lo,
+                          int32_t s_n, int32_t b, const int32_t *n_utts, int most, uint64_t sweep, double anneal_temp,
+                          int32_t consider_unassigned, const int32_t *new_tok, int32_t *n_new, double *probe_ll, int64_t probe_ld,
+                          const FbtList *tok, void *stream)
+{
+    const int n_wg = m.off[s_n];
+    hipStream_t st = (hipStream_t)stream;
+    const double *fc_ll = nullptr;
+    int fc_ucap = 0;
+    size_t lds = 0;
+    int per_launch = n_wg;
+    double *zbuf = nullptr;
+    if (f->cov_type == 2) {
+        if (!tok && consider_unassigned) {
+            hipLaunchKernelGGL(k_fbi_mark, dim3((unsigned)((most + 255) / 256), (unsigned)s_n), dim3(256), 0, st, *bt, s_lo, b, n_new);
+            SEGK_LAUNCH_CHECK();
+        }
+        if (int rc = segk_fcb_token_ll(ctx, c, f, bt, s_lo, s_n, b, n_utts, new_tok, n_new, &fc_ll, &fc_ucap, stream)) return rc;
+    } else {
+        const size_t stage = fbi_stage_doubles(c->D) * sizeof(double), tile = (size_t)FBI_T * f->K_max * sizeof(double);
+        SEGK_REQUIRE(stage <= FBI_LDS_MAX, "the rows and the staged slots of a tile do not fit in LDS");
+        if (stage + tile <= FBI_LDS_MAX) {
+            lds = stage + tile;
+        } else {
+            lds = stage;
+            const int mib = segk_env_int("SEGK_FBI_Z_MIB", FBI_Z_MIB);
+            const size_t cap = ((size_t)(mib > 0 ? mib : FBI_Z_MIB) << 20) / tile;
+            per_launch = cap < 1 ? 1 : (cap < (size_t)n_wg ? (int)cap : n_wg);
+            const int64_t need = (int64_t)per_launch * FBI_T * f->K_max;
+            if (int rc = segk_ws_grow(ctx, &ctx->fbi_z, &ctx->fbi_z_n, need, (size_t)need * sizeof(double), st)) return rc;
+            zbuf = ctx->fbi_z;
+        }
+    }
+    const FbtList none = {};
+#define SEGK_FBI(XT, COV, TOK)                                                                                                  \
+    do {                                                                                                                        \
+        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbi_assign<XT, COV, TOK>, lds));                                            \
+        for (int wg0 = 0; wg0 < n_wg; wg0 += per_launch) {                                                                      \
+            const int n = n_wg - wg0 < per_launch ? n_wg - wg0 : per_launch;                                                    \
+            hipLaunchKernelGGL((k_fbi_assign<XT, COV, TOK>), dim3((unsigned)n), dim3(FBI_NT), lds, st, *c, *f, *bt, m, wg0, b,   \
+                               sweep, f->alpha, anneal_temp, consider_unassigned ? 1 : 0, n_new, zbuf, fc_ll, fc_ucap, probe_ll, \
+                               probe_ld, tok ? *tok : none);                                                                    \
+        }                                                                                                                       \
+    } while (0)
+#define SEGK_FBI_COV(XT, TOK)                                                                                                   \
+    do {                                                                                                                        \
+        if (f->cov_type == 0) SEGK_FBI(XT, 0, TOK);                                                                             \
+        else if (f->cov_type == 1) SEGK_FBI(XT, 1, TOK);                                                                        \
+        else SEGK_FBI(XT, 2, TOK);                                                                                              \
+    } while (0)
+    if (c->x_dtype == SEGK_F32) {
+        if (tok) SEGK_FBI_COV(float, true);
+        else SEGK_FBI_COV(float, false);
+    } else {
+        if (tok) SEGK_FBI_COV(double, true);
+        else SEGK_FBI_COV(double, false);
+    }
+#undef SEGK_FBI_COV
+#undef SEGK_FBI
+    SEGK_LAUNCH_CHECK();
+    return SEGK_OK;
 }
 
 extern "C" {
@@ -168,57 +331,58 @@ int32_t segk_fbi_assign(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f
         m.off[s + 1] = m.off[s] + (n_items[s] + FBI_T - 1) / FBI_T;
         most = n_items[s] > most ? n_items[s] : most;
     }
-    const int n_wg = m.off[s_n];
-    if (n_wg == 0) return SEGK_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const double *fc_ll = nullptr;
-    int fc_ucap = 0;
-    size_t lds = 0;
-    int per_launch = n_wg;
-    double *zbuf = nullptr;
-    if (f->cov_type == 2) {
-        if (consider_unassigned) {
-            hipLaunchKernelGGL(k_fbi_mark, dim3((unsigned)((most + 255) / 256), (unsigned)s_n), dim3(256), 0, st, *bt, s_lo, b, n_new);
-            SEGK_LAUNCH_CHECK();
-        }
-        if (int rc = segk_fcb_token_ll(ctx, c, f, bt, s_lo, s_n, b, n_items, new_tok, n_new, &fc_ll, &fc_ucap, stream)) return rc;
-    } else {
-        const size_t stage = fbi_stage_doubles(c->D) * sizeof(double), tile = (size_t)FBI_T * f->K_max * sizeof(double);
-        SEGK_REQUIRE(stage <= FBI_LDS_MAX, "the rows and the staged slots of a tile do not fit in LDS");
-        if (stage + tile <= FBI_LDS_MAX) {
-            lds = stage + tile;
-        } else {
-            lds = stage;
-            const int mib = segk_env_int("SEGK_FBI_Z_MIB", FBI_Z_MIB);
-            const size_t cap = ((size_t)(mib > 0 ? mib : FBI_Z_MIB) << 20) / tile;
-            per_launch = cap < 1 ? 1 : (cap < (size_t)n_wg ? (int)cap : n_wg);
-            const int64_t need = (int64_t)per_launch * FBI_T * f->K_max;
-            if (int rc = segk_ws_grow(ctx, &ctx->fbi_z, &ctx->fbi_z_n, need, (size_t)need * sizeof(double), st)) return rc;
-            zbuf = ctx->fbi_z;
-        }
+    if (m.off[s_n] == 0) return SEGK_OK;
+    return fbi_launch(ctx, c, f, bt, m, s_lo, s_n, b, n_items, most, sweep, anneal_temp, consider_unassigned, new_tok, n_new, probe_ll,
+                      probe_ld, nullptr, stream);
+}
+
+int32_t segk_fbt_assign(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,
+                        int32_t s_n, int32_t b, const int32_t *n_utts, const int32_t *tok_cap, uint64_t sweep, double anneal_temp,
+                        const int32_t *new_tok, const int32_t *n_new, double *probe_ll, int64_t probe_ld, void *stream)
+{
+    SEGK_REQUIRE(ctx && c && f && bt && n_utts && tok_cap && new_tok && n_new, "NULL argument");
+    if (f->lm_unigram) {
+        segk_set_error("segk_fbt_assign: the acoustic-model batch sweep takes no language model (the bigram segmenter has no inner "
+                       "sweeps: its reference asserts at am_n_iter > 0)");
+        return SEGK_ERR_UNSUPPORTED;
     }
-#define SEGK_FBI(XT, COV)                                                                                                       \
-    do {                                                                                                                        \
-        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbi_assign<XT, COV>, lds));                                                 \
-        for (int wg0 = 0; wg0 < n_wg; wg0 += per_launch) {                                                                      \
-            const int n = n_wg - wg0 < per_launch ? n_wg - wg0 : per_launch;                                                    \
-            hipLaunchKernelGGL((k_fbi_assign<XT, COV>), dim3((unsigned)n), dim3(FBI_NT), lds, st, *c, *f, *bt, m, wg0, b, sweep, \
-                               f->alpha, anneal_temp, consider_unassigned ? 1 : 0, n_new, zbuf, fc_ll, fc_ucap, probe_ll,       \
-                               probe_ld);                                                                                       \
-        }                                                                                                                       \
-    } while (0)
-    if (c->x_dtype == SEGK_F32) {
-        if (f->cov_type == 0) SEGK_FBI(float, 0);
-        else if (f->cov_type == 1) SEGK_FBI(float, 1);
-        else SEGK_FBI(float, 2);
-    } else {
-        if (f->cov_type == 0) SEGK_FBI(double, 0);
-        else if (f->cov_type == 1) SEGK_FBI(double, 1);
-        else SEGK_FBI(double, 2);
+    SEGK_REQUIRE(c->x_dtype == SEGK_F32 || c->x_dtype == SEGK_F64, "unsupported dtype");
+    SEGK_REQUIRE(f->cov_type >= 0 && f->cov_type <= 2, "cov_type must be 0 (fixed), 1 (diag) or 2 (full)");
+    SEGK_REQUIRE((c->vec_ids || c->band_ids) && c->n_utt > 0 && c->N_max > 0,
+                 "a segmenter's corpus: utterances with span tables (the items of a stand-alone model go through segk_fbi_assign)");
+    SEGK_REQUIRE(c->D > 0 && c->D <= 256, "batch mode supports D <= 256");
+    SEGK_REQUIRE(f->K_max >= 1 && f->K_max <= 8192, "K_max");
+    SEGK_REQUIRE(bt->n_slices >= 1 && bt->n_slices <= 16 && bt->n_blocks >= 1, "slices / blocks");
+    SEGK_REQUIRE(s_lo >= 0 && s_n >= 1 && s_n <= 16 && s_lo + s_n <= bt->n_slices && b >= 0 && b < bt->n_blocks, "slice / block range");
+    SEGK_REQUIRE(bt->prior_rows && bt->utt_range && bt->slot && bt->cnt && bt->mean_t && bt->q_t && bt->lconst && bt->half,
+                 "batch state (prior_rows, ranges, slot, slot tables)");
+    SEGK_REQUIRE(!probe_ll || probe_ld >= f->K_max, "probe leading dimension");
+    if (f->cov_type == 2)
+        if (int rc = segk_fcb_check(c, f, bt, "segk_fbt_assign")) return rc;
+    FbbMap m;
+    FbtList L = {};
+    m.n = s_n;
+    m.off[0] = 0;
+    L.off[0] = 0;
+    for (int s = 0; s < s_n; s++) {
+        SEGK_REQUIRE(n_utts[s] >= 0 && n_utts[s] <= c->n_utt, "utterance counts");
+        SEGK_REQUIRE(tok_cap[s] >= 0 && (int64_t)tok_cap[s] <= (int64_t)n_utts[s] * c->N_max, "token bounds (the landmarks of the cell)");
+        SEGK_REQUIRE((int64_t)L.off[s] + tok_cap[s] < (int64_t)1 << 30, "token bounds of a block");
+        m.lo[s] = s_lo + s;
+        m.off[s + 1] = m.off[s] + (tok_cap[s] + FBI_T - 1) / FBI_T;
+        L.off[s + 1] = L.off[s] + tok_cap[s];
     }
-#undef SEGK_FBI
+    if (m.off[s_n] == 0) return SEGK_OK;
+    const int64_t cap = L.off[s_n], need = 16 + 3 * cap;
+    if (int rc = segk_ws_grow(ctx, &ctx->fbt_tok, &ctx->fbt_tok_n, need, (size_t)need * sizeof(int32_t), (hipStream_t)stream)) return rc;
+    L.count = ctx->fbt_tok;
+    L.row = ctx->fbt_tok + 16;
+    L.utt = L.row + cap;
+    L.pos = L.utt + cap;
+    hipLaunchKernelGGL(k_fbt_compact, dim3((unsigned)s_n), dim3(FBT_NT), 0, (hipStream_t)stream, *c, *bt, L, s_lo, b, new_tok, n_new);
     SEGK_LAUNCH_CHECK();
-    return SEGK_OK;
+    return fbi_launch(ctx, c, f, bt, m, s_lo, s_n, b, n_utts, 0, sweep, anneal_temp, 0, new_tok, const_cast<int32_t *>(n_new), probe_ll,
+                      probe_ld, &L, stream);
 }
 
 }  // extern "C"

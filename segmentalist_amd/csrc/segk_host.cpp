@@ -154,6 +154,7 @@ int32_t segk_destroy(segk_ctx *ctx)
         if (ctx->fc_terms) (void)hipFree(ctx->fc_terms);
         if (ctx->fcb_ll) (void)hipFree(ctx->fcb_ll);
         if (ctx->fbi_z) (void)hipFree(ctx->fbi_z);
+        if (ctx->fbt_tok) (void)hipFree(ctx->fbt_tok);
         for (int i = 0; i < SEGK_PROF_SLOTS; i++)
             for (int j = 0; j < 2; j++)
                 if (ctx->prof_ev[i][j]) (void)hipEventDestroy(ctx->prof_ev[i][j]);

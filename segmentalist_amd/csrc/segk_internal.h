@@ -72,6 +72,8 @@ struct segk_ctx {
     int64_t fcb_ll_n;            // ... doubles allocated
     double *fbi_z;               // item step of the stand-alone batch sweep (k_fbi_assign): [tiles of a launch][FBI_T][K_max] logits where
     int64_t fbi_z_n;             // ... a tile's do not fit in LDS; doubles allocated (bounded: segk_fbitems.hip FBI_Z_MIB)
+    int32_t *fbt_tok;            // token step of the segmenter's acoustic-model batch sweep (k_fbt_compact): [16] tokens per local slice,
+    int64_t fbt_tok_n;           // ... then [3][cap] (row, utterance, position) of the block's tokens; cap = int32 words per list
     // hinted score path (segk_score_hint.hip): the filter's partial top-2 per (range, row), then the hint waves' result per row
     void *hint_part;
     size_t hint_part_bytes;
@@ -181,8 +183,9 @@ int segk_rows_by_label(segk_ctx *ctx, const int32_t *labels, int64_t n, int K_ma
 // Full-covariance components (segk_fbgmm.cov_type 2, segk_fullcov.hip) exist behind the entry points of the stand-alone FBGMM
 // and of the unigram segmenter's launches per utterance (init_stats, update ops 0 / 1 / 2 / 4, score, pred_vector, assign,
 // gibbs_items, record_metrics with urn = 0) and behind those of a unigram batch step (segk_fbb_prior_rows, _partials, _prepare,
-// _score, _segment, _segment_map, _assign, _assign_map, _canonical: segk_fbb_dev.h) and behind segk_fbi_assign (the stand-alone
-// batch sweep's item step, segk_fbitems.hip); every other one refuses them by name.
+// _score, _segment, _segment_map, _assign, _assign_map, _canonical: segk_fbb_dev.h) and behind segk_fbi_assign / segk_fbt_assign
+// (the item step of the stand-alone batch sweep, the token step of the segmenter's acoustic-model batch sweep: segk_fbitems.hip);
+// every other one refuses them by name.
 #define SEGK_REFUSE_FULLCOV(f, who)                                                                                 \
     do {                                                                                                            \
         if ((f) && (f)->cov_type == 2) {                                                                            \

@@ -1073,6 +1073,14 @@ class FbgmmBatchSweeper(object):
                         for b in range(self.B)]
         self._n_utts = [I32(*[int(ur[self.s_lo + i, b, 1] - ur[self.s_lo + i, b, 0]) for i in range(self.s_n)])
                         for b in range(self.B)]
+        # acoustic-model batch sweeps (am_sweep): the landmarks of every cell's utterances, the host's bound on its tokens
+        self._tok_cap = None
+        if c.lengths_np is not None:
+            lens = c.lengths_np.astype(np.int64)
+            self._tok_cap = [I32(*[int(lens[ur[self.s_lo + i, b, 0]:ur[self.s_lo + i, b, 1]].sum()) for i in range(self.s_n)])
+                             for b in range(self.B)]
+        self.score_precision = score_precision
+        self.probe_ll = None             # am_sweep: a [n_utt * N_max, >= K_max] float64 device tensor, the likelihoods (tests)
         self.ll_mat = None
         if self.score_f16:
             # token likelihoods of the assignment step from the matrix cores: per block, the positions of its
@@ -1214,6 +1222,37 @@ class FbgmmBatchSweeper(object):
                 check(L.segk_fbb_lm_apply(ctx, cp, fp, bp, b, 1, st))
             check(L.segk_fbb_partials(ctx, cp, fp, bp, self.s_lo, self.s_n, b, ptr(df.new_tok), ptr(df.n_new), st))
             self._gather(self.partials, b)
+        self.sweep_index += 1
+
+    def am_sweep(self, boundaries, anneal_temp=1.0):
+        """One ACOUSTIC-MODEL batch sweep (specification tests/am_batch.py): the boundaries stay, every current
+        token of block b is resampled against the statistics of all other blocks -- per block segk_fbb_prepare(b),
+        segk_fbt_assign, segk_fbb_partials(b), all enqueued on the current stream.  Consumes one sweep index, the counter of
+        `sweep`.  One process, fp64 scores, no language model."""
+        df = self.df
+        if df.lm is not None:
+            raise SegkError("acoustic-model batch sweeps (am_sweep) exist without a language model only: the bigram segmenter "
+                            "has no inner sweeps (its reference asserts at am_n_iter > 0)")
+        if self.world > 1:
+            raise SegkError("acoustic-model batch sweeps (am_sweep) run in one process only (%d ranks)" % self.world)
+        if self.score_precision != "f64":
+            raise SegkError("acoustic-model batch sweeps (am_sweep) take score_precision='f64' only (got %r): the "
+                            "reduced-precision sweepers keep their state in other coordinates" % (self.score_precision,))
+        if self.fullcov and df.K_max > 1024:
+            raise SegkError("the batch sampler takes full-covariance components (cov_type 2) with K_max <= 1024, got %d"
+                            % df.K_max)
+        if self._tok_cap is None:
+            raise SegkError("acoustic-model batch sweeps (am_sweep) need a segmenter's corpus (utterances with span tables)")
+        if not self.in_batch_state:
+            self.enter(boundaries)
+        L, ctx, cp, fp, bp, st = self._args()
+        pl = self.probe_ll
+        for b in range(self.B):
+            check(L.segk_fbb_prepare(ctx, cp, fp, bp, b, st))
+            check(L.segk_fbt_assign(ctx, cp, fp, bp, self.s_lo, self.s_n, b, self._n_utts[b], self._tok_cap[b], self.sweep_index,
+                                    float(anneal_temp), ptr(df.new_tok), ptr(df.n_new), ptr(pl),
+                                    pl.shape[1] if pl is not None else 0, st))
+            check(L.segk_fbb_partials(ctx, cp, fp, bp, self.s_lo, self.s_n, b, ptr(df.new_tok), ptr(df.n_new), st))
         self.sweep_index += 1
 
     def cell_partials(self, b, s):

@@ -4,7 +4,15 @@ config 2 shapes (1 000 utterances, D = 39, K = 100) -- development measurement, 
 --fb-type viterbi: the Viterbi / MAP sweeps of the unigram segmenters, with either --sync (the bigram one has no such mode).
 --cov full: the unigram segmenter with full-covariance components in place of --which (D <= 64): --sync sequential its
 serial chain (four launches per utterance), --sync batch its batch sweeps (profiles/README.md "Full-covariance batch
-sampler"); no oracle timing."""
+sampler"); no oracle timing.
+--am-n-iter M (with --sync batch): the time of ONE inner acoustic-model sweep of gibbs_sample(n, am_n_iter=M) over the segmenter's
+current tokens, --sweeps repeats of M sweeps each from the batch state, median and range, by the route --am-sync names:
+  batch       the acoustic-model batch sweep (am_batch_sweep_async: prepare, segk_fbt_assign, partials per block)
+  sequential  what gibbs_sample does without am_sync: leave batch mode (materialise), the serial chain over the tokens, and the
+              re-entry into batch mode the next outer sweep pays
+  fbb         the same step with segk_fbb_assign on the unchanged token lists (prepare, assign, partials per block), driven
+              from this tool only
+(profiles/README.md "Acoustic-model batch sweeps")."""
 import argparse
 import os
 import random
@@ -30,7 +38,11 @@ def main():
     ap.add_argument("--fb-type", default="standard", choices=["standard", "viterbi"])
     ap.add_argument("--cov", default=None, choices=["full"])
     ap.add_argument("--slices", type=int, default=8)
+    ap.add_argument("--am-n-iter", type=int, default=0)
+    ap.add_argument("--am-sync", default="batch", choices=["batch", "sequential", "fbb"])
     args = ap.parse_args()
+    if args.am_n_iter > 0 and args.sync != "batch":
+        ap.error("--am-n-iter times the inner sweeps of batch mode: it needs --sync batch")
     if args.cov == "full":
         args.which = "full"
     import torch
@@ -75,6 +87,9 @@ def main():
                                             fb_type="unigram", **kw, **pk)
         torch.cuda.synchronize()
         t_init = time.perf_counter() - t0
+        if args.am_n_iter > 0:
+            inner_sweeps(seg, which, args)
+            continue
         if args.sync == "batch":
             st = []
             for _ in range(args.sweeps + 1):
@@ -113,6 +128,51 @@ def main():
         dt = time.perf_counter() - t0
         print("%-6s oracle (1 core): %.2f ms/utterance -> %.4f sweeps/s" % (which, 1e3 * dt / len(keys),
                                                                           len(keys) / dt / args.utts), flush=True)
+
+
+def inner_sweeps(seg, which, args):
+    """--am-n-iter: one outer batch sweep (the batch state exists, the workspaces are grown), one untimed repeat, then
+    --sweeps timed repeats of args.am_n_iter inner sweeps by the route --am-sync names."""
+    import json
+    import torch
+    from segmentalist_amd._abi import check, ptr
+    sw, df, m = seg._get_sweeper(), seg._df, args.am_n_iter
+    seg.batch_sweep_async()
+    torch.cuda.synchronize()
+
+    def batch():
+        for _ in range(m):
+            seg.am_batch_sweep_async()
+
+    def sequential():
+        seg._leave_batch()
+        seg.acoustic_model.gibbs_sample(m, consider_unassigned=False)
+        sw.enter(seg._dev_bounds)
+
+    def fbb():
+        L, ctx, cp, fp, bp, st = sw._args()
+        for _ in range(m):
+            for b in range(sw.B):
+                check(L.segk_fbb_prepare(ctx, cp, fp, bp, b, st))
+                check(L.segk_fbb_assign(ctx, cp, fp, bp, sw.s_lo, sw.s_n, b, sw._n_utts[b], sw.sweep_index, 1.0, ptr(df.new_tok),
+                                        ptr(df.n_new), None, 0, st))
+                check(L.segk_fbb_partials(ctx, cp, fp, bp, sw.s_lo, sw.s_n, b, ptr(df.new_tok), ptr(df.n_new), st))
+            sw.sweep_index += 1
+
+    route = {"batch": batch, "sequential": sequential, "fbb": fbb}[args.am_sync]
+    times = []
+    for rep in range(args.sweeps + 1):
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        route()
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t1) / m)
+    df.check_status()
+    times = sorted(times[1:])
+    n_tok = int(df.n_new.sum().item())
+    print(json.dumps({"inner_sweep": which, "am_sync": args.am_sync, "am_n_iter": m, "repeats": len(times), "tokens": n_tok,
+                      "median_ms": 1e3 * float(np.median(times)), "min_ms": 1e3 * times[0], "max_ms": 1e3 * times[-1],
+                      "range_ms": 1e3 * (times[-1] - times[0]), "tokens_per_s": n_tok / float(np.median(times))}), flush=True)
 
 
 if __name__ == "__main__":
