@@ -78,13 +78,13 @@ static __device__ __forceinline__ void fbb_sum_slices(const segk_fbatch &bt, int
     }
 }
 
-// The slot of one token without a language model, by one wave: zr[k] holds the likelihood part of the logits of all K_max slots
-// (LDS or memory; overwritten).  The prior's term lms log(alpha / K_max + n_k) (fbgmm.py:436-440), the softmax, the annealing
-// (fbgmm.py:446-449) and the inverse-CDF walk on u01(seed, sweep, utt, j).  The sums keep the association of the block-wide
-// form at 256 threads (per wave of 64 consecutive slots a butterfly, the waves' results added in order), so the
-// probabilities -- and the draws -- are the bits of k_fbb_assign's wave-per-token branch (segk_fbbatch.hip), whose statements
-// these are: called from there instead, the function changed that kernel's generated code (instruction order), so the kernel
-// keeps its own copy and k_fbi_assign (a wave per item of a tile) calls this one.  Keep the two alike.  Result in all lanes.
+// THE draw of one token's slot without a language model, by one wave (k_fbb_slots of segk_fbbatch.hip: a wave per token of an
+// utterance; k_fbi_assign of segk_fbitems.hip: a wave per item of a tile): zr[k] holds the likelihood part of the logits of all
+// K_max slots (LDS or memory; overwritten).  The prior's term lms log(alpha / K_max + n_k) (fbgmm.py:436-440), the softmax, the
+// annealing (fbgmm.py:446-449) and the inverse-CDF walk on u01(seed, sweep, utt, j).  The sums keep the association of a
+// block-wide sum at 256 threads (per wave of 64 consecutive slots a butterfly, the waves' results added in order: block_sum,
+// as k_fbb_assign_lm uses it), so the probabilities -- and the draws -- are the bits a block-wide softmax of the same logits
+// gives.  Result in all lanes.
 static __device__ __forceinline__ int fbb_draw_row(const segk_fbgmm &f, const segk_fbatch &bt, int KM, double prior_alpha, double zc_empty,
                                                    double anneal_temp, double *zr, uint64_t sweep, uint64_t utt, uint64_t j, int lane)
 {
@@ -132,7 +132,7 @@ int segk_fcb_prepare(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatc
 int segk_fcb_score(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int s_lo, int s_n, int b, const int32_t *n_rows,
                    double *score, void *stream);
 // token likelihoods of the block's new segments into a table the context owns: row (local slice * *u_cap + utterance of the
-// cell) * N_max + token, [K_max] each, the row's prior predictive in the empty slots (k_fbb_assign / _assign_map read it)
+// cell) * N_max + token, [K_max] each, the row's prior predictive in the empty slots (k_fbb_slots reads it)
 int segk_fcb_token_ll(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int s_lo, int s_n, int b,
                       const int32_t *n_utts, const int32_t *new_tok, const int32_t *n_new, const double **ll, int *u_cap,
                       void *stream);

@@ -15,8 +15,10 @@
 //   k_fbb_segment   one workgroup per utterance: score vector, DP, backward sampling with the
 //                   counter-based uniforms (or the max-plus DP, fb_type "viterbi"), new token list (corpora with
 //                   an utterance of more than 64 landmarks: the span tables as a band of n_slices_max columns)
-//   k_fbb_assign    one workgroup per utterance: logits -> softmax -> draw for each new token
-//                   (with a language model: the bigram prior of the previous token's slot)
+//   k_fbb_slots     one workgroup per utterance, a wave per new token: logits -> softmax -> draw (or the argmax,
+//                   fb_type "viterbi")
+//   k_fbb_assign_lm the same step with a language model: the bigram prior of the previous token's slot makes the draws of
+//                   an utterance a chain, block-wide (k_fbb_assign_lm_wave: one wave per utterance)
 //   k_fbb_partials  the block's partial sums from its new tokens (token order per slot)
 // Everything is fp64; the 1e-4 contract of the path would allow fp32 matrix arithmetic for the
 // fixed-variance score -- left for a later round.
@@ -808,7 +810,7 @@ __global__ __launch_bounds__(256) void k_fbb_score_diag32(segk_corpus c, segk_fb
 
 // ---------------------------------------------------------------------------------------
 // One Gibbs step of the diagonal (Student-t) sampler in float32 terms as ONE kernel (round 4): span scores, boundaries and
-// slots of an utterance by the workgroup that owns it -- k_fbb_score_diag32, k_fbb_segment and k_fbb_assign back to back
+// slots of an utterance by the workgroup that owns it -- k_fbb_score_diag32, k_fbb_segment and k_fbb_slots back to back
 // were three launches of ~25 us each for 125 utterances (6.6 us of each the empty launch, the rest one workgroup's chain
 // of round trips), and the assignment kernel evaluated the token likelihoods a second time.  Here:
 //   (1) the utterance's spans that have an embedding are listed (band or triangle), their rows and the slot tables staged
@@ -820,9 +822,9 @@ __global__ __launch_bounds__(256) void k_fbb_score_diag32(segk_corpus c, segk_fb
 //       of k_fbb_score_diag32 (also written to `score`);
 //   (4) vec, forward filtering / backward sampling by wave 0 (fb_dp_sample, as k_fbb_segment), old tokens' slots cleared;
 //   (5) every new token's slot: one wave per token, softmax over L's row in the log2 domain (v_exp_f32 / v_log_f32), the
-//       draw walking the slots in order on the token's uniform (fb_draw_chunked, as k_fbb_assign).
+//       draw walking the slots in order on the token's uniform (fb_draw_chunked, as k_fbb_slots).
 // Applies where the tables and L fit in LDS (K_max <= 256; the host checks), no language model; probes as the kernels
-// it replaces (segk_fbb_set_probe).  Token likelihoods differ from k_fbb_assign's float32 form in the last bits (one
+// it replaces (segk_fbb_set_probe).  Token likelihoods differ from k_fbb_slots' float32 form in the last bits (one
 // multiply-add instead of multiply and add): both within the 1e-4 contract, the draws are checked against their
 // slots' intervals (tests/test_gpu_tolerance_modes.py).
 // ---------------------------------------------------------------------------------------
@@ -1259,16 +1261,15 @@ __global__ __launch_bounds__(128) void k_fbb_segment(segk_corpus c, segk_fbatch 
 }
 
 // ---------------------------------------------------------------------------------------
-// The diagonal / fixed-variance token likelihoods of one chunk of an utterance's new tokens, shared by k_fbb_assign (sampled
-// slots) and k_fbb_assign_map (MAP slots): ll[r][k] = lconst_k - half_k * sum_d term(row r, slot k, d) for an occupied slot,
-// the row's prior predictive for an empty one.
+// The diagonal / fixed-variance token likelihoods of one chunk of an utterance's new tokens, shared by k_fbb_slots (sampled
+// and MAP slots) and k_fbb_assign_lm (the chain with a language model): ll[r][k] = lconst_k - half_k * sum_d term(row r,
+// slot k, d) for an occupied slot, the row's prior predictive for an empty one.
 //
 // fbb_slot_ll: slot k against a group of NR rows, the first `nr` of them tokens; xr, lpr and ll point at the group's first row.
-// F32: the terms in float32 on the hardware logarithm (fbb_accumulate_rows32), else fp64 (fbb_accumulate_rows).  Dt: the
-// dimensions walked (D; the sampled kernel's development ablation walks one).
+// F32: the terms in float32 on the hardware logarithm (fbb_accumulate_rows32), else fp64 (fbb_accumulate_rows).
 // ---------------------------------------------------------------------------------------
 template <int COV, int F32, int NR>
-static __device__ __forceinline__ void fbb_slot_ll(const segk_fbatch &bt, int KM, int k, int Dt, const double *xr, const double *lpr,
+static __device__ __forceinline__ void fbb_slot_ll(const segk_fbatch &bt, int KM, int k, int D, const double *xr, const double *lpr,
                                                    int nr, double *ll)
 {
     if (bt.cnt[k] > 0.0) {
@@ -1279,11 +1280,11 @@ static __device__ __forceinline__ void fbb_slot_ll(const segk_fbatch &bt, int KM
             float a32[NR];
 #pragma unroll
             for (int r = 0; r < NR; r++) a32[r] = 0.f;
-            fbb_accumulate_rows32<NR>(bt, KM, k, Dt, xr, a32);
+            fbb_accumulate_rows32<NR>(bt, KM, k, D, xr, a32);
 #pragma unroll
             for (int r = 0; r < NR; r++) acc[r] = 0.6931471805599453 * (double)a32[r];
         } else
-            fbb_accumulate_rows<COV, NR>(bt, KM, k, Dt, xr, acc);
+            fbb_accumulate_rows<COV, NR>(bt, KM, k, D, xr, acc);
         const double lc = bt.lconst[k], h = bt.half[k];
 #pragma unroll
         for (int r = 0; r < NR; r++)
@@ -1304,8 +1305,7 @@ static __device__ __forceinline__ void fbb_slot_ll(const segk_fbatch &bt, int KM
 // Per (row, slot) the sequence of operations is the same in both.  Ends without a barrier: the caller's follows.
 template <typename XT, int COV, int F32>
 static __device__ __forceinline__ void fbb_token_ll(const segk_corpus &c, const segk_fbgmm &f, const segk_fbatch &bt, int utt, int t0,
-                                                    int nr, int rcap, int Dt, const int32_t *new_tok, double *xs, double *lpr,
-                                                    double *ll)
+                                                    int nr, int rcap, const int32_t *new_tok, double *xs, double *lpr, double *ll)
 {
     const int D = c.D, KM = f.K_max, tid = threadIdx.x, nt = blockDim.x;
     const XT *X = (const XT *)c.X;
@@ -1325,25 +1325,62 @@ static __device__ __forceinline__ void fbb_token_ll(const segk_corpus &c, const 
     __syncthreads();
     if (nt >= 4 * 128 && KM <= 128) {
         const int k = tid & 127, r0 = 4 * (tid >> 7);
-        if (k < KM && r0 < nr) fbb_slot_ll<COV, F32, 4>(bt, KM, k, Dt, xs + r0 * D, lpr + r0, nr - r0, ll + (int64_t)r0 * KM);
+        if (k < KM && r0 < nr) fbb_slot_ll<COV, F32, 4>(bt, KM, k, D, xs + r0 * D, lpr + r0, nr - r0, ll + (int64_t)r0 * KM);
     } else {
-        for (int k = tid; k < KM; k += nt) fbb_slot_ll<COV, F32, FBB_R>(bt, KM, k, Dt, xs, lpr, nr, ll);
+        for (int k = tid; k < KM; k += nt) fbb_slot_ll<COV, F32, FBB_R>(bt, KM, k, D, xs, lpr, nr, ll);
     }
 }
 
-// ---------------------------------------------------------------------------------------
-// slots of the new tokens of one utterance per workgroup
-// ---------------------------------------------------------------------------------------
-template <typename XT, int COV, int F32 = 0>
-__global__ __launch_bounds__(512) void k_fbb_assign(segk_corpus c, segk_fbgmm f, segk_fbatch bt, FbbMap map, int b, uint64_t sweep,
-                             double prior_alpha, double anneal_temp, const int32_t *new_tok, const int32_t *n_new,
-                             int rcap, int dbg, const float *llmat, int64_t ll_ld, double *probe_ll, int64_t probe_ld,
-                             const double *fc_ll, int fc_ucap)
+// The same rows from the matrix-core contraction (segk_fbb_token_scores; fixed-variance components only): row wg * N_max + t of
+// llmat holds acc_k = (zconst_k - s_k/2 - norm + <.,.>) log2 e per packed slot and the empty-slot row at K_max
+static __device__ __forceinline__ void fbb_mat_ll(const segk_corpus &c, const segk_fbgmm &f, const segk_fbatch &bt, int t0, int nr,
+                                                  double prior_alpha, const float *llmat, int64_t ll_ld, double *ll)
 {
-    // The likelihood part of the logits does not depend on the previous segment's slot, so it is
-    // evaluated for up to `rcap` (<= FBA_R) tokens of the utterance at once (fbb_token_ll) -- the component
-    // parameters are streamed once per chunk -- and kept in LDS; the draws then run in token order
-    // (with a language model each needs the slot of the one before).
+    const int KM = f.K_max, tid = threadIdx.x, nt = blockDim.x;
+    const double LN2 = 0.6931471805599453;
+    const double zc_empty = f.lms * log(prior_alpha / (double)KM);
+    const double norm = f.lms * log(bt.scal[0] + prior_alpha);
+    const double n_empty = (double)KM - bt.scal[1];
+    const int32_t *cm = fbb_cmap(&bt, KM);
+    const int pc = cm[KM];
+    for (int r = 0; r < nr; r++) {
+        const float *mrow = llmat + ((int64_t)blockIdx.x * c.N_max + t0 + r) * ll_ld;
+        for (int k = tid; k < KM; k += nt) {
+            const int ck = cm[k];
+            ll[(int64_t)r * KM + k] = bt.cnt[k] > 0.0 && ck >= 0 ? (double)mrow[ck] * LN2 - (bt.zconst[k] - bt.lconst[k]) + norm
+                                                                 : (double)mrow[pc] * LN2 - zc_empty - log(n_empty) + norm;
+        }
+    }
+}
+
+// segk_fbb_set_probe: the likelihood part of the logits of a chunk, as the draws or the argmax after it use it (the sampled
+// draws then overwrite ll: barrier)
+static __device__ __forceinline__ void fbb_probe_store(const segk_corpus &c, int KM, int utt, int t0, int nr, const double *ll,
+                                                       double *probe_ll, int64_t probe_ld)
+{
+    for (int j = threadIdx.x; j < nr * KM; j += blockDim.x) {
+        const int r = j / KM, k = j - r * KM;
+        probe_ll[((int64_t)utt * c.N_max + t0 + r) * probe_ld + k] = ll[(int64_t)r * KM + k];
+    }
+    __syncthreads();
+}
+
+// ---------------------------------------------------------------------------------------
+// Slots of the new tokens of one utterance per workgroup, with a language model: the block-wide chain.
+//
+// The likelihood part of the logits does not depend on the previous segment's slot, so it is evaluated for up to `rcap`
+// (<= FBB_R) tokens of the utterance at once -- from the matrix-core rows (fbb_mat_ll) or by fbb_token_ll, the component
+// parameters streamed once per chunk -- and kept in LDS; the draws then run in token order, each on the slot of the token
+// before it: all threads form the logits, the softmax by block_max / block_sum, the draw by wave 0, the slot handed on
+// through sh_k -- seven barriers per token.  Always 256 threads (fbb_assign_chunks); no full-covariance form (check_fbb
+// refuses a language model there).  k_fbb_assign_lm_wave below replaces it where the matrix-core rows are at hand.
+// ---------------------------------------------------------------------------------------
+template <typename XT, int COV, int F32>
+__global__ __launch_bounds__(256) void k_fbb_assign_lm(segk_corpus c, segk_fbgmm f, segk_fbatch bt, FbbMap map, int b, uint64_t sweep,
+                                                       double prior_alpha, double anneal_temp, const int32_t *new_tok,
+                                                       const int32_t *n_new, int rcap, const float *llmat, int64_t ll_ld,
+                                                       double *probe_ll, int64_t probe_ld)
+{
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int D = c.D, KM = f.K_max, tid = threadIdx.x, nt = blockDim.x;
     double *z = (double *)smem;                  // [K_max]
@@ -1357,98 +1394,22 @@ __global__ __launch_bounds__(512) void k_fbb_assign(segk_corpus c, segk_fbgmm f,
     const int slice = map.lo[s];
     const int utt = bt.utt_range[(slice * bt.n_blocks + b) * 2] + idx;
     const int nn = n_new[utt];
-    const double zc_empty = f.lms * log(prior_alpha / (double)KM);
     const double tot = bt.scal[0];
     int j_prev = -1;
     for (int t0 = 0; t0 < nn; t0 += rcap) {
         const int nr = nn - t0 < rcap ? nn - t0 : rcap;
         __syncthreads();
-        if (llmat) {
-            // token likelihoods from the matrix-core contraction (segk_fbb_token_scores): row blockIdx.x*N_max + t
-            // holds acc_k = (zconst_k - s_k/2 - norm + <.,.>) log2 e per slot and the empty-slot row at K_max
-            const double LN2 = 0.6931471805599453;
-            const double norm = f.lms * log(tot + prior_alpha);
-            const double n_empty = (double)KM - bt.scal[1];
-            const int32_t *cm = fbb_cmap(&bt, KM);
-            const int pc = cm[KM];
-            for (int r = 0; r < nr; r++) {
-                const float *mrow = llmat + ((int64_t)blockIdx.x * c.N_max + t0 + r) * ll_ld;
-                for (int k = tid; k < KM; k += nt) {
-                    const int ck = cm[k];
-                    ll[(int64_t)r * KM + k] = bt.cnt[k] > 0.0 && ck >= 0 ? (double)mrow[ck] * LN2 - (bt.zconst[k] - bt.lconst[k]) + norm
-                                                                         : (double)mrow[pc] * LN2 - zc_empty - log(n_empty) + norm;
-                }
-            }
-        } else if constexpr (COV == 2) {
-            // full covariance: the block's token likelihoods were formed by k_fcb_token_ll (the row's prior predictive in the
-            // empty slots)
-            const double *tab = fc_ll + (((int64_t)s * fc_ucap + idx) * c.N_max + t0) * KM;
-            for (int j = tid; j < nr * KM; j += nt) ll[j] = tab[j];
-        } else {
-            fbb_token_ll<XT, COV, F32>(c, f, bt, utt, t0, nr, rcap, (dbg & 1) ? 1 : D, new_tok, xs, lpr, ll);
-        }
+        if (llmat) fbb_mat_ll(c, f, bt, t0, nr, prior_alpha, llmat, ll_ld, ll);
+        else fbb_token_ll<XT, COV, F32>(c, f, bt, utt, t0, nr, rcap, new_tok, xs, lpr, ll);
         __syncthreads();
-        if (probe_ll) {         // segk_fbb_set_probe: the likelihood part of the logits, as the draws below use it
-            for (int j = tid; j < nr * KM; j += nt) {
-                const int r = j / KM, k = j - r * KM;
-                probe_ll[((int64_t)utt * c.N_max + t0 + r) * probe_ld + k] = ll[(int64_t)r * KM + k];
-            }
-            __syncthreads();
-        }
-        if (!f.lm_unigram) {
-            // Without a language model a token's draw does not depend on the token before it: one WAVE per token, maxima
-            // and sums by shuffles.  The sums keep the association of the block-wide form below at 256 threads (per wave
-            // of 64 consecutive slots a butterfly, the waves' results added in order), so the probabilities -- and the
-            // draws -- are the same bits.
-            const int w = tid >> 6, lane = tid & 63, nw = nt >> 6;
-            for (int r = w; r < ((dbg & 2) ? 1 : nr); r += nw) {
-                const int64_t e = new_tok[(int64_t)utt * c.N_max + t0 + r];
-                // (fbb_draw_row of segk_fbb_dev.h restates the statements from here to the draw for k_fbi_assign: keep the two alike)
-                double *zr = ll + (int64_t)r * KM;
-                double mx = NEG_INF_D;
-                for (int k = lane; k < KM; k += 64) {
-                    const double n = bt.cnt[k];
-                    const double v = (n > 0.0 ? f.lms * log(prior_alpha / (double)KM + n) : zc_empty) + zr[k];      // fbgmm.py:436-440
-                    zr[k] = v;
-                    mx = v > mx ? v : mx;
-                }
-                mx = fb_wave_max(mx, false);
-                auto sum_exp = [&](double shift) -> double {       // sum_k exp(zr[k] - shift) in the order of block_sum at 256 threads
-                    double tot = 0.0;
-                    for (int cw = 0; cw < 4 && cw * 64 < KM; cw++) {
-                        double sv = 0.0;
-                        for (int k = cw * 64 + lane; k < KM; k += 256) sv += exp(zr[k] - shift);
-                        sv = fb_wave_sum(sv);
-                        tot = cw == 0 ? sv : tot + sv;
-                    }
-                    return tot;
-                };
-                double lse = log(sum_exp(mx)) + mx;
-                if (anneal_temp != 1.0) {                           // fbgmm.py:446-449
-                    double mx2 = NEG_INF_D;
-                    for (int k = lane; k < KM; k += 64) {
-                        const double v = (1. / anneal_temp) * (zr[k] - lse);
-                        zr[k] = v;
-                        mx2 = v > mx2 ? v : mx2;
-                    }
-                    mx2 = fb_wave_max(mx2, false);
-                    lse = log(sum_exp(mx2)) + mx2;
-                }
-                for (int k = lane; k < KM; k += 64) zr[k] = exp(zr[k] - lse);
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                const int k = (dbg & 4) ? 0 : fb_draw_chunked(zr, KM, segk_u01(bt.seed, sweep, (uint64_t)utt, (uint64_t)(c.N_max + t0 + r)), lane);
-                if (lane == 0) bt.slot[e] = k;
-            }
-        } else
-        for (int r = 0; r < ((dbg & 2) ? 1 : nr); r++) {
+        if (probe_ll) fbb_probe_store(c, KM, utt, t0, nr, ll, probe_ll, probe_ld);
+        for (int r = 0; r < nr; r++) {
             const int64_t e = new_tok[(int64_t)utt * c.N_max + t0 + r];
             for (int k = tid; k < KM; k += nt) {
                 const double n = bt.cnt[k];
                 double pz;
-                if (!f.lm_unigram) pz = n > 0.0 ? f.lms * log(prior_alpha / (double)KM + n) : zc_empty;   // fbgmm.py:436-440
-                else if (j_prev < 0) pz = (log(n + f.lm_a / (double)KM) - log(tot + f.lm_a)) * f.lms;  // bigram_lms.py:64-69
-                else {                                                                                // bigram_lms.py:84-91
+                if (j_prev < 0) pz = (log(n + f.lm_a / (double)KM) - log(tot + f.lm_a)) * f.lms;       // bigram_lms.py:64-69
+                else {                                                                         // bigram_lms.py:84-91
                     const double pi = (n + f.lm_a / (double)KM) / (tot + f.lm_a);
                     const double pij = (1. - f.lm_lambda) * ((double)f.lm_bigram[(int64_t)j_prev * KM + k] + f.lm_b / (double)KM)
                                        / (bt.cnt[j_prev] + f.lm_b);
@@ -1479,29 +1440,34 @@ __global__ __launch_bounds__(512) void k_fbb_assign(segk_corpus c, segk_fbgmm f,
             for (int k = tid; k < KM; k += nt) z[k] = exp(z[k] - lse);
             __syncthreads();
             if (tid < 64) {
-                const int k = (dbg & 4) ? 0 : fb_draw_chunked(z, KM, segk_u01(bt.seed, sweep, (uint64_t)utt, (uint64_t)(c.N_max + t0 + r)), tid);
+                const int k = fb_draw_chunked(z, KM, segk_u01(bt.seed, sweep, (uint64_t)utt, (uint64_t)(c.N_max + t0 + r)), tid);
                 if (tid == 0) {
                     bt.slot[e] = k;
                     sh_k = k;
                 }
             }
             __syncthreads();
-            if (f.lm_unigram) j_prev = sh_k;
+            j_prev = sh_k;
         }
     }
 }
 
 // ---------------------------------------------------------------------------------------
-// The MAP slot of every new token (FBGMM.map_assign_i, fbgmm.py:465-494, on slots): k = the first index of the maximum of
-// z_k = log(alpha / K_max + n_k) + loglik_k(x) -- no `lms` on the prior term (fbgmm.py:475-479 has none), no temperature, no
-// uniform, no softmax (the reference's argmax(exp(z - logsumexp z)) is the argmax of z: tests/test_map_batch_cpu.py holds
-// that on every token of the test corpora).  k_fbb_assign without a language model with the draw replaced: one workgroup per
-// utterance; the prior terms once per workgroup into LDS; the likelihoods of a chunk of tokens by the same code (fbb_token_ll:
-// the same staging, row groups and accumulation, with Dt = D) into LDS; then one WAVE per token: a
-// per-lane (value, index) over k = lane, lane + 64, ... with strict >, the wave's maximum by DPP and the lowest index among
-// the lanes that hold it.  All empty slots of a token carry one value, so the first of them wins a tie among them without
-// being treated apart.  Never reads ll_mat: in the fixed-variance tolerance modes the token likelihood is the fp64 quadratic
-// (F32 = 1: the float32 Student-t terms of segk_fbb_assign_diag32).
+// Slots of the new tokens of one utterance per workgroup, without a language model: a token's slot does not depend on the
+// token before it.  Per chunk of up to `rcap` (<= FBA_R) tokens the likelihoods of all K_max slots into LDS -- the
+// matrix-core rows (fbb_mat_ll; sampled slots only), with full covariance the table of k_fcb_token_ll (the row's prior
+// predictive in the empty slots), else fbb_token_ll -- then one WAVE per token:
+//   * sampled (MAP = false): prior term, softmax, annealing and the draw on u01(seed, sweep, utt, N_max + t) -- fbb_draw_row
+//     (segk_fbb_dev.h), which overwrites the token's row of ll;
+//   * MAP = true (FBGMM.map_assign_i, fbgmm.py:465-494, on slots): k = the first index of the maximum of
+//     z_k = log(alpha / K_max + n_k) + loglik_k(x) -- no `lms` on the prior term (fbgmm.py:475-479 has none), no temperature,
+//     no uniform, no softmax (the reference's argmax(exp(z - logsumexp z)) is the argmax of z: tests/test_map_batch_cpu.py
+//     holds that on every token of the test corpora).  The prior terms once per workgroup into LDS; a per-lane (value, index)
+//     over k = lane, lane + 64, ... with strict >, the wave's maximum by DPP and the lowest index among the lanes that hold it.
+//     All empty slots of a token carry one value, so the first of them wins a tie among them without being treated apart.
+//     Never reads ll_mat: in the fixed-variance tolerance modes the token likelihood is the fp64 quadratic.
+// F32 = 1: the float32 Student-t terms of segk_fbb_assign_diag32.  The LDS image is k_fbb_assign_lm's (fbb_assign_plan): the
+// leading K_max doubles are pz with MAP and unused without.
 // ---------------------------------------------------------------------------------------
 static __device__ __forceinline__ int fbb_wave_min_i32(int v)       // minimum over the 64 lanes, wave-uniform
 {
@@ -1519,14 +1485,15 @@ static __device__ __forceinline__ int fbb_wave_min_i32(int v)       // minimum o
     return c < a ? c : a;
 }
 
-template <typename XT, int COV, int F32 = 0>
-__global__ __launch_bounds__(512) void k_fbb_assign_map(segk_corpus c, segk_fbgmm f, segk_fbatch bt, FbbMap map, int b, double prior_alpha,
-                                 const int32_t *new_tok, const int32_t *n_new, int rcap, double *probe_ll, int64_t probe_ld,
-                                 const double *fc_ll, int fc_ucap)
+template <typename XT, int COV, int F32, bool MAP>
+__global__ __launch_bounds__(512) void k_fbb_slots(segk_corpus c, segk_fbgmm f, segk_fbatch bt, FbbMap map, int b, uint64_t sweep,
+                                                   double prior_alpha, double anneal_temp, const int32_t *new_tok,
+                                                   const int32_t *n_new, int rcap, const float *llmat, int64_t ll_ld,
+                                                   double *probe_ll, int64_t probe_ld, const double *fc_ll, int fc_ucap)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int D = c.D, KM = f.K_max, tid = threadIdx.x, nt = blockDim.x;
-    double *pz = (double *)smem;                 // [K_max] log(alpha / K_max + n_k)
+    double *pz = (double *)smem;                 // [K_max] MAP: log(alpha / K_max + n_k)
     double *ll = pz + KM;                        // [rcap][K_max]
     double *xs = ll + (int64_t)rcap * KM;        // [FBA_R][D]
     double *lpr = xs + FBA_R * D;                // [FBA_R]
@@ -1536,35 +1503,39 @@ __global__ __launch_bounds__(512) void k_fbb_assign_map(segk_corpus c, segk_fbgm
     const int utt = bt.utt_range[(slice * bt.n_blocks + b) * 2] + idx;
     const int nn = n_new[utt];
     if (nn == 0) return;
-    for (int k = tid; k < KM; k += nt) pz[k] = log(prior_alpha / (double)KM + bt.cnt[k]);      // fbgmm.py:475-479
+    const double zc_empty = f.lms * log(prior_alpha / (double)KM);
+    if (MAP)
+        for (int k = tid; k < KM; k += nt) pz[k] = log(prior_alpha / (double)KM + bt.cnt[k]);      // fbgmm.py:475-479
     for (int t0 = 0; t0 < nn; t0 += rcap) {
         const int nr = nn - t0 < rcap ? nn - t0 : rcap;
         __syncthreads();
-        if constexpr (COV == 2) {
-            // full covariance: the block's token likelihoods were formed by k_fcb_token_ll (k_fbb_assign)
+        if (!MAP && llmat) fbb_mat_ll(c, f, bt, t0, nr, prior_alpha, llmat, ll_ld, ll);
+        else if constexpr (COV == 2) {
             const double *tab = fc_ll + (((int64_t)s * fc_ucap + idx) * c.N_max + t0) * KM;
             for (int j = tid; j < nr * KM; j += nt) ll[j] = tab[j];
         } else {
-            fbb_token_ll<XT, COV, F32>(c, f, bt, utt, t0, nr, rcap, D, new_tok, xs, lpr, ll);
+            fbb_token_ll<XT, COV, F32>(c, f, bt, utt, t0, nr, rcap, new_tok, xs, lpr, ll);
         }
         __syncthreads();
-        if (probe_ll)           // segk_fbb_set_probe: the likelihood part of the logits, as the argmax below uses it
-            for (int j = tid; j < nr * KM; j += nt) {
-                const int r = j / KM, k = j - r * KM;
-                probe_ll[((int64_t)utt * c.N_max + t0 + r) * probe_ld + k] = ll[(int64_t)r * KM + k];
-            }
+        if (probe_ll) fbb_probe_store(c, KM, utt, t0, nr, ll, probe_ll, probe_ld);
         const int w = tid >> 6, lane = tid & 63, nw = nt >> 6;
         for (int r = w; r < nr; r += nw) {
-            const double *zr = ll + (int64_t)r * KM;
-            double best = NEG_INF_D;
-            int bk = KM;
-            for (int k = lane; k < KM; k += 64) {
-                const double z = pz[k] + zr[k];
-                if (z > best) { best = z; bk = k; }
-            }
-            const double m = fb_wave_max(best, false);
-            const int k = fbb_wave_min_i32(best == m ? bk : KM);
-            if (lane == 0) bt.slot[new_tok[(int64_t)utt * c.N_max + t0 + r]] = k < KM ? k : 0;
+            double *zr = ll + (int64_t)r * KM;
+            int k;
+            if (MAP) {
+                double best = NEG_INF_D;
+                int bk = KM;
+                for (int kk = lane; kk < KM; kk += 64) {
+                    const double z = pz[kk] + zr[kk];
+                    if (z > best) { best = z; bk = kk; }
+                }
+                const double m = fb_wave_max(best, false);
+                k = fbb_wave_min_i32(best == m ? bk : KM);
+                k = k < KM ? k : 0;
+            } else
+                k = fbb_draw_row(f, bt, KM, prior_alpha, zc_empty, anneal_temp, zr, sweep, (uint64_t)utt,
+                                 (uint64_t)(c.N_max + t0 + r), lane);
+            if (lane == 0) bt.slot[new_tok[(int64_t)utt * c.N_max + t0 + r]] = k;
         }
     }
 }
@@ -2174,7 +2145,7 @@ static int check_fbb_long(const segk_corpus *c, int n_slices_max)
     return SEGK_OK;
 }
 
-// Chunks and threads of the assignment kernels (k_fbb_assign, k_fbb_assign_map).  Tokens per chunk: as many likelihood rows
+// Chunks and threads of the slot kernels (k_fbb_slots, k_fbb_assign_lm).  Tokens per chunk: as many likelihood rows
 // of K_max doubles as fit beside the `fixed_b` bytes of the rest (two workgroups per CU).  512 threads where the slots alone
 // would leave most of 256 idle and the tokens' draws are independent (no language model): four row groups of four rows in
 // the likelihood phase (fbb_token_ll), a wave per token in the draw phase.  512 threads come with chunks of FBA_R = 16 tokens
@@ -2531,7 +2502,7 @@ int32_t segk_fbb_token_scores(segk_ctx *ctx, const segk_corpus *c, const segk_fb
 
 // What the slot entry points do before they launch: the arguments checked, the step's utterances mapped to workgroups
 // (p->m.off[s_n] == 0: nothing to launch), with cov_type 2 the token table of segk_fcb_token_ll formed, chunks and threads
-// chosen.  map_slots: segk_fbb_assign_map -- no language model, and no `red` in the fixed part of the kernel's LDS.
+// chosen.  map_slots: segk_fbb_assign_map -- no language model, and no `red` in the fixed part of the kernels' LDS.
 struct FbbAssignPlan {
     FbbMap m;
     FbbChunks ch;
@@ -2564,11 +2535,43 @@ static int32_t fbb_assign_plan(FbbAssignPlan *p, bool map_slots, segk_ctx *ctx, 
         rc = segk_fcb_token_ll(ctx, c, f, bt, s_lo, s_n, b, n_utts, new_tok, n_new, &p->fc_ll, &p->fc_ucap, stream);
         if (rc) return rc;
     }
-    // (the fixed part: the logits z or the prior terms pz, the token rows xs, their prior predictive lpr, the sixteen doubles of
-    // the sampled kernel's red)
+    // (the fixed part: K_max doubles -- the chain's logits z, the MAP prior terms pz, unused by the sampled k_fbb_slots --, the
+    // token rows xs, their prior predictive lpr, and with sampled slots sixteen doubles -- the chain's red, unused by
+    // k_fbb_slots.  The unused doubles stay reserved: without them more tokens would fit a chunk at large banks, a change of
+    // the launch plan and of the speed, not of this layout's meaning)
     p->ch = fbb_assign_chunks((size_t)(f->K_max + FBA_R * c->D + FBA_R + (map_slots ? 0 : 16)) * sizeof(double), f->K_max,
                               f->lm_unigram != nullptr);
     SEGK_REQUIRE(p->ch.lds <= 160 * 1024, "K_max too large for the LDS logits buffer");
+    return SEGK_OK;
+}
+
+// k_fbb_slots on a plan with work in it: sampled slots (segk_fbb_assign / _assign_diag32 without a language model) or MAP slots
+// (segk_fbb_assign_map: sweep, anneal_temp and ll_mat unused)
+static int32_t fbb_slots_launch(bool map_slots, const FbbAssignPlan &p, segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt,
+                                int32_t s_n, int32_t b, uint64_t sweep, double anneal_temp, const int32_t *new_tok,
+                                const int32_t *n_new, const float *ll_mat, int64_t ll_ld, int f32, void *stream)
+{
+#define SEGK_SLOTS(COV, F32, MAP)                                                                                               \
+    do {                                                                                                                        \
+        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbb_slots<XT, COV, F32, MAP>, p.ch.lds));                                   \
+        hipLaunchKernelGGL((k_fbb_slots<XT, COV, F32, MAP>), dim3(p.m.off[s_n]), dim3(p.ch.threads), p.ch.lds, (hipStream_t)stream, \
+                           *c, *f, *bt, p.m, b, sweep, f->alpha, anneal_temp, new_tok, n_new, p.ch.rcap, ll_mat, ll_ld,          \
+                           ctx->probe_ll, ctx->probe_ll_ld, p.fc_ll, p.fc_ucap);                                                \
+    } while (0)
+#define SEGK_SLOTS_OF(MAP)                                                                                                      \
+    do {                                                                                                                        \
+        if (f->cov_type == 0) SEGK_SLOTS(0, 0, MAP);                                                                            \
+        else if (f->cov_type == 2) SEGK_SLOTS(2, 0, MAP);                                                                       \
+        else if (f32) SEGK_SLOTS(1, 1, MAP);                                                                                    \
+        else SEGK_SLOTS(1, 0, MAP);                                                                                             \
+    } while (0)
+    DISPATCH_XT(c, {
+        if (map_slots) SEGK_SLOTS_OF(true);
+        else SEGK_SLOTS_OF(false);
+    });
+#undef SEGK_SLOTS_OF
+#undef SEGK_SLOTS
+    SEGK_LAUNCH_CHECK();
     return SEGK_OK;
 }
 
@@ -2580,13 +2583,12 @@ static int32_t fbb_assign_impl(segk_ctx *ctx, const segk_corpus *c, const segk_f
     FbbAssignPlan p;
     const int rc = fbb_assign_plan(&p, false, ctx, c, f, bt, s_lo, s_n, b, n_utts, new_tok, n_new, ll_mat, f32, stream);
     if (rc || p.m.off[s_n] == 0) return rc;
+    if (!f->lm_unigram) return fbb_slots_launch(false, p, ctx, c, f, bt, s_n, b, sweep, anneal_temp, new_tok, n_new, ll_mat, ll_ld, f32, stream);
     const FbbMap &m = p.m;
     const FbbChunks &ch = p.ch;
-    const double alpha = f->lm_unigram ? f->lm_a : f->alpha;
-    // timing-only ablation knob (development): 1 = one dimension, 2 = one token, 4 = no draw
-    const int dbg = segk_dev_env("SEGK_FBB_DBG");       // -DSEGK_DEV builds only
-    // language model + matrix-core likelihoods: one wave per utterance (SEGK_FBB_ASSIGN_WAVE=0: the block-wide form)
-    if (f->lm_unigram && ll_mat && dbg == 0 && segk_env_int("SEGK_FBB_ASSIGN_WAVE", 1) != 0 && 4 * (size_t)f->K_max * sizeof(double) <= 146 * 1024) {
+    const double alpha = f->lm_a;
+    // matrix-core likelihoods: one wave per utterance (SEGK_FBB_ASSIGN_WAVE=0: the block-wide form)
+    if (ll_mat && segk_env_int("SEGK_FBB_ASSIGN_WAVE", 1) != 0 && 4 * (size_t)f->K_max * sizeof(double) <= 146 * 1024) {
         const size_t ldsw = 4 * (size_t)f->K_max * sizeof(double) + sizeof(int) * (size_t)(f->K_max + 2);
         const int n_items = m.off[s_n];
 #define SEGK_LM_WAVE(PP)                                                                                                        \
@@ -2601,20 +2603,20 @@ static int32_t fbb_assign_impl(segk_ctx *ctx, const segk_corpus *c, const segk_f
         SEGK_LAUNCH_CHECK();
         return SEGK_OK;
     }
-#define SEGK_ASSIGN(COV, F32)                                                                                                   \
+    // the block-wide chain (cov_type 2 with a language model: refused by check_fbb)
+#define SEGK_ASSIGN_LM(COV, F32)                                                                                                \
     do {                                                                                                                        \
-        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbb_assign<XT, COV, F32>, ch.lds));                                         \
-        hipLaunchKernelGGL((k_fbb_assign<XT, COV, F32>), dim3(m.off[s_n]), dim3(ch.threads), ch.lds, (hipStream_t)stream, *c, *f, *bt, \
-                           m, b, sweep, alpha, anneal_temp, new_tok, n_new, ch.rcap, dbg, ll_mat, ll_ld, ctx->probe_ll,          \
-                           ctx->probe_ll_ld, p.fc_ll, p.fc_ucap);                                                               \
+        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbb_assign_lm<XT, COV, F32>, ch.lds));                                      \
+        hipLaunchKernelGGL((k_fbb_assign_lm<XT, COV, F32>), dim3(m.off[s_n]), dim3(ch.threads), ch.lds, (hipStream_t)stream, *c, *f, \
+                           *bt, m, b, sweep, alpha, anneal_temp, new_tok, n_new, ch.rcap, ll_mat, ll_ld, ctx->probe_ll,          \
+                           ctx->probe_ll_ld);                                                                                   \
     } while (0)
     DISPATCH_XT(c, {
-        if (f->cov_type == 0) SEGK_ASSIGN(0, 0);
-        else if (f->cov_type == 2) SEGK_ASSIGN(2, 0);
-        else if (f32) SEGK_ASSIGN(1, 1);
-        else SEGK_ASSIGN(1, 0);
+        if (f->cov_type == 0) SEGK_ASSIGN_LM(0, 0);
+        else if (f32) SEGK_ASSIGN_LM(1, 1);
+        else SEGK_ASSIGN_LM(1, 0);
     });
-#undef SEGK_ASSIGN
+#undef SEGK_ASSIGN_LM
     SEGK_LAUNCH_CHECK();
     return SEGK_OK;
 }
@@ -2639,27 +2641,11 @@ int32_t segk_fbb_assign_map(segk_ctx *ctx, const segk_corpus *c, const segk_fbgm
                             int32_t s_n, int32_t b, const int32_t *n_utts, uint64_t sweep, const int32_t *new_tok,
                             const int32_t *n_new, int32_t f32_terms, void *stream)
 {
-    (void)sweep;                  // no uniforms are consumed
     FbbAssignPlan p;
     const int rc = fbb_assign_plan(&p, true, ctx, c, f, bt, s_lo, s_n, b, n_utts, new_tok, n_new, nullptr, f32_terms, stream);
     if (rc || p.m.off[s_n] == 0) return rc;
-    const FbbMap &m = p.m;
-    const FbbChunks &ch = p.ch;
-#define SEGK_ASSIGN_MAP(COV, F32)                                                                                               \
-    do {                                                                                                                        \
-        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbb_assign_map<XT, COV, F32>, ch.lds));                                     \
-        hipLaunchKernelGGL((k_fbb_assign_map<XT, COV, F32>), dim3(m.off[s_n]), dim3(ch.threads), ch.lds, (hipStream_t)stream, *c, *f, \
-                           *bt, m, b, f->alpha, new_tok, n_new, ch.rcap, ctx->probe_ll, ctx->probe_ll_ld, p.fc_ll, p.fc_ucap);   \
-    } while (0)
-    DISPATCH_XT(c, {
-        if (f->cov_type == 0) SEGK_ASSIGN_MAP(0, 0);
-        else if (f->cov_type == 2) SEGK_ASSIGN_MAP(2, 0);
-        else if (f32_terms) SEGK_ASSIGN_MAP(1, 1);
-        else SEGK_ASSIGN_MAP(1, 0);
-    });
-#undef SEGK_ASSIGN_MAP
-    SEGK_LAUNCH_CHECK();
-    return SEGK_OK;
+    // (no uniforms are consumed: the sweep index goes unread, as do the temperature and the matrix)
+    return fbb_slots_launch(true, p, ctx, c, f, bt, s_n, b, sweep, 1.0, new_tok, n_new, nullptr, 0, f32_terms, stream);
 }
 
 int32_t segk_fbb_step_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,

@@ -8,9 +8,9 @@
 //                           waves over the slots.  The slots are walked FBI_KC = 16 at a time, their (mean, q) staged in LDS once
 //                           per tile and read as broadcasts; per (item, slot) the operations are those of fbb_accumulate_rows
 //                           / fbb_slot_ll (segk_fbbatch.hip), dimensions in increasing order, so the likelihoods are the bits
-//                           k_fbb_assign forms for the same row and statistics.  The tile's logits [64][K_max] stay in LDS
+//                           k_fbb_slots forms for the same row and statistics.  The tile's logits [64][K_max] stay in LDS
 //                           where they fit (FBI_LDS_MAX) and go to a workspace of the context otherwise; then one wave per
-//                           item: prior term, softmax, annealing and draw (fbb_draw_row: k_fbb_assign's statements).
+//                           item: prior term, softmax, annealing and draw (fbb_draw_row, the call k_fbb_slots makes).
 //   cov_type 2              the likelihoods of the block's items are formed by k_fcb_token_ll (segk_fullcov.hip: one slot's
 //                           packed triangle staged per 256 items) into its context table; k_fbi_assign<XT, 2> is the draw half
 //                           reading that table.
@@ -23,7 +23,7 @@
 //                           token list (row, utterance, position) and its length into a workspace of the context -- utterance
 //                           order, then position, the order of the partial sums
 //   k_fbi_assign<.., true>  a tile is 64 consecutive entries of that list (TOK): the rows are gathered through it, the draw of
-//                           token t of utterance i uses u01(seed, sweep, i, N_max + t) as k_fbb_assign does, n_new / new_tok
+//                           token t of utterance i uses u01(seed, sweep, i, N_max + t) as k_fbb_slots does, n_new / new_tok
 //                           are only read.  The grid is sized from the host's bound on the cell's tokens (its landmarks); a
 //                           tile that begins at or beyond the list's length returns at once.
 // No grid barrier, no spin loop, no cooperative launch, no atomics: a plain grid over the tiles.
@@ -296,6 +296,24 @@ static int32_t fbi_launch(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm 
     return SEGK_OK;
 }
 
+// what both entry points ask of their arguments beyond the corpus' shape
+static int fbi_check(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo, int32_t s_n, int32_t b,
+                     const double *probe_ll, int64_t probe_ld, const char *who)
+{
+    SEGK_REQUIRE(c->x_dtype == SEGK_F32 || c->x_dtype == SEGK_F64, "unsupported dtype");
+    SEGK_REQUIRE(f->cov_type >= 0 && f->cov_type <= 2, "cov_type must be 0 (fixed), 1 (diag) or 2 (full)");
+    SEGK_REQUIRE(c->D > 0 && c->D <= 256, "batch mode supports D <= 256");
+    SEGK_REQUIRE(f->K_max >= 1 && f->K_max <= 8192, "K_max");
+    SEGK_REQUIRE(bt->n_slices >= 1 && bt->n_slices <= 16 && bt->n_blocks >= 1, "slices / blocks");
+    SEGK_REQUIRE(s_lo >= 0 && s_n >= 1 && s_n <= 16 && s_lo + s_n <= bt->n_slices && b >= 0 && b < bt->n_blocks, "slice / block range");
+    SEGK_REQUIRE(bt->prior_rows && bt->utt_range && bt->slot && bt->cnt && bt->mean_t && bt->q_t && bt->lconst && bt->half,
+                 "batch state (prior_rows, ranges, slot, slot tables)");
+    SEGK_REQUIRE(!probe_ll || probe_ld >= f->K_max, "probe leading dimension");
+    if (f->cov_type == 2)
+        if (int rc = segk_fcb_check(c, f, bt, who)) return rc;
+    return SEGK_OK;
+}
+
 extern "C" {
 
 int32_t segk_fbi_assign(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,
@@ -308,19 +326,9 @@ int32_t segk_fbi_assign(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f
         segk_set_error("segk_fbi_assign: the stand-alone batch sweep takes no language model");
         return SEGK_ERR_UNSUPPORTED;
     }
-    SEGK_REQUIRE(c->x_dtype == SEGK_F32 || c->x_dtype == SEGK_F64, "unsupported dtype");
-    SEGK_REQUIRE(f->cov_type >= 0 && f->cov_type <= 2, "cov_type must be 0 (fixed), 1 (diag) or 2 (full)");
     SEGK_REQUIRE(!c->vec_ids && !c->band_ids && c->N_max == 1 && c->n_utt == c->n_emb,
                  "a corpus of items: one one-landmark utterance per row, no span tables");
-    SEGK_REQUIRE(c->D > 0 && c->D <= 256, "batch mode supports D <= 256");
-    SEGK_REQUIRE(f->K_max >= 1 && f->K_max <= 8192, "K_max");
-    SEGK_REQUIRE(bt->n_slices >= 1 && bt->n_slices <= 16 && bt->n_blocks >= 1, "slices / blocks");
-    SEGK_REQUIRE(s_lo >= 0 && s_n >= 1 && s_n <= 16 && s_lo + s_n <= bt->n_slices && b >= 0 && b < bt->n_blocks, "slice / block range");
-    SEGK_REQUIRE(bt->prior_rows && bt->utt_range && bt->slot && bt->cnt && bt->mean_t && bt->q_t && bt->lconst && bt->half,
-                 "batch state (prior_rows, ranges, slot, slot tables)");
-    SEGK_REQUIRE(!probe_ll || probe_ld >= f->K_max, "probe leading dimension");
-    if (f->cov_type == 2)
-        if (int rc = segk_fcb_check(c, f, bt, "segk_fbi_assign")) return rc;
+    if (int rc = fbi_check(c, f, bt, s_lo, s_n, b, probe_ll, probe_ld, "segk_fbi_assign")) return rc;
     FbbMap m;
     m.n = s_n;
     m.off[0] = 0;
@@ -346,19 +354,9 @@ int32_t segk_fbt_assign(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f
                        "sweeps: its reference asserts at am_n_iter > 0)");
         return SEGK_ERR_UNSUPPORTED;
     }
-    SEGK_REQUIRE(c->x_dtype == SEGK_F32 || c->x_dtype == SEGK_F64, "unsupported dtype");
-    SEGK_REQUIRE(f->cov_type >= 0 && f->cov_type <= 2, "cov_type must be 0 (fixed), 1 (diag) or 2 (full)");
     SEGK_REQUIRE((c->vec_ids || c->band_ids) && c->n_utt > 0 && c->N_max > 0,
                  "a segmenter's corpus: utterances with span tables (the items of a stand-alone model go through segk_fbi_assign)");
-    SEGK_REQUIRE(c->D > 0 && c->D <= 256, "batch mode supports D <= 256");
-    SEGK_REQUIRE(f->K_max >= 1 && f->K_max <= 8192, "K_max");
-    SEGK_REQUIRE(bt->n_slices >= 1 && bt->n_slices <= 16 && bt->n_blocks >= 1, "slices / blocks");
-    SEGK_REQUIRE(s_lo >= 0 && s_n >= 1 && s_n <= 16 && s_lo + s_n <= bt->n_slices && b >= 0 && b < bt->n_blocks, "slice / block range");
-    SEGK_REQUIRE(bt->prior_rows && bt->utt_range && bt->slot && bt->cnt && bt->mean_t && bt->q_t && bt->lconst && bt->half,
-                 "batch state (prior_rows, ranges, slot, slot tables)");
-    SEGK_REQUIRE(!probe_ll || probe_ld >= f->K_max, "probe leading dimension");
-    if (f->cov_type == 2)
-        if (int rc = segk_fcb_check(c, f, bt, "segk_fbt_assign")) return rc;
+    if (int rc = fbi_check(c, f, bt, s_lo, s_n, b, probe_ll, probe_ld, "segk_fbt_assign")) return rc;
     FbbMap m;
     FbtList L = {};
     m.n = s_n;

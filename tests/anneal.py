@@ -56,14 +56,14 @@ TP0 = dict(time_power_term=0.0)
 EXACT = {
     # k_fbb_segment (N_max <= 64), window <= 16: fb_dp_sample_on's LDS path with triangular addressing
     "fixed_w5_fb": _chain("fixed", 24, 8, 10, 77, 5, 3, 4, 10.0, False, "k_fbb_segment, window <= 16; boundaries only", **TP0),
-    "fixed_w5_am": _chain("fixed", 24, 8, 10, 77, 5, 3, 4, 10.0, True, "k_fbb_assign<COV 0>, 512 threads: wave per token", **TP0),
+    "fixed_w5_am": _chain("fixed", 24, 8, 10, 77, 5, 3, 4, 10.0, True, "k_fbb_slots<COV 0>, 512 threads: wave per token", **TP0),
     # (n_slices_min = 1: the batch entry points take 0 or 1; see test_anneal_batch_cpu.py for what it changes)
-    "diag_w5_am": _chain("diag", 24, 8, 10, 78, 5, 3, 4, 10.0, True, "k_fbb_assign<COV 1>, 512 threads: wave per token",
+    "diag_w5_am": _chain("diag", 24, 8, 10, 78, 5, 3, 4, 10.0, True, "k_fbb_slots<COV 1>, 512 threads: wave per token",
                          n_slices_min=1, **TP0),
     "diag_w5_fb_T2": _chain("diag", 24, 8, 10, 78, 5, 3, 4, 2.0, False, "k_fbb_segment; boundaries only", **TP0),
     "diag_w5_T05": _chain("diag", 24, 8, 10, 78, 5, 3, 4, 0.5, True, "T < 1, boundaries and slots", **TP0),
     "bigram_w5_fb": _chain("bigram", 30, 8, 12, 91, 5, 3, 4, 10.0, False, "k_fbb_segment; boundaries only, language model", **TP0),
-    "bigram_w5_am": _chain("bigram", 30, 8, 12, 91, 5, 3, 4, 10.0, True, "k_fbb_assign, block-wide draw (language model)", **TP0),
+    "bigram_w5_am": _chain("bigram", 30, 8, 12, 91, 5, 3, 4, 10.0, True, "k_fbb_assign_lm, block-wide draw (language model)", **TP0),
     "bigram_n40_T05": _chain("bigram", 12, 8, 12, 91, 5, 3, 4, 0.5, False, "T < 1, language model", n_landmarks=40, **TP0),
     "fixed_n64_w6_T05": _chain("fixed", 8, 8, 10, 93, 6, 2, 2, 0.5, False, "T < 1, 64 landmarks", n_landmarks=64, **TP0),
     # ... window 17..64: candidates beyond one row of sixteen lanes
@@ -77,12 +77,12 @@ EXACT = {
     "long_ragged_diag": _long("ragged_diag", 0.5, True, "k_fbb_segment<BAND>, T < 1", **TP0),
     "long_ragged_bigram": _long("ragged_bigram", 0.5, True, "k_fbb_segment<BAND>, T < 1; block-wide draw", **TP0),
     "long_diag_100_w20": _long("diag_100_w20", 2.0, True, "k_fbb_segment<BAND>, window 20", **TP0),
-    # k_fbb_assign by bank size.  The large banks' log-marginals sit near +52 (D = 100) and +285 (D = 256) per span: the word
+    # k_fbb_slots by bank size.  The large banks' log-marginals sit near +52 (D = 100) and +285 (D = 256) per span: the word
     # insertion penalty takes that off, or the segmentation with the most segments wins at every temperature
-    "K300_am": _chain("fixed", 19, 6, 300, 81, 5, 5, 1, 10.0, True, "k_fbb_assign, 256 threads (K_max > 128)", **TP0),
-    "bank_rcap4_fixed": _chain("fixed", 40, 100, 1000, 101, 5, 3, 4, 10.0, True, "k_fbb_assign, four tokens per chunk",
+    "K300_am": _chain("fixed", 19, 6, 300, 81, 5, 5, 1, 10.0, True, "k_fbb_slots, 256 threads (K_max > 128)", **TP0),
+    "bank_rcap4_fixed": _chain("fixed", 40, 100, 1000, 101, 5, 3, 4, 10.0, True, "k_fbb_slots, four tokens per chunk",
                                time_power_term=0.0, wip=-52.0),
-    "bank_rcap1_diag": _chain("diag", 16, 256, 4000, 106, 5, 2, 2, 10.0, True, "k_fbb_assign, one token per chunk",
+    "bank_rcap1_diag": _chain("diag", 16, 256, 4000, 106, 5, 2, 2, 10.0, True, "k_fbb_slots, one token per chunk",
                               time_power_term=0.0, wip=-252.0),
 }
 # Dropped: the bigram D = 100, K = 40 corpus of tests/test_gpu_fbgmm_batch.py::CASES (at most 1 utterance in 30 moves at any
@@ -103,15 +103,15 @@ RANKS = "long_ragged_fixed"
 # ---------------------------------------------------------------------------------------------------------------------
 TOLERANCE = {
     "diag_f32_launches": _bench("diag", "f32", 24, 39, 100, None, 10.0,
-                                "fb_dp_sample_fast32; k_fbb_assign<COV 1, F32> (segk_fbb_assign_diag32)", wip=-46.0, **TP0),
+                                "fb_dp_sample_fast32; k_fbb_slots<COV 1, F32> (segk_fbb_assign_diag32)", wip=-46.0, **TP0),
     "diag_f32_fused_K100": _bench("diag", "f32", 24, 39, 100, "fused", 10.0, "k_fbb_step_diag32, one chunk of slots", wip=-46.0,
                                   **TP0),
     "diag_f32_fused_K160": _bench("diag", "f32", 24, 20, 160, "fused", 10.0, "k_fbb_step_diag32, three chunks of 64 slots", **TP0),
-    "fixed_f16": _bench("fixed", "f16", 24, 39, 100, None, 10.0, "fb_dp_sample_fast32; k_fbb_assign with llmat", wip=-45.0, **TP0),
-    "fixed_f32": _bench("fixed", "f32", 24, 39, 100, None, 10.0, "fb_dp_sample_fast32; k_fbb_assign<COV 0>, fp64 likelihoods",
+    "fixed_f16": _bench("fixed", "f16", 24, 39, 100, None, 10.0, "fb_dp_sample_fast32; k_fbb_slots with llmat", wip=-45.0, **TP0),
+    "fixed_f32": _bench("fixed", "f32", 24, 39, 100, None, 10.0, "fb_dp_sample_fast32; k_fbb_slots<COV 0>, fp64 likelihoods",
                         wip=-45.0, **TP0),
     "bigram_f16_wave": _bench("bigram", "f16", 24, 16, 300, None, 10.0, "k_fbb_assign_lm_wave, register form", **TP0),
-    "bigram_f16_blockwide": _bench("bigram", "f16", 24, 16, 300, "0", 10.0, "k_fbb_assign with llmat, block-wide draw", **TP0),
+    "bigram_f16_blockwide": _bench("bigram", "f16", 24, 16, 300, "0", 10.0, "k_fbb_assign_lm with llmat, block-wide draw", **TP0),
     "bigram_f16_K1100": _bench("bigram", "f16", 24, 16, 1100, None, 10.0, "k_fbb_assign_lm_wave, per-slot loops (K_max > 1024)",
                                **TP0),
     # more than 64 landmarks: the fp64 recurrence with the hardware exponential and logarithm (fb_logsumexp_wave_fast,

@@ -2,8 +2,8 @@
 
   * score_precision="f64": the specification's chain (oracle/np_fbgmm_batch.py::FbgmmBatch.sweep(sweep, T, am)) bit for bit,
     per kernel form -- k_fbb_segment on triangles and on the band (fb_dp_sample_on leaves its register path for the LDS path
-    whenever T != 1), k_fbb_assign's wave-per-token and block-wide draws at every chunk size --, through gibbs_sample's
-    schedule and on two ranks;
+    whenever T != 1), the wave-per-token draws of k_fbb_slots and the block-wide draws of k_fbb_assign_lm at every chunk
+    size --, through gibbs_sample's schedule and on two ranks;
   * score_precision "f32" / "f16": every boundary draw and every slot draw of one sweep, value by value, against the fp64
     probabilities of the device's own span scores, alphas and token likelihoods (segk_fbb_set_probe) -- fb_dp_sample_fast32's
     float32 re-normalisation, k_fbb_assign_lm_wave's two forms, k_fbb_step_diag32's float32 inverse temperature on base-2
@@ -33,8 +33,8 @@ def gpu():
 
 # ------------------------------------------------------------------ exact mode
 def _assign_form(c):
-    """(threads of k_fbb_assign, tokens per chunk) as fbb_assign_impl picks them: 512 threads and sixteen tokens where the bank
-    has at most 128 slots, no language model and the rows fit; else 256 threads and _fbb_rcap tokens."""
+    """(threads of k_fbb_slots / k_fbb_assign_lm, tokens per chunk) as fbb_assign_plan picks them: 512 threads and sixteen
+    tokens where the bank has at most 128 slots, no language model and the rows fit; else 256 threads and _fbb_rcap tokens."""
     from tests.test_gpu_large_banks import _fbb_rcap
     K, D = c["K"], c["D"]
     rcap = _fbb_rcap(K, D)

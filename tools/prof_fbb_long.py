@@ -15,7 +15,7 @@ from segmentalist_amd.synth import make_corpus
 from tests.golden import cases
 
 which = sys.argv[1]
-fb_type = sys.argv[2] if len(sys.argv) > 2 else "standard"      # viterbi: k_fbb_segment<BAND, true> / k_fbb_assign_map
+fb_type = sys.argv[2] if len(sys.argv) > 2 else "standard"      # viterbi: k_fbb_segment<BAND, true> / k_fbb_slots<.., true>
 D, K, W, U = 8, 10, 6, 2000
 t0 = time.time()
 if which == "ragged":
