@@ -68,7 +68,9 @@ const char *segk_last_error(void);
  *  15 (no bump) segk_fbt_assign: the token step of the unigram segmenter's acoustic-model batch sweeps.  The rule above concerns
  *     changed signatures and structures: this adds one entry point, changes none and grows no structure, so a binding written
  *     against 15 keeps working with this library; segk_fbb_partials / _prepare accept n_blocks = 1 on a segmenter's corpus too
- *     (every token against the prior), the span-score, boundary and slot entry points keep refusing it                       */
+ *     (every token against the prior), the span-score, boundary and slot entry points keep refusing it
+ *  15 (no bump) segk_fbi_assign_diag32: segk_fbi_assign for diagonal components with the Student-t terms in float32.  As for
+ *     segk_fbt_assign: one entry point added, no signature or structure changed (it reads the centre / tab32 fields of 9)    */
 #define SEGK_ABI_VERSION 15
 int32_t segk_abi_version(void);
 
@@ -832,6 +834,24 @@ int32_t segk_fbi_assign(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f
                         int32_t s_lo, int32_t s_n, int32_t b, const int32_t *n_items, uint64_t sweep,
                         double anneal_temp, int32_t consider_unassigned, const int32_t *new_tok,
                         int32_t *n_new, double *probe_ll, int64_t probe_ld, void *stream);
+/* segk_fbi_assign for diagonal components (cov_type 1) with float32 item likelihoods (added at ABI 15 without a bump;
+ * FBGMM(..., sync="batch", score_precision="f32")): the same arguments, the same role in a step, the same slots written.
+ * Only the likelihood half differs.  Per (item, slot) the Student-t terms are those of segk_fbb_assign_diag32 /
+ * segk_fbb_step_diag32: m = float(mean - centre) and q = float(q) from bt->tab32 (segk_fbb_prepare(b) writes it when the
+ * pointer is set), x = float(X[i][d] - centre[d]) with the difference formed in fp64, acc += log2(1 + (m - x)^2 q) on the
+ * hardware logarithm, dimensions ascending, then ll = lconst - half * (ln 2 * acc) in fp64.  An empty slot keeps
+ * bt->prior_rows[i] (fp64).  The prior's term, the softmax, the annealing and the inverse-CDF walk are segk_fbi_assign's, in
+ * fp64 on these logits: the draws are the fp64 function of likelihoods that lie within the tolerance contract of the float32
+ * modes (1e-4 max(|ll|, 1)) of segk_fbi_assign's.  The statistics stay fp64 and exact.
+ * Refused before any launch: cov_type 0 or 2 and a language model with SEGK_ERR_UNSUPPORTED; bt->tab32, bt->centre or
+ * bt->prior_rows NULL, D > 256 or a corpus with span tables with SEGK_ERR_ARG.  probe_ll as for segk_fbi_assign, the rows of the considered items only (an
+ * unassigned item that is not considered leaves its row as it was).  One launch per
+ * 64 items x all slots; the rows and 32 slots' tables are staged as float32 (516 D bytes of LDS), a tile's logits are 64 rows of
+ * K_max | 1 doubles, in LDS where both fit in 144 KiB, else in the bounded workspace of segk_fbi_assign (SEGK_FBI_Z_MIB).        */
+int32_t segk_fbi_assign_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt,
+                               int32_t s_lo, int32_t s_n, int32_t b, const int32_t *n_items, uint64_t sweep,
+                               double anneal_temp, int32_t consider_unassigned, const int32_t *new_tok,
+                               int32_t *n_new, double *probe_ll, int64_t probe_ld, void *stream);
 /* Acoustic-model batch sweeps of the unigram segmenter (added at ABI 15 without a bump; the inner sweeps of
  * UnigramAcousticWordseg.gibbs_sample(n, am_n_iter=m), unigram_acoustic_wordseg.py:440-443 -- FBGMM.gibbs_sample(m,
  * consider_unassigned=False) over the currently assigned tokens -- as a blocked sampler on the segmenter's batch state;

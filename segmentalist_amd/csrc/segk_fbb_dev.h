@@ -1,7 +1,7 @@
 // segk_fbb_dev.h -- what the batch sampler's translation units share (segk_fbbatch.hip; segk_fullcov.hip for the
 // full-covariance forms of its kernels; segk_fbitems.hip for the stand-alone model's item step): the record of a (block,
-// slice) cell, the workgroup -> (slice, index) map of a launch, the specification's balanced tree, the draw of one token's
-// slot.  Not part of the ABI.
+// slice) cell, the workgroup -> (slice, index) map of a launch, the specification's balanced tree, the float32 Student-t
+// term, the draw of one token's slot.  Not part of the ABI.
 #pragma once
 #include "segk_internal.h"
 #include "segk_fb_common.h"
@@ -76,6 +76,16 @@ static __device__ __forceinline__ void fbb_sum_slices(const segk_fbatch &bt, int
         for (int i = 0; i < 8; i++)
             if (s0 + i < S) my[(s0 + i) * stride] = a[i];
     }
+}
+
+// THE float32 Student-t term of one (row, slot, dimension) on the hardware logarithm (v_log_f32: log2; the caller multiplies
+// the sum by ln 2): m = float(mean - centre), q = float(q), x = float(x - centre), the differences formed in fp64.  The one
+// copy behind fbb_accumulate_rows32 (segk_fbbatch.hip: the segmenter's `score_precision="f32"` token likelihoods) and
+// k_fbi_assign_diag32 (segk_fbitems.hip: the stand-alone model's), so the two routes cannot drift apart.
+static __device__ __forceinline__ float fbb_term32(float m, float q, float x)
+{
+    const float delta = m - x;
+    return __builtin_amdgcn_logf(1.f + (delta * delta) * q);
 }
 
 // THE draw of one token's slot without a language model, by one wave (k_fbb_slots of segk_fbbatch.hip: a wave per token of an

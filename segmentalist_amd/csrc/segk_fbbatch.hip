@@ -484,10 +484,7 @@ static __device__ __forceinline__ void fbb_terms32(const segk_fbatch &bt, int KM
 #pragma unroll
     for (int j = 0; j < NB; j++) {
 #pragma unroll
-        for (int r = 0; r < NR; r++) {
-            const float delta = m[j] - (float)(xs[r * D + d + j] - cj[j]);
-            acc[r] += __builtin_amdgcn_logf(1.f + (delta * delta) * q[j]);
-        }
+        for (int r = 0; r < NR; r++) acc[r] += fbb_term32(m[j], q[j], (float)(xs[r * D + d + j] - cj[j]));
     }
 }
 
@@ -503,10 +500,7 @@ static __device__ __forceinline__ void fbb_accumulate_rows32(const segk_fbatch &
         const double cd = fbb_centre(bt, d);
         const float m = (float)(bt.mean_t[(int64_t)d * KM + k] - cd), q = (float)bt.q_t[(int64_t)d * KM + k];
 #pragma unroll
-        for (int r = 0; r < NR; r++) {
-            const float delta = m - (float)(xs[r * D + d] - cd);
-            acc[r] += __builtin_amdgcn_logf(1.f + (delta * delta) * q);
-        }
+        for (int r = 0; r < NR; r++) acc[r] += fbb_term32(m, q, (float)(xs[r * D + d] - cd));
     }
 }
 

@@ -14,6 +14,8 @@
 //   cov_type 2              the likelihoods of the block's items are formed by k_fcb_token_ll (segk_fullcov.hip: one slot's
 //                           packed triangle staged per 256 items) into its context table; k_fbi_assign<XT, 2> is the draw half
 //                           reading that table.
+//   k_fbi_assign_diag32<XT> cov_type 1 with the Student-t terms in float32 on the hardware logarithm (segk_fbi_assign_diag32;
+//                           described where it stands): rows and slot tables staged as float32, the draw half unchanged.
 //
 // The same tile serves the TOKEN step of the unigram segmenter's acoustic-model batch sweep (segk_fbt_assign: the inner sweeps
 // of UnigramAcousticWordseg.gibbs_sample(..., am_n_iter, am_sync="batch"); specification tests/am_batch.py): the boundaries are
@@ -230,6 +232,126 @@ __global__ __launch_bounds__(FBI_NT) void k_fbi_assign(segk_corpus c, segk_fbgmm
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// k_fbi_assign_diag32<XT>: the item step with the Student-t terms of diagonal components in float32 on the hardware logarithm
+// (FBGMM(..., sync="batch", score_precision="f32"); segk_fbi_assign_diag32).  A sibling of k_fbi_assign<XT, 1>, not a further
+// template axis of it: the fp64 forms keep their code.  Only the likelihood half differs:
+//   * the tile's rows are staged as float(X[i][d] - centre[d]) (the difference in fp64), the slots' (float(mean - centre),
+//     float(q)) pairs come from bt.tab32 (segk_fbb_prepare wrote them), FBI32_KC = 32 slots per pass, two side by side per wave
+//     (one LDS read of x per dimension for the two, the pairs as 8-byte broadcasts);
+//   * per (item, slot) acc += fbb_term32(m, q, x), dimensions ascending -- the term of fbb_accumulate_rows32 -- then
+//     ll = lconst - half * (ln 2 * acc) in fp64; an empty slot keeps prior_rows[i].
+// The logits stay fp64 and the draw half is k_fbi_assign's: fbb_draw_row on them, a wave per item.
+// Sixteen waves, not k_fbi_assign's eight: with the logarithms on the hardware the draw half (fp64 exp / log per slot and the
+// inverse-CDF walk, a chain of dependent steps per item) is most of the kernel, and a wave walks four of the tile's items in a
+// row instead of eight.  N = 100 000, D = 39, K_max = 100, B = S = 8: 63.9 us per step with 512 threads (four slots per wave),
+// 52 with 1 024; the sweep 0.80 -> 0.71 ms.  92 VGPRs: the sixteen waves are four per SIMD of the five the registers allow, so
+// the smaller LDS image buys the second eight waves inside the workgroup, not a second workgroup (200 tiles a step on 256 CUs).
+// LDS: fbi32_stage_bytes(D) = 516 D rounded up to 16 (pairs [32][D] of 8 bytes, rows [D][65] floats: the row stride 65 puts
+// the staging stores of consecutive dimensions in consecutive banks), then the logits [64][K_max | 1] doubles (the odd row
+// stride spreads a wave's 64 stores of one slot over the banks; at K_max = 100 a stride of 100 doubles put them on four) where
+// both fit in FBI_LDS_MAX, else in the bounded workspace as for k_fbi_assign.  D = 39, K_max = 100: 71 840 bytes.
+// ---------------------------------------------------------------------------------------
+#define FBI32_NT 1024                             // threads: sixteen waves over the slots (likelihoods), over the items (draws)
+#define FBI32_KW 2                                // slots a wave accumulates side by side
+#define FBI32_KC (FBI32_KW * (FBI32_NT / 64))       // slots staged per pass
+#define FBI32_XS (FBI_T + 1)                      // floats between the staged rows' dimensions
+
+static __host__ __device__ __forceinline__ size_t fbi32_stage_bytes(int D)
+{
+    return ((2 * (size_t)FBI32_KC * D + (size_t)FBI32_XS * D) * sizeof(float) + 15) & ~(size_t)15;
+}
+// doubles between the logit rows of a tile
+static __host__ __device__ __forceinline__ int fbi32_ldl(int KM) { return KM | 1; }
+
+template <typename XT>
+__global__ __launch_bounds__(FBI32_NT) void k_fbi_assign_diag32(segk_corpus c, segk_fbgmm f, segk_fbatch bt, FbbMap map, int wg0, int b,
+                                                             uint64_t sweep, double prior_alpha, double anneal_temp,
+                                                             int consider_unassigned, int32_t *n_new, double *zbuf, double *probe_ll,
+                                                             int64_t probe_ld)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int D = c.D, KM = f.K_max, ldl = fbi32_ldl(KM), tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);        // (wave-uniform, and known to be)
+    int s, idx;
+    if (!fbb_locate(map, wg0 + blockIdx.x, &s, &idx)) return;
+    const int slice = map.lo[s];
+    const int u0 = bt.utt_range[(slice * bt.n_blocks + b) * 2], u1 = bt.utt_range[(slice * bt.n_blocks + b) * 2 + 1];
+    const int i0 = u0 + idx * FBI_T;                        // the tile's first item
+    if (i0 >= u1) return;                                   // a tile beyond its cell's count (workgroup-uniform)
+    const int nr = u1 - i0 < FBI_T ? u1 - i0 : FBI_T;
+    float2 *pm = (float2 *)smem;                            // [FBI32_KC][D]: (mean - centre, q) of the staged slots
+    float *xs = (float *)(pm + (size_t)FBI32_KC * D);       // [D][FBI32_XS]: the lanes' centred rows side by side
+    double *ll = zbuf ? zbuf + (int64_t)blockIdx.x * FBI_T * ldl : (double *)(smem + fbi32_stage_bytes(D));     // [FBI_T][ldl]
+    const XT *X = (const XT *)c.X;
+    for (int j = tid; j < FBI_T * D; j += FBI32_NT) {
+        const int r = j / D, d = j - r * D;
+        xs[d * FBI32_XS + r] = r < nr ? (float)((double)X[(int64_t)(i0 + r) * c.ldx + d] - bt.centre[d]) : 0.f;
+    }
+    const bool valid = lane < nr;
+    const double lp = valid ? bt.prior_rows[i0 + lane] : 0.0;          // an empty slot's likelihood: the row's prior predictive
+    const float *tm = bt.tab32, *tq = bt.tab32 + (int64_t)D * KM;
+    for (int k0 = 0; k0 < KM; k0 += FBI32_KC) {
+        __syncthreads();                                    // (the rows are staged; the previous pass has read its parameters)
+        for (int j = tid; j < FBI32_KC * D; j += FBI32_NT) {
+            const int kk = j % FBI32_KC, d = j / FBI32_KC, k = k0 + kk;
+            pm[kk * D + d] = k < KM ? make_float2(tm[(int64_t)d * KM + k], tq[(int64_t)d * KM + k]) : make_float2(0.f, 0.f);
+        }
+        __syncthreads();
+        const int kw = k0 + w * FBI32_KW;                   // this wave's slots kw .. kw + FBI32_KW - 1 (wave-uniform)
+        bool occ[FBI32_KW];
+        float acc[FBI32_KW];
+        bool any = false;
+#pragma unroll
+        for (int j = 0; j < FBI32_KW; j++) {
+            occ[j] = kw + j < KM && bt.cnt[kw + j] > 0.0;
+            acc[j] = 0.f;
+            any = any || occ[j];
+        }
+        if (any) {
+            // all four slots, occupied or not (an empty slot's tables are finite -- the prior's -- and a slot beyond K_max is
+            // staged as zeros; their sums are dropped below): a test per slot inside the loop made every term wait for its own
+            // LDS read
+            const float2 *pw = pm + (size_t)(w * FBI32_KW) * D;
+#pragma unroll 4
+            for (int d = 0; d < D; d++) {
+                const float x = xs[d * FBI32_XS + lane];
+#pragma unroll
+                for (int j = 0; j < FBI32_KW; j++) {
+                    const float2 mq = pw[j * D + d];
+                    acc[j] += fbb_term32(mq.x, mq.y, x);
+                }
+            }
+        }
+        if (valid) {
+#pragma unroll
+            for (int j = 0; j < FBI32_KW; j++) {
+                const int k = kw + j;
+                if (k >= KM) continue;
+                ll[(int64_t)lane * ldl + k] = occ[j] ? bt.lconst[k] - bt.half[k] * (0.6931471805599453 * (double)acc[j]) : lp;
+            }
+        }
+    }
+    __syncthreads();
+    if (probe_ll) {             // the likelihood part of the logits, as the draws below use it: the rows of the items they take
+        for (int j = tid; j < nr * KM; j += FBI32_NT) {
+            const int r = j / KM, k = j - r * KM;
+            if (consider_unassigned || bt.slot[i0 + r] >= 0) probe_ll[(int64_t)(i0 + r) * probe_ld + k] = ll[(int64_t)r * ldl + k];
+        }
+        __syncthreads();
+    }
+    const double zc_empty = f.lms * log(prior_alpha / (double)KM);
+    for (int r = w; r < nr; r += FBI32_NT / 64) {             // a wave per item
+        const int i = i0 + r;
+        if (!consider_unassigned && bt.slot[i] < 0) continue;           // (wave-uniform) keeps -1 and contributes to nothing
+        const int k = fbb_draw_row(f, bt, KM, prior_alpha, zc_empty, anneal_temp, ll + (int64_t)r * ldl, sweep, (uint64_t)i, 1ull, lane);
+        if (lane == 0) {
+            bt.slot[i] = k;
+            n_new[i] = 1;
+        }
+    }
+}
+
 // What both entry points do once their arguments are checked: the tiles of block b mapped to workgroups (m: FBI_T entries
 // each), with cov_type 2 the token-likelihood table formed, the logits placed (LDS, or the bounded workspace and several
 // launches), the launches.  tok: the lists of segk_fbt_assign (NULL: items).
@@ -314,6 +436,21 @@ static int fbi_check(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatc
     return SEGK_OK;
 }
 
+// the tiles of block b of the local slices mapped to workgroups (FBI_T items each); *most: the items of the largest cell
+static int fbi_item_map(const int32_t *n_items, int32_t s_lo, int32_t s_n, FbbMap *m, int *most)
+{
+    m->n = s_n;
+    m->off[0] = 0;
+    *most = 0;
+    for (int s = 0; s < s_n; s++) {
+        SEGK_REQUIRE(n_items[s] >= 0, "item counts");
+        m->lo[s] = s_lo + s;
+        m->off[s + 1] = m->off[s] + (n_items[s] + FBI_T - 1) / FBI_T;
+        *most = n_items[s] > *most ? n_items[s] : *most;
+    }
+    return SEGK_OK;
+}
+
 extern "C" {
 
 int32_t segk_fbi_assign(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,
@@ -330,18 +467,68 @@ int32_t segk_fbi_assign(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f
                  "a corpus of items: one one-landmark utterance per row, no span tables");
     if (int rc = fbi_check(c, f, bt, s_lo, s_n, b, probe_ll, probe_ld, "segk_fbi_assign")) return rc;
     FbbMap m;
-    m.n = s_n;
-    m.off[0] = 0;
     int most = 0;
-    for (int s = 0; s < s_n; s++) {
-        SEGK_REQUIRE(n_items[s] >= 0, "item counts");
-        m.lo[s] = s_lo + s;
-        m.off[s + 1] = m.off[s] + (n_items[s] + FBI_T - 1) / FBI_T;
-        most = n_items[s] > most ? n_items[s] : most;
-    }
+    if (int rc = fbi_item_map(n_items, s_lo, s_n, &m, &most)) return rc;
     if (m.off[s_n] == 0) return SEGK_OK;
     return fbi_launch(ctx, c, f, bt, m, s_lo, s_n, b, n_items, most, sweep, anneal_temp, consider_unassigned, new_tok, n_new, probe_ll,
                       probe_ld, nullptr, stream);
+}
+
+int32_t segk_fbi_assign_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,
+                               int32_t s_n, int32_t b, const int32_t *n_items, uint64_t sweep, double anneal_temp,
+                               int32_t consider_unassigned, const int32_t *new_tok, int32_t *n_new, double *probe_ll,
+                               int64_t probe_ld, void *stream)
+{
+    SEGK_REQUIRE(ctx && c && f && bt && n_items && new_tok && n_new, "NULL argument");
+    if (f->cov_type != 1) {
+        segk_set_error("segk_fbi_assign_diag32: the float32 item step exists for diagonal components (cov_type 1) only, got "
+                       "cov_type %d (fixed-variance and full-covariance components go through segk_fbi_assign)", (int)f->cov_type);
+        return SEGK_ERR_UNSUPPORTED;
+    }
+    if (f->lm_unigram) {
+        segk_set_error("segk_fbi_assign_diag32: the stand-alone batch sweep takes no language model");
+        return SEGK_ERR_UNSUPPORTED;
+    }
+    SEGK_REQUIRE(bt->tab32 && bt->centre && bt->prior_rows,
+                 "the float32 item step needs segk_fbatch.tab32 (written by segk_fbb_prepare), .centre and .prior_rows");
+    SEGK_REQUIRE(!c->vec_ids && !c->band_ids && c->N_max == 1 && c->n_utt == c->n_emb,
+                 "a corpus of items: one one-landmark utterance per row, no span tables");
+    if (int rc = fbi_check(c, f, bt, s_lo, s_n, b, probe_ll, probe_ld, "segk_fbi_assign_diag32")) return rc;
+    FbbMap m;
+    int most = 0;
+    if (int rc = fbi_item_map(n_items, s_lo, s_n, &m, &most)) return rc;
+    const int n_wg = m.off[s_n];
+    if (n_wg == 0) return SEGK_OK;
+    hipStream_t st = (hipStream_t)stream;
+    // the placement rule of fbi_launch with this form's byte counts
+    const size_t stage = fbi32_stage_bytes(c->D), tile = (size_t)FBI_T * fbi32_ldl(f->K_max) * sizeof(double);
+    SEGK_REQUIRE(stage <= FBI_LDS_MAX, "the rows and the staged slots of a tile do not fit in LDS");
+    size_t lds = stage + tile;
+    int per_launch = n_wg;
+    double *zbuf = nullptr;
+    if (lds > FBI_LDS_MAX) {
+        lds = stage;
+        const int mib = segk_env_int("SEGK_FBI_Z_MIB", FBI_Z_MIB);
+        const size_t cap = ((size_t)(mib > 0 ? mib : FBI_Z_MIB) << 20) / tile;
+        per_launch = cap < 1 ? 1 : (cap < (size_t)n_wg ? (int)cap : n_wg);
+        const int64_t need = (int64_t)per_launch * FBI_T * fbi32_ldl(f->K_max);
+        if (int rc = segk_ws_grow(ctx, &ctx->fbi_z, &ctx->fbi_z_n, need, (size_t)need * sizeof(double), st)) return rc;
+        zbuf = ctx->fbi_z;
+    }
+#define SEGK_FBI32(XT)                                                                                                          \
+    do {                                                                                                                        \
+        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbi_assign_diag32<XT>, lds));                                               \
+        for (int wg0 = 0; wg0 < n_wg; wg0 += per_launch) {                                                                      \
+            const int n = n_wg - wg0 < per_launch ? n_wg - wg0 : per_launch;                                                    \
+            hipLaunchKernelGGL((k_fbi_assign_diag32<XT>), dim3((unsigned)n), dim3(FBI32_NT), lds, st, *c, *f, *bt, m, wg0, b,    \
+                               sweep, f->alpha, anneal_temp, consider_unassigned ? 1 : 0, n_new, zbuf, probe_ll, probe_ld);     \
+        }                                                                                                                       \
+    } while (0)
+    if (c->x_dtype == SEGK_F32) SEGK_FBI32(float);
+    else SEGK_FBI32(double);
+#undef SEGK_FBI32
+    SEGK_LAUNCH_CHECK();
+    return SEGK_OK;
 }
 
 int32_t segk_fbt_assign(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,

@@ -70,7 +70,7 @@ struct segk_ctx {
     int64_t fc_terms_n;          // ... doubles allocated
     double *fcb_ll;              // full-covariance batch step (k_fcb_token_ll): [token positions of the block][K_max] token likelihoods
     int64_t fcb_ll_n;            // ... doubles allocated
-    double *fbi_z;               // item step of the stand-alone batch sweep (k_fbi_assign): [tiles of a launch][FBI_T][K_max] logits where
+    double *fbi_z;               // item step of the stand-alone batch sweep (k_fbi_assign; k_fbi_assign_diag32: rows of K_max | 1): [tiles of a launch][FBI_T][K_max] logits where
     int64_t fbi_z_n;             // ... a tile's do not fit in LDS; doubles allocated (bounded: segk_fbitems.hip FBI_Z_MIB)
     int32_t *fbt_tok;            // token step of the segmenter's acoustic-model batch sweep (k_fbt_compact): [16] tokens per local slice,
     int64_t fbt_tok_n;           // ... then [3][cap] (row, utterance, position) of the block's tokens; cap = int32 words per list

@@ -1330,11 +1330,22 @@ class FbgmmItemSweeper(object):
     The items 0..N-1 are cut into `n_stat_blocks` slices x `n_gibbs_blocks` blocks.  Step b: segk_fbb_prepare(b) (the
     statistics of all other blocks), segk_fbi_assign (logits and draw of every considered item of block b),
     segk_fbb_partials(b).  The statistics kernels see the items as a corpus of one-landmark utterances: new_tok[i] = i,
-    n_new[i] = does item i hold a slot.  One process, fp64 scores, no language model."""
+    n_new[i] = does item i hold a slot.  One process, no language model.
+    score_precision: "f64", or "f32" for diagonal components -- the Student-t terms of the item likelihoods in float32 on
+    the hardware logarithm (segk_fbi_assign_diag32); statistics, logits and draws stay fp64."""
 
-    def __init__(self, df, n_gibbs_blocks=8, n_stat_blocks=8, seed=0, group=None):
+    def __init__(self, df, n_gibbs_blocks=8, n_stat_blocks=8, seed=0, group=None, score_precision="f64"):
         torch = _torch()
         c = df.corpus
+        if score_precision not in ("f64", "f32"):
+            raise SegkError("the stand-alone mixture model's batch sweeps take score_precision 'f64' or 'f32', got %r"
+                            % (score_precision,))
+        if score_precision == "f32" and df.cov_type != 1:
+            raise SegkError("score_precision='f32' of the stand-alone mixture model's batch sweeps exists for diagonal components "
+                            "only (covariance_type=\"diag\"; this model has %s components)"
+                            % ("fixed-variance" if df.cov_type == 0 else "full-covariance"))
+        self.score_precision = score_precision
+        self.score_diag32 = score_precision == "f32"
         if c.n_utt:
             raise SegkError("this mixture model is the acoustic model of a segmenter (its corpus carries utterances): batch "
                             "sweeps of its tokens are the segmenter's gibbs_sample(sync=\"batch\")")
@@ -1384,7 +1395,17 @@ class FbgmmItemSweeper(object):
         self.f = _abi.FbgmmDev.from_buffer_copy(df.f)
         self.prior_rows = torch.zeros(N, dtype=f64, device=dev)
         check(df._L.segk_fbb_prior_rows(df._ctx, C.byref(self.c), C.byref(self.f), self.prior_rows.data_ptr(), _abi.stream()))
+        # float32 likelihoods: the coordinates centred on the corpus column mean as in FbgmmBatchSweeper (fp64, row order, on
+        # the host), and the float32 slot tables segk_fbb_prepare writes for the item kernel
+        self.centre = self.tab32 = None
+        if self.score_diag32:
+            xh = c.X.cpu().numpy()
+            mean = np.add.reduce(xh, axis=0, dtype=np.float64) / max(N, 1)
+            self.centre = torch.from_numpy(np.ascontiguousarray(mean[:D])).to(dev)
+            self.tab32 = torch.zeros(2 * D * K, dtype=torch.float32, device=dev)
         self.bt = _abi.FbatchDev(
+            centre=self.centre.data_ptr() if self.centre is not None else None,
+            tab32=self.tab32.data_ptr() if self.tab32 is not None else None,
             prior_rows=self.prior_rows.data_ptr(), n_slices=self.S, n_blocks=self.B, u_max=0, fast_dp=0,
             utt_range=self.utt_range.data_ptr(), row_range=self.utt_range.data_ptr(), partials=self.partials.data_ptr(),
             cnt=self.cnt.data_ptr(), mean_t=self.mean_t.data_ptr(), q_t=self.q_t.data_ptr(), lconst=self.lconst.data_ptr(),
@@ -1417,11 +1438,12 @@ class FbgmmItemSweeper(object):
             self.enter()
         L, ctx, cp, fp, bp, st = self._args()
         pl = self.probe_ll
+        assign = L.segk_fbi_assign_diag32 if self.score_diag32 else L.segk_fbi_assign
         for b in range(self.B):
             check(L.segk_fbb_prepare(ctx, cp, fp, bp, b, st))
-            check(L.segk_fbi_assign(ctx, cp, fp, bp, 0, self.S, b, self._n_items[b], self.sweep_index, float(anneal_temp),
-                                    1 if consider_unassigned else 0, ptr(self.new_tok), ptr(self.n_new), ptr(pl),
-                                    pl.shape[1] if pl is not None else 0, st))
+            check(assign(ctx, cp, fp, bp, 0, self.S, b, self._n_items[b], self.sweep_index, float(anneal_temp),
+                         1 if consider_unassigned else 0, ptr(self.new_tok), ptr(self.n_new), ptr(pl),
+                         pl.shape[1] if pl is not None else 0, st))
             check(L.segk_fbb_partials(ctx, cp, fp, bp, 0, self.S, b, ptr(self.new_tok), ptr(self.n_new), st))
         self.sweep_index += 1
 

@@ -11,6 +11,7 @@ from scipy.special import gammaln
 from .gaussian_components import GaussianComponents
 from .gaussian_components_diag import GaussianComponentsDiag
 from .gaussian_components_fixedvar import GaussianComponentsFixedVar
+from ._abi import SegkError
 from .kmeans import _consecutive
 
 logger = logging.getLogger(__name__)
@@ -18,15 +19,25 @@ logger = logging.getLogger(__name__)
 
 class FBGMM(object):
     def __init__(self, X, prior, alpha, K, assignments="rand", covariance_type="full", lms=1.0, _corpus=None,
-                 sync="sequential", n_gibbs_blocks=8, n_stat_blocks=8, batch_seed=0):
+                 sync="sequential", n_gibbs_blocks=8, n_stat_blocks=8, batch_seed=0, score_precision="f64"):
         """fbgmm.py:43-91.  sync: the mode of gibbs_sample -- "sequential" is the reference's serial chain over the items
         (draw for draw); "batch" the batch-synchronous blocked Gibbs sampler specified in tests/fbgmm_items.py (the items cut
         into n_stat_blocks slices x n_gibbs_blocks blocks, every block resampled in parallel against the statistics of all
         other blocks, uniforms from the counter-based stream of batch_seed).  The two modes mix freely: gibbs_sample(...,
         sync=...) chooses per call, batch_sweep_async() / materialise() are the asynchronous form.  Direct calls of
         components.add_item / del_item between batch sweeps are not intercepted: call materialise() first; the next batch
-        sweep then has to re-enter from the serial state (`_leave_batch()`)."""
+        sweep then has to re-enter from the serial state (`_leave_batch()`).
+        score_precision: the arithmetic of the batch sweeps' item likelihoods -- "f64", or "f32" with covariance_type="diag":
+        the Student-t terms in float32 on the hardware logarithm, within 1e-4 max(|ll|, 1) of the fp64 likelihoods (the
+        tolerance contract of the segmenter's score_precision="f32"); statistics, logits and draws stay fp64.  The serial
+        sweeps are fp64 either way."""
         assert sync in ("sequential", "batch")
+        if score_precision not in ("f64", "f32"):
+            raise SegkError("FBGMM takes score_precision 'f64' or 'f32', got %r" % (score_precision,))
+        if score_precision == "f32" and covariance_type != "diag":
+            raise SegkError("score_precision='f32' exists for diagonal components only (covariance_type=\"diag\", got %r)"
+                            % (covariance_type,))
+        self.score_precision = score_precision
         self.sync = sync
         self._batch_args = (n_gibbs_blocks, n_stat_blocks, batch_seed)
         self._sweeper = None
@@ -82,7 +93,7 @@ class FBGMM(object):
         if self._sweeper is None:
             from .device import FbgmmItemSweeper
             B, S, seed = self._batch_args
-            self._sweeper = FbgmmItemSweeper(self.components.dev, B, S, seed)
+            self._sweeper = FbgmmItemSweeper(self.components.dev, B, S, seed, score_precision=self.score_precision)
         return self._sweeper
 
     def batch_sweep_async(self, anneal_temp=1, consider_unassigned=True):

@@ -3,7 +3,8 @@
 the per-sweep materialise()) -- development measurement, not bench.py; the table of profiles/README.md "Stand-alone batch
 sweeps" comes from it.
 
---route items      the new path: --sweeps calls of batch_sweep_async, one HIP event pair around each, after --warmup
+--route items      the new path: --sweeps calls of batch_sweep_async, one HIP event pair around each, after --warmup;
+                   --score-precision f32 (diagonal shapes only) runs it with float32 item likelihoods
 --route segmenter  the same rows as one-landmark utterances through UnigramAcousticWordseg.batch_sweep_async (the route that
                    existed before: span scores, boundaries and slots of one token per utterance), timed the same way
 --route serial     FBGMM.gibbs_sample(sweeps), the serial chain over the items: the record's sample_time of every sweep (host
@@ -65,19 +66,26 @@ def main():
     ap.add_argument("--slices", type=int, default=8)
     ap.add_argument("--sweeps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--score-precision", choices=("f64", "f32"), default="f64")
     args = ap.parse_args()
     import torch
     from segmentalist_amd.fbgmm import FBGMM
     torch.cuda.set_device(0)
-    print("route %s on %s: N %d, K_max %d, B x S %d x %d, %d sweeps after %d" % (
-        args.route, torch.cuda.get_device_name(0), args.n, args.k_max, args.blocks, args.slices, args.sweeps, args.warmup), flush=True)
+    if args.score_precision != "f64" and args.route != "items":
+        ap.error("--score-precision applies to --route items")
+    print("route %s (%s) on %s: N %d, K_max %d, B x S %d x %d, %d sweeps after %d" % (
+        args.route, args.score_precision, torch.cuda.get_device_name(0), args.n, args.k_max, args.blocks, args.slices, args.sweeps,
+        args.warmup), flush=True)
+    # (the keyword only where it is asked for: the fp64 routes of this file also run on a checkout without it)
+    kw = {"score_precision": args.score_precision} if args.score_precision != "f64" else {}
     for name in args.shapes.split(","):
         cov, D = SHAPES[name]
         X, assign, prior = inputs(cov, D, args.n, args.k_max)
         random.seed(1)
         np.random.seed(1)
         if args.route == "items":
-            m = FBGMM(X, prior, 1.0, args.k_max, assign, covariance_type=cov, n_gibbs_blocks=args.blocks, n_stat_blocks=args.slices)
+            m = FBGMM(X, prior, 1.0, args.k_max, assign, covariance_type=cov, n_gibbs_blocks=args.blocks, n_stat_blocks=args.slices,
+                      **kw)
             ms = timed(torch, m.batch_sweep_async, args.sweeps, args.warmup)
             m.materialise()
             m.components.dev.check_status()
