@@ -70,7 +70,9 @@ const char *segk_last_error(void);
  *     against 15 keeps working with this library; segk_fbb_partials / _prepare accept n_blocks = 1 on a segmenter's corpus too
  *     (every token against the prior), the span-score, boundary and slot entry points keep refusing it
  *  15 (no bump) segk_fbi_assign_diag32: segk_fbi_assign for diagonal components with the Student-t terms in float32.  As for
- *     segk_fbt_assign: one entry point added, no signature or structure changed (it reads the centre / tab32 fields of 9)    */
+ *     segk_fbt_assign: one entry point added, no signature or structure changed (it reads the centre / tab32 fields of 9)
+ *  15 (no bump) segk_fbt_assign_diag32: segk_fbt_assign for diagonal components with the Student-t terms in float32 (the
+ *     token axis of segk_fbi_assign_diag32).  Again one entry point added, no signature or structure changed              */
 #define SEGK_ABI_VERSION 15
 int32_t segk_abi_version(void);
 
@@ -876,6 +878,26 @@ int32_t segk_fbt_assign(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f
                         int32_t s_lo, int32_t s_n, int32_t b, const int32_t *n_utts, const int32_t *tok_cap,
                         uint64_t sweep, double anneal_temp, const int32_t *new_tok, const int32_t *n_new,
                         double *probe_ll, int64_t probe_ld, void *stream);
+/* segk_fbt_assign for diagonal components (cov_type 1) with float32 token likelihoods (added at ABI 15 without a bump; the
+ * inner sweeps of UnigramAcousticWordseg.gibbs_sample(..., am_sync="batch", am_score_precision="f32"); specification
+ * tests/am_batch.py, emulation tests/am_batch_f32.py).  It replaces what segk_fbt_assign replaces -- fbgmm.py:422-463 over the
+ * tokens, the inner sweeps of unigram_acoustic_wordseg.py:440-443 -- with the same arguments, the same role in a step (after
+ * segk_fbb_prepare(b), which writes bt->tab32, before segk_fbb_partials(b)) and the same writes: bt->slot[row] of every
+ * current token and nothing else.  Only the likelihood half differs, exactly as segk_fbi_assign_diag32 differs from
+ * segk_fbi_assign: m = float(mean - centre), q = float(q) from bt->tab32, x = float(X[row][d] - centre[d]) with the difference
+ * in fp64, acc += log2(1 + (m - x)^2 q) on the hardware logarithm, dimensions ascending, ll = lconst - half * (ln 2 * acc) in
+ * fp64; an empty slot keeps bt->prior_rows[row].  Logits, prior term, softmax, annealing and the inverse-CDF walk on
+ * u01(bt->seed, sweep, i, N_max + t) are fp64: the draws are the fp64 function of likelihoods within the tolerance contract
+ * (1e-4 max(|ll|, 1)) of segk_fbt_assign's; segk_fbb_assign_diag32 on the same token lists forms the same term in the same
+ * order of dimensions (both are held to the contract, not to each other's bits).  The token lists are segk_fbt_assign's (the same compaction kernel and workspace);
+ * the tile kernel is segk_fbi_assign_diag32's with the rows gathered through them; LDS and the bounded workspace
+ * (SEGK_FBI_Z_MIB) as there.  Refused before any launch: cov_type 0 or 2 and a language model with SEGK_ERR_UNSUPPORTED;
+ * bt->tab32, bt->centre or bt->prior_rows NULL, a corpus without span tables or D > 256 with SEGK_ERR_ARG.  probe_ll as for
+ * segk_fbt_assign.                                                                                                            */
+int32_t segk_fbt_assign_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt,
+                               int32_t s_lo, int32_t s_n, int32_t b, const int32_t *n_utts, const int32_t *tok_cap,
+                               uint64_t sweep, double anneal_temp, const int32_t *new_tok, const int32_t *n_new,
+                               double *probe_ll, int64_t probe_ld, void *stream);
 /* bigram table += sign * (transcripts of block b, all slices) from bt->lm_tok                  */
 int32_t segk_fbb_lm_apply(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f,
                           const segk_fbatch *bt, int32_t b, int32_t sign, void *stream);

@@ -28,6 +28,8 @@
 //                           token t of utterance i uses u01(seed, sweep, i, N_max + t) as k_fbb_slots does, n_new / new_tok
 //                           are only read.  The grid is sized from the host's bound on the cell's tokens (its landmarks); a
 //                           tile that begins at or beyond the list's length returns at once.
+//   k_fbi_assign_diag32<.., true>  the same axis on the float32 form (segk_fbt_assign_diag32: the inner sweeps of
+//                           am_sweep(..., score_precision="f32"), diagonal components; tests/am_batch_f32.py)
 // No grid barrier, no spin loop, no cooperative launch, no atomics: a plain grid over the tiles.
 #include "segk_fb_common.h"
 #include "segk_fbb_dev.h"
@@ -264,11 +266,15 @@ static __host__ __device__ __forceinline__ size_t fbi32_stage_bytes(int D)
 // doubles between the logit rows of a tile
 static __host__ __device__ __forceinline__ int fbi32_ldl(int KM) { return KM | 1; }
 
-template <typename XT>
+// TOK = false: the items of the stand-alone model; TOK = true: the tokens of a segmenter's cell through the lists `L`, the axis
+// of k_fbi_assign (segk_fbt_assign_diag32; the float32 inner sweeps of am_sweep(..., score_precision="f32")): the rows are
+// gathered through L.row, an entry that names no row of the corpus is staged as zeros and left alone, the draw of token t of
+// utterance i uses u01(seed, sweep, i, N_max + t), only bt.slot is written (n_new / new_tok are read by k_fbt_compact alone)
+template <typename XT, bool TOK = false>
 __global__ __launch_bounds__(FBI32_NT) void k_fbi_assign_diag32(segk_corpus c, segk_fbgmm f, segk_fbatch bt, FbbMap map, int wg0, int b,
                                                              uint64_t sweep, double prior_alpha, double anneal_temp,
                                                              int consider_unassigned, int32_t *n_new, double *zbuf, double *probe_ll,
-                                                             int64_t probe_ld)
+                                                             int64_t probe_ld, FbtList L)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int D = c.D, KM = f.K_max, ldl = fbi32_ldl(KM), tid = threadIdx.x, lane = tid & 63;
@@ -277,19 +283,41 @@ __global__ __launch_bounds__(FBI32_NT) void k_fbi_assign_diag32(segk_corpus c, s
     if (!fbb_locate(map, wg0 + blockIdx.x, &s, &idx)) return;
     const int slice = map.lo[s];
     const int u0 = bt.utt_range[(slice * bt.n_blocks + b) * 2], u1 = bt.utt_range[(slice * bt.n_blocks + b) * 2 + 1];
-    const int i0 = u0 + idx * FBI_T;                        // the tile's first item
-    if (i0 >= u1) return;                                   // a tile beyond its cell's count (workgroup-uniform)
-    const int nr = u1 - i0 < FBI_T ? u1 - i0 : FBI_T;
+    int i0, nr;
+    const int32_t *trow = nullptr, *tutt = nullptr, *tpos = nullptr;    // TOK: the tile's entries of the token lists
+    if constexpr (TOK) {
+        const int n_tok = L.count[s];
+        i0 = idx * FBI_T;                                   // the tile's first token of the cell's list
+        if (i0 >= n_tok) return;                            // (workgroup-uniform: the grid is sized from the host's bound)
+        nr = n_tok - i0 < FBI_T ? n_tok - i0 : FBI_T;
+        trow = L.row + L.off[s] + i0;
+        tutt = L.utt + L.off[s] + i0;
+        tpos = L.pos + L.off[s] + i0;
+    } else {
+        i0 = u0 + idx * FBI_T;                              // the tile's first item
+        if (i0 >= u1) return;                               // a tile beyond its cell's count (workgroup-uniform)
+        nr = u1 - i0 < FBI_T ? u1 - i0 : FBI_T;
+    }
+    // the embedding row of the tile's entry r (TOK: -1 where the list names none -- such an entry is left alone)
+    auto row_of = [&](int r) -> int64_t {
+        if constexpr (TOK) {
+            const int64_t e = trow[r];
+            return e >= 0 && e < c.n_emb ? e : -1;
+        } else
+            return i0 + r;
+    };
     float2 *pm = (float2 *)smem;                            // [FBI32_KC][D]: (mean - centre, q) of the staged slots
     float *xs = (float *)(pm + (size_t)FBI32_KC * D);       // [D][FBI32_XS]: the lanes' centred rows side by side
     double *ll = zbuf ? zbuf + (int64_t)blockIdx.x * FBI_T * ldl : (double *)(smem + fbi32_stage_bytes(D));     // [FBI_T][ldl]
     const XT *X = (const XT *)c.X;
     for (int j = tid; j < FBI_T * D; j += FBI32_NT) {
         const int r = j / D, d = j - r * D;
-        xs[d * FBI32_XS + r] = r < nr ? (float)((double)X[(int64_t)(i0 + r) * c.ldx + d] - bt.centre[d]) : 0.f;
+        const int64_t e = r < nr ? row_of(r) : -1;
+        xs[d * FBI32_XS + r] = e >= 0 ? (float)((double)X[e * c.ldx + d] - bt.centre[d]) : 0.f;
     }
-    const bool valid = lane < nr;
-    const double lp = valid ? bt.prior_rows[i0 + lane] : 0.0;          // an empty slot's likelihood: the row's prior predictive
+    const int64_t e_lane = lane < nr ? row_of(lane) : -1;
+    const bool valid = e_lane >= 0;
+    const double lp = valid ? bt.prior_rows[e_lane] : 0.0;             // an empty slot's likelihood: the row's prior predictive
     const float *tm = bt.tab32, *tq = bt.tab32 + (int64_t)D * KM;
     for (int k0 = 0; k0 < KM; k0 += FBI32_KC) {
         __syncthreads();                                    // (the rows are staged; the previous pass has read its parameters)
@@ -336,12 +364,23 @@ __global__ __launch_bounds__(FBI32_NT) void k_fbi_assign_diag32(segk_corpus c, s
     if (probe_ll) {             // the likelihood part of the logits, as the draws below use it: the rows of the items they take
         for (int j = tid; j < nr * KM; j += FBI32_NT) {
             const int r = j / KM, k = j - r * KM;
-            if (consider_unassigned || bt.slot[i0 + r] >= 0) probe_ll[(int64_t)(i0 + r) * probe_ld + k] = ll[(int64_t)r * ldl + k];
+            if constexpr (TOK) {
+                if (row_of(r) >= 0) probe_ll[((int64_t)tutt[r] * c.N_max + tpos[r]) * probe_ld + k] = ll[(int64_t)r * ldl + k];
+            } else if (consider_unassigned || bt.slot[i0 + r] >= 0)
+                probe_ll[(int64_t)(i0 + r) * probe_ld + k] = ll[(int64_t)r * ldl + k];
         }
         __syncthreads();
     }
     const double zc_empty = f.lms * log(prior_alpha / (double)KM);
     for (int r = w; r < nr; r += FBI32_NT / 64) {             // a wave per item
+        if constexpr (TOK) {
+            const int64_t e = row_of(r);                    // (wave-uniform)
+            if (e < 0) continue;
+            const int k = fbb_draw_row(f, bt, KM, prior_alpha, zc_empty, anneal_temp, ll + (int64_t)r * ldl, sweep, (uint64_t)tutt[r],
+                                       (uint64_t)(c.N_max + tpos[r]), lane);
+            if (lane == 0) bt.slot[e] = k;
+            continue;
+        }
         const int i = i0 + r;
         if (!consider_unassigned && bt.slot[i] < 0) continue;           // (wave-uniform) keeps -1 and contributes to nothing
         const int k = fbb_draw_row(f, bt, KM, prior_alpha, zc_empty, anneal_temp, ll + (int64_t)r * ldl, sweep, (uint64_t)i, 1ull, lane);
@@ -418,6 +457,52 @@ static int32_t fbi_launch(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm 
     return SEGK_OK;
 }
 
+// fbi_launch for the float32 form (segk_fbi_assign_diag32 / segk_fbt_assign_diag32): the placement rule with this form's byte
+// counts -- the logits in LDS while fbi32_stage_bytes(D) + 512 (K_max | 1) <= FBI_LDS_MAX, else in the bounded workspace of the
+// context (SEGK_FBI_Z_MIB) and several launches -- then the launches.  tok: the lists of segk_fbt_assign_diag32 (NULL: items).
+static int32_t fbi32_launch(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, const FbbMap &m, int32_t s_n,
+                            int32_t b, uint64_t sweep, double anneal_temp, int32_t consider_unassigned, int32_t *n_new,
+                            double *probe_ll, int64_t probe_ld, const FbtList *tok, void *stream)
+{
+    const int n_wg = m.off[s_n];
+    hipStream_t st = (hipStream_t)stream;
+    const size_t stage = fbi32_stage_bytes(c->D), tile = (size_t)FBI_T * fbi32_ldl(f->K_max) * sizeof(double);
+    SEGK_REQUIRE(stage <= FBI_LDS_MAX, "the rows and the staged slots of a tile do not fit in LDS");
+    size_t lds = stage + tile;
+    int per_launch = n_wg;
+    double *zbuf = nullptr;
+    if (lds > FBI_LDS_MAX) {
+        lds = stage;
+        const int mib = segk_env_int("SEGK_FBI_Z_MIB", FBI_Z_MIB);
+        const size_t cap = ((size_t)(mib > 0 ? mib : FBI_Z_MIB) << 20) / tile;
+        per_launch = cap < 1 ? 1 : (cap < (size_t)n_wg ? (int)cap : n_wg);
+        const int64_t need = (int64_t)per_launch * FBI_T * fbi32_ldl(f->K_max);
+        if (int rc = segk_ws_grow(ctx, &ctx->fbi_z, &ctx->fbi_z_n, need, (size_t)need * sizeof(double), st)) return rc;
+        zbuf = ctx->fbi_z;
+    }
+    const FbtList none = {};
+#define SEGK_FBI32(XT, TOK)                                                                                                     \
+    do {                                                                                                                        \
+        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbi_assign_diag32<XT, TOK>, lds));                                          \
+        for (int wg0 = 0; wg0 < n_wg; wg0 += per_launch) {                                                                      \
+            const int n = n_wg - wg0 < per_launch ? n_wg - wg0 : per_launch;                                                    \
+            hipLaunchKernelGGL((k_fbi_assign_diag32<XT, TOK>), dim3((unsigned)n), dim3(FBI32_NT), lds, st, *c, *f, *bt, m, wg0, \
+                               b, sweep, f->alpha, anneal_temp, consider_unassigned ? 1 : 0, n_new, zbuf, probe_ll, probe_ld,   \
+                               tok ? *tok : none);                                                                              \
+        }                                                                                                                       \
+    } while (0)
+    if (c->x_dtype == SEGK_F32) {
+        if (tok) SEGK_FBI32(float, true);
+        else SEGK_FBI32(float, false);
+    } else {
+        if (tok) SEGK_FBI32(double, true);
+        else SEGK_FBI32(double, false);
+    }
+#undef SEGK_FBI32
+    SEGK_LAUNCH_CHECK();
+    return SEGK_OK;
+}
+
 // what both entry points ask of their arguments beyond the corpus' shape
 static int fbi_check(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo, int32_t s_n, int32_t b,
                      const double *probe_ll, int64_t probe_ld, const char *who)
@@ -448,6 +533,36 @@ static int fbi_item_map(const int32_t *n_items, int32_t s_lo, int32_t s_n, FbbMa
         m->off[s + 1] = m->off[s] + (n_items[s] + FBI_T - 1) / FBI_T;
         *most = n_items[s] > *most ? n_items[s] : *most;
     }
+    return SEGK_OK;
+}
+
+// the token lists of block b: the tiles mapped to workgroups from the host's bounds, the workspace, k_fbt_compact
+static int32_t fbt_lists(segk_ctx *ctx, const segk_corpus *c, const segk_fbatch *bt, int32_t s_lo, int32_t s_n, int32_t b,
+                         const int32_t *n_utts, const int32_t *tok_cap, const int32_t *new_tok, const int32_t *n_new, FbbMap *mp,
+                         FbtList *Lp, void *stream)
+{
+    FbbMap &m = *mp;
+    FbtList &L = *Lp;
+    m.n = s_n;
+    m.off[0] = 0;
+    L.off[0] = 0;
+    for (int s = 0; s < s_n; s++) {
+        SEGK_REQUIRE(n_utts[s] >= 0 && n_utts[s] <= c->n_utt, "utterance counts");
+        SEGK_REQUIRE(tok_cap[s] >= 0 && (int64_t)tok_cap[s] <= (int64_t)n_utts[s] * c->N_max, "token bounds (the landmarks of the cell)");
+        SEGK_REQUIRE((int64_t)L.off[s] + tok_cap[s] < (int64_t)1 << 30, "token bounds of a block");
+        m.lo[s] = s_lo + s;
+        m.off[s + 1] = m.off[s] + (tok_cap[s] + FBI_T - 1) / FBI_T;
+        L.off[s + 1] = L.off[s] + tok_cap[s];
+    }
+    if (m.off[s_n] == 0) return SEGK_OK;
+    const int64_t cap = L.off[s_n], need = 16 + 3 * cap;
+    if (int rc = segk_ws_grow(ctx, &ctx->fbt_tok, &ctx->fbt_tok_n, need, (size_t)need * sizeof(int32_t), (hipStream_t)stream)) return rc;
+    L.count = ctx->fbt_tok;
+    L.row = ctx->fbt_tok + 16;
+    L.utt = L.row + cap;
+    L.pos = L.utt + cap;
+    hipLaunchKernelGGL(k_fbt_compact, dim3((unsigned)s_n), dim3(FBT_NT), 0, (hipStream_t)stream, *c, *bt, L, s_lo, b, new_tok, n_new);
+    SEGK_LAUNCH_CHECK();
     return SEGK_OK;
 }
 
@@ -497,38 +612,8 @@ int32_t segk_fbi_assign_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_f
     FbbMap m;
     int most = 0;
     if (int rc = fbi_item_map(n_items, s_lo, s_n, &m, &most)) return rc;
-    const int n_wg = m.off[s_n];
-    if (n_wg == 0) return SEGK_OK;
-    hipStream_t st = (hipStream_t)stream;
-    // the placement rule of fbi_launch with this form's byte counts
-    const size_t stage = fbi32_stage_bytes(c->D), tile = (size_t)FBI_T * fbi32_ldl(f->K_max) * sizeof(double);
-    SEGK_REQUIRE(stage <= FBI_LDS_MAX, "the rows and the staged slots of a tile do not fit in LDS");
-    size_t lds = stage + tile;
-    int per_launch = n_wg;
-    double *zbuf = nullptr;
-    if (lds > FBI_LDS_MAX) {
-        lds = stage;
-        const int mib = segk_env_int("SEGK_FBI_Z_MIB", FBI_Z_MIB);
-        const size_t cap = ((size_t)(mib > 0 ? mib : FBI_Z_MIB) << 20) / tile;
-        per_launch = cap < 1 ? 1 : (cap < (size_t)n_wg ? (int)cap : n_wg);
-        const int64_t need = (int64_t)per_launch * FBI_T * fbi32_ldl(f->K_max);
-        if (int rc = segk_ws_grow(ctx, &ctx->fbi_z, &ctx->fbi_z_n, need, (size_t)need * sizeof(double), st)) return rc;
-        zbuf = ctx->fbi_z;
-    }
-#define SEGK_FBI32(XT)                                                                                                          \
-    do {                                                                                                                        \
-        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbi_assign_diag32<XT>, lds));                                               \
-        for (int wg0 = 0; wg0 < n_wg; wg0 += per_launch) {                                                                      \
-            const int n = n_wg - wg0 < per_launch ? n_wg - wg0 : per_launch;                                                    \
-            hipLaunchKernelGGL((k_fbi_assign_diag32<XT>), dim3((unsigned)n), dim3(FBI32_NT), lds, st, *c, *f, *bt, m, wg0, b,    \
-                               sweep, f->alpha, anneal_temp, consider_unassigned ? 1 : 0, n_new, zbuf, probe_ll, probe_ld);     \
-        }                                                                                                                       \
-    } while (0)
-    if (c->x_dtype == SEGK_F32) SEGK_FBI32(float);
-    else SEGK_FBI32(double);
-#undef SEGK_FBI32
-    SEGK_LAUNCH_CHECK();
-    return SEGK_OK;
+    if (m.off[s_n] == 0) return SEGK_OK;
+    return fbi32_launch(ctx, c, f, bt, m, s_n, b, sweep, anneal_temp, consider_unassigned, n_new, probe_ll, probe_ld, nullptr, stream);
 }
 
 int32_t segk_fbt_assign(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,
@@ -546,28 +631,38 @@ int32_t segk_fbt_assign(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f
     if (int rc = fbi_check(c, f, bt, s_lo, s_n, b, probe_ll, probe_ld, "segk_fbt_assign")) return rc;
     FbbMap m;
     FbtList L = {};
-    m.n = s_n;
-    m.off[0] = 0;
-    L.off[0] = 0;
-    for (int s = 0; s < s_n; s++) {
-        SEGK_REQUIRE(n_utts[s] >= 0 && n_utts[s] <= c->n_utt, "utterance counts");
-        SEGK_REQUIRE(tok_cap[s] >= 0 && (int64_t)tok_cap[s] <= (int64_t)n_utts[s] * c->N_max, "token bounds (the landmarks of the cell)");
-        SEGK_REQUIRE((int64_t)L.off[s] + tok_cap[s] < (int64_t)1 << 30, "token bounds of a block");
-        m.lo[s] = s_lo + s;
-        m.off[s + 1] = m.off[s] + (tok_cap[s] + FBI_T - 1) / FBI_T;
-        L.off[s + 1] = L.off[s] + tok_cap[s];
-    }
+    if (int rc = fbt_lists(ctx, c, bt, s_lo, s_n, b, n_utts, tok_cap, new_tok, n_new, &m, &L, stream)) return rc;
     if (m.off[s_n] == 0) return SEGK_OK;
-    const int64_t cap = L.off[s_n], need = 16 + 3 * cap;
-    if (int rc = segk_ws_grow(ctx, &ctx->fbt_tok, &ctx->fbt_tok_n, need, (size_t)need * sizeof(int32_t), (hipStream_t)stream)) return rc;
-    L.count = ctx->fbt_tok;
-    L.row = ctx->fbt_tok + 16;
-    L.utt = L.row + cap;
-    L.pos = L.utt + cap;
-    hipLaunchKernelGGL(k_fbt_compact, dim3((unsigned)s_n), dim3(FBT_NT), 0, (hipStream_t)stream, *c, *bt, L, s_lo, b, new_tok, n_new);
-    SEGK_LAUNCH_CHECK();
     return fbi_launch(ctx, c, f, bt, m, s_lo, s_n, b, n_utts, 0, sweep, anneal_temp, 0, new_tok, const_cast<int32_t *>(n_new), probe_ll,
                       probe_ld, &L, stream);
+}
+
+int32_t segk_fbt_assign_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,
+                               int32_t s_n, int32_t b, const int32_t *n_utts, const int32_t *tok_cap, uint64_t sweep,
+                               double anneal_temp, const int32_t *new_tok, const int32_t *n_new, double *probe_ll, int64_t probe_ld,
+                               void *stream)
+{
+    SEGK_REQUIRE(ctx && c && f && bt && n_utts && tok_cap && new_tok && n_new, "NULL argument");
+    if (f->cov_type != 1) {
+        segk_set_error("segk_fbt_assign_diag32: the float32 token step exists for diagonal components (cov_type 1) only, got "
+                       "cov_type %d (fixed-variance and full-covariance components go through segk_fbt_assign)", (int)f->cov_type);
+        return SEGK_ERR_UNSUPPORTED;
+    }
+    if (f->lm_unigram) {
+        segk_set_error("segk_fbt_assign_diag32: the acoustic-model batch sweep takes no language model (the bigram segmenter has "
+                       "no inner sweeps: its reference asserts at am_n_iter > 0)");
+        return SEGK_ERR_UNSUPPORTED;
+    }
+    SEGK_REQUIRE(bt->tab32 && bt->centre && bt->prior_rows,
+                 "the float32 token step needs segk_fbatch.tab32 (written by segk_fbb_prepare), .centre and .prior_rows");
+    SEGK_REQUIRE((c->vec_ids || c->band_ids) && c->n_utt > 0 && c->N_max > 0,
+                 "a segmenter's corpus: utterances with span tables (the items of a stand-alone model go through segk_fbi_assign_diag32)");
+    if (int rc = fbi_check(c, f, bt, s_lo, s_n, b, probe_ll, probe_ld, "segk_fbt_assign_diag32")) return rc;
+    FbbMap m;
+    FbtList L = {};
+    if (int rc = fbt_lists(ctx, c, bt, s_lo, s_n, b, n_utts, tok_cap, new_tok, n_new, &m, &L, stream)) return rc;
+    if (m.off[s_n] == 0) return SEGK_OK;
+    return fbi32_launch(ctx, c, f, bt, m, s_n, b, sweep, anneal_temp, 0, const_cast<int32_t *>(n_new), probe_ll, probe_ld, &L, stream);
 }
 
 }  // extern "C"

@@ -5,12 +5,21 @@ PyTorch is used for exactly three things here: allocating device buffers, host<-
 copies, and the stream handle.  All arithmetic of the hot path runs in libsegk.so.
 """
 import ctypes as C
+import os
 
 import numpy as np
 
 from . import _abi
 from ._abi import SEGK_F32, SEGK_F64, SegkError, check, ptr
 from .comm import SingleComm, get_comm
+
+# FbgmmBatchSweeper.am_sweep(..., score_precision="f32"): the token bound of a block (the landmarks of its utterances over the
+# local slices) from which the tile kernel (segk_fbt_assign_diag32) takes the step; below it segk_fbb_assign_diag32 on the
+# unchanged token lists does.  Measured, not guessed (profiles/README.md "Acoustic-model batch sweeps in float32", DESIGN.md
+# 4.17.1): at D 39, K_max 100 the other route wins up to a bound of 10 080 landmarks per block (by 0.07 ms a sweep, the larger
+# range 0.05) and the tiles win from 20 000 on (by 0.22 ms); the constant is the middle of the two.  SEGK_AM32_TILE_MIN
+# overrides it per sweep.
+AM32_TILE_MIN = 15000
 
 
 def _torch():
@@ -1044,11 +1053,7 @@ class FbgmmBatchSweeper(object):
         # rounding of their float32 / fp16x2 operands then follows the data's spread, not its distance from the origin.  One
         # pass over X per sampler, in fp64 and in row order on the host, so every rank (each holds the whole corpus) gets the
         # same bits
-        self.centre = None
-        if score_precision != "f64":
-            xh = c.X.cpu().numpy()
-            mean = np.add.reduce(xh, axis=0, dtype=np.float64) / max(c.n_emb, 1)
-            self.centre = torch.from_numpy(np.ascontiguousarray(mean[:D])).to(dev)
+        self.centre = self._corpus_centre() if score_precision != "f64" else None
         # diagonal float32 mode: segk_fbb_prepare writes the float32 slot tables the score / step kernels stage
         self.tab32 = torch.zeros(2 * D * K, dtype=torch.float32, device=dev) if self.score_diag32 else None
         self.bt = _abi.FbatchDev(
@@ -1081,6 +1086,7 @@ class FbgmmBatchSweeper(object):
                              for b in range(self.B)]
         self.score_precision = score_precision
         self.probe_ll = None             # am_sweep: a [n_utt * N_max, >= K_max] float64 device tensor, the likelihoods (tests)
+        self._bt32 = None                # am_sweep(score_precision="f32") on an fp64 sweeper: the copy of `bt` (_bt_am32)
         self.ll_mat = None
         if self.score_f16:
             # token likelihoods of the assignment step from the matrix cores: per block, the positions of its
@@ -1224,17 +1230,91 @@ class FbgmmBatchSweeper(object):
             self._gather(self.partials, b)
         self.sweep_index += 1
 
-    def am_sweep(self, boundaries, anneal_temp=1.0):
+    def _corpus_centre(self):
+        """the corpus column mean the reduced-precision kernels centre their operands on (segk_fbatch.centre), as a device
+        tensor: one pass over X in fp64 and in row order on the host, so every rank (each holds the whole corpus) gets the
+        same bits"""
+        c = self.df.corpus
+        xh = c.X.cpu().numpy()
+        mean = np.add.reduce(xh, axis=0, dtype=np.float64) / max(c.n_emb, 1)
+        return _torch().from_numpy(np.ascontiguousarray(mean[:c.D])).to(_dev())
+
+    def _bt_am32(self):
+        """The batch state the float32 inner sweeps pass to the library.  A sweeper built with score_precision="f32" (diagonal)
+        has `centre` and `tab32` in `bt`.  An fp64 sweeper has neither, and setting them there would change the bits of its
+        outer sweeps (fbb_centre): it gets, once, a COPY of `bt` -- the same buffers -- with a centre and a table of its own."""
+        if self.score_diag32:
+            return self.bt
+        if self._bt32 is None:
+            K, D = self.df.K_max, self.df.corpus.D
+            self._centre32 = self._corpus_centre()
+            self._tab32_am = _torch().zeros(2 * D * K, dtype=_torch().float32, device=_dev())
+            bt = _abi.FbatchDev.from_buffer_copy(self.bt)
+            bt.centre, bt.tab32 = self._centre32.data_ptr(), self._tab32_am.data_ptr()
+            self._bt32 = bt
+        return self._bt32
+
+    def _am_sweep_f32(self, boundaries, anneal_temp):
+        """am_sweep(..., score_precision="f32") once its refusals have passed: per block prepare (which writes tab32), the token
+        step in float32 by one of two routes, partials.  The route is chosen on the host from the block's token bound: the tile
+        kernel (segk_fbt_assign_diag32) from AM32_TILE_MIN tokens on, segk_fbb_assign_diag32 on the unchanged token lists
+        below it -- the same uniforms and the same draw (fbb_draw_row) on likelihoods of the same float32 terms.
+        SEGK_AM32_TILE_MIN overrides the constant (read per sweep; 0 = always tiles): a launch-plan switch like SEGK_FBI_Z_MIB."""
+        df = self.df
+        bt32 = self._bt_am32()
+        if not self.in_batch_state:
+            self.enter(boundaries)
+        L, ctx, cp, fp, _, st = self._args()
+        bp = C.byref(bt32)
+        try:
+            tile_min = int(os.environ.get("SEGK_AM32_TILE_MIN", AM32_TILE_MIN))
+        except ValueError:
+            raise SegkError("SEGK_AM32_TILE_MIN must be an integer, got %r" % (os.environ.get("SEGK_AM32_TILE_MIN"),))
+        pl = self.probe_ll
+        ld = pl.shape[1] if pl is not None else 0
+        for b in range(self.B):
+            check(L.segk_fbb_prepare(ctx, cp, fp, bp, b, st))
+            if sum(self._tok_cap[b]) >= tile_min:
+                check(L.segk_fbt_assign_diag32(ctx, cp, fp, bp, self.s_lo, self.s_n, b, self._n_utts[b], self._tok_cap[b],
+                                               self.sweep_index, float(anneal_temp), ptr(df.new_tok), ptr(df.n_new), ptr(pl), ld, st))
+            else:
+                if pl is not None:
+                    check(L.segk_fbb_set_probe(ctx, None, ptr(pl), ld))
+                try:
+                    check(L.segk_fbb_assign_diag32(ctx, cp, fp, bp, self.s_lo, self.s_n, b, self._n_utts[b], self.sweep_index,
+                                                   float(anneal_temp), ptr(df.new_tok), ptr(df.n_new), st))
+                finally:
+                    if pl is not None:
+                        check(L.segk_fbb_set_probe(ctx, None, None, 0))
+            check(L.segk_fbb_partials(ctx, cp, fp, bp, self.s_lo, self.s_n, b, ptr(df.new_tok), ptr(df.n_new), st))
+        self.sweep_index += 1
+
+    def am_sweep(self, boundaries, anneal_temp=1.0, score_precision=None):
         """One ACOUSTIC-MODEL batch sweep (specification tests/am_batch.py): the boundaries stay, every current
         token of block b is resampled against the statistics of all other blocks -- per block segk_fbb_prepare(b),
         segk_fbt_assign, segk_fbb_partials(b), all enqueued on the current stream.  Consumes one sweep index, the counter of
-        `sweep`.  One process, fp64 scores, no language model."""
+        `sweep`.  One process, no language model.
+        score_precision: the precision of THIS sweep's token likelihoods, whatever the sweeper was built with.  None / "f64":
+        the fp64 step (a sweeper built with reduced-precision scores refuses it, as before); "f32" (diagonal components;
+        DESIGN.md 4.17.1): the Student-t terms in float32 on the hardware logarithm, on a sweeper of either precision --
+        statistics, logits and draws stay fp64."""
         df = self.df
+        if score_precision not in (None, "f64", "f32"):
+            raise SegkError("acoustic-model batch sweeps (am_sweep) take score_precision None, 'f64' or 'f32', got %r"
+                            % (score_precision,))
         if df.lm is not None:
             raise SegkError("acoustic-model batch sweeps (am_sweep) exist without a language model only: the bigram segmenter "
                             "has no inner sweeps (its reference asserts at am_n_iter > 0)")
         if self.world > 1:
             raise SegkError("acoustic-model batch sweeps (am_sweep) run in one process only (%d ranks)" % self.world)
+        if score_precision == "f32":
+            if df.cov_type != 1:
+                raise SegkError("acoustic-model batch sweeps (am_sweep) with score_precision='f32' exist for diagonal components "
+                                "only (covariance_type=\"diag\"): fixed-variance and full-covariance components take the fp64 "
+                                "inner sweeps")
+            if self._tok_cap is None:
+                raise SegkError("acoustic-model batch sweeps (am_sweep) need a segmenter's corpus (utterances with span tables)")
+            return self._am_sweep_f32(boundaries, anneal_temp)
         if self.score_precision != "f64":
             raise SegkError("acoustic-model batch sweeps (am_sweep) take score_precision='f64' only (got %r): the "
                             "reduced-precision sweepers keep their state in other coordinates" % (self.score_precision,))

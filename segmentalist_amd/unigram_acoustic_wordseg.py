@@ -183,10 +183,12 @@ class UnigramAcousticWordseg(object):
                                   viterbi=self.fb_type == "viterbi")
         self.utterances.mark_device_dirty()
 
-    def am_batch_sweep_async(self, anneal_temp=1):
+    def am_batch_sweep_async(self, anneal_temp=1, score_precision=None):
         """Enqueue one ACOUSTIC-MODEL batch sweep: the boundaries stay, every current token is resampled (the batch form of
-        the inner sweeps `acoustic_model.gibbs_sample(1, consider_unassigned=False)`); results stay on the device."""
-        self._get_sweeper().am_sweep(self._dev_bounds, anneal_temp)
+        the inner sweeps `acoustic_model.gibbs_sample(1, consider_unassigned=False)`); results stay on the device.
+        score_precision: the precision of this sweep's token likelihoods -- None / "f64", or "f32" for diagonal components (on
+        a segmenter of either `score_precision`; statistics and draws stay fp64)."""
+        self._get_sweeper().am_sweep(self._dev_bounds, anneal_temp, score_precision)
 
     def materialise(self):
         """Bring the reference's view (components.K / assignments / statistics) up to date with the
@@ -220,18 +222,22 @@ class UnigramAcousticWordseg(object):
 
     # ------------------------------------------------------------------ sweeps
     def gibbs_sample(self, n_iter, am_n_iter=0, anneal_schedule=None, anneal_start_temp_inv=0.1,
-                     anneal_end_temp_inv=1, n_anneal_steps=-1, anneal_gibbs_am=False, sync=None, am_sync=None):
+                     anneal_end_temp_inv=1, n_anneal_steps=-1, anneal_gibbs_am=False, sync=None, am_sync=None,
+                     am_score_precision=None):
         """unigram_acoustic_wordseg.py:362-472; same record keys.  sync: None = the mode the object was built with; "batch" /
         "sequential" = the sweeps of this call in that mode (the two modes mix freely: every switch rebuilds the state the
         other one reads).  am_sync: how the `am_n_iter` inner sweeps of the acoustic model run -- None / "sequential": the
         reference's serial chain over the assigned tokens (batch mode is left for it); "batch" (with sync "batch" only):
         `am_n_iter` acoustic-model batch sweeps at temperature 1 (the reference's inner sweeps are not annealed) without
-        leaving batch mode; they always sample, whatever the fb_type."""
+        leaving batch mode; they always sample, whatever the fb_type.  am_score_precision (with am_sync "batch" only): the
+        precision of the inner sweeps' token likelihoods, passed to every one of them (am_batch_sweep_async)."""
         import torch
         assert sync in (None, "sequential", "batch")
         sync = self.sync if sync is None else sync
         assert am_sync in (None, "sequential", "batch")
         assert am_sync != "batch" or sync == "batch", "am_sync=\"batch\" runs inside batch mode: it needs sync=\"batch\""
+        assert am_score_precision is None or am_sync == "batch", \
+            "am_score_precision is the precision of the batch inner sweeps: it needs am_sync=\"batch\""
         if anneal_schedule is None:
             get_anneal_temp = iter([])
         elif anneal_schedule == "linear":
@@ -253,7 +259,7 @@ class UnigramAcousticWordseg(object):
             start_time = time.time()
             if am_n_iter > 0 and am_sync == "batch":
                 for _ in range(am_n_iter):
-                    self.am_batch_sweep_async()
+                    self.am_batch_sweep_async(score_precision=am_score_precision)
             elif am_n_iter > 0:                                   # unigram_acoustic_wordseg.py:440-443
                 self._leave_batch()
                 self.acoustic_model.gibbs_sample(am_n_iter, consider_unassigned=False)

@@ -12,7 +12,10 @@ current tokens, --sweeps repeats of M sweeps each from the batch state, median a
               re-entry into batch mode the next outer sweep pays
   fbb         the same step with segk_fbb_assign on the unchanged token lists (prepare, assign, partials per block), driven
               from this tool only
-(profiles/README.md "Acoustic-model batch sweeps")."""
+(profiles/README.md "Acoustic-model batch sweeps").
+--am-precision f32 (diagonal components): the float32 inner sweeps -- route `batch` is
+am_batch_sweep_async(score_precision="f32") (the tile kernel segk_fbt_assign_diag32 or segk_fbb_assign_diag32 by the dispatch
+constant; SEGK_AM32_TILE_MIN=0 forces the tiles), route `fbb` drives segk_fbb_assign_diag32 on the unchanged token lists."""
 import argparse
 import os
 import random
@@ -40,6 +43,7 @@ def main():
     ap.add_argument("--slices", type=int, default=8)
     ap.add_argument("--am-n-iter", type=int, default=0)
     ap.add_argument("--am-sync", default="batch", choices=["batch", "sequential", "fbb"])
+    ap.add_argument("--am-precision", default="f64", choices=["f64", "f32"])
     args = ap.parse_args()
     if args.am_n_iter > 0 and args.sync != "batch":
         ap.error("--am-n-iter times the inner sweeps of batch mode: it needs --sync batch")
@@ -140,9 +144,13 @@ def inner_sweeps(seg, which, args):
     seg.batch_sweep_async()
     torch.cuda.synchronize()
 
+    f32 = args.am_precision == "f32"
+    if f32 and args.am_sync == "sequential":
+        raise SystemExit("--am-precision f32 names the batch inner sweeps: --am-sync batch or fbb")
+
     def batch():
         for _ in range(m):
-            seg.am_batch_sweep_async()
+            seg.am_batch_sweep_async(score_precision="f32" if f32 else None)
 
     def sequential():
         seg._leave_batch()
@@ -150,12 +158,19 @@ def inner_sweeps(seg, which, args):
         sw.enter(seg._dev_bounds)
 
     def fbb():
+        import ctypes
         L, ctx, cp, fp, bp, st = sw._args()
+        if f32:
+            bp = ctypes.byref(sw._bt_am32())
         for _ in range(m):
             for b in range(sw.B):
                 check(L.segk_fbb_prepare(ctx, cp, fp, bp, b, st))
-                check(L.segk_fbb_assign(ctx, cp, fp, bp, sw.s_lo, sw.s_n, b, sw._n_utts[b], sw.sweep_index, 1.0, ptr(df.new_tok),
-                                        ptr(df.n_new), None, 0, st))
+                if f32:
+                    check(L.segk_fbb_assign_diag32(ctx, cp, fp, bp, sw.s_lo, sw.s_n, b, sw._n_utts[b], sw.sweep_index, 1.0,
+                                                   ptr(df.new_tok), ptr(df.n_new), st))
+                else:
+                    check(L.segk_fbb_assign(ctx, cp, fp, bp, sw.s_lo, sw.s_n, b, sw._n_utts[b], sw.sweep_index, 1.0, ptr(df.new_tok),
+                                            ptr(df.n_new), None, 0, st))
                 check(L.segk_fbb_partials(ctx, cp, fp, bp, sw.s_lo, sw.s_n, b, ptr(df.new_tok), ptr(df.n_new), st))
             sw.sweep_index += 1
 
@@ -170,7 +185,8 @@ def inner_sweeps(seg, which, args):
     df.check_status()
     times = sorted(times[1:])
     n_tok = int(df.n_new.sum().item())
-    print(json.dumps({"inner_sweep": which, "am_sync": args.am_sync, "am_n_iter": m, "repeats": len(times), "tokens": n_tok,
+    print(json.dumps({"inner_sweep": which, "am_sync": args.am_sync, "am_precision": args.am_precision,
+                      "token_bound_per_block": max(sum(cap) for cap in sw._tok_cap), "am_n_iter": m, "repeats": len(times), "tokens": n_tok,
                       "median_ms": 1e3 * float(np.median(times)), "min_ms": 1e3 * times[0], "max_ms": 1e3 * times[-1],
                       "range_ms": 1e3 * (times[-1] - times[0]), "tokens_per_s": n_tok / float(np.median(times))}), flush=True)
 
