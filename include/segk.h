@@ -425,6 +425,42 @@ int32_t segk_kmeans_assignments_from_tokens(segk_ctx *ctx, const segk_corpus *c,
                                             const int32_t *new_k, const int32_t *n_new,
                                             void *stream);
 
+/* Batch refit: one Lloyd iteration over the CURRENT tokens between two batch sweeps (the reference's
+ * acoustic_model.fit(m, consider_unassigned=False) of kmeans_acoustic_wordseg.py:425, kmeans.py:97-173, with the statistics
+ * summed in the batch sweep's fixed order; specification: tests/kmeans_refit.py).  Entry points added at ABI 15, nothing
+ * changed.  A step is: segk_kmeans_refit_collect -> segk_kmeans_score[_hinted] on the id list -> segk_kmeans_refit_apply ->
+ * segk_kmeans_batch_partials -> [all-gather] -> segk_kmeans_batch_finalize, all on one stream.
+ *  (1) segk_kmeans_refit_collect: the rows of the live token slots (new_k >= 0, as segk_kmeans_batch_partials reads them) of
+ *      utterances [utt_lo, utt_hi) as a dense list ids [dev] int32 [n_list] in slot order, in the device's row numbering;
+ *      slots [dev] int32 [n_list] or NULL: each entry's slot (utt * N_max + t); *count_out [dev] int32: the number of tokens.
+ *      Entries [count, n_list) are -1 (skipped by the score calls), so the caller can score n_list entries without knowing the
+ *      count: any n_list with count <= n_list <= min((utt_hi - utt_lo) * N_max, n_emb) will do; count > n_list sets status bit
+ *      8 and lists the first n_list.  chunk_scratch [dev] int32 [segk_kmeans_refit_scratch_words(slots of the range)].
+ *  (2) segk_kmeans_refit_apply: new_k[slot] = cand->k[row] for those tokens (np.argmax over all K_max rows), n_flag[utt] =
+ *      the utterance's tokens with k >= K as segk_kmeans_segment leaves it, *moved [dev] int32 = tokens whose label changed
+ *      (cleared by the call).  out_total is not touched.  A token whose row carries no result (cand->k < 0) keeps its label
+ *      and sets status bit 8.  Drops the delta score pass's state: the next whole-range hinted call runs the full pass.
+ *  (3) segk_kmeans_hint_relabel: cand->k[e] = table[cand->k[e]] for ALL rows e (table [dev] int32 [K_max], e.g. the
+ *      finalize's remap_scratch); entries outside [0, K_max) before or after the translation become -1 = no hint, exactly what
+ *      segk_kmeans_score_hinted makes of a hint and its table.  With two relabellings between a row's hint and its next use
+ *      (a refit between two sweeps) the caller applies each as it happens and hints with the identity (hint_remap NULL).
+ *  (4) segk_kmeans_refit_record: segk_kmeans_batch_record plus out_scalars[7] = *moved: one device-to-host copy per step.  */
+int64_t segk_kmeans_refit_scratch_words(int64_t n_slots);
+int32_t segk_kmeans_refit_collect(segk_ctx *ctx, const segk_corpus *c, int32_t utt_lo, int32_t utt_hi,
+                                  const int32_t *new_tok, const int32_t *new_k, int32_t *chunk_scratch,
+                                  int32_t *ids, int32_t *slots, int64_t n_list, int32_t *count_out,
+                                  int32_t *status, void *stream);
+int32_t segk_kmeans_refit_apply(segk_ctx *ctx, const segk_corpus *c, const segk_kmeans *m,
+                                const segk_cand *cand, int32_t utt_lo, int32_t utt_hi,
+                                const int32_t *new_tok, int32_t *new_k, int32_t *n_flag, int32_t *moved,
+                                int32_t *status, void *stream);
+int32_t segk_kmeans_hint_relabel(segk_ctx *ctx, const segk_corpus *c, const segk_kmeans *m,
+                                 const segk_cand *cand, const int32_t *table, void *stream);
+int32_t segk_kmeans_refit_record(segk_ctx *ctx, const segk_corpus *c, const segk_kmeans *m, int32_t utt_lo,
+                                 int32_t utt_hi, const int32_t *new_tok, const int32_t *new_k,
+                                 const int32_t *status, const int32_t *moved, double *out_scalars,
+                                 void *stream);
+
 /* KMeansComponents.sum_neg_sqrd_norm (kmeans_components.py:234-247), record metric.
  * out [dev] double [1]; tolerance-level parity (summation order differs). */
 int32_t segk_kmeans_sum_neg_sqrd_norm(segk_ctx *ctx, const segk_corpus *c, const segk_kmeans *m,

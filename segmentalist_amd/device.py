@@ -237,6 +237,7 @@ class DeviceKMeans(object):
         self.utt_arange = torch.arange(nu, dtype=torch.int32, device=dev)
         self.remap = torch.zeros(self.K_max, dtype=torch.int32, device=dev)
         self.out_scalars = torch.zeros(8, dtype=torch.float64, device=dev)
+        self.refit_moved = torch.zeros(1, dtype=torch.int32, device=dev)      # tokens a batch refit relabelled (this rank's)
         # batch sweeps leave `assignments` untouched: `assign_stale` = (lo, hi, world) of the token
         # lists it must be rebuilt from, or None when it is current
 
@@ -308,19 +309,20 @@ class DeviceKMeans(object):
     def prepare(self):
         check(self._L.segk_kmeans_prepare(self._ctx, self._cp(), C.byref(self.m), _abi.stream()))
 
-    def score_rows(self, ids=None, row0=0, n=None, hint_remap=None):
+    def score_rows(self, ids=None, row0=0, n=None, hint_remap=None, hint_identity=False):
         """A1 over rows (device int32 tensor `ids`, or the range row0..row0+n): afterwards
         cand_k / cand_s hold np.argmax / np.max of neg_sqrd_norm for those rows.
         hint_remap (device int32 [K_max]): cand_k of these rows holds what the previous call left there, in the labelling
         that table translates into the current one -- the library then verifies those hints against the dense filter values
-        instead of tracking the winner's index (segk_kmeans_score_hinted); the results are the same bits either way."""
+        instead of tracking the winner's index (segk_kmeans_score_hinted); the results are the same bits either way.
+        hint_identity: the same with cand_k already in the current labelling (no table)."""
         if ids is not None:
             n = ids.numel()
             p = ptr(ids)
         else:
             p = None
             n = self.corpus.n_emb - row0 if n is None else n
-        if hint_remap is not None:
+        if hint_remap is not None or hint_identity:
             check(self._L.segk_kmeans_score_hinted(self._ctx, self._cp(), C.byref(self.m), p, int(row0), int(n),
                                                    C.byref(self.cand), ptr(hint_remap), ptr(self.status), _abi.stream()))
             return
@@ -462,7 +464,21 @@ class DeviceKMeans(object):
         self._raise_status(int(o[5]))
         return float(o[0]), int(o[1]), int(o[2]), float(o[4])
 
+    def refit_record(self, lo, hi, moved):
+        """The record values of the batch refit just enqueued, in ONE device-to-host copy (segk_kmeans_refit_record):
+        (n_mean_updates of this rank's tokens, K, n_tokens, sum_neg_sqrd_norm of this rank's tokens); raises like
+        check_status."""
+        check(self._L.segk_kmeans_refit_record(self._ctx, self._cp(), C.byref(self.m), int(lo), int(hi), ptr(self.new_tok),
+                                               ptr(self.new_k), ptr(self.status), ptr(moved), ptr(self.out_scalars),
+                                               _abi.stream()))
+        o = self.out_scalars.cpu().numpy()
+        self._raise_status(int(o[5]))
+        return int(o[7]), int(o[1]), int(o[2]), float(o[4])
+
     def _raise_status(self, bits):
+        if bits & 8:
+            raise SegkError("batch refit: a token's row was not scored (more tokens than the id list was sized for, or a row "
+                            "without a result): the labels of this refit are not usable")
         if bits & 1:
             raise AssertionError("a new segment has no embedding (vec_id == -1): the reference asserts in "
                                  "KMeansComponents.add_item (kmeans_components.py:100)")
@@ -566,6 +582,12 @@ class KMeansBatchSweeper(object):
         check(dk._L.segk_kmeans_hint_feedback(dk._ctx, C.byref(_l), C.byref(_s), C.byref(_p)))
         self._fb_seen = _l.value     # figures of hinted calls enqueued before this sweeper existed are not its business
         self._mb = None              # (n_batches, per-step launch tables) of sweep_minibatch
+        # batch refits (refit): after one, cand_k of every row has been translated through each finalize's relabel table as it
+        # happened, so the next hinted call takes the identity; a sweep's finalize leaves its table to the next call again
+        self._hints_current = False
+        self._refits_done = 0
+        self._refit = None           # refit's buffers: (id list, chunk scratch, token count [dev], host bound of the token count)
+        self._n_tok = None           # this rank's token count where the host knows it (note_token_count), else None
         dk.batch_comm = self.comm
 
     HINT_MISS_PERMILLE = 450
@@ -619,13 +641,16 @@ class KMeansBatchSweeper(object):
         # one's relabelling is in dk.remap: while components are still being removed some hints are stale -- they are verified
         # like any other and cost one pass of the band stage, never a wrong result)
         hints = self._use_hints()
+        self._n_tok = None
         for (utt0, n_utts, row0, n_rows, utts, rows) in self._minibatch_tables(n_batches):
-            remap = dk.remap if hints else None
+            # (after a refit the first step's hints are in the current labelling; every step's finalize relabels again)
+            hint = {} if not hints else {"hint_identity": True} if self._hints_current else {"hint_remap": dk.remap}
+            self._hints_current = False
             if rows is None:
-                dk.score_rows(row0=row0, n=n_rows, hint_remap=remap)
+                dk.score_rows(row0=row0, n=n_rows, **hint)
                 dk.segment(boundaries, n_slices_min, n_slices_max, wip, utt0=utt0, n_utts=n_utts)
             else:
-                dk.score_rows(ids=rows, hint_remap=remap)
+                dk.score_rows(ids=rows, **hint)
                 check(L.segk_kmeans_segment(ctx, cp, mp, ptr(utts), 0, n_utts, int(n_slices_min), int(n_slices_max), float(wip),
                                             C.byref(dk.cand), ptr(boundaries), ptr(dk.old_tok), ptr(dk.new_tok), ptr(dk.new_k),
                                             ptr(dk.n_old), ptr(dk.n_new), ptr(dk.n_flag), ptr(dk.out_total), ptr(dk.status), st))
@@ -644,7 +669,9 @@ class KMeansBatchSweeper(object):
         L, ctx, cp, mp, st = dk._L, dk._ctx, dk._cp(), C.byref(dk.m), _abi.stream()
         # from the second sweep on cand_k holds every row's argmax of the previous sweep and dk.remap the relabelling of
         # that sweep's finalize: hints for the score stage (same results)
-        dk.score_rows(row0=pt.row_lo - dk.row_base, n=pt.row_hi - pt.row_lo, hint_remap=dk.remap if self._use_hints() else None)
+        # (after a refit the hints are in the current labelling already: refit)
+        hint = {} if not self._use_hints() else {"hint_identity": True} if self._hints_current else {"hint_remap": dk.remap}
+        dk.score_rows(row0=pt.row_lo - dk.row_base, n=pt.row_hi - pt.row_lo, **hint)
         dk.segment(boundaries, n_slices_min, n_slices_max, wip, utt0=pt.utt_lo, n_utts=pt.utt_hi - pt.utt_lo)
         check(L.segk_kmeans_batch_partials(ctx, cp, mp, ptr(self.blk_lo), pt.nbl, ptr(dk.new_tok), ptr(dk.new_k),
                                            ptr(dk.n_flag), ptr(dk.out_total), self._sorted_ptr, ptr(self.koff),
@@ -669,6 +696,66 @@ class KMeansBatchSweeper(object):
         dk.assign_stale = (pt.utt_lo, pt.utt_hi, pt.world)
         dk.bounds_stale = (boundaries, pt) if pt.world > 1 else None
         self._sweeps_done += 1
+        self._hints_current = False
+        self._n_tok = None
+
+    # ------------------------------------------------------------------ batch refit between sweeps
+    def note_token_count(self, n):
+        """This rank's number of tokens, where the caller has it on the host (one rank: the record of the sweep or refit just
+        run): the refit then scores exactly that many rows instead of the bound the host can know without it."""
+        self._n_tok = int(n)
+
+    def _relabel_hints(self):
+        dk = self.dk
+        check(dk._L.segk_kmeans_hint_relabel(dk._ctx, dk._cp(), C.byref(dk.m), C.byref(dk.cand), ptr(dk.remap), _abi.stream()))
+
+    def refit(self, boundaries):
+        """Enqueue one batch refit (specification: tests/kmeans_refit.py kmeans_batch_refit): every current token of this rank's
+        utterances gets the argmax against the means as they stand, then the statistics are rebuilt from the relabelled token
+        lists exactly as after a sweep -- partial sums, ONE all-gather, finalize.  The segmentation, `out_total` and the
+        communication pattern of a sweep stay; `dk.refit_moved` holds the number of this rank's tokens whose label changed."""
+        torch = _torch()
+        dk, pt, c = self.dk, self.part, self.dk.corpus
+        L, ctx, cp, mp, st = dk._L, dk._ctx, dk._cp(), C.byref(dk.m), _abi.stream()
+        if dk.assign_stale is None:
+            dk.ensure_boundaries()
+            self._tokens_from_state(boundaries)
+            self._n_tok = None
+        if self.use_graph:
+            # a captured sweep holds the addresses of the score path's workspaces, which scoring an id list of another length
+            # may reallocate: the next sweep runs eagerly and is captured again
+            self._drop_graph()
+            self._warm = 0
+        n_slots = (pt.utt_hi - pt.utt_lo) * c.N_max
+        if self._refit is None:
+            # a token spans at least one landmark: the landmarks of the local utterances bound the tokens
+            bound = min(int(c.lengths_np[pt.utt_lo:pt.utt_hi].sum()), n_slots, c.n_emb)
+            dev = dk.new_k.device
+            self._refit = (torch.zeros(max(bound, 1), dtype=torch.int32, device=dev),
+                           torch.zeros(int(L.segk_kmeans_refit_scratch_words(n_slots)), dtype=torch.int32, device=dev),
+                           torch.zeros(1, dtype=torch.int32, device=dev), bound)
+        ids, chunks, count, bound = self._refit
+        n_list = bound if self._n_tok is None else min(self._n_tok, bound)
+        hints = self._use_hints()
+        # the hints of ALL rows into the current labelling, here and after the finalize below (two relabellings lie between
+        # a span row's hint and the next sweep, and dk.remap holds only the latest): the hinted calls then take the identity
+        if not self._hints_current and self._sweeps_done + self._refits_done > 0:
+            self._relabel_hints()
+        check(L.segk_kmeans_refit_collect(ctx, cp, pt.utt_lo, pt.utt_hi, ptr(dk.new_tok), ptr(dk.new_k), ptr(chunks), ptr(ids),
+                                          None, n_list, ptr(count), ptr(dk.status), st))
+        dk.score_rows(ids=ids[:n_list], hint_identity=hints)
+        check(L.segk_kmeans_refit_apply(ctx, cp, mp, C.byref(dk.cand), pt.utt_lo, pt.utt_hi, ptr(dk.new_tok), ptr(dk.new_k),
+                                        ptr(dk.n_flag), ptr(dk.refit_moved), ptr(dk.status), st))
+        check(L.segk_kmeans_batch_partials(ctx, cp, mp, ptr(self.blk_lo), pt.nbl, ptr(dk.new_tok), ptr(dk.new_k),
+                                           ptr(dk.n_flag), ptr(dk.out_total), self._sorted_ptr, ptr(self.koff),
+                                           ptr(self.pack), self.cap, self.flag_rows, ptr(dk.out_scalars), st))
+        if pt.world > 1:
+            self.comm.all_gather_rows(self.pack_all, self.pack)
+        self._enqueue_back()
+        self._relabel_hints()
+        self._hints_current = True
+        self._refits_done += 1
+        dk.assign_stale = (pt.utt_lo, pt.utt_hi, pt.world)
 
     # ------------------------------------------------------------------ hipGraph replay
     def _capture(self, fn):

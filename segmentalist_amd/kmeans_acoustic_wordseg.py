@@ -127,6 +127,7 @@ class SegmentalKMeansWordseg(object):
 
         # batch mode plumbing (single process unless torch.distributed is initialised)
         self._sweeper = None
+        self.kmeans_refit_records = []       # segment(..., kmeans_sync="batch"): one fit-style record per sweep
         # flag_cap: tokens per statistics block and sweep that may found new components (more: an error, never a wrong result).
         # Default 4 096; 1 024 with a sharded corpus, whose records carry flag_cap embedding rows per block over the wire.
         if flag_cap is None:
@@ -183,10 +184,58 @@ class SegmentalKMeansWordseg(object):
             self._get_sweeper().sweep(self._dev_bounds, self.n_slices_min, self.n_slices_max, self.wip)
         self.utterances.mark_device_dirty()
 
+    def kmeans_refit_async(self):
+        """Enqueue one batch refit (sync="batch"): a Lloyd iteration over the current tokens with the statistics rebuilt in the
+        batch sweep's fixed order (tests/kmeans_refit.py kmeans_batch_refit); results stay on the device.  The counterpart
+        of the reference's acoustic_model.fit(1, consider_unassigned=False) between sweeps (kmeans_acoustic_wordseg.py:425),
+        for any number of ranks and a sharded corpus; the segmentation does not change."""
+        assert self.sync == "batch", "kmeans_refit_async needs sync=\"batch\""
+        self._get_sweeper().refit(self._dev_bounds)
+
+    def _kmeans_refit_record(self):
+        """(n_mean_updates, K, n_tokens, sum_neg_sqrd_norm) of the refit just enqueued: one device-to-host copy, and with
+        several ranks one exchange of the two per-rank values (every rank gets the same sums, in rank order)."""
+        sw = self._get_sweeper()
+        pt = sw.part
+        moved, n_comp, n_tok, sum_neg = self._dk.refit_record(pt.utt_lo, pt.utt_hi, self._dk.refit_moved)
+        if pt.world > 1:
+            parts = sw.comm.all_gather_object((moved, sum_neg))
+            moved, sum_neg = sum(p[0] for p in parts), float(sum(p[1] for p in parts))
+        else:
+            sw.note_token_count(n_tok)
+        return moved, n_comp, n_tok, sum_neg
+
+    def _kmeans_batch_fit(self, n_iter):
+        """KMeans.fit(n_iter, consider_unassigned=False) as batch refits: same record keys, same early stop."""
+        rec = {"sum_neg_sqrd_norm": [], "components": [], "n_mean_updates": [], "sample_time": []}
+        for i_iter in range(n_iter):
+            start_time = time.time()
+            self.kmeans_refit_async()
+            moved, n_comp, _, sum_neg = self._kmeans_refit_record()
+            rec["sum_neg_sqrd_norm"].append(sum_neg)
+            rec["components"].append(n_comp)
+            rec["n_mean_updates"].append(moved)
+            rec["sample_time"].append(time.time() - start_time)
+            info = "k-means refit: " + str(i_iter)
+            for key in sorted(rec):
+                info += ", " + key + ": " + str(rec[key][-1])
+            logger.info(info)
+            if moved == 0:
+                break
+        return rec
+
     # ------------------------------------------------------------------ driver
-    def segment(self, n_iter, n_iter_inbetween_kmeans=0):
-        """kmeans_acoustic_wordseg.py:353-426; same record keys."""
+    def segment(self, n_iter, n_iter_inbetween_kmeans=0, kmeans_sync=None):
+        """kmeans_acoustic_wordseg.py:353-426; same record keys.
+        kmeans_sync: how the n_iter_inbetween_kmeans Lloyd iterations after every sweep run.  None / "sequential": the
+        reference's acoustic_model.fit (item by item; needs the whole corpus on this device).  "batch" (sync="batch" only): up
+        to that many batch refits (kmeans_refit_async), stopping after the first that moves nothing; their fit-style records
+        are kept in self.kmeans_refit_records, one dict per sweep."""
         import torch
+        assert kmeans_sync in (None, "sequential", "batch"), "invalid value for `kmeans_sync`: " + str(kmeans_sync)
+        if kmeans_sync == "batch":
+            assert self.sync == "batch", "kmeans_sync=\"batch\" needs a segmenter constructed with sync=\"batch\""
+        self.kmeans_refit_records = []
         logger.info("Segmenting for " + str(n_iter) + " iterations")
         record_dict = {"sum_neg_sqrd_norm": [], "sum_neg_len_sqrd_norm": [], "components": [],
                        "sample_time": [], "n_tokens": []}
@@ -219,6 +268,7 @@ class SegmentalKMeansWordseg(object):
                     # every record value of the sweep from one device-to-host copy (the metric from the token lists)
                     sum_neg_len_sqrd_norm, n_comp, n_tok, sum_neg = self._dk.batch_record(pt.utt_lo, pt.utt_hi)
                     batch_rec = (sum_neg, n_comp, n_tok)
+                    self._get_sweeper().note_token_count(n_tok)
                 else:
                     torch.cuda.synchronize()
                     self._dk.check_status()
@@ -239,7 +289,10 @@ class SegmentalKMeansWordseg(object):
                 info += ", " + key + ": " + str(record_dict[key][-1])
             logger.info(info)
             if n_iter_inbetween_kmeans > 0:
-                self.acoustic_model.fit(n_iter_inbetween_kmeans, consider_unassigned=False)
+                if kmeans_sync == "batch":
+                    self.kmeans_refit_records.append(self._kmeans_batch_fit(n_iter_inbetween_kmeans))
+                else:
+                    self.acoustic_model.fit(n_iter_inbetween_kmeans, consider_unassigned=False)
         return record_dict
 
     def get_unsup_transcript_i(self, i):
