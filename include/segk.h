@@ -461,6 +461,28 @@ int32_t segk_kmeans_refit_record(segk_ctx *ctx, const segk_corpus *c, const segk
                                  const int32_t *status, const int32_t *moved, double *out_scalars,
                                  void *stream);
 
+/* KMeans.fit on the device: ONE Lloyd iteration of kmeans.py:97-173 -- the loop over the items (:113-131: np.argmax of
+ * neg_sqrd_norm against the means as they stand, kmeans_components.py:225-226), the del_item / add_item of every moved item in
+ * item order (kmeans.py:133-137; kmeans_components.py:93-132, add_item's clamp :101-104 included), clean_components (:263-266)
+ * and the record (kmeans.py:150-153) -- enqueued by one call, with the reference's bits: assignments, means, mean_numerators,
+ * counts and K are those of the item-by-item route (segk_kmeans_del_item + segk_kmeans_add_item per moved item, then
+ * segk_kmeans_clean_components); specification: tests/kmeans_fit_device.py.  Entry points added at ABI 15, nothing changed.
+ *   consider_unassigned != 0: every row is an item, n_items_max must be n_emb.  0: the rows with a label are (kmeans.py:118-121),
+ *     listed on the device; n_items_max is any bound of their number in [1, n_emb] -- the score call runs over that many list
+ *     entries, the ones behind the count are skipped; more labelled rows than n_items_max set status bit 8 (the iteration is
+ *     then not usable).
+ *   The number of launches does not depend on the data; the operands stay on the device.  cand->k / cand->s of the items hold
+ *     np.argmax / np.max afterwards, as after segk_kmeans_score, which the call uses.  The delta score pass's state is dropped
+ *     and the operand images are refreshed (segk_kmeans_prepare), as by the item-by-item route.  K_max <= 8192.
+ *   scratch [dev] int32 [segk_kmeans_fit_scratch_words(n_emb, n_items_max, K_max)], contents irrelevant before and after.
+ *   record [dev] double [8] = {n_mean_updates (items moved), K, items, K before, sum_neg_sqrd_norm (kmeans_components.py:234-247,
+ *     tolerance-level parity as segk_kmeans_sum_neg_sqrd_norm), status[0], status[1], moves that named a row >= K}: one
+ *     device-to-host copy serves the iteration's record and the early stop. */
+int64_t segk_kmeans_fit_scratch_words(int64_t n_emb, int64_t n_items_max, int32_t K_max);
+int32_t segk_kmeans_fit_step(segk_ctx *ctx, const segk_corpus *c, segk_kmeans *m, const segk_cand *cand,
+                             int32_t consider_unassigned, int64_t n_items_max, int32_t *scratch, double *record,
+                             int32_t *status, void *stream);
+
 /* KMeansComponents.sum_neg_sqrd_norm (kmeans_components.py:234-247), record metric.
  * out [dev] double [1]; tolerance-level parity (summation order differs). */
 int32_t segk_kmeans_sum_neg_sqrd_norm(segk_ctx *ctx, const segk_corpus *c, const segk_kmeans *m,

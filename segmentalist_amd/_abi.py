@@ -116,6 +116,8 @@ SIGNATURES = {
     "segk_kmeans_refit_apply": (_i32, [_P, _CP, _KP, _DP, _i32, _i32, _P, _P, _P, _P, _P, _P]),
     "segk_kmeans_hint_relabel": (_i32, [_P, _CP, _KP, _DP, _P, _P]),
     "segk_kmeans_refit_record": (_i32, [_P, _CP, _KP, _i32, _i32, _P, _P, _P, _P, _P, _P]),
+    "segk_kmeans_fit_scratch_words": (_i64, [_i64, _i64, _i32]),
+    "segk_kmeans_fit_step": (_i32, [_P, _CP, _KP, _DP, _i32, _i64, _P, _P, _P, _P]),
     "segk_kmeans_sum_neg_sqrd_norm": (_i32, [_P, _CP, _KP, _P, _P]),
     "segk_fbgmm_record_metrics": (_i32, [_P, _CP, _FP, _i32, _f64, _P, _P]),
     "segk_fbgmm_init_stats": (_i32, [_P, _CP, _FP, _P]),

@@ -475,6 +475,29 @@ class DeviceKMeans(object):
         self._raise_status(int(o[5]))
         return int(o[7]), int(o[1]), int(o[2]), float(o[4])
 
+    def fit_step(self, consider_unassigned, n_items_max=None):
+        """One Lloyd iteration of KMeans.fit enqueued by ONE library call (segk_kmeans_fit_step) and its record
+        in ONE device-to-host copy -> (n_mean_updates, K, items, sum_neg_sqrd_norm); raises like check_status.  The state
+        afterwards is that of the item-by-item route (exact_max, del_item + add_item per moved item, clean_components), bit
+        for bit.  n_items_max (consider_unassigned=False): a bound of the number of rows with a label, n_emb when None."""
+        torch = _torch()
+        self.require_whole_corpus("KMeans.fit")
+        self.ensure_assignments()
+        c = self.corpus
+        n_max = c.n_emb if consider_unassigned or n_items_max is None else max(1, min(int(n_items_max), c.n_emb))
+        words = int(self._L.segk_kmeans_fit_scratch_words(c.n_emb, n_max, self.K_max))
+        if getattr(self, "_fit_scratch", None) is None or self._fit_scratch.numel() < words:
+            self._fit_scratch = torch.zeros(words, dtype=torch.int32, device=self.means.device)
+            self._fit_record = torch.zeros(8, dtype=torch.float64, device=self.means.device)
+        check(self._L.segk_kmeans_fit_step(self._ctx, self._cp(), C.byref(self.m), C.byref(self.cand), 1 if consider_unassigned else 0,
+                                           n_max, ptr(self._fit_scratch), ptr(self._fit_record), ptr(self.status), _abi.stream()))
+        o = self._fit_record.cpu().numpy()
+        if int(o[5]) & 8:
+            raise SegkError("KMeans.fit on the device: more rows carry a label than the item list was sized for, or a row holds a "
+                            "label outside [-1, K_max): the statistics of this iteration are not usable")
+        self._raise_status(int(o[5]))
+        return int(o[0]), int(o[1]), int(o[2]), float(o[4])
+
     def _raise_status(self, bits):
         if bits & 8:
             raise SegkError("batch refit: a token's row was not scored (more tokens than the id list was sized for, or a row "

@@ -45,17 +45,40 @@ class KMeans(object):
         assignments = _consecutive(np.asarray(assignments))
         self.components = KMeansComponents(X, assignments, K, _corpus=self._corpus, _shard=getattr(self, "_shard", None))
 
-    def fit(self, n_iter, consider_unassigned=True, no_empty=True):
+    def fit(self, n_iter, consider_unassigned=True, no_empty=True, on_device=False, _n_items_bound=None):
         """
         kmeans.py:97-173: batch (Lloyd) iterations -- every considered item gets the argmax of
         `neg_sqrd_norm` against the means frozen at the start of the iteration, then the changed
         items are moved (del_item/add_item in item order) and empty components removed.
+        on_device=True: every iteration is one library call and one small device-to-host copy (DeviceKMeans.fit_step,
+        DESIGN.md 4.19) -- no launch per item, no host loop over items, the label vectors stay on the device; the same
+        state and the same record, bit for bit (sum_neg_sqrd_norm to its usual tolerance).
         """
         c = self.components
         dk = c.dev
         dk.require_whole_corpus("KMeans.fit")
         record_dict = {"sum_neg_sqrd_norm": [], "components": [], "n_mean_updates": [], "sample_time": []}
         start_time = time.time()
+        if on_device:
+            # _n_items_bound: what the caller knows about the number of labelled rows (consider_unassigned=False); from the
+            # second iteration on the record has the number itself -- moving items does not change it
+            bound = None if consider_unassigned else _n_items_bound
+            for i_iter in range(n_iter):
+                moved, n_comp, n_items, sum_neg = dk.fit_step(consider_unassigned, bound)
+                if not consider_unassigned:
+                    bound = n_items
+                record_dict["sum_neg_sqrd_norm"].append(sum_neg)
+                record_dict["components"].append(n_comp)
+                record_dict["n_mean_updates"].append(moved)
+                record_dict["sample_time"].append(time.time() - start_time)
+                start_time = time.time()
+                info = "iteration: " + str(i_iter)
+                for key in sorted(record_dict):
+                    info += ", " + key + ": " + str(record_dict[key][-1])
+                logger.info(info)
+                if moved == 0:
+                    break
+            return record_dict
         for i_iter in range(n_iter):
             old = c.assignments
             items = np.arange(c.N) if consider_unassigned else np.where(old != -1)[0]

@@ -224,15 +224,29 @@ class SegmentalKMeansWordseg(object):
                 break
         return rec
 
+    def _kmeans_device_fit(self, n_iter):
+        """acoustic_model.fit(n_iter, consider_unassigned=False) with the iterations on the device.  A token spans at least one
+        landmark, so the landmarks bound the rows with a label; a captured sweep holds the addresses of the score path's
+        workspaces, which scoring an id list of another length may reallocate (as in KMeansBatchSweeper.refit): the next sweep
+        runs eagerly and is captured again."""
+        sw = self._sweeper
+        if sw is not None and sw.use_graph:
+            sw._drop_graph()
+            sw._warm = 0
+        return self.acoustic_model.fit(n_iter, consider_unassigned=False, on_device=True,
+                                       _n_items_bound=int(self._corpus.lengths_np.sum()))
+
     # ------------------------------------------------------------------ driver
     def segment(self, n_iter, n_iter_inbetween_kmeans=0, kmeans_sync=None):
         """kmeans_acoustic_wordseg.py:353-426; same record keys.
         kmeans_sync: how the n_iter_inbetween_kmeans Lloyd iterations after every sweep run.  None / "sequential": the
         reference's acoustic_model.fit (item by item; needs the whole corpus on this device).  "batch" (sync="batch" only): up
         to that many batch refits (kmeans_refit_async), stopping after the first that moves nothing; their fit-style records
-        are kept in self.kmeans_refit_records, one dict per sweep."""
+        are kept in self.kmeans_refit_records, one dict per sweep.  "device" (either sync): the reference's acoustic_model.fit
+        with every iteration run on the device (KMeans.fit(..., on_device=True)): the results of None, bit for
+        bit, without a launch per moved token; needs the whole corpus on this device like None."""
         import torch
-        assert kmeans_sync in (None, "sequential", "batch"), "invalid value for `kmeans_sync`: " + str(kmeans_sync)
+        assert kmeans_sync in (None, "sequential", "batch", "device"), "invalid value for `kmeans_sync`: " + str(kmeans_sync)
         if kmeans_sync == "batch":
             assert self.sync == "batch", "kmeans_sync=\"batch\" needs a segmenter constructed with sync=\"batch\""
         self.kmeans_refit_records = []
@@ -291,6 +305,8 @@ class SegmentalKMeansWordseg(object):
             if n_iter_inbetween_kmeans > 0:
                 if kmeans_sync == "batch":
                     self.kmeans_refit_records.append(self._kmeans_batch_fit(n_iter_inbetween_kmeans))
+                elif kmeans_sync == "device":
+                    self._kmeans_device_fit(n_iter_inbetween_kmeans)
                 else:
                     self.acoustic_model.fit(n_iter_inbetween_kmeans, consider_unassigned=False)
         return record_dict
