@@ -1,4 +1,6 @@
 """Shared host-side shell of the device-backed Gaussian component classes."""
+import weakref
+
 import numpy as np
 
 from .device import DeviceCorpus, DeviceFbgmm
@@ -25,6 +27,7 @@ class _DeviceGaussianComponents(object):
         corpus = _corpus if _corpus is not None else DeviceCorpus(X)
         self.dev = DeviceFbgmm(corpus, self._cov_type, K_max, alpha, lms, prior_a, prior_b, prior_c, k_0, v_0,
                                assignments, lm=lm)
+        self.dev._components = weakref.ref(self)        # record_metrics at D = 1 asks log_marg() back
 
     # state snapshots -------------------------------------------------------------------
     @property

@@ -12,6 +12,8 @@
 // ascending order accumulated sequentially in XT.  The lists come from the stable counting sort of the k-means batch
 // statistics (k_batch_sort) run over the ROWS (key = assignments[row], blocks of rows instead of blocks of
 // utterances; token order would not do: the numbering of an utterance's spans is the corpus's business).
+// Row after row is numpy's order for D >= 2 only: an (n, 1) matrix reduces as a contiguous vector, pairwise, so for D == 1
+// DeviceFbgmm.record_metrics takes log_prob_X_given_z from the host expression instead of term[] (device.py).
 // Everything after those sums is float64, where the order of a sum changes the last bits only (the contract for
 // record values is 1e-8).
 // The bigram driver's log_prob_z is, in the reference, the sequential Polya-urn probability of the tokens under the

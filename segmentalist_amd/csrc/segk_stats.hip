@@ -427,6 +427,16 @@ static inline __host__ __device__ int64_t segk_flag_words(int cap) { return (2 +
 // ======================================================================================
 #define SORT_THREADS 1024
 #define SORT_KEYS_LDS 32768          /* slots of a block whose keys are staged in LDS (int16); larger blocks read them from memory */
+// ... or fewer, where the counters of a wide bank leave less room: base [K_max + 2] and NW x K_max counters come first, and a
+// workgroup has 160 KB (256 bytes are left to the kernel's static arrays).  At K_max = 8192 the full 32 768 keys made the
+// request 163 848 bytes and hipFuncSetAttribute refused every bank from 8187 components on.
+#define SORT_LDS_MAX (160 * 1024 - 256)
+static inline __host__ __device__ int sort_nw(int K_max) { return K_max <= 1024 ? 16 : K_max <= 2048 ? 8 : K_max <= 4096 ? 4 : 2; }
+static inline __host__ __device__ int sort_keys_cap(int K_max)
+{
+    const int room = (SORT_LDS_MAX - (K_max + 2) * 4 - sort_nw(K_max) * K_max * 4) / 2;
+    return room < SORT_KEYS_LDS ? room : SORT_KEYS_LDS;
+}
 // the lanes of the wave whose key equals this lane's (valid lanes only): one ballot per key bit
 __device__ __forceinline__ unsigned long long dev_match_key(int k, bool ok, int nbits)
 {
@@ -448,7 +458,7 @@ __device__ __forceinline__ void dev_batch_sort(const segk_corpus &c, const segk_
     const int K_max = m.K_max;
     const int64_t p0 = (int64_t)u0 * c.N_max;
     const int S = (u1 - u0) * c.N_max;
-    const bool staged = S <= SORT_KEYS_LDS;
+    const bool staged = S <= sort_keys_cap(K_max);
     const int per = ((S + NW - 1) / NW + 63) & ~63;              // slots per wave, whole chunks of 64
     int nbits = 1;
     while ((1 << nbits) < K_max) nbits++;
@@ -1828,8 +1838,8 @@ int segk_launch_batch_sort(const segk_corpus *c, const segk_kmeans *m, const int
                            const int32_t *new_k, const int32_t *n_flag, const double *out_total, int32_t *sorted, int32_t *koff,
                            double *part_tot, int32_t *flags, int cap, double *out_scalars, hipStream_t st)
 {
-    const int nw = m->K_max <= 1024 ? 16 : m->K_max <= 2048 ? 8 : m->K_max <= 4096 ? 4 : 2;
-    size_t lds = (size_t)(m->K_max + 2) * 4 + (size_t)nw * m->K_max * 4 + (size_t)SORT_KEYS_LDS * 2;
+    const int nw = sort_nw(m->K_max);
+    size_t lds = (size_t)(m->K_max + 2) * 4 + (size_t)nw * m->K_max * 4 + (size_t)sort_keys_cap(m->K_max) * 2;
     if (lds < 2048 * sizeof(double)) lds = 2048 * sizeof(double);
     SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_batch_sort, lds));
     segk_tstamp_bind();

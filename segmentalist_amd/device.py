@@ -1036,7 +1036,16 @@ class DeviceFbgmm(object):
         check(self._L.segk_fbgmm_record_metrics(self._ctx, self._cp(), C.byref(self.f), 1 if urn else 0, float(urn_a),
                                                 ptr(self._metric_out), _abi.stream()))
         o = self._metric_out.cpu().numpy()
-        return float(o[0]), float(o[1]), int(o[2]), int(o[3])
+        lpx = float(o[1])
+        if self.cov_type == 0 and self.corpus.D == 1:
+            # numpy reduces an (n, 1) matrix along axis 0 as a contiguous vector, pairwise, where the kernel adds row after
+            # row (8e-7 apart in float32, against 1e-8 for record values): D = 1 is no workload, the host expression answers
+            comp = self._components() if getattr(self, "_components", None) is not None else None
+            if comp is None:
+                raise SegkError("record_metrics at D = 1 evaluates the components' host expression: build the model through "
+                                "GaussianComponentsFixedVar")
+            lpx = float(comp.log_marg())
+        return float(o[0]), lpx, int(o[2]), int(o[3])
 
     def check_status(self):
         st = int(self.status[0].item())
