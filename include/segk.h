@@ -72,7 +72,9 @@ const char *segk_last_error(void);
  *  15 (no bump) segk_fbi_assign_diag32: segk_fbi_assign for diagonal components with the Student-t terms in float32.  As for
  *     segk_fbt_assign: one entry point added, no signature or structure changed (it reads the centre / tab32 fields of 9)
  *  15 (no bump) segk_fbt_assign_diag32: segk_fbt_assign for diagonal components with the Student-t terms in float32 (the
- *     token axis of segk_fbi_assign_diag32).  Again one entry point added, no signature or structure changed              */
+ *     token axis of segk_fbi_assign_diag32).  Again one entry point added, no signature or structure changed
+ *  15 (no bump) segk_fbi_assign_orphans: the orphan pass of FBGMM.set_K(..., sync="batch").  One entry point added, no
+ *     signature or structure changed                                                                                       */
 #define SEGK_ABI_VERSION 15
 int32_t segk_abi_version(void);
 
@@ -956,6 +958,28 @@ int32_t segk_fbt_assign_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_f
                                int32_t s_lo, int32_t s_n, int32_t b, const int32_t *n_utts, const int32_t *tok_cap,
                                uint64_t sweep, double anneal_temp, const int32_t *new_tok, const int32_t *n_new,
                                double *probe_ll, int64_t probe_ld, void *stream);
+/* The orphan pass of FBGMM.set_K(K, sync="batch") (added at ABI 15 without a bump; it replaces fbgmm.py:174-180, the loop that
+ * re-homes, one gibbs_sample_inside_loop_i after the other, every item whose component went when the bank was cut to its K
+ * largest; specification tests/fbgmm_set_k.py).  The arguments and the corpus of items are segk_fbi_assign's.  This call is the
+ * item half of step b of the pass, after segk_fbb_prepare(-1) -- the statistics of every item that holds a slot, in all blocks: an
+ * orphan holds none, so nothing is left out -- and before segk_fbb_partials(b): every ORPHAN i of block b of the local slices
+ * [s_lo, s_lo + s_n) -- was[i] >= 0 and bt->slot[i] < 0 -- forms segk_fbi_assign's logits at temperature 1 and draws its slot on
+ * u01(bt->seed, sweep, i, 1): the likelihood bits and the draw segk_fbi_assign would give item i on the same statistics.
+ * bt->slot[i] and n_new[i] = 1 are written; every other item is left alone (an item with was[i] < 0 keeps -1).
+ * was [dev] int32 [n_emb]: the assignments before the cut (any value >= 0: the item was assigned).
+ * A first kernel (one workgroup per local slice, an ordered scan, no atomics) compacts the ids of the cell's orphans, in index
+ * order, into the workspace of segk_fbt_assign and marks their n_new; the tile kernel of segk_fbi_assign then takes 64 listed
+ * items per workgroup against all slots, the rows gathered through the list.  Nothing is read back: n_items [host] [s_n] (the
+ * cell's items, an upper bound on its orphans) sizes the grid, and a tile beyond the device-side count returns at once.  With
+ * cov_type 2 the token-likelihood kernel of segk_fbb_assign runs over the block's items that n_new names (the orphans and the
+ * items that kept their slot), the tile kernel draws for the listed ones.  The likelihoods are fp64 whatever bt->tab32 holds.
+ * The logits in LDS or the bounded workspace of segk_fbi_assign (SEGK_FBI_Z_MIB).  A language model (f->lm_unigram) and the
+ * cov_type 2 limits are SEGK_ERR_UNSUPPORTED, a corpus with span tables or D > 256 SEGK_ERR_ARG, all before any launch.
+ * probe_ll as for segk_fbi_assign, the rows of the listed items only.                                                          */
+int32_t segk_fbi_assign_orphans(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt,
+                                int32_t s_lo, int32_t s_n, int32_t b, const int32_t *n_items, uint64_t sweep,
+                                const int32_t *was, const int32_t *new_tok, int32_t *n_new, double *probe_ll,
+                                int64_t probe_ld, void *stream);
 /* bigram table += sign * (transcripts of block b, all slices) from bt->lm_tok                  */
 int32_t segk_fbb_lm_apply(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f,
                           const segk_fbatch *bt, int32_t b, int32_t sign, void *stream);

@@ -152,6 +152,7 @@ SIGNATURES = {
     "segk_fbb_set_probe": (_i32, [_P, _P, _P, _i64]),
     "segk_fbi_assign": (_i32, [_P, _CP, _FP, _BP, _i32, _i32, _i32, _P, _u64, _f64, _i32, _P, _P, _P, _i64, _P]),
     "segk_fbi_assign_diag32": (_i32, [_P, _CP, _FP, _BP, _i32, _i32, _i32, _P, _u64, _f64, _i32, _P, _P, _P, _i64, _P]),
+    "segk_fbi_assign_orphans": (_i32, [_P, _CP, _FP, _BP, _i32, _i32, _i32, _P, _u64, _P, _P, _P, _P, _i64, _P]),
     "segk_fbt_assign": (_i32, [_P, _CP, _FP, _BP, _i32, _i32, _i32, _P, _P, _u64, _f64, _P, _P, _P, _i64, _P]),
     "segk_fbt_assign_diag32": (_i32, [_P, _CP, _FP, _BP, _i32, _i32, _i32, _P, _P, _u64, _f64, _P, _P, _P, _i64, _P]),
     "segk_fbb_lm_apply": (_i32, [_P, _CP, _FP, _BP, _i32, _i32, _P]),

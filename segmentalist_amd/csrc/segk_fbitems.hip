@@ -30,6 +30,16 @@
 //                           tile that begins at or beyond the list's length returns at once.
 //   k_fbi_assign_diag32<.., true>  the same axis on the float32 form (segk_fbt_assign_diag32: the inner sweeps of
 //                           am_sweep(..., score_precision="f32"), diagonal components; tests/am_batch_f32.py)
+// And it serves the ORPHAN pass of FBGMM.set_K(..., sync="batch") (segk_fbi_assign_orphans; fbgmm.py:174-180 as one blocked
+// pass; specification tests/fbgmm_set_k.py): the items that lost their component when the bank was cut to its K largest are
+// few and scattered, so they are listed like tokens.
+//
+//   k_fbi_orphans           one workgroup per local slice: an ordered scan over the cell's items writes the ids of its orphans
+//                           (was[i] >= 0, slot[i] < 0), in index order, into the token lists' workspace as (row i, utterance i,
+//                           position 0) and marks n_new[i] = 1 -- the item holds a slot once the tile kernel has run
+//   k_fbi_assign<.., true>  as for tokens: with N_max = 1 the draw of entry (i, 0) uses u01(seed, sweep, i, 1), the uniform of
+//                           k_fbi_assign<.., false> for item i, and with cov_type 2 its row of k_fcb_token_ll's table is item
+//                           i's.  Always the fp64 likelihoods (bt.mean_t / q_t), also on a sweeper of float32 scores.
 // No grid barrier, no spin loop, no cooperative launch, no atomics: a plain grid over the tiles.
 #include "segk_fb_common.h"
 #include "segk_fbb_dev.h"
@@ -83,6 +93,42 @@ __global__ __launch_bounds__(FBT_NT) void k_fbt_compact(segk_corpus c, segk_fbat
             L.row[o0 + j] = new_tok[(int64_t)utt * NM + t];
             L.utt[o0 + j] = utt;
             L.pos[o0 + j] = t;
+        }
+        base += sc[FBT_NT - 1];
+        __syncthreads();
+    }
+    if (tid == 0) L.count[s] = base < cap ? base : cap;
+}
+
+// The orphans of block b of the local slices, listed for k_fbi_assign<.., true>: item i of the cell with was[i] >= 0 (it held a
+// component before FBGMM.set_K cut the bank) and bt.slot[i] < 0 (its component went).  k_fbt_compact's scan with one entry per
+// orphan: row = utterance = i, position 0.  n_new[i] = 1 is written here: the tile kernel gives every listed item a slot, and with
+// cov_type 2 k_fcb_token_ll evaluates the items n_new names.
+__global__ __launch_bounds__(FBT_NT) void k_fbi_orphans(segk_corpus c, segk_fbatch bt, FbtList L, int s_lo, int b, const int32_t *was,
+                                                       int32_t *n_new)
+{
+    __shared__ int sc[FBT_NT];
+    const int s = blockIdx.x, slice = s_lo + s, tid = threadIdx.x;
+    const int u0 = bt.utt_range[(slice * bt.n_blocks + b) * 2], u1 = bt.utt_range[(slice * bt.n_blocks + b) * 2 + 1];
+    const int o0 = L.off[s], cap = L.off[s + 1] - o0;
+    int base = 0;                                           // orphans among the items before this pass (uniform)
+    for (int c0 = u0; c0 < u1; c0 += FBT_NT) {
+        const int i = c0 + tid;
+        const int n = i < u1 && i >= 0 && i < c.n_emb && was[i] >= 0 && bt.slot[i] < 0 ? 1 : 0;
+        sc[tid] = n;
+        __syncthreads();
+        for (int o = 1; o < FBT_NT; o <<= 1) {              // inclusive scan, index order
+            const int v = tid >= o ? sc[tid - o] : 0;
+            __syncthreads();
+            sc[tid] += v;
+            __syncthreads();
+        }
+        const int j = base + sc[tid] - n;
+        if (n && j < cap) {                                 // (always: cap counts the cell's items)
+            L.row[o0 + j] = i;
+            L.utt[o0 + j] = i;
+            L.pos[o0 + j] = 0;
+            n_new[i] = 1;
         }
         base += sc[FBT_NT - 1];
         __syncthreads();
@@ -536,10 +582,11 @@ static int fbi_item_map(const int32_t *n_items, int32_t s_lo, int32_t s_n, FbbMa
     return SEGK_OK;
 }
 
-// the token lists of block b: the tiles mapped to workgroups from the host's bounds, the workspace, k_fbt_compact
+// the token lists of block b: the tiles mapped to workgroups from the host's bounds, the workspace, k_fbt_compact -- or, with
+// `was` (segk_fbi_assign_orphans), k_fbi_orphans: the lists of the block's orphans, n_new marked
 static int32_t fbt_lists(segk_ctx *ctx, const segk_corpus *c, const segk_fbatch *bt, int32_t s_lo, int32_t s_n, int32_t b,
-                         const int32_t *n_utts, const int32_t *tok_cap, const int32_t *new_tok, const int32_t *n_new, FbbMap *mp,
-                         FbtList *Lp, void *stream)
+                         const int32_t *n_utts, const int32_t *tok_cap, const int32_t *new_tok, int32_t *n_new, FbbMap *mp,
+                         FbtList *Lp, void *stream, const int32_t *was = nullptr)
 {
     FbbMap &m = *mp;
     FbtList &L = *Lp;
@@ -561,7 +608,10 @@ static int32_t fbt_lists(segk_ctx *ctx, const segk_corpus *c, const segk_fbatch 
     L.row = ctx->fbt_tok + 16;
     L.utt = L.row + cap;
     L.pos = L.utt + cap;
-    hipLaunchKernelGGL(k_fbt_compact, dim3((unsigned)s_n), dim3(FBT_NT), 0, (hipStream_t)stream, *c, *bt, L, s_lo, b, new_tok, n_new);
+    if (was)
+        hipLaunchKernelGGL(k_fbi_orphans, dim3((unsigned)s_n), dim3(FBT_NT), 0, (hipStream_t)stream, *c, *bt, L, s_lo, b, was, n_new);
+    else
+        hipLaunchKernelGGL(k_fbt_compact, dim3((unsigned)s_n), dim3(FBT_NT), 0, (hipStream_t)stream, *c, *bt, L, s_lo, b, new_tok, n_new);
     SEGK_LAUNCH_CHECK();
     return SEGK_OK;
 }
@@ -616,6 +666,26 @@ int32_t segk_fbi_assign_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_f
     return fbi32_launch(ctx, c, f, bt, m, s_n, b, sweep, anneal_temp, consider_unassigned, n_new, probe_ll, probe_ld, nullptr, stream);
 }
 
+int32_t segk_fbi_assign_orphans(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,
+                                int32_t s_n, int32_t b, const int32_t *n_items, uint64_t sweep, const int32_t *was,
+                                const int32_t *new_tok, int32_t *n_new, double *probe_ll, int64_t probe_ld, void *stream)
+{
+    SEGK_REQUIRE(ctx && c && f && bt && n_items && was && new_tok && n_new, "NULL argument");
+    if (f->lm_unigram) {
+        segk_set_error("segk_fbi_assign_orphans: the stand-alone mixture model takes no language model");
+        return SEGK_ERR_UNSUPPORTED;
+    }
+    SEGK_REQUIRE(!c->vec_ids && !c->band_ids && c->N_max == 1 && c->n_utt == c->n_emb,
+                 "a corpus of items: one one-landmark utterance per row, no span tables");
+    if (int rc = fbi_check(c, f, bt, s_lo, s_n, b, probe_ll, probe_ld, "segk_fbi_assign_orphans")) return rc;
+    // the cell's items bound its orphans: the lists and the grid are sized from them, a tile beyond the count returns at once
+    FbbMap m;
+    FbtList L = {};
+    if (int rc = fbt_lists(ctx, c, bt, s_lo, s_n, b, n_items, n_items, new_tok, n_new, &m, &L, stream, was)) return rc;
+    if (m.off[s_n] == 0) return SEGK_OK;
+    return fbi_launch(ctx, c, f, bt, m, s_lo, s_n, b, n_items, 0, sweep, 1.0, 0, new_tok, n_new, probe_ll, probe_ld, &L, stream);
+}
+
 int32_t segk_fbt_assign(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,
                         int32_t s_n, int32_t b, const int32_t *n_utts, const int32_t *tok_cap, uint64_t sweep, double anneal_temp,
                         const int32_t *new_tok, const int32_t *n_new, double *probe_ll, int64_t probe_ld, void *stream)
@@ -631,7 +701,7 @@ int32_t segk_fbt_assign(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f
     if (int rc = fbi_check(c, f, bt, s_lo, s_n, b, probe_ll, probe_ld, "segk_fbt_assign")) return rc;
     FbbMap m;
     FbtList L = {};
-    if (int rc = fbt_lists(ctx, c, bt, s_lo, s_n, b, n_utts, tok_cap, new_tok, n_new, &m, &L, stream)) return rc;
+    if (int rc = fbt_lists(ctx, c, bt, s_lo, s_n, b, n_utts, tok_cap, new_tok, const_cast<int32_t *>(n_new), &m, &L, stream)) return rc;
     if (m.off[s_n] == 0) return SEGK_OK;
     return fbi_launch(ctx, c, f, bt, m, s_lo, s_n, b, n_utts, 0, sweep, anneal_temp, 0, new_tok, const_cast<int32_t *>(n_new), probe_ll,
                       probe_ld, &L, stream);
@@ -660,7 +730,7 @@ int32_t segk_fbt_assign_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_f
     if (int rc = fbi_check(c, f, bt, s_lo, s_n, b, probe_ll, probe_ld, "segk_fbt_assign_diag32")) return rc;
     FbbMap m;
     FbtList L = {};
-    if (int rc = fbt_lists(ctx, c, bt, s_lo, s_n, b, n_utts, tok_cap, new_tok, n_new, &m, &L, stream)) return rc;
+    if (int rc = fbt_lists(ctx, c, bt, s_lo, s_n, b, n_utts, tok_cap, new_tok, const_cast<int32_t *>(n_new), &m, &L, stream)) return rc;
     if (m.off[s_n] == 0) return SEGK_OK;
     return fbi32_launch(ctx, c, f, bt, m, s_n, b, sweep, anneal_temp, 0, const_cast<int32_t *>(n_new), probe_ll, probe_ld, &L, stream);
 }

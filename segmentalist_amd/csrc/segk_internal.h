@@ -74,6 +74,7 @@ struct segk_ctx {
     int64_t fbi_z_n;             // ... a tile's do not fit in LDS; doubles allocated (bounded: segk_fbitems.hip FBI_Z_MIB)
     int32_t *fbt_tok;            // token step of the segmenter's acoustic-model batch sweep (k_fbt_compact): [16] tokens per local slice,
     int64_t fbt_tok_n;           // ... then [3][cap] (row, utterance, position) of the block's tokens; cap = int32 words per list
+                                 // (k_fbi_orphans, the orphan pass of FBGMM.set_K: the same layout, an entry (i, i, 0) per orphan)
     // hinted score path (segk_score_hint.hip): the filter's partial top-2 per (range, row), then the hint waves' result per row
     void *hint_part;
     size_t hint_part_bytes;

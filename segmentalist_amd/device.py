@@ -1646,6 +1646,27 @@ class FbgmmItemSweeper(object):
             check(L.segk_fbb_partials(ctx, cp, fp, bp, 0, self.S, b, ptr(self.new_tok), ptr(self.n_new), st))
         self.sweep_index += 1
 
+    def reassign_orphans(self, was_assigned):
+        """The orphan pass of FBGMM.set_K(..., sync="batch") (specification tests/fbgmm_set_k.py), enqueued on the current
+        stream: per block b the statistics of every item that holds a slot (segk_fbb_prepare(-1)), a draw at temperature 1 for
+        every item of the block that holds none but did before the cut (`was_assigned`: the old assignments, >= 0 where the
+        item was assigned), segk_fbb_partials(b) -- the orphans of later blocks see those placed in earlier ones.  Always the
+        fp64 likelihoods.  The pass takes one value of the sweep counter."""
+        if not self.in_batch_state:
+            self.enter()
+        was = to_dev(np.asarray(was_assigned), np.int32)
+        assert was.numel() == self.N
+        L, ctx, cp, fp, bp, st = self._args()
+        pl = self.probe_ll
+        for b in range(self.B):
+            check(L.segk_fbb_prepare(ctx, cp, fp, bp, -1, st))
+            check(L.segk_fbi_assign_orphans(ctx, cp, fp, bp, 0, self.S, b, self._n_items[b], self.sweep_index, ptr(was),
+                                            ptr(self.new_tok), ptr(self.n_new), ptr(pl), pl.shape[1] if pl is not None else 0,
+                                            st))
+            check(L.segk_fbb_partials(ctx, cp, fp, bp, 0, self.S, b, ptr(self.new_tok), ptr(self.n_new), st))
+        self._was = was                                   # (kept alive: the pass is only enqueued)
+        self.sweep_index += 1
+
     cell_partials = FbgmmBatchSweeper.cell_partials
 
     def totals(self):

@@ -52,6 +52,7 @@ class FBGMM(object):
         """fbgmm.py:93-137."""
         self._leave_batch()
         self._sweeper = None                # (bound to the components it was built from)
+        self._sweep_index = 0               # the counter a new sweeper starts from (set_K carries the old one over)
         if X is None:
             assert hasattr(self, "components")
             X = self.components.X
@@ -74,6 +75,65 @@ class FBGMM(object):
         else:
             assert False, "Invalid covariance type."
 
+    def set_K(self, K, reassign=True, sync=None):
+        """fbgmm.py:139-180: keep the `K` largest components -- the kept component at rank r of the ascending order of the
+        counts gets label r --, rebuild the bank with K_max = K (`setup_components`), and with `reassign` re-home every
+        orphan: an item that was assigned and whose component went.
+
+        sync: None = the mode the object was built with.  "sequential" is the reference's form, draw for draw: the orphans
+        in index order through gibbs_sample_inside_loop_i at temperature 1, one random.random() each (one call of the serial
+        item kernel over the orphan list).  "batch": the same ranking, relabelling and rebuild, then ONE blocked pass over
+        the orphans (specification tests/fbgmm_set_k.py): per block the statistics of every item that holds a slot, a draw
+        for each of the block's orphans from the counter-based stream of batch_seed, the orphans of later blocks seeing
+        those placed in earlier ones; no random.random() is consumed, the likelihoods are fp64 whatever score_precision,
+        the sweep counter goes on from where it stood, and the model is left in batch state (materialise() brings
+        `components` up to date, as after batch_sweep_async()).
+
+        Ties: the ranking is np.argsort(counts, kind="stable") on all K_max counts (zeros for the inactive components).
+        The reference sorts with NumPy's default kind, which is not stable: among components of equal size its choice
+        depends on the NumPy build and the CPU's vector extensions.  With pairwise distinct counts the two agree.
+
+        `components.K <= K`: the reference only overwrites the attribute K_max; its arrays keep their old length and its own
+        gibbs_sample then fails on the mismatch.  Here the bank is rebuilt at the new size from the current assignments: K,
+        counts, assignments and statistics unchanged, K_max = K -- the model equals FBGMM(X, prior, alpha, K,
+        assignments=current).  No uniform is consumed.
+
+        Refused on the acoustic model of a segmenter: the segmenter holds the device object that the rebuild replaces."""
+        assert sync in (None, "sequential", "batch")
+        sync = self.sync if sync is None else sync
+        K = int(K)
+        if self.components.dev.corpus.n_utt:
+            raise SegkError("set_K: this mixture model is the acoustic model of a segmenter (its corpus carries utterances); "
+                            "the segmenter holds the device object that setup_components would replace")
+        if K < 1:
+            raise SegkError("set_K takes K >= 1, got %d" % K)
+        sweep_index = 0 if self._sweeper is None else self._sweeper.sweep_index
+        if sync == "batch":
+            self._get_sweeper()             # (the refusals, before anything runs)
+        self._leave_batch()                 # (materialise(): the reference's view is what is ranked)
+        c = self.components
+        old = c.assignments
+        if c.K <= K:
+            new = old
+        else:
+            keep = np.argsort(c.counts, kind="stable")[-K:]
+            table = np.full(c.K_max + 1, -1, dtype=np.int64)            # (the last entry serves the label -1)
+            table[keep] = np.arange(K)
+            new = table[old]
+        self.setup_components(K, new)
+        self._sweep_index = sweep_index
+        orphans = np.flatnonzero((old != -1) & (new == -1))
+        if sync == "batch":
+            sw = self._get_sweeper()
+            sw.enter()
+            if reassign and len(orphans):
+                sw.reassign_orphans(old)
+        elif reassign and len(orphans):
+            dev = self.components.dev
+            used = dev.gibbs_items([random.random() for _ in orphans], True, 1, ids=orphans)
+            dev.check_status()
+            assert used == len(orphans)
+
     # record metrics (host, from device snapshots) ------------------------------------------------
     def log_prob_z(self):
         """fbgmm.py:208-225."""
@@ -94,6 +154,7 @@ class FBGMM(object):
             from .device import FbgmmItemSweeper
             B, S, seed = self._batch_args
             self._sweeper = FbgmmItemSweeper(self.components.dev, B, S, seed, score_precision=self.score_precision)
+            self._sweeper.sweep_index = self._sweep_index
         return self._sweeper
 
     def batch_sweep_async(self, anneal_temp=1, consider_unassigned=True):
