@@ -41,7 +41,8 @@
 //       (packed into leading tiles), and the merge certifies against base U delta, a superset as above.  See k_delta_prep.
 //       K1 is ONE launch either way: it reads the mode word k_delta_prep left and takes the full or the delta parameter set
 //       (HintArgs), with the larger of the two grids and LDS sizes.  The hint waves decide which positions take their score
-//       over from the previous call for a chunk of steps per round trip (hint_wave_rows).
+//       over from the previous call for a chunk of steps per round trip, and score the others -- the rows of the means that
+//       moved -- 32 at a time in dense bodies, whichever steps they come from (hint_wave_rows).
 //
 //   Carry-over of a row's winner across the unchanged means (k_hint_merge in delta mode).  The certificate above cannot decide
 //       a near-tie row -- its runner-up sits in the base within tau, sweep after sweep -- and the band stage then finds the
@@ -219,9 +220,11 @@ __device__ __forceinline__ void hint_wave_rows(const HintArgs &H, const int32_t 
         const int64_t p_ = s_ * 32 + row;
         return p_ < H.n ? (H.ids ? H.ids[p_] : (int32_t)(H.row0 + p_)) : -1;
     };
-    // one step: the hinted component `hint` (-1: none) of row rid_c (-1: no row) scored and stored unless `skip`; `mid` runs
-    // between the step's loads and its arithmetic (the serial loop's prefetch of the next step)
-    auto step_body = [&](int64_t s, int32_t rid_c, int32_t hint, bool skip, auto &&mid) {
+    // one body: 32 positions, one per lane pair.  The hinted component `hint` (-1: none) of row rid_c (-1: no row) scored and
+    // stored at position p unless `skip`; position, row and hint are the lane's own (a step of 32 consecutive rows in the serial
+    // loop, 32 entries of the pending list in the delta score pass).  `mid` runs between the body's loads and its arithmetic
+    // (the serial loop's prefetch of the next step)
+    auto step_body = [&](int64_t p, int32_t rid_c, int32_t hint, bool skip, auto &&mid) {
         f32x4_t xv[NX], mv[NX];
 #pragma unroll
         for (int b = 0; b < NX; b++) { xv[b] = f32x4_t{0.f, 0.f, 0.f, 0.f}; mv[b] = xv[b]; }
@@ -262,7 +265,6 @@ __device__ __forceinline__ void hint_wave_rows(const HintArgs &H, const int32_t 
             if (rem > 3) res += th.y;
         }
         const float sc = -res;                                     // -|x - m_h|^2
-        const int64_t p = s * 32 + row;
         if (h == 0 && p < H.n && !skip) H.hint_out[p] = make_float4(sc, 0.5f * (sc - nx), __int_as_float(rid_c >= 0 ? hint : -1), 0.f);
     };
     int n_skipped = 0;
@@ -272,11 +274,23 @@ __device__ __forceinline__ void hint_wave_rows(const HintArgs &H, const int32_t 
         // no mean, no store.  Once the chain has settled that is nearly every position, and a step that waits for its labels
         // only to find nothing to do is a bare round trip (32 of them in a row per wave on the headline corpus).  So the test is
         // taken for a CHUNK of the wave's steps at once, one lane per position and SEGK_HINT_CHUNK / 2 positions per lane, all
-        // its loads in flight together; only steps with a position that is not skipped run the body, their labels handed over
-        // by shuffles.
+        // its loads in flight together.
+        //
+        // Dense bodies.  The positions that are NOT skipped (the live ones) are the rows of the means that moved, scattered over
+        // the corpus: with 5 % of them live, four steps in five have one or two, and a body per such step is a dependent round
+        // trip with one or two of its 32 row slots in use.  So the live positions of a chunk go onto a pending list in a fixed
+        // order (step by step, row by row: the chunk's order), and a body runs whenever 32 are pending, and once more at the end
+        // of the wave's steps.  The list is not stored anywhere: entry j of a chunk is the j-th set bit of the chunk's ballots,
+        // a lane pair finds the lane that holds it (sel_bit) and pulls row and hint from it (ds_bpermute); the fewer than 32
+        // entries left over at a chunk's end stay in the lane pairs' registers (c_*).  Registers, not LDS: the LDS behind the
+        // label map is what the tile plan (segk_hint_plan) and the delta launch's tile cap are sized from, and a list there
+        // (4 waves x 287 entries, 14 KB) would move both for every table -- this way no launch's plan changes.  The next chunk's
+        // loads are issued in front of the current chunk's bodies, so the test's round trip is not between bodies.  (Two bodies
+        // in flight -- the next body's rows loaded under this one's arithmetic -- would need a second row and mean set, 104 more
+        // registers at D = 100: above the kernel's budget, left out.)  A position is written only by the wave that owns its step.
         constexpr int CH = SEGK_HINT_CHUNK, PPL = CH / 2;
         const int crow = lane & 31, chalf = lane >> 5;             // the test's lane: position crow of the chunk's step 2 u + chalf
-        auto chunk_load = [&](int64_t s0, int32_t (&rd)[PPL], int32_t (&kp)[PPL], int32_t (&pzv)[PPL]) {
+        auto chunk_load = [&](int64_t s0, int32_t (&rd)[PPL], int32_t (&kp)[PPL], int32_t (&pzv)[PPL]) __attribute__((always_inline)) {
 #pragma unroll
             for (int u = 0; u < PPL; u++) {
                 const int64_t s_ = s0 + (int64_t)(2 * u + chalf) * n_w, p_ = s_ * 32 + crow;
@@ -287,44 +301,97 @@ __device__ __forceinline__ void hint_wave_rows(const HintArgs &H, const int32_t 
 #pragma unroll
             for (int u = 0; u < PPL; u++) kp[u] = rd[u] >= 0 ? H.cand_k[rd[u]] : -1;
         };
-        for (int64_t s0 = w; s0 < n_steps; s0 += (int64_t)CH * n_w) {
-            int32_t rd[PPL], hv[PPL];                              // per position: row, hint (| SEGK_MEANCHG_BIT here: skipped)
-            unsigned long long live[PPL];
-            {
-                int32_t kp[PPL], pzv[PPL];
-                chunk_load(s0, rd, kp, pzv);
+        // the n-th set bit (0 .. 31) of w_, n_ < popcount(w_) (anything in 0 .. 31 otherwise)
+        auto sel_bit = [](unsigned w_, int n_) __attribute__((always_inline)) -> int {
+            int base = 0;
 #pragma unroll
-                for (int u = 0; u < PPL; u++) {
-                    const int64_t s_ = s0 + (int64_t)(2 * u + chalf) * n_w;
-                    const bool in = s_ < n_steps && s_ * 32 + crow < H.n;
-                    int32_t hint = (rd[u] >= 0 && kp[u] >= 0 && kp[u] < H.K_max) ? map[kp[u]] : -1;
-                    const bool mchg = hint >= 0 && (hint & SEGK_MEANCHG_BIT) != 0;
-                    if (hint >= 0) hint &= ~SEGK_MEANCHG_BIT;
-                    const bool skip = rd[u] >= 0 && hint >= 0 && !mchg && pzv[u] == hint;
-                    hv[u] = skip ? (hint | SEGK_MEANCHG_BIT) : hint;
-                    live[u] = __ballot(in && !skip);
-                    n_skipped += __popcll(__ballot(skip));
-                }
+            for (int sh = 16; sh >= 1; sh >>= 1) {
+                const int t = __popc(w_ & ((1u << sh) - 1u));
+                const bool up = n_ >= t;
+                w_ = up ? w_ >> sh : w_;
+                base += up ? sh : 0;
+                n_ -= up ? t : 0;
             }
-#pragma unroll 1
-            for (int i = 0; i < CH; i++) {
-                const int64_t s_ = s0 + (int64_t)i * n_w;
-                if (s_ >= n_steps) break;
-                int32_t rd_s = rd[0], hv_s = hv[0];
-                unsigned long long lv = live[0];
+            return base & 31;
+        };
+        int c_n = 0;                                               // entries carried over from the chunks before: 0 .. 31
+        int64_t c_p = 0;                                           // ... lane pair `row` holds entry `row`: position, row, hint
+        int32_t c_rid = -1, c_hint = -1;
+        int32_t rd_n[PPL], kp_n[PPL], pz_n[PPL];                   // the loads of the chunk ahead
+        chunk_load(w, rd_n, kp_n, pz_n);
+        for (int64_t s0 = w; s0 < n_steps; s0 += (int64_t)CH * n_w) {
+            int32_t rd[PPL], hv[PPL];                              // per position of the chunk: row, hint
+            unsigned long long live[PPL];
+            int pre[PPL + 1];                                      // live positions in front of part u of the chunk
+            pre[0] = 0;
 #pragma unroll
-                for (int u = 1; u < PPL; u++)
-                    if ((i >> 1) == u) { rd_s = rd[u]; hv_s = hv[u]; lv = live[u]; }
-                const int sh = 32 * (i & 1);
-                if ((unsigned)(lv >> sh) == 0u) continue;           // every position of the step skipped (or beyond the rows)
-                const int src = sh + row;
-                const int32_t rid_c = __shfl(rd_s, src);
-                int32_t hint = __shfl(hv_s, src);
-                const bool skip = hint >= 0 && (hint & SEGK_MEANCHG_BIT) != 0;
+            for (int u = 0; u < PPL; u++) {
+                const int64_t s_ = s0 + (int64_t)(2 * u + chalf) * n_w;
+                const bool in = s_ < n_steps && s_ * 32 + crow < H.n;
+                rd[u] = rd_n[u];
+                int32_t hint = (rd[u] >= 0 && kp_n[u] >= 0 && kp_n[u] < H.K_max) ? map[kp_n[u]] : -1;
+                const bool mchg = hint >= 0 && (hint & SEGK_MEANCHG_BIT) != 0;
                 if (hint >= 0) hint &= ~SEGK_MEANCHG_BIT;
-                step_body(s_, rid_c, rid_c >= 0 ? hint : -1, skip, [] {});
+                const bool skip = rd[u] >= 0 && hint >= 0 && !mchg && pz_n[u] == hint;
+                hv[u] = hint;
+                live[u] = __ballot(in && !skip);
+                pre[u + 1] = pre[u] + __popcll(live[u]);
+                n_skipped += __popcll(__ballot(skip));
+            }
+            const int64_t s1 = s0 + (int64_t)CH * n_w;
+            chunk_load(s1, rd_n, kp_n, pz_n);                     // (beyond the last step: no load, every lane masks its own)
+            if (pre[PPL] == 0) continue;                           // nothing new: the carried entries wait on
+            const int total = c_n + pre[PPL];
+            // entry g0 + row of the list (the carried entries, then the chunk's) for this lane pair; false: beyond the list
+            // (step i of the chunk is word i of the ballots -- the low half of live[i / 2] for an even i, the high half for an odd
+            // one -- and `at` the entries in front of it.  Every choice below is a chain of selects on thresholds of j_:
+            // written as "the u-th of an array" the compiler puts the array into scratch and indexes it per lane.)
+            auto fetch = [&](int g0, int64_t &p_e, int32_t &rid_e, int32_t &hint_e) __attribute__((always_inline)) -> bool {
+                const int g_ = g0 + row, j_ = g_ - c_n;
+                unsigned w_ = (unsigned)live[0];
+                int i_ = 0, jj = j_;
+#pragma unroll
+                for (int i = 1; i < CH; i++) {
+                    const int at = (i & 1) ? pre[i >> 1] + __popc((unsigned)live[i >> 1]) : pre[i >> 1];
+                    const unsigned wi = (i & 1) ? (unsigned)(live[i >> 1] >> 32) : (unsigned)live[i >> 1];
+                    const bool up = j_ >= at;
+                    w_ = up ? wi : w_;
+                    i_ = up ? i : i_;
+                    jj = up ? j_ - at : jj;
+                }
+                const int src = 32 * (i_ & 1) + sel_bit(w_, jj);    // the test's lane that holds the entry
+                int32_t r_ = __shfl(rd[0], src), h_ = __shfl(hv[0], src);
+#pragma unroll
+                for (int u = 1; u < PPL; u++) {
+                    const int32_t ru = __shfl(rd[u], src), hu = __shfl(hv[u], src);
+                    const bool up = j_ >= pre[u];
+                    r_ = up ? ru : r_;
+                    h_ = up ? hu : h_;
+                }
+                const int64_t s_ = s0 + (int64_t)i_ * n_w;
+                const bool carried = j_ < 0;
+                p_e = carried ? c_p : s_ * 32 + (src & 31);
+                rid_e = carried ? c_rid : r_;
+                hint_e = carried ? c_hint : (r_ >= 0 ? h_ : -1);
+                return g_ < total;
+            };
+            int done = 0;
+#pragma unroll 1
+            for (; total - done >= 32; done += 32) {
+                int64_t p_e;
+                int32_t rid_e, hint_e;
+                fetch(done, p_e, rid_e, hint_e);
+                step_body(p_e, rid_e, hint_e, false, [] {});
+            }
+            {
+                int64_t p_e;
+                int32_t rid_e, hint_e;
+                const bool on = fetch(done, p_e, rid_e, hint_e);
+                c_p = p_e; c_rid = on ? rid_e : -1; c_hint = on ? hint_e : -1;
+                c_n = total - done;
             }
         }
+        if (c_n > 0) step_body(c_p, c_rid, c_hint, row >= c_n, [] {});
         if (n_skipped > 0 && lane == 0) atomicAdd(H.ctl + 3, n_skipped);
         return;
     }
@@ -340,7 +407,7 @@ __device__ __forceinline__ void hint_wave_rows(const HintArgs &H, const int32_t 
         int32_t hint = (rid >= 0 && kprev >= 0 && kprev < H.K_max) ? map[kprev] : -1;
         if (hint >= 0) hint &= ~SEGK_MEANCHG_BIT;
         // the next step's previous labels and the row ids of the step after it travel under this step's arithmetic
-        step_body(s, rid, hint, false, [&] {
+        step_body(s * 32 + row, rid, hint, false, [&] {
             rid = rid_n;
             kprev = rid >= 0 ? H.cand_k[rid] : -1;
             const int64_t s2 = s + 2 * n_w;

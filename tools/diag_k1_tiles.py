@@ -7,7 +7,13 @@ fresh base (the image exponent changes), then the first 32 (t - 1) + 1 means mov
 
 Prints per tile count the median, the minimum and the maximum call time in microseconds and the statistics of the timed call
 (mode, changed columns, packed tiles, skipped positions).  Under rocprofv3 --kernel-trace the K1 launches can be read off by
-their order."""
+their order.
+
+DIAG_MOVED=m1,m2,... adds a second axis: how many of the moved means HAVE rows.  The tile count follows the changed columns of the
+image, the hint waves' work the rows whose hinted mean moved (the live rows), and moving the first 32 (t - 1) + 1 means varies both
+together.  With DIAG_MOVED the last 32 max(t) components get no rows (idle means: moving one changes a column and no row's
+hint); a point (t, m), m <= 32, moves m of the first 32 means, m / (K - idle) of the rows live, and as many idle means as t packed
+tiles need beyond them.  Without it the tool is what it was."""
 import os
 import sys
 
@@ -23,8 +29,12 @@ def main():
     a = [int(v) for v in sys.argv[1:]]
     n, D, K, reps = (a + [1050000, 100, 1000, 5][len(a):])[:4]
     rs = np.random.RandomState(0)
+    tiles = [int(t) for t in os.environ.get("DIAG_TILES", "0,1,2,4,8,16").split(",")]
+    moved = [int(m) for m in os.environ["DIAG_MOVED"].split(",")] if os.environ.get("DIAG_MOVED") else None
+    idle = 32 * max(tiles) if moved else 0                      # components without rows, the last ones
+    assert moved is None or (max(moved) <= 32 and min(moved) >= 1 and 32 + idle < K), "DIAG_MOVED: 1 .. 32 means of tile 0"
     mu = rs.randn(K, D).astype(np.float32)
-    X = mu[rs.randint(0, K, n)] + np.float32(0.3) * rs.randn(n, D).astype(np.float32)
+    X = mu[rs.randint(0, K - idle, n)] + np.float32(0.3) * rs.randn(n, D).astype(np.float32)
     X /= np.linalg.norm(X, axis=1, keepdims=True)
     means = mu / np.linalg.norm(mu, axis=1, keepdims=True)
     np.random.seed(0)
@@ -46,10 +56,9 @@ def main():
         torch.cuda.synchronize()
         return ev[0].elapsed_time(ev[1]) * 1e3 if timed else 0.0
 
-    tiles = [int(t) for t in os.environ.get("DIAG_TILES", "0,1,2,4,8,16").split(",")]
     f = 4.0
     print("rows %d  D %d  K %d; microseconds per hinted call, median of %d" % (n, D, K, reps))
-    for t in tiles:
+    for t, mv in [(t, m) for t in tiles for m in (moved if moved and t > 0 else [None])]:
         us = []
         for _ in range(reps):
             means = means * np.float32(f)
@@ -58,11 +67,15 @@ def main():
             call(); call(); call()                              # the new base, then settled: every position skipped
             if t > 0:
                 m = means.copy()
-                m[:32 * (t - 1) + 1] *= np.float32(1.01)
+                if mv is None:
+                    m[:32 * (t - 1) + 1] *= np.float32(1.01)
+                else:
+                    m[:mv] *= np.float32(1.01)
+                    m[K - max(32 * (t - 1) + 1 - mv, 0):] *= np.float32(1.01)
                 write(m)
             us.append(call(timed=True))
             stats = d.delta_stats()
-        print("tiles %2d: median %7.1f  min %7.1f  max %7.1f   last call: %s" % (t, float(np.median(us)), min(us), max(us), (stats,)))
+        print("tiles %2d%s: median %7.1f  min %7.1f  max %7.1f   last call: %s" % (t, "" if mv is None else " moved %2d" % mv, float(np.median(us)), min(us), max(us), (stats,)))
     d.check_status()
 
 
