@@ -74,7 +74,10 @@ const char *segk_last_error(void);
  *  15 (no bump) segk_fbt_assign_diag32: segk_fbt_assign for diagonal components with the Student-t terms in float32 (the
  *     token axis of segk_fbi_assign_diag32).  Again one entry point added, no signature or structure changed
  *  15 (no bump) segk_fbi_assign_orphans: the orphan pass of FBGMM.set_K(..., sync="batch").  One entry point added, no
- *     signature or structure changed                                                                                       */
+ *     signature or structure changed
+ *  15 (no bump) segk_kmeans_batch_partials_keep + segk_kmeans_batch_keep_words: segk_kmeans_batch_partials with a caller-owned
+ *     buffer through which the sums of token lists that did not change since the previous call are kept.  Two entry points
+ *     added, no signature or structure changed                                                                             */
 #define SEGK_ABI_VERSION 15
 int32_t segk_abi_version(void);
 
@@ -405,6 +408,22 @@ int32_t segk_kmeans_batch_partials(segk_ctx *ctx, const segk_corpus *c, const se
                                    const double *out_total, int32_t *sorted_scratch,
                                    int32_t *koff_scratch, double *record, int32_t flag_cap, int32_t flag_rows,
                                    double *out_scalars, void *stream);
+/* segk_kmeans_batch_partials with `keep` [dev] int32 [keep_words >= segk_kmeans_batch_keep_words(K_max, n_blocks_local)], owned by
+ * the caller together with sorted_scratch, koff_scratch and record, zeroed when allocated and passed to every call on those
+ * three: a (block, component) list whose row ids are the ones the previous call left in sorted_scratch keeps its sum and count
+ * in the record (the sum is a function of the row ids alone), every other list is summed as before -- the record is the same bit
+ * for bit.  The kernel decides from a header per (block, component range) in `keep` that names the corpus, the shape and the
+ * three buffers, and from the lists themselves; there is no host-side state.  Per (block b, range r) the words
+ * keep[(b * NR + r) * 32 + 20 / 21] hold the lists kept / the non-empty lists summed again in the last call
+ * (NR = keep_words(K_max, 1) / 32).  keep = NULL: segk_kmeans_batch_partials.  SEGK_BATCH_KEEP=0 in the environment (read per
+ * call): nothing is kept.  Float64 data, odd D and D > 128 keep nothing. */
+int64_t segk_kmeans_batch_keep_words(int32_t K_max, int32_t n_blocks_local);
+int32_t segk_kmeans_batch_partials_keep(segk_ctx *ctx, const segk_corpus *c, const segk_kmeans *m,
+                                        const int32_t *blk_lo, int32_t n_blocks_local,
+                                        const int32_t *new_tok, const int32_t *new_k, const int32_t *n_flag,
+                                        const double *out_total, int32_t *sorted_scratch,
+                                        int32_t *koff_scratch, double *record, int32_t flag_cap, int32_t flag_rows,
+                                        double *out_scalars, void *stream, int32_t *keep, int64_t keep_words);
 int32_t segk_kmeans_batch_finalize(segk_ctx *ctx, const segk_corpus *c, segk_kmeans *m,
                                    int32_t utt_lo, int32_t utt_hi, const double *records,
                                    int32_t n_blocks_total, int32_t n_blocks_per_rank,

@@ -107,6 +107,8 @@ SIGNATURES = {
     "segk_kmeans_batch_record_words": (_i64, [_i32, _i32, _i32, _i32, _i32]),
     "segk_kmeans_batch_scratch_words": (_i32, [_i32, _i64, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
     "segk_kmeans_batch_partials": (_i32, [_P, _CP, _KP, _P, _i32, _P, _P, _P, _P, _P, _P, _P, _i32, _i32, _P, _P]),
+    "segk_kmeans_batch_partials_keep": (_i32, [_P, _CP, _KP, _P, _i32, _P, _P, _P, _P, _P, _P, _P, _i32, _i32, _P, _P, _P, _i64]),
+    "segk_kmeans_batch_keep_words": (_i64, [_i32, _i32]),
     "segk_kmeans_batch_finalize": (_i32, [_P, _CP, _KP, _i32, _i32, _P, _i32, _i32, _i64, _i32, _i32, _i32, _P, _P, _P, _P,
                                           _P]),
     "segk_kmeans_batch_record": (_i32, [_P, _CP, _KP, _i32, _i32, _P, _P, _P, _P, _P]),

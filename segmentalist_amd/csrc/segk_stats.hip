@@ -692,10 +692,52 @@ static inline __host__ __device__ int segk_sort_nsh(int K_max)
 }
 static inline __host__ __device__ int segk_sort_ranges(int K_max) { return 1 << segk_sort_nsh(K_max); }
 
+// ---- lists that stand keep their sums (segk_kmeans_batch_partials_keep).  A partial sum is a function of the list's
+// row ids alone (X never changes), so range workgroup (b, r) compares every new list with the one the previous call left in its
+// region and walks, in phase S, only the lists that differ; the sums and counts of the others already stand in the record.
+// `keep` holds one record of KEEP_REC words per (local block, range), read and written by that workgroup alone: a header that
+// names everything the region, koff2 and the record's sums were built from, and two counters (lists kept, non-empty lists
+// summed again in the last call).  Validity is decided here, on the device, from the header and the lists' contents.
+#define KEEP_MAGIC 0x6b656570
+#define KEEP_HDR 20                  /* header words */
+#define KEEP_REC 32                  /* words per (block, range): header, {kept, summed again}, padding to a 128-byte line */
+#ifndef KEEP_CAP
+#define KEEP_CAP 4096                /* leading entries of the region held in LDS for the compare (a multiple of SORT_THREADS); an old
+                                        list that ends behind them is summed again */
+#endif
+static_assert(KEEP_CAP % SORT_THREADS == 0 && KEEP_CAP / SORT_THREADS <= 4, "KEEP_CAP");
+static __device__ __forceinline__ int32_t keep_hdr_word(int i, const segk_corpus &c, int K_max, int u0, int u1, int NR, const void *sorted,
+                                                         const void *koff2, const void *part_sum, int live)
+{
+    const unsigned long long ax = (unsigned long long)c.X, as = (unsigned long long)sorted, ak = (unsigned long long)koff2,
+                             ap = (unsigned long long)part_sum;
+    switch (i) {
+    case 0: return live ? KEEP_MAGIC : 0;        // (a launch that keeps nothing and cannot vouch for the sums: 0)
+    case 1: return u0;
+    case 2: return u1;
+    case 3: return NR;
+    case 4: return c.D;
+    case 5: return (int32_t)c.ldx;
+    case 6: return (int32_t)c.n_emb;
+    case 7: return c.N_max;
+    case 8: return K_max;
+    case 9: return c.x_dtype;
+    case 10: return (int32_t)ax;
+    case 11: return (int32_t)(ax >> 32);
+    case 12: return (int32_t)as;
+    case 13: return (int32_t)(as >> 32);
+    case 14: return (int32_t)ak;
+    case 15: return (int32_t)(ak >> 32);
+    case 16: return (int32_t)ap;
+    case 17: return (int32_t)(ap >> 32);
+    default: return 0;
+    }
+}
+
 __global__ __launch_bounds__(SORT_THREADS) void k_batch_sort_sum(
     segk_corpus c, segk_kmeans m, const int32_t *blk_lo, int n_blocks, const int32_t *new_tok, const int32_t *new_k,
     const double *out_total, int32_t *sorted, int32_t *koff2, double *part_tot, int32_t *flags, int cap, double *out_scalars, int NR,
-    int rsh, int nsh, double *part_sum, int64_t *part_cnt, int fuse_sum)
+    int rsh, int nsh, double *part_sum, int64_t *part_cnt, int fuse_sum, int32_t *keep, int keep_mode)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char sort_lds[];
     __shared__ int32_t wcount[16], wscan[2];
@@ -749,6 +791,28 @@ __global__ __launch_bounds__(SORT_THREADS) void k_batch_sort_sum(
     const int s0 = wv * per < S ? wv * per : S, s1 = s0 + per < S ? s0 + per : S;
     auto in_range = [&](int k) -> bool { return flg ? k >= Kb : (k >= 0 && k < Kb && (k & (NR - 1)) == r); };
     for (int i = tid; i < 16 * RS; i += SORT_THREADS) cntw[i] = 0;
+    // ---- keep: this workgroup's record, the previous call's koff2 of its components and the head of its region as that call
+    // left it, requested beside the keys (nothing of P1 depends on them); the region's entries are in LDS before the barrier
+    // behind P1, so before P3's first store to the region
+    int32_t *region = sorted + p0 * NR + (int64_t)r * S;
+    int32_t *prev = reinterpret_cast<int32_t *>(cnts + RS) + 16 * SORT_CL;      // [KEEP_CAP]
+    int32_t *keepf = prev + KEEP_CAP;                                           // [RS] 1: the list stands
+    int32_t *kshift = keepf + RS;                                               // [RS] old offset - new offset
+    int32_t *krec = keep && !flg ? keep + ((int64_t)b * NR + r) * KEEP_REC : nullptr;
+    const bool kp = krec && keep_mode == 1 && fuse_sum;
+    const int prevn = S < KEEP_CAP ? S : KEEP_CAP;
+    int hexp = 0, hgot = 0, pv[KEEP_CAP / SORT_THREADS];
+    int2 kold = make_int2(0, 0);
+    if (krec && tid < KEEP_HDR) hexp = keep_hdr_word(tid, c, K_max, u0, u1, NR, sorted, koff2, part_sum, kp ? 1 : 0);
+    if (kp) {
+        if (tid < KEEP_HDR) hgot = krec[tid];
+        if (tid < RS && (tid << nsh) + r < K_max) kold = *reinterpret_cast<const int2 *>(koff2 + ((int64_t)b * K_max + (tid << nsh) + r) * 2);
+#pragma unroll
+        for (int j = 0; j < KEEP_CAP / SORT_THREADS; j++) {
+            const int i = j * SORT_THREADS + tid;
+            pv[j] = prevn > 0 ? region[i < prevn ? i : 0] : 0;
+        }
+    }
     int n_mine = 0;                                              // wave-uniform: in-range tokens of this wave's run
     if (preload) {
         // (P1) every key of the run fetched up front (unconditional loads, clamped index), then compacted in order
@@ -785,7 +849,13 @@ __global__ __launch_bounds__(SORT_THREADS) void k_batch_sort_sum(
         }
     }
     if (lane == 0) wcount[wv] = n_mine;
+    if (kp) {
+#pragma unroll
+        for (int j = 0; j < KEEP_CAP / SORT_THREADS; j++) prev[j * SORT_THREADS + tid] = pv[j];
+    }
     const bool compact = !__syncthreads_or(!preload || n_mine > SORT_CL);      // workgroup-uniform (and the barrier after P1)
+    // every word of the header as this launch would write it, or nothing is kept
+    const bool keep_ok = !__syncthreads_or(!kp || (tid < KEEP_HDR && hgot != hexp));
     SEGK_TSTAMP(1, 2);
     if (flg) {
         // ---- the flagged tokens, in token order: {count, 0, (slot, k, row) x cap}
@@ -852,11 +922,16 @@ __global__ __launch_bounds__(SORT_THREADS) void k_batch_sort_sum(
             koff2[((int64_t)b * K_max + k) * 2 + 0] = ex;
             koff2[((int64_t)b * K_max + k) * 2 + 1] = run;
         }
+        // keep: a non-empty list of the old length whose old place lies inside the entries held in LDS is a candidate; P3
+        // compares its rows one by one.  (The old offset and length are compared and bounded here, never used as an address
+        // into global memory.  An empty list is always written: it costs nothing.)
+        const bool cand = keep_ok && run > 0 && kold.y == run && kold.x >= 0 && kold.x <= prevn - run;
+        keepf[tid] = cand ? 1 : 0;
+        kshift[tid] = cand ? kold.x - ex : 0;
     }
     __syncthreads();
     SEGK_TSTAMP(1, 3);
     // (P3) placement, stable: `sorted` receives the token's embedding row (new_tok of its slot)
-    int32_t *region = sorted + p0 * NR + (int64_t)r * S;
     int32_t *mine = cntw + wv * RS;
     if (compact) {
         for (int ib = 0; ib < n_mine; ib += 64) {
@@ -869,7 +944,9 @@ __global__ __launch_bounds__(SORT_THREADS) void k_batch_sort_sum(
             if (ok) {
                 const int rank = __popcll(same & ((1ull << lane) - 1ull));
                 const int before = mine[kk];
-                region[base[kk] + before + rank] = row;
+                const int pos = base[kk] + before + rank;
+                region[pos] = row;
+                if (keep_ok && keepf[kk] && prev[pos + kshift[kk]] != row) keepf[kk] = 0;      // (only zeros are ever stored here)
                 if (rank == __popcll(same) - 1) mine[kk] = before + rank + 1;       // the last of its component in the chunk
             }
         }
@@ -884,13 +961,21 @@ __global__ __launch_bounds__(SORT_THREADS) void k_batch_sort_sum(
             if (ok) {
                 const int rank = __popcll(same & ((1ull << lane) - 1ull));
                 const int before = mine[kk];
-                region[base[kk] + before + rank] = new_tok[p0 + sidx];
+                const int pos = base[kk] + before + rank, row = new_tok[p0 + sidx];
+                region[pos] = row;
+                if (keep_ok && keepf[kk] && prev[pos + kshift[kk]] != row) keepf[kk] = 0;
                 if (rank == __popcll(same) - 1) mine[kk] = before + rank + 1;
             }
         }
     }
     SEGK_TSTAMP_MAX(1, 4);
-    if (!fuse_sum) return;
+    // keep: the header this launch vouches for (magic 0 where it keeps nothing and another kernel writes the sums).  The threads
+    // that store it are the ones that read the old one above; only the next launch reads it again
+    if (krec && tid < KEEP_HDR) krec[tid] = hexp;
+    if (!fuse_sum) {
+        if (krec && tid == 0) krec[KEEP_HDR] = krec[KEEP_HDR + 1] = 0;
+        return;
+    }
     // (S) float32 rows of even D <= 128; everything else: k_batch_partials
     // (the barrier orders this workgroup's stores to `region` before its own loads of them: workgroup scope is all that is
     // needed -- one CU, one vector L1 that has never held these lines.  An agent-scope __threadfence() here writes back and
@@ -898,6 +983,22 @@ __global__ __launch_bounds__(SORT_THREADS) void k_batch_sort_sum(
     __syncthreads();
     {
         const int T = base[RS - 1] + cnts[RS - 1];
+        // keep: the lists that stand, as two wave-uniform masks; wave 0 leaves the counters of this call
+        unsigned long long kq0 = 0ull, kq1 = 0ull;
+        if (keep_ok) {
+            kq0 = __ballot(lane < RS && keepf[lane < RS ? lane : 0] != 0);
+            kq1 = __ballot(64 + lane < RS && keepf[64 + lane < RS ? 64 + lane : 0] != 0);
+        }
+        auto kept = [&](int kk) -> bool { return ((kk < 64 ? kq0 >> kk : kq1 >> (kk - 64)) & 1ull) != 0ull; };
+        if (krec && wv == 0) {
+            const int live = __popcll(__ballot(lane < RS && cnts[lane < RS ? lane : 0] > 0)) +
+                             __popcll(__ballot(64 + lane < RS && cnts[64 + lane < RS ? 64 + lane : 0] > 0));
+            const int nk = __popcll(kq0) + __popcll(kq1);
+            if (lane == 0) {
+                krec[KEEP_HDR] = nk;
+                krec[KEEP_HDR + 1] = live - nk;
+            }
+        }
         auto owner = [&](int kk) -> int {
             const int o = T > 0 ? (int)(((long long)base[kk] * 16) / T) : 0;
             return o < 15 ? o : 15;
@@ -911,9 +1012,8 @@ __global__ __launch_bounds__(SORT_THREADS) void k_batch_sort_sum(
         const int D = c.D;
         const float *Xf = (const float *)c.X;
         const int dl = 2 * lane < D ? 2 * lane : 0;              // clamped: always a valid address
-        const int t_lo = base[ka], t_hi = base[kb - 1] + cnts[kb - 1];
         double a0 = 0.0, a1 = 0.0;
-        int kk = ka, rem = cnts[ka];
+        int kk = ka, rem = 0, cb = kb;
         auto flush = [&]() {                                     // component kk is complete (rem == 0): write it out, move on
             for (;;) {
                 const int k = (kk << nsh) + r;
@@ -924,28 +1024,43 @@ __global__ __launch_bounds__(SORT_THREADS) void k_batch_sort_sum(
                 a0 = 0.0;
                 a1 = 0.0;
                 kk++;
-                if (kk >= kb) { rem = 0x7fffffff; return; }
+                if (kk >= cb) { rem = 0x7fffffff; return; }
                 rem = cnts[kk];
                 if (rem > 0) return;
             }
         };
-        if (rem == 0) flush();
-        for (int c0 = t_lo; c0 < t_hi; c0 += 64) {
-            const int nb = t_hi - c0 < 64 ? t_hi - c0 : 64;
-            const int mine_row = region[c0 + (lane < nb ? lane : 0)];
-            for (int q0 = 0; q0 < nb; q0 += 32) {
-                float2 xv[32];
+        // the wave's components in stretches [ca, cb) of lists that are summed again; a list that stands is stepped over
+        // (with nothing kept: one stretch, [ka, kb))
+        for (int ca = ka; ca < kb; ca = cb) {
+            cb = ca + 1;
+            if (kept(ca)) continue;
+            while (cb < kb && !kept(cb)) cb++;
+            const int t_lo = base[ca], t_hi = base[cb - 1] + cnts[cb - 1];
+            a0 = 0.0;
+            a1 = 0.0;
+            kk = ca;
+            rem = cnts[ca];
+            if (rem == 0) flush();
+            for (int c0 = t_lo; c0 < t_hi; c0 += 64) {
+                const int nb = t_hi - c0 < 64 ? t_hi - c0 : 64;
+                // (keep: the head of the region went through this CU's vector L1 at entry, so the read-back of P3's stores asks the L2:
+                // an agent-scope relaxed load, no fence)
+                const int mine_row = kp ? __hip_atomic_load(region + c0 + (lane < nb ? lane : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                                        : region[c0 + (lane < nb ? lane : 0)];
+                for (int q0 = 0; q0 < nb; q0 += 32) {
+                    float2 xv[32];
 #pragma unroll
-                for (int q = 0; q < 32; q++) {
-                    const int e = __shfl(mine_row, q0 + q < nb ? q0 + q : 0);       // clamped: always a valid row
-                    xv[q] = *reinterpret_cast<const float2 *>(Xf + (int64_t)e * c.ldx + dl);
-                }
+                    for (int q = 0; q < 32; q++) {
+                        const int e = __shfl(mine_row, q0 + q < nb ? q0 + q : 0);       // clamped: always a valid row
+                        xv[q] = *reinterpret_cast<const float2 *>(Xf + (int64_t)e * c.ldx + dl);
+                    }
 #pragma unroll
-                for (int q = 0; q < 32; q++) {
-                    if (q0 + q < nb) {                                               // wave-uniform
-                        a0 += (double)xv[q].x;
-                        a1 += (double)xv[q].y;
-                        if (--rem == 0) flush();
+                    for (int q = 0; q < 32; q++) {
+                        if (q0 + q < nb) {                                               // wave-uniform
+                            a0 += (double)xv[q].x;
+                            a1 += (double)xv[q].y;
+                            if (--rem == 0) flush();
+                        }
                     }
                 }
             }
@@ -1962,11 +2077,46 @@ int64_t segk_kmeans_batch_record_words(int32_t K_max, int32_t D, int32_t n_block
     return (int64_t)n_blocks_local * ((int64_t)K_max * D + 1 + K_max + segk_flag_words(flag_cap) + rw);
 }
 
+int64_t segk_kmeans_batch_keep_words(int32_t K_max, int32_t n_blocks_local)
+{
+    if (K_max < 1) return 0;
+    return (int64_t)(n_blocks_local > 0 ? n_blocks_local : 1) * segk_sort_ranges(K_max) * KEEP_REC;
+}
+
+static int32_t batch_partials(segk_ctx *ctx, const segk_corpus *c, const segk_kmeans *m, const int32_t *blk_lo, int32_t n_blocks_local,
+                              const int32_t *new_tok, const int32_t *new_k, const int32_t *n_flag, const double *out_total,
+                              int32_t *sorted_scratch, int32_t *koff_scratch, double *record, int32_t flag_cap, int32_t flag_rows,
+                              double *out_scalars, void *stream, int32_t *keep, int keep_mode);
+
 int32_t segk_kmeans_batch_partials(segk_ctx *ctx, const segk_corpus *c, const segk_kmeans *m,
                                    const int32_t *blk_lo, int32_t n_blocks_local,
                                    const int32_t *new_tok, const int32_t *new_k, const int32_t *n_flag,
                                    const double *out_total, int32_t *sorted_scratch, int32_t *koff_scratch,
                                    double *record, int32_t flag_cap, int32_t flag_rows, double *out_scalars, void *stream)
+{
+    return batch_partials(ctx, c, m, blk_lo, n_blocks_local, new_tok, new_k, n_flag, out_total, sorted_scratch, koff_scratch, record,
+                          flag_cap, flag_rows, out_scalars, stream, nullptr, 0);
+}
+
+int32_t segk_kmeans_batch_partials_keep(segk_ctx *ctx, const segk_corpus *c, const segk_kmeans *m,
+                                        const int32_t *blk_lo, int32_t n_blocks_local,
+                                        const int32_t *new_tok, const int32_t *new_k, const int32_t *n_flag,
+                                        const double *out_total, int32_t *sorted_scratch, int32_t *koff_scratch,
+                                        double *record, int32_t flag_cap, int32_t flag_rows, double *out_scalars, void *stream,
+                                        int32_t *keep, int64_t keep_words)
+{
+    SEGK_REQUIRE(!keep || keep_words >= segk_kmeans_batch_keep_words(m->K_max, n_blocks_local), "keep_words");
+    // SEGK_BATCH_KEEP=0 (read per call): every list is summed again, and the headers say that nothing is vouched for
+    const char *e = getenv("SEGK_BATCH_KEEP");
+    return batch_partials(ctx, c, m, blk_lo, n_blocks_local, new_tok, new_k, n_flag, out_total, sorted_scratch, koff_scratch, record,
+                          flag_cap, flag_rows, out_scalars, stream, keep, keep ? (e && e[0] == '0' && !e[1] ? 2 : 1) : 0);
+}
+
+// keep_mode 0: no keep buffer; 1: lists that stand keep their sums; 2: nothing is kept and the headers are withdrawn
+static int32_t batch_partials(segk_ctx *ctx, const segk_corpus *c, const segk_kmeans *m, const int32_t *blk_lo, int32_t n_blocks_local,
+                              const int32_t *new_tok, const int32_t *new_k, const int32_t *n_flag, const double *out_total,
+                              int32_t *sorted_scratch, int32_t *koff_scratch, double *record, int32_t flag_cap, int32_t flag_rows,
+                              double *out_scalars, void *stream, int32_t *keep, int keep_mode)
 {
     (void)ctx;
     int rc = check_corpus(c);
@@ -1987,11 +2137,13 @@ int32_t segk_kmeans_batch_partials(segk_ctx *ctx, const segk_corpus *c, const se
     const int NR = segk_sort_ranges(m->K_max), rsh = segk_sort_rsh(m->K_max), nsh = segk_sort_nsh(m->K_max);
     const bool fuse = c->x_dtype == SEGK_F32 && c->D <= 128 && (c->D & 1) == 0 && (c->ldx & 1) == 0;
     {
-        size_t lds = (size_t)(16 + 2) * (1 << rsh) * 4 + (size_t)16 * SORT_CL * 4;
+        // (16 + 2) * RS counters, the waves' compacted entries, and for the keep compare KEEP_CAP old entries + 2 * RS words:
+        // 51.7 KB at K_max <= 2048, 59.4 KB above
+        size_t lds = (size_t)(16 + 2) * (1 << rsh) * 4 + (size_t)16 * SORT_CL * 4 + (size_t)KEEP_CAP * 4 + (size_t)2 * (1 << rsh) * 4;
         if (lds < 2048 * sizeof(double)) lds = 2048 * sizeof(double);
         hipLaunchKernelGGL(k_batch_sort_sum, dim3((unsigned)(nbl * (NR + 2))), dim3(SORT_THREADS), lds, st, *c, *m, blk_lo,
                            n_blocks_local, new_tok, new_k, out_total, sorted_scratch, koff_scratch, part_tot, flags, flag_cap,
-                           out_scalars, NR, rsh, nsh, part_sum, part_cnt, fuse ? 1 : 0);
+                           out_scalars, NR, rsh, nsh, part_sum, part_cnt, fuse ? 1 : 0, keep, keep_mode);
         SEGK_LAUNCH_CHECK();
     }
     if (flag_rows) {

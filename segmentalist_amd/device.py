@@ -587,6 +587,9 @@ class KMeansBatchSweeper(object):
         nr = ws.value // max(n_loc, 1)
         self._sorted_ptr = C.c_void_p(self.sorted.data_ptr() - 4 * part.utt_lo * c.N_max * nr)
         self.koff = torch.zeros(wk.value, dtype=torch.int32, device=dev)
+        # the sums of token lists that stand from call to call stay in `pack` (segk_kmeans_batch_partials_keep): the kernel's
+        # own record of what `sorted`, `koff` and `pack` hold, zeroed with them; no state on the host
+        self.keep = torch.zeros(int(dk._L.segk_kmeans_batch_keep_words(dk.K_max, part.nbl)), dtype=torch.int32, device=dev)
         # SEGK_SWEEP_GRAPH=1: the sweep replayed as a hipGraph from its second run on.  Default 0: measured on MI355X
         # the replay is SLOWER than the plain launches it replaces (full corpus 0.661 vs 0.634 ms per sweep, a
         # 1 250-utterance shard 0.258 vs 0.216 ms: the launches of sweep i + 1 are enqueued while sweep i runs, so
@@ -677,9 +680,10 @@ class KMeansBatchSweeper(object):
                 check(L.segk_kmeans_segment(ctx, cp, mp, ptr(utts), 0, n_utts, int(n_slices_min), int(n_slices_max), float(wip),
                                             C.byref(dk.cand), ptr(boundaries), ptr(dk.old_tok), ptr(dk.new_tok), ptr(dk.new_k),
                                             ptr(dk.n_old), ptr(dk.n_new), ptr(dk.n_flag), ptr(dk.out_total), ptr(dk.status), st))
-            check(L.segk_kmeans_batch_partials(ctx, cp, mp, ptr(self.blk_lo), pt.nbl, ptr(dk.new_tok), ptr(dk.new_k),
-                                               ptr(dk.n_flag), ptr(dk.out_total), self._sorted_ptr, ptr(self.koff),
-                                               ptr(self.pack), self.cap, self.flag_rows, ptr(dk.out_scalars), st))
+            check(L.segk_kmeans_batch_partials_keep(ctx, cp, mp, ptr(self.blk_lo), pt.nbl, ptr(dk.new_tok), ptr(dk.new_k),
+                                                    ptr(dk.n_flag), ptr(dk.out_total), self._sorted_ptr, ptr(self.koff),
+                                                    ptr(self.pack), self.cap, self.flag_rows, ptr(dk.out_scalars), st,
+                                                    ptr(self.keep), self.keep.numel()))
             if pt.world > 1:
                 self.comm.all_gather_rows(self.pack_all, self.pack)
             self._enqueue_back()
@@ -696,9 +700,10 @@ class KMeansBatchSweeper(object):
         hint = {} if not self._use_hints() else {"hint_identity": True} if self._hints_current else {"hint_remap": dk.remap}
         dk.score_rows(row0=pt.row_lo - dk.row_base, n=pt.row_hi - pt.row_lo, **hint)
         dk.segment(boundaries, n_slices_min, n_slices_max, wip, utt0=pt.utt_lo, n_utts=pt.utt_hi - pt.utt_lo)
-        check(L.segk_kmeans_batch_partials(ctx, cp, mp, ptr(self.blk_lo), pt.nbl, ptr(dk.new_tok), ptr(dk.new_k),
-                                           ptr(dk.n_flag), ptr(dk.out_total), self._sorted_ptr, ptr(self.koff),
-                                           ptr(self.pack), self.cap, self.flag_rows, ptr(dk.out_scalars), st))
+        check(L.segk_kmeans_batch_partials_keep(ctx, cp, mp, ptr(self.blk_lo), pt.nbl, ptr(dk.new_tok), ptr(dk.new_k),
+                                                ptr(dk.n_flag), ptr(dk.out_total), self._sorted_ptr, ptr(self.koff),
+                                                ptr(self.pack), self.cap, self.flag_rows, ptr(dk.out_scalars), st,
+                                                ptr(self.keep), self.keep.numel()))
 
     def _enqueue_back(self):
         dk, pt = self.dk, self.part
@@ -769,9 +774,10 @@ class KMeansBatchSweeper(object):
         dk.score_rows(ids=ids[:n_list], hint_identity=hints)
         check(L.segk_kmeans_refit_apply(ctx, cp, mp, C.byref(dk.cand), pt.utt_lo, pt.utt_hi, ptr(dk.new_tok), ptr(dk.new_k),
                                         ptr(dk.n_flag), ptr(dk.refit_moved), ptr(dk.status), st))
-        check(L.segk_kmeans_batch_partials(ctx, cp, mp, ptr(self.blk_lo), pt.nbl, ptr(dk.new_tok), ptr(dk.new_k),
-                                           ptr(dk.n_flag), ptr(dk.out_total), self._sorted_ptr, ptr(self.koff),
-                                           ptr(self.pack), self.cap, self.flag_rows, ptr(dk.out_scalars), st))
+        check(L.segk_kmeans_batch_partials_keep(ctx, cp, mp, ptr(self.blk_lo), pt.nbl, ptr(dk.new_tok), ptr(dk.new_k),
+                                                ptr(dk.n_flag), ptr(dk.out_total), self._sorted_ptr, ptr(self.koff),
+                                                ptr(self.pack), self.cap, self.flag_rows, ptr(dk.out_scalars), st,
+                                                ptr(self.keep), self.keep.numel()))
         if pt.world > 1:
             self.comm.all_gather_rows(self.pack_all, self.pack)
         self._enqueue_back()

@@ -2,13 +2,14 @@
 """Development: wall-clock stamps (s_memrealtime, 100 MHz) of the phases of the sweep's tail kernels -- segment, sort,
 partial sums, finalize, post -- from a library built with -DSEGK_STAMP (kept beside the product build:
   make -C segmentalist_amd/csrc OUT=$PWD/build_stamp/libsegk_stamp.so OBJDIR=/tmp/stampbuild/obj HIPFLAGS="... -DSEGK_STAMP").
+SEGK_LIB_PATH names another stamp build (a parent's kept beside the change's).
 usage: diag_tail_stamps.py [n_utterances]"""
 import os, random, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np, torch
 from segmentalist_amd import _abi
-_abi.LIB_PATH = os.path.join(ROOT, "build_stamp", "libsegk_stamp.so")
+_abi.LIB_PATH = os.environ.get("SEGK_LIB_PATH") or os.path.join(ROOT, "build_stamp", "libsegk_stamp.so")
 from segmentalist_amd import kmeans_acoustic_wordseg as kaw
 from segmentalist_amd.synth import make_corpus
 n_utt = int(sys.argv[1]) if len(sys.argv) > 1 else 10000
@@ -33,11 +34,19 @@ for k, nm in enumerate(names):
     print("== %s" % nm)
     rows = v[k]
     if k == 1:
-        nb = 8
-        for lab, sl in (("sort workgroups", slice(0, nb)), ("flags + totals workgroups", slice(nb, 2 * nb))):
+        # k_batch_sort_sum: workgroup (b, r) = blockIdx b * (NR + 2) + r; r < NR the range workgroups, NR the flag list, NR + 1 the totals
+        nb, NR = 8, 32
+        idx = np.arange(1024)
+        live = idx < nb * (NR + 2)
+        for lab, sl in (("sort workgroups", live & (idx % (NR + 2) < NR)), ("flags + totals workgroups", live & (idx % (NR + 2) >= NR))):
             print("  %s" % lab)
             for ph in range(6):
                 print("    phase %d: %8.2f %8.2f %8.2f" % ((ph,) + rel(rows[sl, ph])))
+        w = rows[live & (idx % (NR + 2) < NR)]
+        w = w[w[:, 0] > 0]
+        for lab, a, z in (("entry -> P1 done", 0, 2), ("P2", 2, 3), ("P3", 3, 4), ("S (4 -> 5)", 4, 5), ("whole workgroup", 0, 5)):
+            dur = w[:, z] - w[:, a]
+            print("    %-18s per workgroup: mean %6.2f  min %6.2f  max %6.2f" % (lab, dur.mean(), dur.min(), dur.max()))
         continue
     if k == 2:
         if not (rows[:, 0] > 0).any():
