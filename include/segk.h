@@ -77,7 +77,9 @@ const char *segk_last_error(void);
  *     signature or structure changed
  *  15 (no bump) segk_kmeans_batch_partials_keep + segk_kmeans_batch_keep_words: segk_kmeans_batch_partials with a caller-owned
  *     buffer through which the sums of token lists that did not change since the previous call are kept.  Two entry points
- *     added, no signature or structure changed                                                                             */
+ *     added, no signature or structure changed
+ *  15 (no bump) segk_fbi_assign_map, segk_fbi_assign_map_diag32, segk_fbgmm_map_items: the MAP sweeps of FBGMM.map_assign, batch
+ *     and serial.  Three entry points added, no signature or structure changed                                             */
 #define SEGK_ABI_VERSION 15
 int32_t segk_abi_version(void);
 
@@ -675,6 +677,17 @@ int32_t segk_fbgmm_gibbs_items(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *
                                int64_t n, int32_t consider_unassigned, double anneal_temp,
                                const double *ustream, int64_t *ucursor, int64_t ucap, int32_t *status,
                                void *stream);
+/* One MAP sweep of the serial chain (added at ABI 15 without a bump; FBGMM.map_assign(sync="sequential")).  It replaces a host
+ * loop over FBGMM.map_assign_i preceded by del_item: the loop of segk_fbgmm_gibbs_items (fbgmm.py:352-405) with its lines
+ * 371-389 -- logits with lms, annealing, utils.draw -- replaced by map_assign_i's 475-491: z_k = log(alpha / K_max + n_k) (no
+ * lms) + log predictive_k(x), k = the first maximum of exp(z - logsumexp z), then `k > K -> K`.  Per considered row in order:
+ * cache_component_stats, del_item, that choice, restore_component_from_stats when the row went back to its component and no
+ * component was deleted (a sweep that moves nothing leaves every statistic bit for bit), add_item otherwise.  No uniform is
+ * read.  *n_moved [dev] += the rows that took the add_item branch, except a singleton that re-founded its own component (K
+ * dropped by one at del_item and the row chose k == K); the caller zeroes it.  cov_type 0, 1 and 2 as segk_fbgmm_gibbs_items; a
+ * language model is refused before the launch.                                                                              */
+int32_t segk_fbgmm_map_items(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *f, const int32_t *ids, int64_t n,
+                             int32_t consider_unassigned, int32_t *status, int32_t *n_moved, void *stream);
 
 /* -------------------------------------------------------------------------------------
  * Batch-synchronous ("blocked parallel Gibbs") sweep of the FBGMM / bigram samplers.  The
@@ -933,6 +946,34 @@ int32_t segk_fbi_assign_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_f
                                int32_t s_lo, int32_t s_n, int32_t b, const int32_t *n_items, uint64_t sweep,
                                double anneal_temp, int32_t consider_unassigned, const int32_t *new_tok,
                                int32_t *n_new, double *probe_ll, int64_t probe_ld, void *stream);
+/* The item half of a step of a MAP sweep of the stand-alone mixture model (added at ABI 15 without a bump;
+ * FBGMM.map_assign(sync="batch"); specification tests/fbgmm_items_map.py).  It stands where segk_fbi_assign stands in a step
+ * -- after segk_fbb_prepare(b), before segk_fbb_partials(b) -- and replaces its draw (fbgmm.py:436-460) by the hard assignment
+ * of FBGMM.map_assign_i (fbgmm.py:465-494) on slots: every considered item i of block b forms
+ * z_k = log(alpha / K_max + n_k) + log predictive_k(X[i]) over all K_max slots -- no lms on the prior term (fbgmm.py:475-479 has
+ * none), the likelihood bits of segk_fbi_assign -- and takes k = the FIRST index of max_k z_k.  No temperature, no uniform, no
+ * softmax, no `k > K` clamp (batch slots are slots); all empty slots of an item tie exactly and the first wins.  `sweep` is not
+ * read (the caller still advances its counter, so that sampled sweeps after a MAP sweep use the uniforms they would have used).
+ * bt->slot[i] and n_new[i] = 1 are written as by segk_fbi_assign.  *n_moved [dev] += the considered items whose slot after the
+ * call differs from before (an unassigned item that gets a slot counts): one integer add per workgroup, so the sum does not
+ * depend on launch order, and it accumulates over the launches of a block and over the blocks of a sweep; the caller zeroes it.
+ * The prior terms are staged once per workgroup as a 65th row of the tile's logits: 65 K_max doubles in LDS next to the staged
+ * rows where they fit in 144 KiB, else in the bounded workspace (SEGK_FBI_Z_MIB); cov_type 2 reads the token-likelihood table
+ * and keeps the K_max prior terms alone in LDS.  Arguments, probe_ll and refusals otherwise as segk_fbi_assign: a language model
+ * and the cov_type 2 limits SEGK_ERR_UNSUPPORTED, a corpus with span tables or D > 256 SEGK_ERR_ARG, all before any launch.      */
+int32_t segk_fbi_assign_map(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt,
+                            int32_t s_lo, int32_t s_n, int32_t b, const int32_t *n_items, uint64_t sweep,
+                            int32_t consider_unassigned, const int32_t *new_tok, int32_t *n_new, double *probe_ll,
+                            int64_t probe_ld, int32_t *n_moved, void *stream);
+/* segk_fbi_assign_map on the float32 item likelihoods of segk_fbi_assign_diag32 (added at ABI 15 without a bump; the MAP sweeps
+ * of FBGMM(..., score_precision="f32"); it replaces fbgmm.py:465-494 as segk_fbi_assign_map does): the likelihood half of
+ * segk_fbi_assign_diag32, then the fp64 first argmax of log(alpha / K_max + n_k) + ll_k and the count of moved items exactly as
+ * above; the tile's logits are 65 rows of K_max | 1 doubles.  Refused before any launch: cov_type 0 or 2 and a language model
+ * with SEGK_ERR_UNSUPPORTED; bt->tab32, bt->centre or bt->prior_rows NULL, D > 256 or a corpus with span tables SEGK_ERR_ARG.   */
+int32_t segk_fbi_assign_map_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt,
+                                   int32_t s_lo, int32_t s_n, int32_t b, const int32_t *n_items, uint64_t sweep,
+                                   int32_t consider_unassigned, const int32_t *new_tok, int32_t *n_new, double *probe_ll,
+                                   int64_t probe_ld, int32_t *n_moved, void *stream);
 /* Acoustic-model batch sweeps of the unigram segmenter (added at ABI 15 without a bump; the inner sweeps of
  * UnigramAcousticWordseg.gibbs_sample(n, am_n_iter=m), unigram_acoustic_wordseg.py:440-443 -- FBGMM.gibbs_sample(m,
  * consider_unassigned=False) over the currently assigned tokens -- as a blocked sampler on the segmenter's batch state;

@@ -130,6 +130,7 @@ SIGNATURES = {
                                     _P, _P, _P, _P, _P]),
     "segk_fbgmm_assign": (_i32, [_P, _CP, _FP, _i32, _i32, _i32, _f64, _P, _P, _P, _P, _i64, _P, _P]),
     "segk_fbgmm_gibbs_items": (_i32, [_P, _CP, _FP, _P, _i64, _i32, _f64, _P, _P, _i64, _P, _P]),
+    "segk_fbgmm_map_items": (_i32, [_P, _CP, _FP, _P, _i64, _i32, _P, _P, _P]),
     "segk_fbgmm_sequential_sweep": (_i32, [_P, _CP, _FP, _P, _i32, _P, _i32, _i32, _i32, _i32, _f64, _f64, _f64, _f64, _f64,
                                            _P, _P, _P, _i64, _P, _P, _P, _P, _P, _P]),
     "segk_fbb_collect": (_i32, [_P, _CP, _P, _P, _P, _P]),
@@ -154,6 +155,8 @@ SIGNATURES = {
     "segk_fbb_set_probe": (_i32, [_P, _P, _P, _i64]),
     "segk_fbi_assign": (_i32, [_P, _CP, _FP, _BP, _i32, _i32, _i32, _P, _u64, _f64, _i32, _P, _P, _P, _i64, _P]),
     "segk_fbi_assign_diag32": (_i32, [_P, _CP, _FP, _BP, _i32, _i32, _i32, _P, _u64, _f64, _i32, _P, _P, _P, _i64, _P]),
+    "segk_fbi_assign_map": (_i32, [_P, _CP, _FP, _BP, _i32, _i32, _i32, _P, _u64, _i32, _P, _P, _P, _i64, _P, _P]),
+    "segk_fbi_assign_map_diag32": (_i32, [_P, _CP, _FP, _BP, _i32, _i32, _i32, _P, _u64, _i32, _P, _P, _P, _i64, _P, _P]),
     "segk_fbi_assign_orphans": (_i32, [_P, _CP, _FP, _BP, _i32, _i32, _i32, _P, _u64, _P, _P, _P, _P, _i64, _P]),
     "segk_fbt_assign": (_i32, [_P, _CP, _FP, _BP, _i32, _i32, _i32, _P, _P, _u64, _f64, _P, _P, _P, _i64, _P]),
     "segk_fbt_assign_diag32": (_i32, [_P, _CP, _FP, _BP, _i32, _i32, _i32, _P, _P, _u64, _f64, _P, _P, _P, _i64, _P]),

@@ -1,7 +1,7 @@
 // segk_fbb_dev.h -- what the batch sampler's translation units share (segk_fbbatch.hip; segk_fullcov.hip for the
 // full-covariance forms of its kernels; segk_fbitems.hip for the stand-alone model's item step): the record of a (block,
 // slice) cell, the workgroup -> (slice, index) map of a launch, the specification's balanced tree, the float32 Student-t
-// term, the draw of one token's slot.  Not part of the ABI.
+// term, the draw of one token's slot and its MAP counterpart.  Not part of the ABI.
 #pragma once
 #include "segk_internal.h"
 #include "segk_fb_common.h"
@@ -131,6 +131,41 @@ static __device__ __forceinline__ int fbb_draw_row(const segk_fbgmm &f, const se
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     return fb_draw_chunked(zr, KM, segk_u01(bt.seed, sweep, utt, j), lane);
+}
+
+static __device__ __forceinline__ int fbb_wave_min_i32(int v)       // minimum over the 64 lanes, wave-uniform
+{
+    int o = __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false);
+    v = o < v ? o : v;
+    o = __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, false);
+    v = o < v ? o : v;
+    o = __builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, false);
+    v = o < v ? o : v;
+    o = __builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false);
+    v = o < v ? o : v;
+    const int r0 = __builtin_amdgcn_readlane(v, 0), r1 = __builtin_amdgcn_readlane(v, 16);
+    const int r2 = __builtin_amdgcn_readlane(v, 32), r3 = __builtin_amdgcn_readlane(v, 48);
+    const int a = r1 < r0 ? r1 : r0, c = r3 < r2 ? r3 : r2;
+    return c < a ? c : a;
+}
+
+// THE MAP slot of one token, by one wave (k_fbb_slots<.., MAP> of segk_fbbatch.hip; the MAP halves of k_fbi_assign and
+// k_fbi_assign_diag32 of segk_fbitems.hip): the first index of the maximum of z_k = pz[k] + zr[k] over the K_max slots, where
+// pz[k] = log(alpha / K_max + n_k) (fbgmm.py:475-479: no lms) and zr the likelihood part of the logits (read only).  A per-lane
+// (value, index) over k = lane, lane + 64, ... with strict >, the wave's maximum by DPP, then the lowest index among the lanes
+// that hold it.  All empty slots of a token carry one value, so the first of them wins a tie among them without being treated
+// apart.  Result in all lanes.
+static __device__ __forceinline__ int fbb_map_row(const double *pz, const double *zr, int KM, int lane)
+{
+    double best = NEG_INF_D;
+    int bk = KM;
+    for (int kk = lane; kk < KM; kk += 64) {
+        const double z = pz[kk] + zr[kk];
+        if (z > best) { best = z; bk = kk; }
+    }
+    const double m = fb_wave_max(best, false);
+    const int k = fbb_wave_min_i32(best == m ? bk : KM);
+    return k < KM ? k : 0;
 }
 
 // segk_fullcov.hip: the cov_type 2 forms of the segk_fbb_* entry points a unigram step uses (arguments checked by the callers

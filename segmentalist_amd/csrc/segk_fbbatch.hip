@@ -1456,29 +1456,14 @@ __global__ __launch_bounds__(256) void k_fbb_assign_lm(segk_corpus c, segk_fbgmm
 //   * MAP = true (FBGMM.map_assign_i, fbgmm.py:465-494, on slots): k = the first index of the maximum of
 //     z_k = log(alpha / K_max + n_k) + loglik_k(x) -- no `lms` on the prior term (fbgmm.py:475-479 has none), no temperature,
 //     no uniform, no softmax (the reference's argmax(exp(z - logsumexp z)) is the argmax of z: tests/test_map_batch_cpu.py
-//     holds that on every token of the test corpora).  The prior terms once per workgroup into LDS; a per-lane (value, index)
-//     over k = lane, lane + 64, ... with strict >, the wave's maximum by DPP and the lowest index among the lanes that hold it.
+//     holds that on every token of the test corpora).  The prior terms once per workgroup into LDS, then fbb_map_row
+//     (segk_fbb_dev.h): a per-lane (value, index) over k = lane, lane + 64, ... with strict >, the wave's maximum by DPP and the
+//     lowest index among the lanes that hold it.
 //     All empty slots of a token carry one value, so the first of them wins a tie among them without being treated apart.
 //     Never reads ll_mat: in the fixed-variance tolerance modes the token likelihood is the fp64 quadratic.
 // F32 = 1: the float32 Student-t terms of segk_fbb_assign_diag32.  The LDS image is k_fbb_assign_lm's (fbb_assign_plan): the
 // leading K_max doubles are pz with MAP and unused without.
 // ---------------------------------------------------------------------------------------
-static __device__ __forceinline__ int fbb_wave_min_i32(int v)       // minimum over the 64 lanes, wave-uniform
-{
-    int o = __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false);
-    v = o < v ? o : v;
-    o = __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, false);
-    v = o < v ? o : v;
-    o = __builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, false);
-    v = o < v ? o : v;
-    o = __builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false);
-    v = o < v ? o : v;
-    const int r0 = __builtin_amdgcn_readlane(v, 0), r1 = __builtin_amdgcn_readlane(v, 16);
-    const int r2 = __builtin_amdgcn_readlane(v, 32), r3 = __builtin_amdgcn_readlane(v, 48);
-    const int a = r1 < r0 ? r1 : r0, c = r3 < r2 ? r3 : r2;
-    return c < a ? c : a;
-}
-
 template <typename XT, int COV, int F32, bool MAP>
 __global__ __launch_bounds__(512) void k_fbb_slots(segk_corpus c, segk_fbgmm f, segk_fbatch bt, FbbMap map, int b, uint64_t sweep,
                                                    double prior_alpha, double anneal_temp, const int32_t *new_tok,
@@ -1516,17 +1501,9 @@ __global__ __launch_bounds__(512) void k_fbb_slots(segk_corpus c, segk_fbgmm f, 
         for (int r = w; r < nr; r += nw) {
             double *zr = ll + (int64_t)r * KM;
             int k;
-            if (MAP) {
-                double best = NEG_INF_D;
-                int bk = KM;
-                for (int kk = lane; kk < KM; kk += 64) {
-                    const double z = pz[kk] + zr[kk];
-                    if (z > best) { best = z; bk = kk; }
-                }
-                const double m = fb_wave_max(best, false);
-                k = fbb_wave_min_i32(best == m ? bk : KM);
-                k = k < KM ? k : 0;
-            } else
+            if (MAP)
+                k = fbb_map_row(pz, zr, KM, lane);
+            else
                 k = fbb_draw_row(f, bt, KM, prior_alpha, zc_empty, anneal_temp, zr, sweep, (uint64_t)utt,
                                  (uint64_t)(c.N_max + t0 + r), lane);
             if (lane == 0) bt.slot[new_tok[(int64_t)utt * c.N_max + t0 + r]] = k;

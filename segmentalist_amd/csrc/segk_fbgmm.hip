@@ -1033,11 +1033,16 @@ __global__ void k_fb_relabel(int32_t *assignments, int64_t n, int64_t skip_lo, i
 // FBGMM.gibbs_sample inner loop (fbgmm.py:352-405) over the items ids[0..n) (NULL: rows 0..n) in
 // order, one workgroup: cache the old component's statistics, del_item, logits, draw, then either
 // restore the cached statistics (same component, no component deleted) or add_item.
+// MAP (segk_fbgmm_map_items; FBGMM.map_assign(sync="sequential")): the same loop with lines 371-389 replaced by map_assign_i's
+// 475-491 -- the logits of mode 2 (no lms on the prior term), the first maximum of prob_z, the `k > K` clamp; no uniform is read
+// and the cursor stays where it is.  The restore branch is kept: a sweep that moves nothing leaves every statistic bit for bit.
+// *n_moved += the items that took the add_item branch, except a singleton that re-founds its own component (K dropped by one at
+// del_item and the item chose k == K).
 // ---------------------------------------------------------------------------------------
-template <typename XT>
+template <typename XT, bool MAP = false>
 __global__ __launch_bounds__(512) void k_fbgmm_gibbs_items(segk_corpus c, segk_fbgmm f, const int32_t *ids, int64_t n,
                                     int consider_unassigned, double anneal_temp, const double *ustream,
-                                    int64_t *ucursor, int64_t ucap, int32_t *status)
+                                    int64_t *ucursor, int64_t ucap, int32_t *status, int32_t *n_moved)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double *z = (double *)smem;                      // [K_max]
@@ -1048,6 +1053,7 @@ __global__ __launch_bounds__(512) void k_fbgmm_gibbs_items(segk_corpus c, segk_f
     __shared__ double sh_lp, sh_kc;
     __shared__ long long sh_cnt;
     const int D = c.D, tid = threadIdx.x, nt = blockDim.x;
+    int moved = 0;                                           // MAP (workgroup-uniform: every term below is)
     if (tid == 0) shK = *f.K;
     __syncthreads();
     for (int64_t t = 0; t < n; t++) {
@@ -1070,9 +1076,10 @@ __global__ __launch_bounds__(512) void k_fbgmm_gibbs_items(segk_corpus c, segk_f
         __syncthreads();
         if (tid == 0) *f.K = shK;
         __syncthreads();
-        fb_logits<XT>(c, f, e, 1, -1, xrow, z, red);
-        fb_draw_component(f, z, red, 0, anneal_temp, ustream, ucursor, ucap, status, shK, &sh_k);
+        fb_logits<XT>(c, f, e, MAP ? 2 : 1, -1, xrow, z, red);
+        fb_draw_component(f, z, red, MAP ? 1 : 0, anneal_temp, ustream, ucursor, ucap, status, shK, &sh_k);
         __syncthreads();
+        if (MAP && !(sh_k == k_old && shK == K_old) && !(shK == K_old - 1 && sh_k == shK)) moved++;
         if (sh_k == k_old && shK == K_old) {                     // restore_component_from_stats (:397-400)
             for (int d = tid; d < D; d += nt) {
                 f.stat_a[(int64_t)kc * D + d] = cache[d];
@@ -1093,6 +1100,7 @@ __global__ __launch_bounds__(512) void k_fbgmm_gibbs_items(segk_corpus c, segk_f
     }
     __syncthreads();
     if (tid == 0) *f.K = shK;
+    if (MAP && tid == 0) *n_moved += moved;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1571,7 +1579,7 @@ int32_t segk_fbgmm_gibbs_items(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *
     SEGK_REQUIRE(ids != NULL || n <= c->n_emb, "n exceeds the number of rows");
     if (n <= 0) return SEGK_OK;
     if (f->cov_type == 2)
-        return segk_fc_gibbs_items(c, f, ids, n, consider_unassigned, anneal_temp, ustream, ucursor, ucap, status, stream);
+        return segk_fc_gibbs_items(c, f, ids, n, consider_unassigned, anneal_temp, ustream, ucursor, ucap, status, stream, nullptr);
     const int nt = fb_nt(f);
     size_t lds = fb_lds(c, f, nt) + (size_t)3 * c->D * sizeof(double);
     SEGK_REQUIRE(lds <= 160 * 1024, "K_max too large for the LDS logits buffer");
@@ -1580,7 +1588,34 @@ int32_t segk_fbgmm_gibbs_items(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *
             SEGK_CHECK_HIP(hipFuncSetAttribute((const void *)k_fbgmm_gibbs_items<XT>,
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(k_fbgmm_gibbs_items<XT>, dim3(1), dim3(nt), lds, (hipStream_t)stream, *c, *f, ids, n,
-                           consider_unassigned, anneal_temp, ustream, ucursor, ucap, status);
+                           consider_unassigned, anneal_temp, ustream, ucursor, ucap, status, (int32_t *)nullptr);
+    });
+    SEGK_LAUNCH_CHECK();
+    return SEGK_OK;
+}
+
+// One MAP sweep of the serial chain (FBGMM.map_assign(sync="sequential")): fbgmm.py:352-405 with lines 371-389 replaced by
+// map_assign_i's 475-491.  segk_fbgmm_gibbs_items' checks and launch on the MAP form of its kernel.
+int32_t segk_fbgmm_map_items(segk_ctx *ctx, const segk_corpus *c, segk_fbgmm *f, const int32_t *ids, int64_t n,
+                             int32_t consider_unassigned, int32_t *status, int32_t *n_moved, void *stream)
+{
+    (void)ctx;
+    int rc = check_fb(c, f, "segk_fbgmm_map_items", true);
+    if (rc) return rc;
+    SEGK_REQUIRE(n_moved != NULL, "NULL argument");
+    SEGK_REQUIRE(f->lm_unigram == NULL, "FBGMM.map_assign_i has no language-model variant in the reference");
+    SEGK_REQUIRE(ids != NULL || n <= c->n_emb, "n exceeds the number of rows");
+    if (n <= 0) return SEGK_OK;
+    if (f->cov_type == 2) return segk_fc_gibbs_items(c, f, ids, n, consider_unassigned, 1.0, nullptr, nullptr, 0, status, stream, n_moved);
+    const int nt = fb_nt(f);
+    size_t lds = fb_lds(c, f, nt) + (size_t)3 * c->D * sizeof(double);
+    SEGK_REQUIRE(lds <= 160 * 1024, "K_max too large for the LDS logits buffer");
+    DISPATCH_XT(c, {
+        if (lds > 48 * 1024)
+            SEGK_CHECK_HIP(hipFuncSetAttribute((const void *)k_fbgmm_gibbs_items<XT, true>,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((k_fbgmm_gibbs_items<XT, true>), dim3(1), dim3(nt), lds, (hipStream_t)stream, *c, *f, ids, n,
+                           consider_unassigned, 1.0, (const double *)nullptr, (int64_t *)nullptr, (int64_t)0, status, n_moved);
     });
     SEGK_LAUNCH_CHECK();
     return SEGK_OK;

@@ -40,7 +40,15 @@
 //   k_fbi_assign<.., true>  as for tokens: with N_max = 1 the draw of entry (i, 0) uses u01(seed, sweep, i, 1), the uniform of
 //                           k_fbi_assign<.., false> for item i, and with cov_type 2 its row of k_fcb_token_ll's table is item
 //                           i's.  Always the fp64 likelihoods (bt.mean_t / q_t), also on a sweeper of float32 scores.
-// No grid barrier, no spin loop, no cooperative launch, no atomics: a plain grid over the tiles.
+// And it serves the MAP sweeps of FBGMM.map_assign(sync="batch") (segk_fbi_assign_map / _map_diag32; fbgmm.py:465-494 on slots;
+// specification tests/fbgmm_items_map.py): the MAP template axis of k_fbi_assign and of the float32 tile body
+// (k_fbi_assign_map_diag32 beside k_fbi_assign_diag32), items only.  The likelihood half and
+// probe_ll as they stand; the draw half (prior term with lms, softmax, annealing, inverse-CDF walk) becomes fbb_map_row
+// (segk_fbb_dev.h, the body of k_fbb_slots<.., MAP>) on pz[k] = log(alpha / K_max + n_k), staged once per workgroup as a 65th
+// row of the tile's logits, and the items whose slot changed are counted.
+// No grid barrier, no spin loop, no cooperative launch: a plain grid over the tiles.  One atomic, in the MAP half only: a
+// workgroup's count of moved items is added to the caller's counter with one integer atomicAdd (the sum does not depend on the
+// order of the workgroups or of the launches of a block); the sampled forms use none.
 #include "segk_fb_common.h"
 #include "segk_fbb_dev.h"
 
@@ -146,13 +154,47 @@ __global__ __launch_bounds__(256) void k_fbi_mark(segk_fbatch bt, int s_lo, int 
     if (i < u1) n_new[i] = 1;
 }
 
+// The MAP half of the item kernels' draw loops (MAP = true), one wave: the slot of item i by fbb_map_row on the staged prior
+// terms, written like a draw; returns 1 where the item's slot changed (an unassigned item that gets one counts).
+static __device__ __forceinline__ int fbi_map_item(const segk_fbatch &bt, const double *pz, const double *zr, int KM, int i,
+                                                   int32_t *n_new, int lane)
+{
+    const int old = bt.slot[i];                             // (wave-uniform)
+    const int k = fbb_map_row(pz, zr, KM, lane);
+    if (lane == 0) {
+        bt.slot[i] = k;
+        n_new[i] = 1;
+    }
+    return k != old ? 1 : 0;
+}
+
+// ... and its end: the waves' counts of moved items summed in LDS, ONE integer add per workgroup to *n_moved (an integer sum:
+// the result does not depend on the order in which the workgroups, or the launches of a block, arrive)
+static __device__ __forceinline__ void fbi_map_count(int moved, int w, int nw, int lane, int32_t *n_moved)
+{
+    __shared__ int sh_moved[16];                            // (nw <= 16: the waves of the larger of the two kernels)
+    if (lane == 0) sh_moved[w] = moved;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int j = 0; j < nw; j++) tot += sh_moved[j];
+        if (tot) atomicAdd(n_moved, tot);
+    }
+}
+
 // TOK = false: the items of the stand-alone model; TOK = true: the tokens of a segmenter's cell through the lists `L`
-template <typename XT, int COV, bool TOK = false>
+// MAP (items only; segk_fbi_assign_map, specification tests/fbgmm_items_map.py): the draw half replaced by the hard assignment
+// of FBGMM.map_assign_i (fbgmm.py:465-494) on slots -- pz[k] = log(alpha / K_max + n_k) (no lms: fbgmm.py:475-479) staged once
+// per workgroup as a 65th row of the tile's logits (LDS or the workspace, wherever they are; with cov_type 2 the K_max doubles
+// are the kernel's whole LDS), then per item one wave: fbb_map_row, the slot written, the items whose slot changed counted into
+// *n_moved.  No temperature, no uniform, no softmax: `sweep` and `anneal_temp` are not read.
+template <typename XT, int COV, bool TOK = false, bool MAP = false>
 __global__ __launch_bounds__(FBI_NT) void k_fbi_assign(segk_corpus c, segk_fbgmm f, segk_fbatch bt, FbbMap map, int wg0, int b,
                                                       uint64_t sweep, double prior_alpha, double anneal_temp, int consider_unassigned,
                                                       int32_t *n_new, double *zbuf, const double *fc_ll, int fc_ucap,
-                                                      double *probe_ll, int64_t probe_ld, FbtList L)
+                                                      double *probe_ll, int64_t probe_ld, FbtList L, int32_t *n_moved)
 {
+    static_assert(!(TOK && MAP), "the MAP half exists for items");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int D = c.D, KM = f.K_max, tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);        // (wave-uniform, and known to be)
@@ -191,13 +233,23 @@ __global__ __launch_bounds__(FBI_NT) void k_fbi_assign(segk_corpus c, segk_fbgmm
         else
             return ll + (int64_t)r * KM;
     };
+    double *pz = nullptr;                                   // MAP: [K_max] log(alpha / K_max + n_k)
     if constexpr (COV == 2) {
         // k_fcb_token_ll's table: row (local slice * u_cap + item of the cell), the row's prior predictive in the empty slots
         if constexpr (!TOK) ll = const_cast<double *>(fc_ll) + ((int64_t)s * fc_ucap + (int64_t)idx * FBI_T) * KM;
+        if constexpr (MAP) {
+            pz = (double *)smem;
+            for (int k = tid; k < KM; k += FBI_NT) pz[k] = log(prior_alpha / (double)KM + bt.cnt[k]);       // fbgmm.py:475-479
+            __syncthreads();
+        }
     } else {
         double *xs = (double *)smem;                        // [D][FBI_T]: the lanes' rows side by side
         double *pm = xs + (size_t)FBI_T * D;                // [FBI_KC][D][2]: (mean, q) of the staged slots
-        ll = zbuf ? zbuf + (int64_t)blockIdx.x * FBI_T * KM : pm + 2 * (size_t)FBI_KC * D;
+        ll = zbuf ? zbuf + (int64_t)blockIdx.x * (FBI_T + (MAP ? 1 : 0)) * KM : pm + 2 * (size_t)FBI_KC * D;
+        if constexpr (MAP) {                                // (published by the barriers of the likelihood loop)
+            pz = ll + (int64_t)FBI_T * KM;
+            for (int k = tid; k < KM; k += FBI_NT) pz[k] = log(prior_alpha / (double)KM + bt.cnt[k]);       // fbgmm.py:475-479
+        }
         const XT *X = (const XT *)c.X;
         for (int j = tid; j < FBI_T * D; j += FBI_NT) {
             const int r = j / D, d = j - r * D;
@@ -260,6 +312,16 @@ __global__ __launch_bounds__(FBI_NT) void k_fbi_assign(segk_corpus c, segk_fbgmm
         }
         __syncthreads();
     }
+    if constexpr (MAP) {
+        int moved = 0;
+        for (int r = w; r < nr; r += FBI_NT / 64) {         // a wave per item
+            const int i = i0 + r;
+            if (!consider_unassigned && bt.slot[i] < 0) continue;       // (wave-uniform) keeps -1 and contributes to nothing
+            moved += fbi_map_item(bt, pz, ll + (int64_t)r * KM, KM, i, n_new, lane);
+        }
+        fbi_map_count(moved, w, FBI_NT / 64, lane, n_moved);
+        return;
+    }
     const double zc_empty = f.lms * log(prior_alpha / (double)KM);
     for (int r = w; r < nr; r += FBI_NT / 64) {             // a wave per item
         if constexpr (TOK) {
@@ -316,13 +378,16 @@ static __host__ __device__ __forceinline__ int fbi32_ldl(int KM) { return KM | 1
 // of k_fbi_assign (segk_fbt_assign_diag32; the float32 inner sweeps of am_sweep(..., score_precision="f32")): the rows are
 // gathered through L.row, an entry that names no row of the corpus is staged as zeros and left alone, the draw of token t of
 // utterance i uses u01(seed, sweep, i, N_max + t), only bt.slot is written (n_new / new_tok are read by k_fbt_compact alone)
-template <typename XT, bool TOK = false>
-__global__ __launch_bounds__(FBI32_NT) void k_fbi_assign_diag32(segk_corpus c, segk_fbgmm f, segk_fbatch bt, FbbMap map, int wg0, int b,
-                                                             uint64_t sweep, double prior_alpha, double anneal_temp,
-                                                             int consider_unassigned, int32_t *n_new, double *zbuf, double *probe_ll,
-                                                             int64_t probe_ld, FbtList L)
+// MAP (items only; k_fbi_assign_map_diag32, segk_fbi_assign_map_diag32): the MAP half of k_fbi_assign on these logits -- pz the
+// 65th row of the tile's logits [FBI_T + 1][K_max | 1], fbi_map_item per item, the moved items counted into *n_moved.
+// The body of both kernels (smem: the workgroup's dynamic LDS):
+template <typename XT, bool TOK, bool MAP>
+static __device__ __forceinline__ void fbi_assign_diag32_tile(char *smem, const segk_corpus &c, const segk_fbgmm &f, const segk_fbatch &bt,
+                                                              const FbbMap &map, int wg0, int b, uint64_t sweep, double prior_alpha,
+                                                              double anneal_temp, int consider_unassigned, int32_t *n_new, double *zbuf,
+                                                              double *probe_ll, int64_t probe_ld, const FbtList &L, int32_t *n_moved)
 {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+    static_assert(!(TOK && MAP), "the MAP half exists for items");
     const int D = c.D, KM = f.K_max, ldl = fbi32_ldl(KM), tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);        // (wave-uniform, and known to be)
     int s, idx;
@@ -354,7 +419,13 @@ __global__ __launch_bounds__(FBI32_NT) void k_fbi_assign_diag32(segk_corpus c, s
     };
     float2 *pm = (float2 *)smem;                            // [FBI32_KC][D]: (mean - centre, q) of the staged slots
     float *xs = (float *)(pm + (size_t)FBI32_KC * D);       // [D][FBI32_XS]: the lanes' centred rows side by side
-    double *ll = zbuf ? zbuf + (int64_t)blockIdx.x * FBI_T * ldl : (double *)(smem + fbi32_stage_bytes(D));     // [FBI_T][ldl]
+    // [FBI_T][ldl], with MAP a further row: pz
+    double *ll = zbuf ? zbuf + (int64_t)blockIdx.x * (FBI_T + (MAP ? 1 : 0)) * ldl : (double *)(smem + fbi32_stage_bytes(D));
+    double *pz = nullptr;
+    if constexpr (MAP) {                                    // (published by the barriers of the likelihood loop)
+        pz = ll + (int64_t)FBI_T * ldl;
+        for (int k = tid; k < KM; k += FBI32_NT) pz[k] = log(prior_alpha / (double)KM + bt.cnt[k]);         // fbgmm.py:475-479
+    }
     const XT *X = (const XT *)c.X;
     for (int j = tid; j < FBI_T * D; j += FBI32_NT) {
         const int r = j / D, d = j - r * D;
@@ -417,6 +488,16 @@ __global__ __launch_bounds__(FBI32_NT) void k_fbi_assign_diag32(segk_corpus c, s
         }
         __syncthreads();
     }
+    if constexpr (MAP) {
+        int moved = 0;
+        for (int r = w; r < nr; r += FBI32_NT / 64) {       // a wave per item
+            const int i = i0 + r;
+            if (!consider_unassigned && bt.slot[i] < 0) continue;       // (wave-uniform) keeps -1 and contributes to nothing
+            moved += fbi_map_item(bt, pz, ll + (int64_t)r * ldl, KM, i, n_new, lane);
+        }
+        fbi_map_count(moved, w, FBI32_NT / 64, lane, n_moved);
+        return;
+    }
     const double zc_empty = f.lms * log(prior_alpha / (double)KM);
     for (int r = w; r < nr; r += FBI32_NT / 64) {             // a wave per item
         if constexpr (TOK) {
@@ -437,13 +518,36 @@ __global__ __launch_bounds__(FBI32_NT) void k_fbi_assign_diag32(segk_corpus c, s
     }
 }
 
+template <typename XT, bool TOK = false>
+__global__ __launch_bounds__(FBI32_NT) void k_fbi_assign_diag32(segk_corpus c, segk_fbgmm f, segk_fbatch bt, FbbMap map, int wg0, int b,
+                                                             uint64_t sweep, double prior_alpha, double anneal_temp,
+                                                             int consider_unassigned, int32_t *n_new, double *zbuf, double *probe_ll,
+                                                             int64_t probe_ld, FbtList L)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    fbi_assign_diag32_tile<XT, TOK, false>(smem, c, f, bt, map, wg0, b, sweep, prior_alpha, anneal_temp, consider_unassigned, n_new, zbuf,
+                                           probe_ll, probe_ld, L, nullptr);
+}
+
+template <typename XT>
+__global__ __launch_bounds__(FBI32_NT) void k_fbi_assign_map_diag32(segk_corpus c, segk_fbgmm f, segk_fbatch bt, FbbMap map, int wg0,
+                                                                 int b, double prior_alpha, int consider_unassigned, int32_t *n_new,
+                                                                 double *zbuf, double *probe_ll, int64_t probe_ld, int32_t *n_moved)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    fbi_assign_diag32_tile<XT, false, true>(smem, c, f, bt, map, wg0, b, 0, prior_alpha, 1.0, consider_unassigned, n_new, zbuf, probe_ll,
+                                            probe_ld, FbtList{}, n_moved);
+}
+
 // What both entry points do once their arguments are checked: the tiles of block b mapped to workgroups (m: FBI_T entries
 // each), with cov_type 2 the token-likelihood table formed, the logits placed (LDS, or the bounded workspace and several
-// launches), the launches.  tok: the lists of segk_fbt_assign (NULL: items).
+// launches), the launches.  tok: the lists of segk_fbt_assign (NULL: items).  n_moved (items only): the MAP half in place of
+// the draws -- the tile's logits are then FBI_T + 1 rows, the last one the prior terms pz, and the same placement rule holds for
+// the 65 rows (cov_type 2: pz alone, K_max <= 1024 doubles of LDS).
 static int32_t fbi_launch(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, const FbbMap &m, int32_t s_lo,
                           int32_t s_n, int32_t b, const int32_t *n_utts, int most, uint64_t sweep, double anneal_temp,
                           int32_t consider_unassigned, const int32_t *new_tok, int32_t *n_new, double *probe_ll, int64_t probe_ld,
-                          const FbtList *tok, void *stream)
+                          const FbtList *tok, void *stream, int32_t *n_moved = nullptr)
 {
     const int n_wg = m.off[s_n];
     hipStream_t st = (hipStream_t)stream;
@@ -452,14 +556,16 @@ static int32_t fbi_launch(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm 
     size_t lds = 0;
     int per_launch = n_wg;
     double *zbuf = nullptr;
+    const int rows = FBI_T + (n_moved ? 1 : 0);             // rows of a tile's logits
     if (f->cov_type == 2) {
         if (!tok && consider_unassigned) {
             hipLaunchKernelGGL(k_fbi_mark, dim3((unsigned)((most + 255) / 256), (unsigned)s_n), dim3(256), 0, st, *bt, s_lo, b, n_new);
             SEGK_LAUNCH_CHECK();
         }
         if (int rc = segk_fcb_token_ll(ctx, c, f, bt, s_lo, s_n, b, n_utts, new_tok, n_new, &fc_ll, &fc_ucap, stream)) return rc;
+        if (n_moved) lds = (size_t)f->K_max * sizeof(double);
     } else {
-        const size_t stage = fbi_stage_doubles(c->D) * sizeof(double), tile = (size_t)FBI_T * f->K_max * sizeof(double);
+        const size_t stage = fbi_stage_doubles(c->D) * sizeof(double), tile = (size_t)rows * f->K_max * sizeof(double);
         SEGK_REQUIRE(stage <= FBI_LDS_MAX, "the rows and the staged slots of a tile do not fit in LDS");
         if (stage + tile <= FBI_LDS_MAX) {
             lds = stage + tile;
@@ -468,34 +574,36 @@ static int32_t fbi_launch(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm 
             const int mib = segk_env_int("SEGK_FBI_Z_MIB", FBI_Z_MIB);
             const size_t cap = ((size_t)(mib > 0 ? mib : FBI_Z_MIB) << 20) / tile;
             per_launch = cap < 1 ? 1 : (cap < (size_t)n_wg ? (int)cap : n_wg);
-            const int64_t need = (int64_t)per_launch * FBI_T * f->K_max;
+            const int64_t need = (int64_t)per_launch * rows * f->K_max;
             if (int rc = segk_ws_grow(ctx, &ctx->fbi_z, &ctx->fbi_z_n, need, (size_t)need * sizeof(double), st)) return rc;
             zbuf = ctx->fbi_z;
         }
     }
     const FbtList none = {};
-#define SEGK_FBI(XT, COV, TOK)                                                                                                  \
+#define SEGK_FBI(XT, COV, TOK, MAP)                                                                                             \
     do {                                                                                                                        \
-        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbi_assign<XT, COV, TOK>, lds));                                            \
+        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbi_assign<XT, COV, TOK, MAP>, lds));                                       \
         for (int wg0 = 0; wg0 < n_wg; wg0 += per_launch) {                                                                      \
             const int n = n_wg - wg0 < per_launch ? n_wg - wg0 : per_launch;                                                    \
-            hipLaunchKernelGGL((k_fbi_assign<XT, COV, TOK>), dim3((unsigned)n), dim3(FBI_NT), lds, st, *c, *f, *bt, m, wg0, b,   \
-                               sweep, f->alpha, anneal_temp, consider_unassigned ? 1 : 0, n_new, zbuf, fc_ll, fc_ucap, probe_ll, \
-                               probe_ld, tok ? *tok : none);                                                                    \
+            hipLaunchKernelGGL((k_fbi_assign<XT, COV, TOK, MAP>), dim3((unsigned)n), dim3(FBI_NT), lds, st, *c, *f, *bt, m, wg0, \
+                               b, sweep, f->alpha, anneal_temp, consider_unassigned ? 1 : 0, n_new, zbuf, fc_ll, fc_ucap,       \
+                               probe_ll, probe_ld, tok ? *tok : none, n_moved);                                                 \
         }                                                                                                                       \
     } while (0)
-#define SEGK_FBI_COV(XT, TOK)                                                                                                   \
+#define SEGK_FBI_COV(XT, TOK, MAP)                                                                                              \
     do {                                                                                                                        \
-        if (f->cov_type == 0) SEGK_FBI(XT, 0, TOK);                                                                             \
-        else if (f->cov_type == 1) SEGK_FBI(XT, 1, TOK);                                                                        \
-        else SEGK_FBI(XT, 2, TOK);                                                                                              \
+        if (f->cov_type == 0) SEGK_FBI(XT, 0, TOK, MAP);                                                                        \
+        else if (f->cov_type == 1) SEGK_FBI(XT, 1, TOK, MAP);                                                                   \
+        else SEGK_FBI(XT, 2, TOK, MAP);                                                                                         \
     } while (0)
     if (c->x_dtype == SEGK_F32) {
-        if (tok) SEGK_FBI_COV(float, true);
-        else SEGK_FBI_COV(float, false);
+        if (tok) SEGK_FBI_COV(float, true, false);
+        else if (n_moved) SEGK_FBI_COV(float, false, true);
+        else SEGK_FBI_COV(float, false, false);
     } else {
-        if (tok) SEGK_FBI_COV(double, true);
-        else SEGK_FBI_COV(double, false);
+        if (tok) SEGK_FBI_COV(double, true, false);
+        else if (n_moved) SEGK_FBI_COV(double, false, true);
+        else SEGK_FBI_COV(double, false, false);
     }
 #undef SEGK_FBI_COV
 #undef SEGK_FBI
@@ -506,13 +614,16 @@ static int32_t fbi_launch(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm 
 // fbi_launch for the float32 form (segk_fbi_assign_diag32 / segk_fbt_assign_diag32): the placement rule with this form's byte
 // counts -- the logits in LDS while fbi32_stage_bytes(D) + 512 (K_max | 1) <= FBI_LDS_MAX, else in the bounded workspace of the
 // context (SEGK_FBI_Z_MIB) and several launches -- then the launches.  tok: the lists of segk_fbt_assign_diag32 (NULL: items).
-static int32_t fbi32_launch(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, const FbbMap &m, int32_t s_n,
-                            int32_t b, uint64_t sweep, double anneal_temp, int32_t consider_unassigned, int32_t *n_new,
-                            double *probe_ll, int64_t probe_ld, const FbtList *tok, void *stream)
+// n_moved (items only; segk_fbi_assign_map_diag32): the MAP kernel, 65 rows of K_max | 1 doubles per tile (520 (K_max | 1)
+// bytes) under the same rule.
+static int32_t fbi32_launch_form(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, const FbbMap &m,
+                                 int32_t s_n, int32_t b, uint64_t sweep, double anneal_temp, int32_t consider_unassigned, int32_t *n_new,
+                                 double *probe_ll, int64_t probe_ld, const FbtList *tok, void *stream, int32_t *n_moved)
 {
     const int n_wg = m.off[s_n];
     hipStream_t st = (hipStream_t)stream;
-    const size_t stage = fbi32_stage_bytes(c->D), tile = (size_t)FBI_T * fbi32_ldl(f->K_max) * sizeof(double);
+    const int rows = FBI_T + (n_moved ? 1 : 0);             // rows of a tile's logits: with the MAP half one more, pz
+    const size_t stage = fbi32_stage_bytes(c->D), tile = (size_t)rows * fbi32_ldl(f->K_max) * sizeof(double);
     SEGK_REQUIRE(stage <= FBI_LDS_MAX, "the rows and the staged slots of a tile do not fit in LDS");
     size_t lds = stage + tile;
     int per_launch = n_wg;
@@ -522,7 +633,7 @@ static int32_t fbi32_launch(segk_ctx *ctx, const segk_corpus *c, const segk_fbgm
         const int mib = segk_env_int("SEGK_FBI_Z_MIB", FBI_Z_MIB);
         const size_t cap = ((size_t)(mib > 0 ? mib : FBI_Z_MIB) << 20) / tile;
         per_launch = cap < 1 ? 1 : (cap < (size_t)n_wg ? (int)cap : n_wg);
-        const int64_t need = (int64_t)per_launch * FBI_T * fbi32_ldl(f->K_max);
+        const int64_t need = (int64_t)per_launch * rows * fbi32_ldl(f->K_max);
         if (int rc = segk_ws_grow(ctx, &ctx->fbi_z, &ctx->fbi_z_n, need, (size_t)need * sizeof(double), st)) return rc;
         zbuf = ctx->fbi_z;
     }
@@ -537,16 +648,37 @@ static int32_t fbi32_launch(segk_ctx *ctx, const segk_corpus *c, const segk_fbgm
                                tok ? *tok : none);                                                                              \
         }                                                                                                                       \
     } while (0)
+#define SEGK_FBI32_MAP(XT)                                                                                                      \
+    do {                                                                                                                        \
+        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbi_assign_map_diag32<XT>, lds));                                           \
+        for (int wg0 = 0; wg0 < n_wg; wg0 += per_launch) {                                                                      \
+            const int n = n_wg - wg0 < per_launch ? n_wg - wg0 : per_launch;                                                    \
+            hipLaunchKernelGGL(k_fbi_assign_map_diag32<XT>, dim3((unsigned)n), dim3(FBI32_NT), lds, st, *c, *f, *bt, m, wg0, b, \
+                               f->alpha, consider_unassigned ? 1 : 0, n_new, zbuf, probe_ll, probe_ld, n_moved);                \
+        }                                                                                                                       \
+    } while (0)
     if (c->x_dtype == SEGK_F32) {
         if (tok) SEGK_FBI32(float, true);
+        else if (n_moved) SEGK_FBI32_MAP(float);
         else SEGK_FBI32(float, false);
     } else {
         if (tok) SEGK_FBI32(double, true);
+        else if (n_moved) SEGK_FBI32_MAP(double);
         else SEGK_FBI32(double, false);
     }
+#undef SEGK_FBI32_MAP
 #undef SEGK_FBI32
     SEGK_LAUNCH_CHECK();
     return SEGK_OK;
+}
+
+// ... the sampled kernel (segk_fbi_assign_diag32 / segk_fbt_assign_diag32)
+static int32_t fbi32_launch(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, const FbbMap &m, int32_t s_n,
+                            int32_t b, uint64_t sweep, double anneal_temp, int32_t consider_unassigned, int32_t *n_new,
+                            double *probe_ll, int64_t probe_ld, const FbtList *tok, void *stream)
+{
+    return fbi32_launch_form(ctx, c, f, bt, m, s_n, b, sweep, anneal_temp, consider_unassigned, n_new, probe_ll, probe_ld, tok, stream,
+                             nullptr);
 }
 
 // what both entry points ask of their arguments beyond the corpus' shape
@@ -664,6 +796,57 @@ int32_t segk_fbi_assign_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_f
     if (int rc = fbi_item_map(n_items, s_lo, s_n, &m, &most)) return rc;
     if (m.off[s_n] == 0) return SEGK_OK;
     return fbi32_launch(ctx, c, f, bt, m, s_n, b, sweep, anneal_temp, consider_unassigned, n_new, probe_ll, probe_ld, nullptr, stream);
+}
+
+// The item half of a step of a MAP sweep (FBGMM.map_assign(sync="batch"); fbgmm.py:465-494 on slots, in place of the draws of
+// fbgmm.py:436-460): segk_fbi_assign's checks, map and launches with the MAP half.
+int32_t segk_fbi_assign_map(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,
+                            int32_t s_n, int32_t b, const int32_t *n_items, uint64_t sweep, int32_t consider_unassigned,
+                            const int32_t *new_tok, int32_t *n_new, double *probe_ll, int64_t probe_ld, int32_t *n_moved,
+                            void *stream)
+{
+    SEGK_REQUIRE(ctx && c && f && bt && n_items && new_tok && n_new && n_moved, "NULL argument");
+    if (f->lm_unigram) {
+        segk_set_error("segk_fbi_assign_map: the stand-alone batch sweep takes no language model");
+        return SEGK_ERR_UNSUPPORTED;
+    }
+    SEGK_REQUIRE(!c->vec_ids && !c->band_ids && c->N_max == 1 && c->n_utt == c->n_emb,
+                 "a corpus of items: one one-landmark utterance per row, no span tables");
+    if (int rc = fbi_check(c, f, bt, s_lo, s_n, b, probe_ll, probe_ld, "segk_fbi_assign_map")) return rc;
+    FbbMap m;
+    int most = 0;
+    if (int rc = fbi_item_map(n_items, s_lo, s_n, &m, &most)) return rc;
+    if (m.off[s_n] == 0) return SEGK_OK;
+    return fbi_launch(ctx, c, f, bt, m, s_lo, s_n, b, n_items, most, sweep, 1.0, consider_unassigned, new_tok, n_new, probe_ll, probe_ld,
+                      nullptr, stream, n_moved);
+}
+
+int32_t segk_fbi_assign_map_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,
+                                   int32_t s_n, int32_t b, const int32_t *n_items, uint64_t sweep, int32_t consider_unassigned,
+                                   const int32_t *new_tok, int32_t *n_new, double *probe_ll, int64_t probe_ld, int32_t *n_moved,
+                                   void *stream)
+{
+    SEGK_REQUIRE(ctx && c && f && bt && n_items && new_tok && n_new && n_moved, "NULL argument");
+    if (f->cov_type != 1) {
+        segk_set_error("segk_fbi_assign_map_diag32: the float32 item step exists for diagonal components (cov_type 1) only, got "
+                       "cov_type %d (fixed-variance and full-covariance components go through segk_fbi_assign_map)", (int)f->cov_type);
+        return SEGK_ERR_UNSUPPORTED;
+    }
+    if (f->lm_unigram) {
+        segk_set_error("segk_fbi_assign_map_diag32: the stand-alone batch sweep takes no language model");
+        return SEGK_ERR_UNSUPPORTED;
+    }
+    SEGK_REQUIRE(bt->tab32 && bt->centre && bt->prior_rows,
+                 "the float32 item step needs segk_fbatch.tab32 (written by segk_fbb_prepare), .centre and .prior_rows");
+    SEGK_REQUIRE(!c->vec_ids && !c->band_ids && c->N_max == 1 && c->n_utt == c->n_emb,
+                 "a corpus of items: one one-landmark utterance per row, no span tables");
+    if (int rc = fbi_check(c, f, bt, s_lo, s_n, b, probe_ll, probe_ld, "segk_fbi_assign_map_diag32")) return rc;
+    FbbMap m;
+    int most = 0;
+    if (int rc = fbi_item_map(n_items, s_lo, s_n, &m, &most)) return rc;
+    if (m.off[s_n] == 0) return SEGK_OK;
+    return fbi32_launch_form(ctx, c, f, bt, m, s_n, b, sweep, 1.0, consider_unassigned, n_new, probe_ll, probe_ld, nullptr, stream,
+                             n_moved);
 }
 
 int32_t segk_fbi_assign_orphans(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,

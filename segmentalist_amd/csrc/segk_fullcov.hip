@@ -678,11 +678,13 @@ __global__ __launch_bounds__(FC_NT) void k_fc_assign(segk_corpus c, segk_fbgmm f
 // FBGMM.gibbs_sample's inner loop (fbgmm.py:352-405) over the rows ids[0 .. n) (NULL: rows 0 .. n) in order, one
 // workgroup: cache the old component (statistics, factor, logdet, constant, count) in LDS, del_item with its refresh,
 // logits, draw, then restore the cache (same component, no component deleted) or add_item with its refresh.
+// MAP (segk_fbgmm_map_items): the MAP form of k_fbgmm_gibbs_items, described there -- fc_logits mode 2, the first maximum, no
+// uniform read, *n_moved += the items that took the add_item branch without re-founding their own singleton.
 // ---------------------------------------------------------------------------------------
-template <typename XT>
+template <typename XT, bool MAP = false>
 __global__ __launch_bounds__(FC_NT) void k_fc_gibbs_items(segk_corpus c, segk_fbgmm f, const int32_t *ids, int64_t n,
                                                          int consider_unassigned, double anneal_temp, const double *ustream,
-                                                         int64_t *ucursor, int64_t ucap, int32_t *status)
+                                                         int64_t *ucursor, int64_t ucap, int32_t *status, int32_t *n_moved)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char *end;
@@ -694,6 +696,7 @@ __global__ __launch_bounds__(FC_NT) void k_fc_gibbs_items(segk_corpus c, segk_fb
     int *sh_i = S.ctl + FC_SHI;
     double &sh_lp = S.dctl[0], &sh_kc = S.dctl[1];
     long long &sh_cnt = *(long long *)(S.dctl + 2);
+    int moved = 0;                                           // MAP (workgroup-uniform: every term below is)
     if (tid == 0) shK = *f.K;
     __syncthreads();
     for (int64_t t = 0; t < n; t++) {
@@ -716,10 +719,11 @@ __global__ __launch_bounds__(FC_NT) void k_fc_gibbs_items(segk_corpus c, segk_fb
         fc_del_item<XT>(c, f, e, &shK, sh_i, S);
         __syncthreads();
         const int K = shK;
-        fc_logits<XT>(c, f, e, 1, K, S);
-        fb_draw_component(f, S.z, S.red, 0, anneal_temp, ustream, ucursor, ucap, status, K, &sh_k);
+        fc_logits<XT>(c, f, e, MAP ? 2 : 1, K, S);
+        fb_draw_component(f, S.z, S.red, MAP ? 1 : 0, anneal_temp, ustream, ucursor, ucap, status, K, &sh_k);
         __syncthreads();
         const int k_new = sh_k;
+        if (MAP && !(k_new == k_old && K == K_old) && !(K == K_old - 1 && k_new == K)) moved++;
         if (k_new == k_old && K == K_old) {                      // restore_component_from_stats (:397-400)
             for (int d = tid; d < D; d += nt) f.stat_a[(int64_t)kc * D + d] = ca[d];
             for (int i = tid; i < D * D; i += nt) {
@@ -739,6 +743,7 @@ __global__ __launch_bounds__(FC_NT) void k_fc_gibbs_items(segk_corpus c, segk_fb
     }
     __syncthreads();
     if (tid == 0) *f.K = shK;
+    if (MAP && tid == 0) *n_moved += moved;
 }
 
 // ======================================================================================
@@ -894,13 +899,20 @@ int segk_fc_assign(const segk_corpus *c, segk_fbgmm *f, int utt, int map_assign,
 }
 
 int segk_fc_gibbs_items(const segk_corpus *c, segk_fbgmm *f, const int32_t *ids, int64_t n, int consider_unassigned,
-                        double anneal_temp, const double *ustream, int64_t *ucursor, int64_t ucap, int32_t *status, void *stream)
+                        double anneal_temp, const double *ustream, int64_t *ucursor, int64_t ucap, int32_t *status, void *stream,
+                        int32_t *n_moved)
 {
     const size_t lds = fc_lds_bytes(f->K_max, c->D) + (size_t)(2 * c->D * c->D + c->D) * sizeof(double);
     FC_DISPATCH_XT(c, {
-        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fc_gibbs_items<XT>, lds));
-        hipLaunchKernelGGL(k_fc_gibbs_items<XT>, dim3(1), dim3(FC_NT), lds, (hipStream_t)stream, *c, *f, ids, n, consider_unassigned,
-                           anneal_temp, ustream, ucursor, ucap, status);
+        if (n_moved) {                                       // the MAP sweep of segk_fbgmm_map_items
+            SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fc_gibbs_items<XT, true>, lds));
+            hipLaunchKernelGGL((k_fc_gibbs_items<XT, true>), dim3(1), dim3(FC_NT), lds, (hipStream_t)stream, *c, *f, ids, n,
+                               consider_unassigned, anneal_temp, ustream, ucursor, ucap, status, n_moved);
+        } else {
+            SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fc_gibbs_items<XT>, lds));
+            hipLaunchKernelGGL(k_fc_gibbs_items<XT>, dim3(1), dim3(FC_NT), lds, (hipStream_t)stream, *c, *f, ids, n,
+                               consider_unassigned, anneal_temp, ustream, ucursor, ucap, status, n_moved);
+        }
     });
     SEGK_LAUNCH_CHECK();
     return SEGK_OK;

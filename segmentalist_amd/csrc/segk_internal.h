@@ -204,7 +204,8 @@ int segk_fc_pred_vector(const segk_corpus *c, const segk_fbgmm *f, int64_t row, 
 int segk_fc_assign(const segk_corpus *c, segk_fbgmm *f, int utt, int map_assign, double anneal_temp, const int32_t *new_tok,
                    const int32_t *n_new, const double *ustream, int64_t *ucursor, int64_t ucap, int32_t *status, void *stream);
 int segk_fc_gibbs_items(const segk_corpus *c, segk_fbgmm *f, const int32_t *ids, int64_t n, int consider_unassigned,
-                        double anneal_temp, const double *ustream, int64_t *ucursor, int64_t ucap, int32_t *status, void *stream);
+                        double anneal_temp, const double *ustream, int64_t *ucursor, int64_t ucap, int32_t *status, void *stream,
+                        int32_t *n_moved);      // n_moved != NULL: the MAP sweep of segk_fbgmm_map_items (no uniform is read)
 
 // A workspace the context owns, grown on demand: *buf replaced by a fresh allocation of `bytes`.  Refuses during a graph capture
 // (workspaces must exist before it), waits for `st` first (work in flight may still use the old block), frees the old block.

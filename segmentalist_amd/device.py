@@ -974,6 +974,15 @@ class DeviceFbgmm(object):
                                              len(uniforms), ptr(self.status), _abi.stream()))
         return int(cur.item())
 
+    def map_items(self, consider_unassigned=True):
+        """One MAP sweep of the serial chain over all rows in index order (fbgmm.py:352-405 with map_assign_i's choice in
+        place of the draw; segk_fbgmm_map_items).  Returns the number of items that moved."""
+        torch = _torch()
+        moved = torch.zeros(1, dtype=torch.int32, device=self.K.device)
+        check(self._L.segk_fbgmm_map_items(self._ctx, self._cp(), C.byref(self.f), None, int(self.corpus.n_emb),
+                                           1 if consider_unassigned else 0, ptr(self.status), ptr(moved), _abi.stream()))
+        return int(moved.item())
+
     def set_uniform_stream(self, u):
         self.ustream = to_dev(u, np.float64)
         self.ucursor.zero_()
@@ -1537,7 +1546,8 @@ class FbgmmItemSweeper(object):
     segk_fbb_partials(b).  The statistics kernels see the items as a corpus of one-landmark utterances: new_tok[i] = i,
     n_new[i] = does item i hold a slot.  One process, no language model.
     score_precision: "f64", or "f32" for diagonal components -- the Student-t terms of the item likelihoods in float32 on
-    the hardware logarithm (segk_fbi_assign_diag32); statistics, logits and draws stay fp64."""
+    the hardware logarithm (segk_fbi_assign_diag32); statistics, logits and draws stay fp64.
+    sweep(map_assign=True) is a MAP sweep (segk_fbi_assign_map / _map_diag32 in the item half)."""
 
     def __init__(self, df, n_gibbs_blocks=8, n_stat_blocks=8, seed=0, group=None, score_precision="f64"):
         torch = _torch()
@@ -1619,6 +1629,7 @@ class FbgmmItemSweeper(object):
         I32 = C.c_int32 * self.S
         self._n_items = [I32(*[int(ur[s, b, 1] - ur[s, b, 0]) for s in range(self.S)]) for b in range(self.B)]
         self.probe_ll = None             # a [N, K_max] float64 device tensor: the likelihood part of the logits (tests)
+        self.n_moved = torch.zeros(1, dtype=torch.int32, device=dev)     # the moved items of the last MAP sweep
         self.in_batch_state = False
         self.sweep_index = 0
 
@@ -1637,20 +1648,37 @@ class FbgmmItemSweeper(object):
             check(L.segk_fbb_partials(ctx, cp, fp, bp, 0, self.S, b, ptr(self.new_tok), ptr(self.n_new), st))
         self.in_batch_state = True
 
-    def sweep(self, anneal_temp=1.0, consider_unassigned=True):
-        """One sweep = n_gibbs_blocks steps, all enqueued on the current stream."""
+    def sweep(self, anneal_temp=1.0, consider_unassigned=True, map_assign=False):
+        """One sweep = n_gibbs_blocks steps, all enqueued on the current stream.
+        map_assign: a MAP sweep (specification tests/fbgmm_items_map.py) -- every considered item takes the first slot of
+        the largest log(alpha / K_max + n_k) + loglik_k (segk_fbi_assign_map / _map_diag32: no temperature, no uniform);
+        the device counter behind `moved()` is zeroed on the stream first and counts the items whose slot changed.  The
+        sweep takes one value of sweep_index like any other."""
         if not self.in_batch_state:
             self.enter()
         L, ctx, cp, fp, bp, st = self._args()
         pl = self.probe_ll
-        assign = L.segk_fbi_assign_diag32 if self.score_diag32 else L.segk_fbi_assign
+        if map_assign:
+            self.n_moved.zero_()
+            assign = L.segk_fbi_assign_map_diag32 if self.score_diag32 else L.segk_fbi_assign_map
+        else:
+            assign = L.segk_fbi_assign_diag32 if self.score_diag32 else L.segk_fbi_assign
         for b in range(self.B):
             check(L.segk_fbb_prepare(ctx, cp, fp, bp, b, st))
-            check(assign(ctx, cp, fp, bp, 0, self.S, b, self._n_items[b], self.sweep_index, float(anneal_temp),
-                         1 if consider_unassigned else 0, ptr(self.new_tok), ptr(self.n_new), ptr(pl),
-                         pl.shape[1] if pl is not None else 0, st))
+            if map_assign:
+                check(assign(ctx, cp, fp, bp, 0, self.S, b, self._n_items[b], self.sweep_index,
+                             1 if consider_unassigned else 0, ptr(self.new_tok), ptr(self.n_new), ptr(pl),
+                             pl.shape[1] if pl is not None else 0, ptr(self.n_moved), st))
+            else:
+                check(assign(ctx, cp, fp, bp, 0, self.S, b, self._n_items[b], self.sweep_index, float(anneal_temp),
+                             1 if consider_unassigned else 0, ptr(self.new_tok), ptr(self.n_new), ptr(pl),
+                             pl.shape[1] if pl is not None else 0, st))
             check(L.segk_fbb_partials(ctx, cp, fp, bp, 0, self.S, b, ptr(self.new_tok), ptr(self.n_new), st))
         self.sweep_index += 1
+
+    def moved(self):
+        """Items whose slot the last MAP sweep changed (reads the device counter back: waits for the sweep)."""
+        return int(self.n_moved.item())
 
     def reassign_orphans(self, was_assigned):
         """The orphan pass of FBGMM.set_K(..., sync="batch") (specification tests/fbgmm_set_k.py), enqueued on the current

@@ -157,10 +157,11 @@ class FBGMM(object):
             self._sweeper.sweep_index = self._sweep_index
         return self._sweeper
 
-    def batch_sweep_async(self, anneal_temp=1, consider_unassigned=True):
+    def batch_sweep_async(self, anneal_temp=1, consider_unassigned=True, map_assign=False):
         """Enqueue one batch-synchronous sweep over the items; results stay on the device (materialise() brings
-        `components` up to date)."""
-        self._get_sweeper().sweep(float(anneal_temp), consider_unassigned)
+        `components` up to date).  map_assign: a MAP sweep (see map_assign; anneal_temp is not used), its moved items
+        counted on the device."""
+        self._get_sweeper().sweep(float(anneal_temp), consider_unassigned, map_assign)
 
     def materialise(self):
         """Bring the reference's view (components.K / assignments / statistics) up to date with the batch state."""
@@ -242,6 +243,55 @@ class FBGMM(object):
             for key in sorted(record_dict):
                 info += ", " + key + ": " + str(record_dict[key][-1])
             logger.info(info)
+        return record_dict
+
+    def map_assign(self, n_iter, consider_unassigned=True, sync=None, until_converged=False):
+        """`n_iter` MAP sweeps over the items: the hard assignment of map_assign_i (fbgmm.py:465-494) in place of the draw
+        of a Gibbs sweep -- the way a sampler run is settled into a reproducible labelling.
+        sync: None = the mode the object was built with.
+          "sequential"  per considered item in index order cache_component_stats, del_item, k = the first maximum of
+                        log(alpha / K_max + counts) + log predictive (no lms), `k > K -> K`, then restore or add_item
+                        (fbgmm.py:352-405 with 371-389 replaced by 475-491), one kernel per sweep; fp64.
+          "batch"       the blocked sweeps of gibbs_sample(sync="batch") with the first slot of the largest logit in place
+                        of the draw (specification tests/fbgmm_items_map.py); the likelihoods in the model's
+                        score_precision; each sweep takes one value of the sweep counter.
+        No random.random() and no uniform of batch_seed is consumed.  Returns the record of gibbs_sample without
+        "anneal_temp" and with "n_moved": per sweep the items whose component (batch: slot) changed.  A sweep with
+        n_moved == 0 is a fixed point: every later MAP sweep changes nothing.  until_converged: stop after the first such
+        sweep; n_iter is then the cap."""
+        assert sync in (None, "sequential", "batch")
+        sync = self.sync if sync is None else sync
+        if sync == "batch":
+            sw = self._get_sweeper()        # (the refusals, before anything runs)
+        else:
+            self._leave_batch()
+        c = self.components
+        dev = c.dev
+        if sync != "batch" and dev.lm is not None:
+            raise SegkError("map_assign: map_assign_i has no language-model variant")
+        record_dict = {k: [] for k in ["sample_time", "log_marg", "log_prob_z", "log_prob_X_given_z", "components", "n_moved"]}
+        start_time = time.time()
+        for i_iter in range(n_iter):
+            if sync == "batch":
+                self.batch_sweep_async(1, consider_unassigned, map_assign=True)
+                self.materialise()              # the record reads the reference's view
+                n_moved = sw.moved()
+            else:
+                n_moved = dev.map_items(consider_unassigned)
+            dev.check_status()
+            record_dict["sample_time"].append(time.time() - start_time)
+            start_time = time.time()
+            record_dict["log_marg"].append(self.log_marg())
+            record_dict["log_prob_z"].append(self.log_prob_z())
+            record_dict["log_prob_X_given_z"].append(self.log_prob_X_given_z())
+            record_dict["components"].append(c.K)
+            record_dict["n_moved"].append(n_moved)
+            info = "iteration: " + str(i_iter)
+            for key in sorted(record_dict):
+                info += ", " + key + ": " + str(record_dict[key][-1])
+            logger.info(info)
+            if until_converged and n_moved == 0:
+                break
         return record_dict
 
     def get_n_assigned(self):

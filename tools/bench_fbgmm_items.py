@@ -10,6 +10,10 @@ sweeps" comes from it.
 --route serial     FBGMM.gibbs_sample(sweeps), the serial chain over the items: the record's sample_time of every sweep (host
                    wall time: the sweep's uniforms, one kernel that walks the items, its synchronisation)
 The segmenter and serial routes use nothing this tool's commit added, so the file also runs on an older checkout.
+--settle N         N sampled batch sweeps before anything is timed (items and serial routes): a chain that has left its start
+--map              the MAP sweeps of FBGMM.map_assign.  items: after the sampled sweeps are timed, --sweeps calls of
+                   batch_sweep_async(map_assign=True) timed the same way in the same process (a second line, "items-MAP");
+                   serial: map_assign(sweeps, sync="sequential") in place of gibbs_sample
 Prints the median, the range and items/s per shape; --shapes picks from SHAPES by name."""
 import argparse
 import os
@@ -67,12 +71,21 @@ def main():
     ap.add_argument("--sweeps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--score-precision", choices=("f64", "f32"), default="f64")
+    ap.add_argument("--settle", type=int, default=0)
+    ap.add_argument("--map", action="store_true")
     args = ap.parse_args()
     import torch
     from segmentalist_amd.fbgmm import FBGMM
     torch.cuda.set_device(0)
     if args.score_precision != "f64" and args.route != "items":
         ap.error("--score-precision applies to --route items")
+    if (args.map or args.settle) and args.route == "segmenter":
+        ap.error("--map and --settle apply to the items and serial routes")
+
+    def line(name, route, ms, occupied):
+        med = float(np.median(ms))
+        print("%-10s %-9s | sweep median %9.3f ms (%9.3f - %9.3f) | %8.2f sweeps/s | %12.0f items/s | K = %d after the run"
+              % (name, route, med, min(ms), max(ms), 1e3 / med, args.n * 1e3 / med, occupied), flush=True)
     print("route %s (%s) on %s: N %d, K_max %d, B x S %d x %d, %d sweeps after %d" % (
         args.route, args.score_precision, torch.cuda.get_device_name(0), args.n, args.k_max, args.blocks, args.slices, args.sweeps,
         args.warmup), flush=True)
@@ -86,10 +99,22 @@ def main():
         if args.route == "items":
             m = FBGMM(X, prior, 1.0, args.k_max, assign, covariance_type=cov, n_gibbs_blocks=args.blocks, n_stat_blocks=args.slices,
                       **kw)
+            for _ in range(args.settle):
+                m.batch_sweep_async()
             ms = timed(torch, m.batch_sweep_async, args.sweeps, args.warmup)
             m.materialise()
             m.components.dev.check_status()
             occupied = m.components.K
+            if args.map:
+                line(name, args.route, ms, occupied)
+                ms = timed(torch, lambda: m.batch_sweep_async(map_assign=True), args.sweeps, args.warmup)
+                moved = m._get_sweeper().moved()
+                m.materialise()
+                m.components.dev.check_status()
+                occupied = m.components.K
+                print("   (the last MAP sweep moved %d items)" % moved)
+                line(name, "items-MAP", ms, occupied)
+                continue
         elif args.route == "segmenter":
             from segmentalist_amd.unigram_acoustic_wordseg import UnigramAcousticWordseg
             keys = ["u%07d" % i for i in range(args.n)]
@@ -104,17 +129,21 @@ def main():
             seg._df.check_status()
             occupied = seg.acoustic_model.components.K
         else:
-            m = FBGMM(X, prior, 1.0, args.k_max, assign, covariance_type=cov)
-            m.gibbs_sample(min(args.warmup, 1))
+            bkw = dict(n_gibbs_blocks=args.blocks, n_stat_blocks=args.slices) if args.settle else {}
+            m = FBGMM(X, prior, 1.0, args.k_max, assign, covariance_type=cov, **bkw)
+            for _ in range(args.settle):
+                m.batch_sweep_async()
+            m.materialise()
+            sweep = (lambda n: m.map_assign(n, sync="sequential")) if args.map else m.gibbs_sample
+            sweep(min(args.warmup, 1))
             t0 = time.time()
-            rec = m.gibbs_sample(args.sweeps)
+            rec = sweep(args.sweeps)
             wall = time.time() - t0
             ms = [1e3 * t for t in rec["sample_time"]]
             occupied = rec["components"][-1]
-            print("   (wall time of the %d calls with their records: %.2f s)" % (args.sweeps, wall))
-        med = float(np.median(ms))
-        print("%-10s %-9s | sweep median %9.3f ms (%9.3f - %9.3f) | %8.2f sweeps/s | %12.0f items/s | K = %d after the run"
-              % (name, args.route, med, min(ms), max(ms), 1e3 / med, args.n * 1e3 / med, occupied), flush=True)
+            print("   (wall time of the %d calls with their records: %.2f s%s)"
+                  % (args.sweeps, wall, "; moved per sweep %s" % rec["n_moved"] if args.map else ""))
+        line(name, args.route + ("-MAP" if args.map and args.route == "serial" else ""), ms, occupied)
 
 
 if __name__ == "__main__":
