@@ -79,7 +79,9 @@ const char *segk_last_error(void);
  *     buffer through which the sums of token lists that did not change since the previous call are kept.  Two entry points
  *     added, no signature or structure changed
  *  15 (no bump) segk_fbi_assign_map, segk_fbi_assign_map_diag32, segk_fbgmm_map_items: the MAP sweeps of FBGMM.map_assign, batch
- *     and serial.  Three entry points added, no signature or structure changed                                             */
+ *     and serial.  Three entry points added, no signature or structure changed
+ *  15 (no bump) segk_fbi_predict, segk_fbi_predict_diag32: labels, log densities and log responsibilities of held-out rows
+ *     (FBGMM.predict / score_samples / predict_log_proba).  Two entry points added, no signature or structure changed       */
 #define SEGK_ABI_VERSION 15
 int32_t segk_abi_version(void);
 
@@ -974,6 +976,41 @@ int32_t segk_fbi_assign_map_diag32(segk_ctx *ctx, const segk_corpus *c, const se
                                    int32_t s_lo, int32_t s_n, int32_t b, const int32_t *n_items, uint64_t sweep,
                                    int32_t consider_unassigned, const int32_t *new_tok, int32_t *n_new, double *probe_ll,
                                    int64_t probe_ld, int32_t *n_moved, void *stream);
+/* Held-out rows against the fitted bank of the stand-alone mixture model (added at ABI 15 without a bump; FBGMM.predict,
+ * score_samples, predict_log_proba; specification tests/fbgmm_predict.py).  The M rows of Xq [dev] (the dtype of c->X, ldq
+ * elements between rows) are in no model; each is treated as an UNASSIGNED item appended to X, against the statistics of all
+ * items that hold a slot -- `bt` in the state segk_fbb_prepare(-1) leaves (counts n_k, N_a = sum n_k in scal[0], the predictive
+ * parameters of every slot).  With ll_k(x) the log predictive of slot k (an empty slot: the prior predictive of the row, which
+ * the call evaluates into prior_rows_q [dev] [M] first -- cov_type 0 / 1 the arithmetic of segk_fbb_prior_rows, cov_type 2 that
+ * of `cached_log_prior`, gaussian_components.py:125-127), per row:
+ *   label [dev] [M]          the first index of max_k log(alpha / K_max + n_k) + ll_k -- map_assign_i's choice, fbgmm.py:475-488:
+ *                            no lms, no softmax, all empty slots tie and the first wins -- in the numbering of the reference's
+ *                            view: an occupied slot its rank among the occupied slots in increasing slot order (what
+ *                            segk_fbb_canonical assigns), an empty slot K, "would found a new component" (:489-490);
+ *   log_density [dev] [M]    logsumexp_k lms (log(alpha / K_max + n_k) - log(N_a + alpha)) + ll_k: log_marg_i of the appended
+ *                            item, fbgmm.py:256-285;
+ *   log_resp [dev]           log_resp[r * resp_ld + k] = lms log(alpha / K_max + n_k) + ll_k - logsumexp(.), the normalised
+ *                            log_prob_z of fbgmm.py:436-451 at temperature 1, in SLOT order (the caller permutes columns).
+ * Each of the three may be NULL.  probe_ll [dev] (tests; may be NULL): probe_ll[r * probe_ld + k] = ll_k of row r.  The call
+ * reads the model and writes only its outputs and workspaces of the context: bt->slot, the partial sums, f->* and prior_c stay
+ * as they are, no uniform and no sweep counter is read.  The likelihood bits are those segk_fbi_assign forms for the same row
+ * and statistics (cov_type 2: segk_fcb_token_ll's, on a view of the query walked in chunks whose table stays within
+ * SEGK_FBI_Z_MIB).  One launch per 64 rows x all slots; a tile's logits in LDS where rows, staged slots, the prior terms, the
+ * rank table and logits fit in 144 KiB, else in the bounded workspace of segk_fbi_assign and several launches.
+ * Refused before any launch: a language model, cov_type 2 beyond D <= 64 / K_max <= 1024 with SEGK_ERR_UNSUPPORTED; a corpus with
+ * span tables, D > 256, NULL Xq or prior_rows_q with M > 0, resp_ld or probe_ld < K_max, missing slot tables with SEGK_ERR_ARG.
+ * M = 0 returns SEGK_OK and launches nothing.                                                                              */
+int32_t segk_fbi_predict(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, const void *Xq,
+                         int64_t ldq, int64_t M, double *prior_rows_q, int32_t *label, double *log_density,
+                         double *log_resp, int64_t resp_ld, double *probe_ll, int64_t probe_ld, void *stream);
+/* segk_fbi_predict on the float32 item likelihoods of segk_fbi_assign_diag32 (added at ABI 15 without a bump; the model's
+ * score_precision="f32"): fbb_term32 on float32 rows and bt->tab32, the centre subtracted in fp64, then the same fp64 epilogue
+ * on logit rows of K_max | 1 doubles.  Refused before any launch: cov_type 0 or 2 and a language model with
+ * SEGK_ERR_UNSUPPORTED; bt->tab32 or bt->centre NULL and the argument errors of segk_fbi_predict with SEGK_ERR_ARG.          */
+int32_t segk_fbi_predict_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt,
+                                const void *Xq, int64_t ldq, int64_t M, double *prior_rows_q, int32_t *label,
+                                double *log_density, double *log_resp, int64_t resp_ld, double *probe_ll, int64_t probe_ld,
+                                void *stream);
 /* Acoustic-model batch sweeps of the unigram segmenter (added at ABI 15 without a bump; the inner sweeps of
  * UnigramAcousticWordseg.gibbs_sample(n, am_n_iter=m), unigram_acoustic_wordseg.py:440-443 -- FBGMM.gibbs_sample(m,
  * consider_unassigned=False) over the currently assigned tokens -- as a blocked sampler on the segmenter's batch state;

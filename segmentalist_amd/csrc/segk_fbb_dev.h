@@ -181,3 +181,6 @@ int segk_fcb_score(const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch 
 int segk_fcb_token_ll(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int s_lo, int s_n, int b,
                       const int32_t *n_utts, const int32_t *new_tok, const int32_t *n_new, const double **ll, int *u_cap,
                       void *stream);
+// the prior predictive (`cached_log_prior`, :125-127) of rows that are not the model's: `c` a view of them (X, ldx, n_emb), written
+// to out [c->n_emb] (segk_fbi_predict: the query rows; segk_fbb_prior_rows with cov_type 2 copies the TRAINING rows' cache)
+int segk_fc_prior_rows_view(const segk_corpus *c, const segk_fbgmm *f, double *out, void *stream);

@@ -748,7 +748,467 @@ static int32_t fbt_lists(segk_ctx *ctx, const segk_corpus *c, const segk_fbatch 
     return SEGK_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// FBGMM.predict / score_samples / predict_log_proba (segk_fbi_predict, segk_fbi_predict_diag32; specification
+// tests/fbgmm_predict.py): query rows that are not in the model, scored against the statistics of ALL items that hold a slot
+// (the state segk_fbb_prepare(-1) leaves) -- an unassigned item appended to X, as fbgmm.py:256-285 (log_marg_i), :436-445 (the
+// logits of gibbs_sample_inside_loop_i) and :475-491 (map_assign_i) see it.  Nothing of the model is written.
+//
+//   k_fbi_predict<XT, COV>     the tile of k_fbi_assign -- 64 query rows per workgroup, a lane each, eight waves over the slots --
+//                              and, for cov_type 0 / 1, a SIBLING of its likelihood half, operation for operation (rows staged
+//                              fp64 [D][64], 16 slots' (mean, q) per pass, dimensions ascending, lconst - half acc, an empty slot
+//                              the row's prior predictive), so the bits are those a batch sweep forms for the same row and
+//                              statistics.  The existing instantiations keep their code.  cov_type 2: the epilogue alone, over the
+//                              table k_fcb_token_ll formed on a view of the query rows.
+//   k_fbi_predict_diag32<XT>   the likelihood half of k_fbi_assign_diag32 (fbb_term32, float32 rows and tables, sixteen waves),
+//                              logit rows of K_max | 1 doubles, the same fp64 epilogue.
+//   epilogue, a wave per row   label: fbb_map_row on pz[k] = log(alpha / K_max + n_k) (no lms), renumbered to the reference's
+//                              view -- an occupied slot its rank among the occupied slots, an empty one K --; density: the
+//                              wave's maximum of t_k = lms pz[k] - lms log(N_a + alpha) + ll[k], exp(t_k - max) summed per lane
+//                              over k = lane, lane + 64, ..., then fb_wave_sum (a fixed order: the value does not depend on
+//                              the launch shape); log_resp[k] = t_k - density (the constant cancels), slot order.
+// LDS: the staged rows and slots of the sibling, then pz [K_max] doubles, the logits where they fit, the rank table [K_max + 1]
+// ints (the last entry K).  A plain grid of independent workgroups: no atomic, no barrier across workgroups.
+// ---------------------------------------------------------------------------------------
+static __host__ __device__ __forceinline__ size_t fbi_predict_rank_bytes(int KM) { return (((size_t)KM + 1) * sizeof(int32_t) + 7) & ~(size_t)7; }
+// bytes of a workgroup beside its logits, fp64 form (COV 2: the two tables alone) and float32 form
+static __host__ __device__ __forceinline__ size_t fbi_predict_fixed_bytes(int D, int KM, bool fullcov)
+{
+    return (fullcov ? 0 : fbi_stage_doubles(D) * sizeof(double)) + (size_t)KM * sizeof(double) + fbi_predict_rank_bytes(KM);
+}
+static __host__ __device__ __forceinline__ size_t fbi32_predict_fixed_bytes(int D, int KM)
+{
+    return fbi32_stage_bytes(D) + (size_t)KM * sizeof(double) + fbi_predict_rank_bytes(KM);
+}
+
+// the workgroup's tables: the prior terms of the label, and per slot the number of occupied slots before it (wave 0: a ballot
+// per 64 slots); the caller's barrier publishes them
+static __device__ __forceinline__ void fbi_predict_tables(const segk_fbatch &bt, int KM, double prior_alpha, double *pz, int32_t *rank, int tid,
+                                                          int nt)
+{
+    for (int k = tid; k < KM; k += nt) pz[k] = log(prior_alpha / (double)KM + bt.cnt[k]);                   // fbgmm.py:475-479
+    if (tid < 64) {
+        int run = 0;
+        for (int k0 = 0; k0 < KM; k0 += 64) {
+            const int k = k0 + tid;
+            const bool occ = k < KM && bt.cnt[k] > 0.0;
+            const unsigned long long m = __ballot(occ);
+            if (k < KM) rank[k] = run + __popcll(m & ((1ull << tid) - 1ull));
+            run += __popcll(m);
+        }
+        if (tid == 0) rank[KM] = run;
+    }
+}
+
+// the epilogue: rows r = w, w + nw, ... of the tile, a wave each; ll: the tile's likelihoods, ldl doubles between rows (read only)
+static __device__ __forceinline__ void fbi_predict_rows(const segk_fbgmm &f, const segk_fbatch &bt, int KM, double prior_alpha, const double *pz,
+                                                        const int32_t *rank, const double *ll, int64_t ldl, int nr, int64_t out0, int w,
+                                                        int nw, int lane, int32_t *label, double *log_density, double *log_resp,
+                                                        int64_t resp_ld)
+{
+    const double lms = f.lms, lt = lms * log(bt.scal[0] + prior_alpha);     // fbgmm.py:268-272
+    for (int r = w; r < nr; r += nw) {
+        const double *zr = ll + (int64_t)r * ldl;
+        const int64_t i = out0 + r;
+        if (label) {
+            const int k = fbb_map_row(pz, zr, KM, lane);    // fbgmm.py:475-488
+            if (lane == 0) label[i] = bt.cnt[k] > 0.0 ? rank[k] : rank[KM];                                   // :489-490
+        }
+        if (!log_density && !log_resp) continue;
+        auto t_of = [&](int k) -> double { return lms * pz[k] - lt + zr[k]; };
+        double mx = NEG_INF_D;
+        for (int k = lane; k < KM; k += 64) {
+            const double v = t_of(k);
+            mx = v > mx ? v : mx;
+        }
+        mx = fb_wave_max(mx, false);
+        double sv = 0.0;
+        for (int k = lane; k < KM; k += 64) sv += exp(t_of(k) - mx);
+        const double dens = log(fb_wave_sum(sv)) + mx;
+        if (log_density && lane == 0) log_density[i] = dens;
+        if (log_resp)
+            for (int k = lane; k < KM; k += 64) log_resp[i * resp_ld + k] = t_of(k) - dens;
+    }
+}
+
+// cq: a view of the query rows of this launch (X its first row, n_emb their number); out0: the index of that row in the
+// caller's arrays.  zbuf: the launch's logits where they do not fit in LDS.  fc_ll (COV 2): row r of the view at fc_ll + r K_max.
+template <typename XT, int COV>
+__global__ __launch_bounds__(FBI_NT) void k_fbi_predict(segk_corpus cq, segk_fbgmm f, segk_fbatch bt, int64_t out0, double prior_alpha,
+                                                       const double *prior_rows_q, double *zbuf, const double *fc_ll, int32_t *label,
+                                                       double *log_density, double *log_resp, int64_t resp_ld, double *probe_ll,
+                                                       int64_t probe_ld)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int D = cq.D, KM = f.K_max, tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);        // (wave-uniform, and known to be)
+    const int64_t i0 = (int64_t)blockIdx.x * FBI_T;
+    if (i0 >= cq.n_emb) return;                             // a tile at or beyond the rows (workgroup-uniform)
+    const int nr = cq.n_emb - i0 < FBI_T ? (int)(cq.n_emb - i0) : FBI_T;
+    double *pz;
+    int32_t *rank;
+    const double *ll;
+    if constexpr (COV == 2) {
+        pz = (double *)smem;
+        rank = (int32_t *)(pz + KM);
+        fbi_predict_tables(bt, KM, prior_alpha, pz, rank, tid, FBI_NT);
+        ll = fc_ll + i0 * KM;
+        __syncthreads();
+    } else {
+        double *xs = (double *)smem;                        // [D][FBI_T]: the lanes' rows side by side
+        double *pm = xs + (size_t)FBI_T * D;                // [FBI_KC][D][2]: (mean, q) of the staged slots
+        pz = pm + 2 * (size_t)FBI_KC * D;
+        double *lw = zbuf ? zbuf + (int64_t)blockIdx.x * FBI_T * KM : pz + KM;
+        rank = (int32_t *)(zbuf ? pz + KM : pz + KM + (size_t)FBI_T * KM);
+        fbi_predict_tables(bt, KM, prior_alpha, pz, rank, tid, FBI_NT);     // (published by the barriers of the likelihood loop)
+        const XT *X = (const XT *)cq.X;
+        for (int j = tid; j < FBI_T * D; j += FBI_NT) {
+            const int r = j / D, d = j - r * D;
+            xs[d * FBI_T + r] = r < nr ? (double)X[(i0 + r) * cq.ldx + d] : 0.0;
+        }
+        const bool valid = lane < nr;
+        const double lp = valid ? prior_rows_q[out0 + i0 + lane] : 0.0;         // an empty slot's likelihood: the row's prior predictive
+        for (int k0 = 0; k0 < KM; k0 += FBI_KC) {
+            __syncthreads();                                // (the rows are staged; the previous pass has read its parameters)
+            for (int j = tid; j < FBI_KC * D; j += FBI_NT) {
+                const int kk = j % FBI_KC, d = j / FBI_KC, k = k0 + kk;
+                pm[((size_t)kk * D + d) * 2] = k < KM ? bt.mean_t[(int64_t)d * KM + k] : 0.0;
+                pm[((size_t)kk * D + d) * 2 + 1] = k < KM ? bt.q_t[(int64_t)d * KM + k] : 0.0;
+            }
+            __syncthreads();
+            const int kw = k0 + w * FBI_KW;                 // this wave's slots kw .. kw + FBI_KW - 1 (wave-uniform)
+            bool occ[FBI_KW];
+            double acc[FBI_KW];
+            bool any = false;
+#pragma unroll
+            for (int j = 0; j < FBI_KW; j++) {
+                occ[j] = kw + j < KM && bt.cnt[kw + j] > 0.0;
+                acc[j] = 0.0;
+                any = any || occ[j];
+            }
+            if (any) {
+                const double *pw = pm + (size_t)(w * FBI_KW) * D * 2;
+                for (int d = 0; d < D; d++) {
+                    const double x = xs[d * FBI_T + lane];
+#pragma unroll
+                    for (int j = 0; j < FBI_KW; j++) {
+                        if (!occ[j]) continue;
+                        const double m = pw[((size_t)j * D + d) * 2], q = pw[((size_t)j * D + d) * 2 + 1];
+                        const double delta = m - x;
+                        if (COV == 0) acc[j] += (delta * delta) * q;
+                        else acc[j] += log(1. + (delta * delta) * q);
+                    }
+                }
+            }
+            if (valid) {
+#pragma unroll
+                for (int j = 0; j < FBI_KW; j++) {
+                    const int k = kw + j;
+                    if (k >= KM) continue;
+                    lw[(int64_t)lane * KM + k] = occ[j] ? bt.lconst[k] - bt.half[k] * acc[j] : lp;
+                }
+            }
+        }
+        __syncthreads();
+        ll = lw;
+    }
+    if (probe_ll)               // the likelihood part of the logits, as the epilogue uses it
+        for (int j = tid; j < nr * KM; j += FBI_NT) {
+            const int r = j / KM, k = j - r * KM;
+            probe_ll[(out0 + i0 + r) * probe_ld + k] = ll[(int64_t)r * KM + k];
+        }
+    fbi_predict_rows(f, bt, KM, prior_alpha, pz, rank, ll, KM, nr, out0 + i0, w, FBI_NT / 64, lane, label, log_density, log_resp, resp_ld);
+}
+
+template <typename XT>
+__global__ __launch_bounds__(FBI32_NT) void k_fbi_predict_diag32(segk_corpus cq, segk_fbgmm f, segk_fbatch bt, int64_t out0,
+                                                              double prior_alpha, const double *prior_rows_q, double *zbuf,
+                                                              int32_t *label, double *log_density, double *log_resp, int64_t resp_ld,
+                                                              double *probe_ll, int64_t probe_ld)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int D = cq.D, KM = f.K_max, ldl = fbi32_ldl(KM), tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);        // (wave-uniform, and known to be)
+    const int64_t i0 = (int64_t)blockIdx.x * FBI_T;
+    if (i0 >= cq.n_emb) return;                             // a tile at or beyond the rows (workgroup-uniform)
+    const int nr = cq.n_emb - i0 < FBI_T ? (int)(cq.n_emb - i0) : FBI_T;
+    float2 *pm = (float2 *)smem;                            // [FBI32_KC][D]: (mean - centre, q) of the staged slots
+    float *xs = (float *)(pm + (size_t)FBI32_KC * D);       // [D][FBI32_XS]: the lanes' centred rows side by side
+    double *pz = (double *)(smem + fbi32_stage_bytes(D));
+    double *ll = zbuf ? zbuf + (int64_t)blockIdx.x * FBI_T * ldl : pz + KM;         // [FBI_T][ldl]
+    int32_t *rank = (int32_t *)(zbuf ? pz + KM : pz + KM + (size_t)FBI_T * ldl);
+    fbi_predict_tables(bt, KM, prior_alpha, pz, rank, tid, FBI32_NT);       // (published by the barriers of the likelihood loop)
+    const XT *X = (const XT *)cq.X;
+    for (int j = tid; j < FBI_T * D; j += FBI32_NT) {
+        const int r = j / D, d = j - r * D;
+        xs[d * FBI32_XS + r] = r < nr ? (float)((double)X[(i0 + r) * cq.ldx + d] - bt.centre[d]) : 0.f;
+    }
+    const bool valid = lane < nr;
+    const double lp = valid ? prior_rows_q[out0 + i0 + lane] : 0.0;        // an empty slot's likelihood: the row's prior predictive
+    const float *tm = bt.tab32, *tq = bt.tab32 + (int64_t)D * KM;
+    for (int k0 = 0; k0 < KM; k0 += FBI32_KC) {
+        __syncthreads();                                    // (the rows are staged; the previous pass has read its parameters)
+        for (int j = tid; j < FBI32_KC * D; j += FBI32_NT) {
+            const int kk = j % FBI32_KC, d = j / FBI32_KC, k = k0 + kk;
+            pm[kk * D + d] = k < KM ? make_float2(tm[(int64_t)d * KM + k], tq[(int64_t)d * KM + k]) : make_float2(0.f, 0.f);
+        }
+        __syncthreads();
+        const int kw = k0 + w * FBI32_KW;                   // this wave's slots kw .. kw + FBI32_KW - 1 (wave-uniform)
+        bool occ[FBI32_KW];
+        float acc[FBI32_KW];
+        bool any = false;
+#pragma unroll
+        for (int j = 0; j < FBI32_KW; j++) {
+            occ[j] = kw + j < KM && bt.cnt[kw + j] > 0.0;
+            acc[j] = 0.f;
+            any = any || occ[j];
+        }
+        if (any) {
+            const float2 *pw = pm + (size_t)(w * FBI32_KW) * D;
+#pragma unroll 4
+            for (int d = 0; d < D; d++) {
+                const float x = xs[d * FBI32_XS + lane];
+#pragma unroll
+                for (int j = 0; j < FBI32_KW; j++) {
+                    const float2 mq = pw[j * D + d];
+                    acc[j] += fbb_term32(mq.x, mq.y, x);
+                }
+            }
+        }
+        if (valid) {
+#pragma unroll
+            for (int j = 0; j < FBI32_KW; j++) {
+                const int k = kw + j;
+                if (k >= KM) continue;
+                ll[(int64_t)lane * ldl + k] = occ[j] ? bt.lconst[k] - bt.half[k] * (0.6931471805599453 * (double)acc[j]) : lp;
+            }
+        }
+    }
+    __syncthreads();
+    if (probe_ll)               // the likelihood part of the logits, as the epilogue uses it
+        for (int j = tid; j < nr * KM; j += FBI32_NT) {
+            const int r = j / KM, k = j - r * KM;
+            probe_ll[(out0 + i0 + r) * probe_ld + k] = ll[(int64_t)r * ldl + k];
+        }
+    fbi_predict_rows(f, bt, KM, prior_alpha, pz, rank, ll, ldl, nr, out0 + i0, w, FBI32_NT / 64, lane, label, log_density, log_resp,
+                     resp_ld);
+}
+
+// the tables of the view of the query rows k_fcb_token_ll walks (cov_type 2): one cell [0, n) of one slice and one block, row i
+// its own one-landmark utterance with one token
+__global__ __launch_bounds__(256) void k_fbi_predict_view(int32_t *range, int32_t *new_tok, int32_t *n_new, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) {
+        range[0] = 0;
+        range[1] = n;
+    }
+    if (i < n) {
+        new_tok[i] = i;
+        n_new[i] = 1;
+    }
+}
+
+// a view of the query rows [r0, r0 + n) as a corpus of items
+static segk_corpus fbi_query_view(const segk_corpus *c, const void *Xq, int64_t ldq, int64_t r0, int64_t n)
+{
+    segk_corpus v = {};
+    const size_t es = c->x_dtype == SEGK_F32 ? sizeof(float) : sizeof(double);
+    v.X = (const char *)Xq + (size_t)r0 * (size_t)ldq * es;
+    v.x_dtype = c->x_dtype;
+    v.D = c->D;
+    v.n_emb = n;
+    v.ldx = ldq;
+    v.n_utt = (int32_t)n;
+    v.N_max = 1;
+    return v;
+}
+
+// what both predict entry points ask of their arguments; *done: nothing to launch
+static int fbi_predict_check(const segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, const void *Xq,
+                             int64_t ldq, int64_t M, const double *prior_rows_q, const double *log_resp, int64_t resp_ld,
+                             const double *probe_ll, int64_t probe_ld, const char *who, bool *done)
+{
+    *done = false;
+    SEGK_REQUIRE(ctx && c && f && bt, "NULL argument");
+    if (f->lm_unigram) {
+        segk_set_error("%s: held-out rows are scored by the stand-alone mixture model, which takes no language model", who);
+        return SEGK_ERR_UNSUPPORTED;
+    }
+    SEGK_REQUIRE(!c->vec_ids && !c->band_ids, "a corpus of items: no span tables");
+    SEGK_REQUIRE(c->x_dtype == SEGK_F32 || c->x_dtype == SEGK_F64, "unsupported dtype");
+    SEGK_REQUIRE(f->cov_type >= 0 && f->cov_type <= 2, "cov_type must be 0 (fixed), 1 (diag) or 2 (full)");
+    SEGK_REQUIRE(c->D > 0 && c->D <= 256, "batch mode supports D <= 256");
+    SEGK_REQUIRE(f->K_max >= 1 && f->K_max <= 8192, "K_max");
+    SEGK_REQUIRE(M >= 0 && M < ((int64_t)1 << 31), "query rows");
+    SEGK_REQUIRE(bt->cnt && bt->mean_t && bt->q_t && bt->lconst && bt->half && bt->scal,
+                 "batch state (the slot tables and totals segk_fbb_prepare(-1) writes)");
+    SEGK_REQUIRE(!log_resp || resp_ld >= f->K_max, "log_resp leading dimension");
+    SEGK_REQUIRE(!probe_ll || probe_ld >= f->K_max, "probe leading dimension");
+    if (f->cov_type == 2) {
+        segk_fbatch with_rows = *bt;                        // (segk_fcb_check asks for prior rows: the query's stand for them)
+        with_rows.prior_rows = const_cast<double *>(prior_rows_q ? prior_rows_q : bt->prior_rows);
+        if (int rc = segk_fcb_check(c, f, &with_rows, who)) return rc;
+    }
+    if (M == 0) {
+        *done = true;
+        return SEGK_OK;
+    }
+    SEGK_REQUIRE(Xq && ldq >= c->D, "query rows (Xq, ldq)");
+    SEGK_REQUIRE(prior_rows_q, "prior_rows_q: M doubles of workspace");
+    return SEGK_OK;
+}
+
+// the prior predictive of every query row (an empty slot's likelihood) into prior_rows_q
+static int fbi_predict_prior_rows(const segk_corpus *c, const segk_fbgmm *f, const void *Xq, int64_t ldq, int64_t M, double *prior_rows_q,
+                                  void *stream)
+{
+    const segk_corpus v = fbi_query_view(c, Xq, ldq, 0, M);
+    if (f->cov_type == 2) return segk_fc_prior_rows_view(&v, f, prior_rows_q, stream);
+    return segk_fbb_prior_rows(nullptr, &v, f, prior_rows_q, stream);
+}
+
+// tiles of a launch and the workspace of their logits, where a tile's do not fit in LDS beside `fixed` bytes
+static int fbi_predict_place(segk_ctx *ctx, size_t fixed, size_t tile, int n_tiles, size_t *lds, int *per_launch, double **zbuf, hipStream_t st)
+{
+    SEGK_REQUIRE(fixed <= FBI_LDS_MAX, "the rows and the staged slots of a tile do not fit in LDS");
+    *per_launch = n_tiles;
+    *zbuf = nullptr;
+    if (fixed + tile <= FBI_LDS_MAX) {
+        *lds = fixed + tile;
+        return SEGK_OK;
+    }
+    *lds = fixed;
+    const size_t cap = segk_env_mib("SEGK_FBI_Z_MIB", FBI_Z_MIB) / tile;
+    *per_launch = cap < 1 ? 1 : (cap < (size_t)n_tiles ? (int)cap : n_tiles);
+    const int64_t need = (int64_t)*per_launch * (int64_t)(tile / sizeof(double));
+    if (int rc = segk_ws_grow(ctx, &ctx->fbi_z, &ctx->fbi_z_n, need, (size_t)need * sizeof(double), st)) return rc;
+    *zbuf = ctx->fbi_z;
+    return SEGK_OK;
+}
+
 extern "C" {
+
+int32_t segk_fbi_predict(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, const void *Xq,
+                         int64_t ldq, int64_t M, double *prior_rows_q, int32_t *label, double *log_density, double *log_resp,
+                         int64_t resp_ld, double *probe_ll, int64_t probe_ld, void *stream)
+{
+    bool done;
+    if (int rc = fbi_predict_check(ctx, c, f, bt, Xq, ldq, M, prior_rows_q, log_resp, resp_ld, probe_ll, probe_ld, "segk_fbi_predict", &done))
+        return rc;
+    if (done) return SEGK_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = fbi_predict_prior_rows(c, f, Xq, ldq, M, prior_rows_q, stream)) return rc;
+    const int KM = f->K_max;
+    if (f->cov_type == 2) {
+        // the second form: the likelihood table by k_fcb_token_ll on a view of a chunk of the query, then the epilogue kernel.
+        // The chunks keep the table within the bound of the logits' workspace (SEGK_FBI_Z_MIB)
+        int64_t ch = (int64_t)((segk_env_mib("SEGK_FBI_Z_MIB", FBI_Z_MIB) / ((size_t)KM * sizeof(double))) / FBI_T) * FBI_T;
+        ch = ch < FBI_T ? FBI_T : ch;
+        ch = ch > M ? M : ch;
+        const int64_t need = 2 + 2 * ch;
+        if (int rc = segk_ws_grow(ctx, &ctx->fbt_tok, &ctx->fbt_tok_n, need, (size_t)need * sizeof(int32_t), st)) return rc;
+        int32_t *range = ctx->fbt_tok, *new_tok = range + 2, *n_new = new_tok + ch;
+        hipLaunchKernelGGL(k_fbi_predict_view, dim3((unsigned)((ch + 255) / 256)), dim3(256), 0, st, range, new_tok, n_new, (int)ch);
+        SEGK_LAUNCH_CHECK();
+        const size_t lds = fbi_predict_fixed_bytes(c->D, KM, true);
+        for (int64_t r0 = 0; r0 < M; r0 += ch) {
+            const int64_t n = M - r0 < ch ? M - r0 : ch;
+            const segk_corpus v = fbi_query_view(c, Xq, ldq, r0, n);
+            segk_fbatch btv = *bt;                          // one cell: the rows of the view (those beyond n_emb are left alone)
+            btv.n_slices = btv.n_blocks = 1;
+            btv.utt_range = btv.row_range = range;
+            btv.prior_rows = prior_rows_q + r0;
+            const int32_t n_utts[1] = {(int32_t)n};
+            const double *fc_ll = nullptr;
+            int ucap = 0;
+            if (int rc = segk_fcb_token_ll(ctx, &v, f, &btv, 0, 1, 0, n_utts, new_tok, n_new, &fc_ll, &ucap, stream)) return rc;
+            const unsigned grid = (unsigned)((n + FBI_T - 1) / FBI_T);
+            if (c->x_dtype == SEGK_F32)
+                hipLaunchKernelGGL((k_fbi_predict<float, 2>), dim3(grid), dim3(FBI_NT), lds, st, v, *f, *bt, r0, f->alpha,
+                                   (const double *)prior_rows_q, (double *)nullptr, fc_ll, label, log_density, log_resp, resp_ld,
+                                   probe_ll, probe_ld);
+            else
+                hipLaunchKernelGGL((k_fbi_predict<double, 2>), dim3(grid), dim3(FBI_NT), lds, st, v, *f, *bt, r0, f->alpha,
+                                   (const double *)prior_rows_q, (double *)nullptr, fc_ll, label, log_density, log_resp, resp_ld,
+                                   probe_ll, probe_ld);
+            SEGK_LAUNCH_CHECK();
+        }
+        return SEGK_OK;
+    }
+    const int64_t n_tiles = (M + FBI_T - 1) / FBI_T;
+    size_t lds;
+    int per_launch;
+    double *zbuf;
+    if (int rc = fbi_predict_place(ctx, fbi_predict_fixed_bytes(c->D, KM, false), (size_t)FBI_T * KM * sizeof(double), (int)n_tiles, &lds,
+                                   &per_launch, &zbuf, st))
+        return rc;
+#define SEGK_FBI_PREDICT(XT, COV)                                                                                               \
+    do {                                                                                                                        \
+        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbi_predict<XT, COV>, lds));                                                \
+        for (int64_t t0 = 0; t0 < n_tiles; t0 += per_launch) {                                                                  \
+            const int64_t r0 = t0 * FBI_T, n = M - r0 < (int64_t)per_launch * FBI_T ? M - r0 : (int64_t)per_launch * FBI_T;     \
+            const segk_corpus v = fbi_query_view(c, Xq, ldq, r0, n);                                                            \
+            hipLaunchKernelGGL((k_fbi_predict<XT, COV>), dim3((unsigned)((n + FBI_T - 1) / FBI_T)), dim3(FBI_NT), lds, st, v, *f, \
+                               *bt, r0, f->alpha, (const double *)prior_rows_q, zbuf, (const double *)nullptr, label,           \
+                               log_density, log_resp, resp_ld, probe_ll, probe_ld);                                             \
+        }                                                                                                                       \
+    } while (0)
+    if (c->x_dtype == SEGK_F32) {
+        if (f->cov_type == 0) SEGK_FBI_PREDICT(float, 0);
+        else SEGK_FBI_PREDICT(float, 1);
+    } else {
+        if (f->cov_type == 0) SEGK_FBI_PREDICT(double, 0);
+        else SEGK_FBI_PREDICT(double, 1);
+    }
+#undef SEGK_FBI_PREDICT
+    SEGK_LAUNCH_CHECK();
+    return SEGK_OK;
+}
+
+int32_t segk_fbi_predict_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, const void *Xq,
+                                int64_t ldq, int64_t M, double *prior_rows_q, int32_t *label, double *log_density,
+                                double *log_resp, int64_t resp_ld, double *probe_ll, int64_t probe_ld, void *stream)
+{
+    SEGK_REQUIRE(ctx && c && f && bt, "NULL argument");
+    if (f->cov_type != 1) {
+        segk_set_error("segk_fbi_predict_diag32: the float32 item likelihoods exist for diagonal components (cov_type 1) only, got "
+                       "cov_type %d (fixed-variance and full-covariance components go through segk_fbi_predict)", (int)f->cov_type);
+        return SEGK_ERR_UNSUPPORTED;
+    }
+    bool done;
+    if (int rc = fbi_predict_check(ctx, c, f, bt, Xq, ldq, M, prior_rows_q, log_resp, resp_ld, probe_ll, probe_ld,
+                                   "segk_fbi_predict_diag32", &done))
+        return rc;
+    SEGK_REQUIRE(bt->tab32 && bt->centre, "the float32 item likelihoods need segk_fbatch.tab32 (written by segk_fbb_prepare) and .centre");
+    if (done) return SEGK_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = fbi_predict_prior_rows(c, f, Xq, ldq, M, prior_rows_q, stream)) return rc;
+    const int KM = f->K_max;
+    const int64_t n_tiles = (M + FBI_T - 1) / FBI_T;
+    size_t lds;
+    int per_launch;
+    double *zbuf;
+    if (int rc = fbi_predict_place(ctx, fbi32_predict_fixed_bytes(c->D, KM), (size_t)FBI_T * fbi32_ldl(KM) * sizeof(double), (int)n_tiles,
+                                   &lds, &per_launch, &zbuf, st))
+        return rc;
+#define SEGK_FBI32_PREDICT(XT)                                                                                                  \
+    do {                                                                                                                        \
+        SEGK_CHECK_HIP(segk_dyn_lds((const void *)k_fbi_predict_diag32<XT>, lds));                                              \
+        for (int64_t t0 = 0; t0 < n_tiles; t0 += per_launch) {                                                                  \
+            const int64_t r0 = t0 * FBI_T, n = M - r0 < (int64_t)per_launch * FBI_T ? M - r0 : (int64_t)per_launch * FBI_T;     \
+            const segk_corpus v = fbi_query_view(c, Xq, ldq, r0, n);                                                            \
+            hipLaunchKernelGGL(k_fbi_predict_diag32<XT>, dim3((unsigned)((n + FBI_T - 1) / FBI_T)), dim3(FBI32_NT), lds, st, v,  \
+                               *f, *bt, r0, f->alpha, (const double *)prior_rows_q, zbuf, label, log_density, log_resp, resp_ld, \
+                               probe_ll, probe_ld);                                                                             \
+        }                                                                                                                       \
+    } while (0)
+    if (c->x_dtype == SEGK_F32) SEGK_FBI32_PREDICT(float);
+    else SEGK_FBI32_PREDICT(double);
+#undef SEGK_FBI32_PREDICT
+    SEGK_LAUNCH_CHECK();
+    return SEGK_OK;
+}
 
 int32_t segk_fbi_assign(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, const segk_fbatch *bt, int32_t s_lo,
                         int32_t s_n, int32_t b, const int32_t *n_items, uint64_t sweep, double anneal_temp,

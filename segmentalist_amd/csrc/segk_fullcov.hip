@@ -440,6 +440,19 @@ __global__ __launch_bounds__(256) void k_fc_prior_rows(segk_corpus c, segk_fbgmm
     if (lane == 0) const_cast<double *>(f.prior_c)[(int64_t)c.D * c.D + e] = v;
 }
 
+// ... of rows that are not the model's (segk_fbi_predict: the query rows as a view `c` -- X, ldx, n_emb theirs --, written to
+// `out`): the arithmetic of k_fc_prior_rows.  The view's n_emb is not the model's, so nothing here may derive an address
+// inside prior_c from it (fc_status, fc_prior_rows): fc_prior_pred reads c.D alone
+template <typename XT>
+__global__ __launch_bounds__(256) void k_fc_prior_rows_view(segk_corpus c, segk_fbgmm f, double *out)
+{
+    const int64_t e = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (e >= c.n_emb) return;
+    const double v = fc_prior_pred<XT>(c, f, (const XT *)c.X + e * c.ldx, lane);
+    if (lane == 0) out[e] = v;
+}
+
 // op 1: add_item(item, k)   op 2: del_item(item)   op 4: del_component(k)
 template <typename XT>
 __global__ __launch_bounds__(FC_NT) void k_fc_update(segk_corpus c, segk_fbgmm f, int op, int64_t item, int k_item)
@@ -1251,4 +1264,14 @@ int segk_fcb_token_ll(segk_ctx *ctx, const segk_corpus *c, const segk_fbgmm *f, 
     int rc;
     FC_DISPATCH_XT(c, rc = fcb_token_launch<XT>(c, f, bt, grid, s_lo, b, new_tok, n_new, ctx->fcb_ll, u_most, (hipStream_t)stream););
     return rc;
+}
+
+int segk_fc_prior_rows_view(const segk_corpus *c, const segk_fbgmm *f, double *out, void *stream)
+{
+    SEGK_REQUIRE(c && f && out && f->prior_c && c->D <= FC_DMAX, "cov_type 2: the prior's factor in prior_c, D <= 64");
+    if (c->n_emb == 0) return SEGK_OK;
+    FC_DISPATCH_XT(c, hipLaunchKernelGGL(k_fc_prior_rows_view<XT>, dim3((unsigned)((c->n_emb + 3) / 4)), dim3(256), 0,
+                                          (hipStream_t)stream, *c, *f, out););
+    SEGK_LAUNCH_CHECK();
+    return SEGK_OK;
 }

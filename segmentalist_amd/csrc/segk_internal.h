@@ -72,9 +72,11 @@ struct segk_ctx {
     int64_t fcb_ll_n;            // ... doubles allocated
     double *fbi_z;               // item step of the stand-alone batch sweep (k_fbi_assign; k_fbi_assign_diag32: rows of K_max | 1): [tiles of a launch][FBI_T][K_max] logits where
     int64_t fbi_z_n;             // ... a tile's do not fit in LDS; doubles allocated (bounded: segk_fbitems.hip FBI_Z_MIB)
+                                 // (k_fbi_predict / _diag32, segk_fbi_predict: the tiles of a launch over the query rows, the same bound)
     int32_t *fbt_tok;            // token step of the segmenter's acoustic-model batch sweep (k_fbt_compact): [16] tokens per local slice,
     int64_t fbt_tok_n;           // ... then [3][cap] (row, utterance, position) of the block's tokens; cap = int32 words per list
                                  // (k_fbi_orphans, the orphan pass of FBGMM.set_K: the same layout, an entry (i, i, 0) per orphan)
+                                 // (segk_fbi_predict with cov_type 2: [2] the range of the query view's one cell, then new_tok and n_new [chunk] each)
     // hinted score path (segk_score_hint.hip): the filter's partial top-2 per (range, row), then the hint waves' result per row
     void *hint_part;
     size_t hint_part_bytes;
@@ -145,6 +147,12 @@ static inline int segk_env_int(const char *name, int dflt)
 {
     const char *e = getenv(name);
     return e ? atoi(e) : dflt;
+}
+// a workspace bound given in MiB (a launch-plan switch: another bound, the same results), in bytes; values below 1 mean the default
+static inline size_t segk_env_mib(const char *name, int dflt_mib)
+{
+    const int mib = segk_env_int(name, dflt_mib);
+    return (size_t)(mib > 0 ? mib : dflt_mib) << 20;
 }
 
 // Development switches that ALTER RESULTS (timing ablations, debug modes) or hand raw pointers to kernels exist only in builds

@@ -1547,7 +1547,8 @@ class FbgmmItemSweeper(object):
     n_new[i] = does item i hold a slot.  One process, no language model.
     score_precision: "f64", or "f32" for diagonal components -- the Student-t terms of the item likelihoods in float32 on
     the hardware logarithm (segk_fbi_assign_diag32); statistics, logits and draws stay fp64.
-    sweep(map_assign=True) is a MAP sweep (segk_fbi_assign_map / _map_diag32 in the item half)."""
+    sweep(map_assign=True) is a MAP sweep (segk_fbi_assign_map / _map_diag32 in the item half).
+    predict() labels and scores rows that are not in the model, read-only (segk_fbi_predict / _predict_diag32)."""
 
     def __init__(self, df, n_gibbs_blocks=8, n_stat_blocks=8, seed=0, group=None, score_precision="f64"):
         torch = _torch()
@@ -1700,6 +1701,61 @@ class FbgmmItemSweeper(object):
             check(L.segk_fbb_partials(ctx, cp, fp, bp, 0, self.S, b, ptr(self.new_tok), ptr(self.n_new), st))
         self._was = was                                   # (kept alive: the pass is only enqueued)
         self.sweep_index += 1
+
+    def predict(self, Xq, want_label=True, want_density=True, want_resp=False, device_out=False, probe_ll=None):
+        """Held-out rows against the fitted bank (FBGMM.predict / score_samples / predict_log_proba; specification
+        tests/fbgmm_predict.py; segk_fbi_predict / _predict_diag32): every row of `Xq` [M, D] (a NumPy array or
+        a device tensor, converted to the model's dtype) as an unassigned item appended to X, against the statistics of all
+        items that hold a component.  Returns (labels int64 [M], log densities float64 [M], log responsibilities float64
+        [M, K_max]) in the reference view's numbering -- the K active components in increasing slot order, then the empty
+        ones; a label K means "would found a new component" --, None where not wanted; NumPy, or with device_out device
+        tensors without a synchronisation.  probe_ll: a [M, >= K_max] float64 device tensor that receives the likelihoods in
+        slot order (tests).
+
+        Read-only.  On a batch state: segk_fbb_prepare(-1), then the call -- slots, partial sums and sweep_index stay.  On a
+        serial state: the tables are built from the current assignments (enter()) and dropped again (invalidate(), no
+        materialise()): assignments, K, counts and the serial statistics are not touched.  No uniform is consumed."""
+        torch = _torch()
+        dev = _dev()
+        c = self.df.corpus
+        D, K = c.D, self.df.K_max
+        if isinstance(Xq, torch.Tensor):
+            xq = Xq.detach().to(device=dev, dtype=c.torch_xdtype)
+        else:
+            xq = np.asarray(Xq)
+            xq = to_dev(xq, c.x_np_dtype) if xq.ndim == 2 else xq
+        if xq.ndim != 2 or xq.shape[1] != D:
+            raise SegkError("predict: the query rows must be [M, %d] like the model's X, got shape %s" % (D, tuple(xq.shape)))
+        xq = xq.contiguous()
+        M = int(xq.shape[0])
+        f64 = torch.float64
+        label = torch.zeros(M, dtype=torch.int32, device=dev) if want_label else None
+        dens = torch.zeros(M, dtype=f64, device=dev) if want_density else None
+        resp = torch.zeros((M, K), dtype=f64, device=dev) if want_resp else None
+        if M:
+            prior_q = torch.empty(M, dtype=f64, device=dev)
+            entered = not self.in_batch_state
+            if entered:
+                self.enter()
+            try:
+                L, ctx, cp, fp, bp, st = self._args()
+                check(L.segk_fbb_prepare(ctx, cp, fp, bp, -1, st))
+                call = L.segk_fbi_predict_diag32 if self.score_diag32 else L.segk_fbi_predict
+                check(call(ctx, cp, fp, bp, ptr(xq), D, M, ptr(prior_q), ptr(label), ptr(dens), ptr(resp), K, ptr(probe_ll),
+                           probe_ll.shape[1] if probe_ll is not None else 0, st))
+            finally:
+                if entered:
+                    self.invalidate()
+            if resp is not None:
+                # the reference view's column order: the occupied slots in increasing slot order, then the empty ones
+                order = torch.sort((self.cnt <= 0).to(torch.int8), stable=True).indices
+                resp = resp.index_select(1, order)
+        if label is not None:
+            label = label.to(torch.int64)
+        out = (label, dens, resp)
+        if device_out:
+            return out
+        return tuple(None if t is None else t.cpu().numpy() for t in out)
 
     cell_partials = FbgmmBatchSweeper.cell_partials
 

@@ -294,6 +294,35 @@ class FBGMM(object):
                 break
         return record_dict
 
+    # held-out rows -----------------------------------------------------------------------------------
+    def _predict(self, Xq, device_out, **want):
+        sw = self._get_sweeper()        # (the item sweeper's refusals)
+        return sw.predict(Xq, device_out=device_out, **want)
+
+    def predict(self, Xq, device_out=False):
+        """Labels of held-out rows `Xq` [M, D] (NumPy or a device tensor; converted to the model's dtype): each row is an
+        UNASSIGNED item appended to X, labelled as map_assign_i (fbgmm.py:475-491) would label it against the statistics of
+        all assigned items -- the first maximum of log(alpha / K_max + counts) + log predictive, no lms -- without adding it.
+        int64 [M] in the numbering of `components` (after materialise()); K means "would found a new component".
+
+        Read-only: assignments, K, counts, the statistics, a batch state's slots and partial sums and the sweep counter stay
+        bit for bit; no random.random() and no uniform of batch_seed is consumed.  A model in batch state is used as it
+        stands (no materialise()).  The likelihoods follow score_precision, as map_assign(sync="batch") does.  device_out:
+        a device tensor, without a synchronisation.  Refused on the acoustic model of a segmenter, with more than one rank
+        and beyond the full-covariance limits (D <= 64, K_max <= 1024)."""
+        return self._predict(Xq, device_out, want_label=True, want_density=False, want_resp=False)[0]
+
+    def score_samples(self, Xq, device_out=False):
+        """Log densities of held-out rows, float64 [M]: log_marg_i (fbgmm.py:256-285, lms included) of each row appended
+        unassigned.  Read-only like predict."""
+        return self._predict(Xq, device_out, want_label=False, want_density=True, want_resp=False)[1]
+
+    def predict_log_proba(self, Xq, device_out=False):
+        """Log responsibilities of held-out rows, float64 [M, K_max]: the normalised log_prob_z of
+        gibbs_sample_inside_loop_i (fbgmm.py:436-451) at temperature 1 of each row appended unassigned, columns as in
+        `components`: the K active components, then the empty ones.  Read-only like predict."""
+        return self._predict(Xq, device_out, want_label=False, want_density=False, want_resp=True)[2]
+
     def get_n_assigned(self):
         """Number of assigned items (the reference counts `assignments != -1`): the sum of the component counts, read
         from the device without copying the assignment vector to the host."""
