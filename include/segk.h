@@ -81,7 +81,9 @@ const char *segk_last_error(void);
  *  15 (no bump) segk_fbi_assign_map, segk_fbi_assign_map_diag32, segk_fbgmm_map_items: the MAP sweeps of FBGMM.map_assign, batch
  *     and serial.  Three entry points added, no signature or structure changed
  *  15 (no bump) segk_fbi_predict, segk_fbi_predict_diag32: labels, log densities and log responsibilities of held-out rows
- *     (FBGMM.predict / score_samples / predict_log_proba).  Two entry points added, no signature or structure changed       */
+ *     (FBGMM.predict / score_samples / predict_log_proba).  Two entry points added, no signature or structure changed
+ *  15 (no bump) segk_fbd_decode: MAP boundaries and transcript of held-out utterances (UnigramAcousticWordseg.decode).  One
+ *     entry point added, no signature or structure changed                                                                 */
 #define SEGK_ABI_VERSION 15
 int32_t segk_abi_version(void);
 
@@ -1011,6 +1013,36 @@ int32_t segk_fbi_predict_diag32(segk_ctx *ctx, const segk_corpus *c, const segk_
                                 const void *Xq, int64_t ldq, int64_t M, double *prior_rows_q, int32_t *label,
                                 double *log_density, double *log_resp, int64_t resp_ld, double *probe_ll, int64_t probe_ld,
                                 void *stream);
+/* Held-out UTTERANCES against the fitted bank of the unigram segmenter (added at ABI 15 without a bump;
+ * UnigramAcousticWordseg.decode; specification tests/wordseg_decode.py): the MAP boundaries and the transcript of every
+ * utterance of `cq`, a corpus that is in no model -- its rows are the M candidate embeddings of the held-out utterances, its
+ * span tables (triangles, and the complete band of segk_corpus.band_ids for n_slices_max where N_max > 64) index them.  The
+ * caller has scored and labelled the rows with segk_fbi_predict / _predict_diag32 on `bt` in the state segk_fbb_prepare(-1)
+ * leaves: density [dev] [M] = log_marg_i of the row appended as an unassigned item (fbgmm.py:256-285, lms included), label
+ * [dev] [M] = map_assign_i's choice (fbgmm.py:475-490) in the reference view's numbering.  Per utterance i of N landmarks:
+ *   vec[j] = density[id_j] * dur_j ** time_power_term + wip, -inf where id_j == -1 or dur_j is NaN
+ *            (get_vec_embed_log_probs, unigram_acoustic_wordseg.py:474-511);
+ *   boundaries [dev] uint8 [n_utt, N_max], log_prob [dev] [n_utt]: forward_backward_viterbi(vec, 0.0, N, n_slices_min,
+ *            n_slices_max) (:759-864) from cleared flags -- among equal maxima the shortest span, the reference's stepping back
+ *            from a dead end (:815-825); the flags beyond N are written 0;
+ *   seg_embed / seg_label [dev] int32, seg_density [dev] double, each [n_utt, N_max]: per chosen segment, in landmark order,
+ *            its embedding row id, label[id] and density[id]; a chosen segment whose span has no embedding (only after
+ *            stepping back from a dead end) is kept as (-1, -1, -inf) so that segment j ends at the j-th set flag; the entries
+ *            beyond the count are written (-1, -1, -inf);
+ *   n_seg [dev] int32 [n_utt]: the number of chosen segments.
+ * Every segment is labelled independently against the same statistics: nothing is added to the bank between segments (a
+ * serial Viterbi visit, :252-360, would add each).  The call reads `cq`, density and label and writes its seven outputs:
+ * no mixture model, no batch state, no old boundaries, no uniform, no temperature.  One launch, one workgroup per utterance,
+ * no atomics; the kernel is a copy of the boundary kernel of segk_fbb_segment_map with the slot clearing and the token lists
+ * taken out, in a unit of its own.  The layout is chosen from cq->N_max, whatever corpus the model was trained on.
+ * SEGK_ERR_ARG before any launch: n_slices_min outside {0, 1}; N_max > 64 with n_slices_max == 0 or > 64, without a complete
+ * band (band_ids / band_dur NULL or band_W != n_slices_max), or with a band beyond 160 KiB of LDS (12 N_max W + 24 N_max + 16 +
+ * N_max rounded up to 16 bytes); N_max <= 64 without triangular tables; a NULL output.  n_utt == 0 returns SEGK_OK and
+ * launches nothing.                                                                                                         */
+int32_t segk_fbd_decode(segk_ctx *ctx, const segk_corpus *cq, int32_t n_slices_min, int32_t n_slices_max, double wip,
+                        double time_power_term, const double *density, const int32_t *label, uint8_t *boundaries,
+                        int32_t *seg_embed, int32_t *seg_label, double *seg_density, int32_t *n_seg, double *log_prob,
+                        void *stream);
 /* Acoustic-model batch sweeps of the unigram segmenter (added at ABI 15 without a bump; the inner sweeps of
  * UnigramAcousticWordseg.gibbs_sample(n, am_n_iter=m), unigram_acoustic_wordseg.py:440-443 -- FBGMM.gibbs_sample(m,
  * consider_unassigned=False) over the currently assigned tokens -- as a blocked sampler on the segmenter's batch state;

@@ -1501,6 +1501,105 @@ class FbgmmBatchSweeper(object):
         sc = self.scal.cpu().numpy()
         return self.cnt.cpu().numpy(), float(sc[0]), int(sc[1])
 
+    def check_decode(self, D, N_max, band_W, n_slices_min, n_slices_max):
+        """What decode() refuses, from host values alone (nothing is launched): the limits of segk_fbi_predict and
+        segk_fbd_decode (include/segk.h), each named."""
+        df = self.df
+        if self.world > 1:
+            raise SegkError("decode runs in one process only (%d ranks): held-out utterances are not sharded" % self.world)
+        if df.lm is not None:
+            raise SegkError("decode exists without a language model only: the reference has no Viterbi mode with one")
+        if D != df.corpus.D:
+            raise SegkError("decode: the held-out embeddings have D = %d, the model's have D = %d" % (D, df.corpus.D))
+        if D > 256:
+            raise SegkError("decode supports D <= 256, got %d" % D)
+        if self.fullcov and D > 64:
+            raise SegkError("full-covariance components (cov_type 2) support D <= 64, got %d" % D)
+        if self.fullcov and df.K_max > 1024:
+            raise SegkError("decode takes full-covariance components (cov_type 2) with K_max <= 1024, got %d" % df.K_max)
+        if n_slices_min not in (0, 1):
+            raise SegkError("decode: n_slices_min must be 0 or 1, got %r" % (n_slices_min,))
+        if N_max > 64:
+            if not 1 <= n_slices_max <= 64:
+                raise SegkError("decode takes held-out utterances of more than 64 landmarks (N_max = %d) with a window of 1..64 "
+                                "slices only (n_slices_max = %d)" % (N_max, n_slices_max))
+            if band_W != n_slices_max:
+                raise SegkError("decode takes held-out utterances of more than 64 landmarks (N_max = %d) only when no span longer "
+                                "than the window has an embedding (no complete band for n_slices_max = %d)" % (N_max, n_slices_max))
+            lds = 12 * N_max * band_W + 24 * N_max + 16 + (N_max + 15) // 16 * 16
+            if lds > 160 * 1024:
+                raise SegkError("decode: the banded span table of the longest held-out utterance does not fit in LDS: N_max = %d "
+                                "landmarks, window W = %d: %d bytes needed, %d available" % (N_max, band_W, lds, 160 * 1024))
+
+    def _canonical_tables(self):
+        """The slot tables segk_fbb_prepare(-1) left, COPIED into the reference view's slot order -- the occupied slots in
+        increasing slot order, then the empty ones, the numbering materialise() gives a serial state -- as (a reference to a
+        copy of `bt` that points at the copies, the copies).  A held-out row's density is a sum over the slots in slot order:
+        on these tables a live batch state gives the bits the serial state of the same model gives.  The batch state itself is
+        not touched; nothing is read back."""
+        torch = _torch()
+        order = torch.sort((self.cnt <= 0).to(torch.int8), stable=True).indices
+        ax = 0 if self.fullcov else 1                         # (full covariance: slot-major tables)
+        t = dict(cnt=self.cnt.index_select(0, order), lconst=self.lconst.index_select(0, order),
+                 zconst=self.zconst.index_select(0, order), half=self.half.index_select(0, order),
+                 mean_t=self.mean_t.index_select(ax, order), q_t=self.q_t.index_select(ax, order))
+        if self.tab32 is not None:
+            t["tab32"] = self.tab32.view(-1, self.df.K_max).index_select(1, order).contiguous()
+        bt = _abi.FbatchDev.from_buffer_copy(self.bt)
+        for k, v in t.items():
+            setattr(bt, k, v.data_ptr())
+        return C.byref(bt), (bt, t)
+
+    def decode(self, cq, boundaries, n_slices_min, n_slices_max, wip, time_power_term):
+        """MAP boundaries and transcript of the HELD-OUT utterances of `cq` (a DeviceCorpus that is in no model: its rows are
+        their candidate embeddings) against the frozen statistics -- UnigramAcousticWordseg.decode; specification
+        tests/wordseg_decode.py; DESIGN.md 4.23.  segk_fbb_prepare(-1), one segk_fbi_predict (_diag32 on a sweeper of float32
+        diagonal scores; fp64 everywhere else) over all rows of `cq`, segk_fbd_decode.  Returns a dict of device tensors,
+        enqueued on the current stream, nothing read back: boundaries uint8 [n_utt, N_max], log_prob [n_utt], n_seg int32
+        [n_utt], seg_embed / seg_label int32 and seg_density float64 [n_utt, N_max], label int32 / density float64 [M] (every
+        candidate row), K (int64 scalar: the occupied slots).
+
+        Read-only.  On a batch state slots, partial sums and sweep_index stay; the rows are scored on copies of the slot tables
+        in the reference view's slot order (_canonical_tables), so that the densities are the bits a serial state gives.  On a serial state the tables are built from the
+        current assignments and `boundaries` (the model's own; enter() -- df.new_tok / df.n_new are its workspaces) and dropped
+        again (invalidate(), no materialise()).  No uniform is consumed."""
+        torch = _torch()
+        dev = _dev()
+        self.check_decode(cq.D, cq.N_max, cq.band_W, int(n_slices_min), int(n_slices_max))
+        if cq.x_dtype != self.df.corpus.x_dtype:
+            raise SegkError("decode: the held-out embeddings must have the dtype of the model's")
+        M, n_utt, NM = cq.n_emb, cq.n_utt, cq.N_max
+        f64, i32 = torch.float64, torch.int32
+        label = torch.zeros(max(M, 1), dtype=i32, device=dev)
+        dens = torch.zeros(max(M, 1), dtype=f64, device=dev)
+        prior_q = torch.empty(max(M, 1), dtype=f64, device=dev)
+        out = dict(boundaries=torch.zeros((n_utt, NM), dtype=torch.uint8, device=dev),
+                   log_prob=torch.zeros(n_utt, dtype=f64, device=dev), n_seg=torch.zeros(n_utt, dtype=i32, device=dev),
+                   seg_embed=torch.full((n_utt, NM), -1, dtype=i32, device=dev),
+                   seg_label=torch.full((n_utt, NM), -1, dtype=i32, device=dev),
+                   seg_density=torch.full((n_utt, NM), -np.inf, dtype=f64, device=dev), label=label[:M], density=dens[:M])
+        # the model's corpus as segk_fbi_predict reads it (x_dtype and D): a corpus of items, no span tables
+        cv = _abi.Corpus.from_buffer_copy(self.df.corpus.c)
+        cv.vec_ids = cv.durations = cv.band_ids = cv.band_dur = None
+        entered = not self.in_batch_state
+        if entered:
+            self.enter(boundaries)
+        try:
+            L, ctx, cp, fp, bp, st = self._args()
+            check(L.segk_fbb_prepare(ctx, cp, fp, bp, -1, st))
+            call = L.segk_fbi_predict_diag32 if self.score_diag32 else L.segk_fbi_predict
+            if not entered:
+                bp, canon = self._canonical_tables()          # (kept alive until the calls are enqueued)
+            check(call(ctx, C.byref(cv), fp, bp, ptr(cq.X), cq.ldx, M, ptr(prior_q), ptr(label), ptr(dens), None, 0, None, 0, st))
+            check(L.segk_fbd_decode(ctx, C.byref(cq.c), int(n_slices_min), int(n_slices_max), float(wip), float(time_power_term),
+                                    ptr(dens), ptr(label), ptr(out["boundaries"]), ptr(out["seg_embed"]), ptr(out["seg_label"]),
+                                    ptr(out["seg_density"]), ptr(out["n_seg"]), ptr(out["log_prob"]), st))
+            out["K"] = (self.cnt > 0).sum()
+        finally:
+            if entered:
+                self.invalidate()
+        return out
+
     def invalidate(self):
         """The sequential-mode state was mutated: rebuild the batch state before the next sweep."""
         self.in_batch_state = False

@@ -68,6 +68,7 @@ class UnigramAcousticWordseg(object):
         assert seed_assignments_dict is None or seed_boundaries_dict is not None
         self.n_slices_min = n_slices_min
         self.n_slices_max = n_slices_max
+        self.min_duration = min_duration
         self.beta_sent_boundary = beta_sent_boundary
         self.wip = wip
         self.time_power_term = time_power_term
@@ -201,6 +202,79 @@ class UnigramAcousticWordseg(object):
         if self._sweeper is not None and self._sweeper.in_batch_state:
             self.materialise()
             self._sweeper.invalidate()
+
+    # ------------------------------------------------------------------ held-out utterances
+    def decode(self, embedding_mats, vec_ids_dict, durations_dict, landmarks_dict, device_out=False):
+        """Segment and label HELD-OUT utterances, read-only (specification tests/wordseg_decode.py; segk_fbd_decode,
+        DESIGN.md 4.23).  The four dictionaries are the constructor's, for utterances that are in no model: their candidate
+        embeddings are unassigned items appended to X, seen against the statistics of all tokens that hold a component.
+        Per utterance, with the model's n_slices_min / n_slices_max / min_duration / wip / time_power_term / lms / alpha:
+        the span scores of get_vec_embed_log_probs (:474-511) on the held-out log density of FBGMM.score_samples, the
+        boundaries and log probability of forward_backward_viterbi (:759-864), and for every chosen segment
+        map_assign_i's choice for its embedding (no lms) in the reference view's numbering, as FBGMM.predict reports it: an
+        active component its index, K for "would found a new component".
+
+        One deliberate difference from a serial Viterbi visit (gibbs_sample_i with fb_type "viterbi"): every segment is
+        labelled independently against the same frozen statistics -- nothing is added to the bank between segments, and the
+        model is not changed at all.  No uniform is consumed (`random` and `np.random` stay where they are); fb_type and the
+        temperatures play no part.  A chosen segment whose span has no embedding (only after the DP stepped back from a dead
+        end) is kept with embedding -1, label -1 and log density -inf.
+
+        Returns a `Decoded`; with device_out=True its arrays are device tensors, enqueued without a synchronisation (the flat
+        segment arrays then have n_utt * N_max entries, the first seg_offsets[-1] of them segments).
+        Raises SegkError before any launch for: beta_sent_boundary != -1, more than one rank, a held-out D other than the
+        model's, D > 256, full-covariance components beyond D <= 64 / K_max <= 1024, and a held-out corpus with an
+        utterance of more than 64 landmarks without a window of 1..64 slices that holds every embedding and fits LDS."""
+        labels, cq = self._heldout_corpus(embedding_mats, vec_ids_dict, durations_dict, landmarks_dict)
+        out = self._decode_corpus(labels, cq)
+        return out if device_out else out.numpy()
+
+    def _heldout_corpus(self, embedding_mats, vec_ids_dict, durations_dict, landmarks_dict):
+        """The checks of decode() and the device image of the held-out utterances: (sorted keys, DeviceCorpus or None for an
+        empty set).  Host work and one upload; nothing of the model is read on the device."""
+        from ._abi import SegkError
+        if self.beta_sent_boundary != -1:
+            raise SegkError("decode needs beta_sent_boundary=-1: calc_p_continue supports no other value "
+                            "(unigram_acoustic_wordseg.py:513-531)")
+        sw = self._get_sweeper()
+        if not embedding_mats:
+            sw.check_decode(self._corpus.D, 0, 0, self.n_slices_min, self.n_slices_max)
+            return [], None
+        embeddings, vec_ids, labels = process_embeddings(embedding_mats, vec_ids_dict)
+        embeddings = np.asarray(embeddings)
+        D = embeddings.shape[1] if embeddings.ndim == 2 else -1
+        lengths = [len(landmarks_dict[i]) for i in labels]
+        u = Utterances(lengths, vec_ids, [durations_dict[i] for i in labels], [landmarks_dict[i] for i in labels],
+                       p_boundary_init=0, n_slices_min=self.n_slices_min, n_slices_max=self.n_slices_max,
+                       min_duration=self.min_duration)
+        band = u.complete_band_tables(self.n_slices_max)
+        sw.check_decode(D, u.N_max, band[0].shape[2] if band is not None else 0, self.n_slices_min, self.n_slices_max)
+        if u.vec_ids.max(initial=-1) >= len(embeddings):
+            raise SegkError("decode: a span id names row %d of %d held-out embeddings" % (u.vec_ids.max(), len(embeddings)))
+        return labels, DeviceCorpus(embeddings.astype(self._corpus.x_np_dtype, copy=False), u.vec_ids, u.durations, u.lengths,
+                                    band=band)
+
+    def _decode_corpus(self, labels, cq):
+        """decode() on the device image of the held-out utterances: a `Decoded` of device tensors, nothing read back."""
+        import torch
+        sw = self._get_sweeper()
+        if cq is None:
+            e_i, e_f = np.zeros(0, np.int64), np.zeros(0)
+            return Decoded([], np.zeros((0, 0), bool), e_f, np.zeros(1, np.int64), e_i, e_i, e_i, e_i, e_f,
+                           int(sw.totals()[2]) if sw.in_batch_state else int(self.acoustic_model.components.K))
+        o = sw.decode(cq, self._dev_bounds, self.n_slices_min, self.n_slices_max, self.wip, self.time_power_term)
+        # segment j of utterance i ends behind its j-th set flag and starts where segment j - 1 ends; the flat arrays are the
+        # rows' first n_seg entries in utterance order (stable sorts: nothing is read back)
+        n_utt, NM = o["boundaries"].shape
+        flags = o["boundaries"] != 0
+        end = torch.sort((~flags).to(torch.int8), dim=1, stable=True).indices + 1
+        start = torch.cat([torch.zeros_like(end[:, :1]), end[:, :-1]], dim=1)
+        valid = torch.arange(NM, device=end.device)[None, :] < o["n_seg"][:, None]
+        order = torch.sort((~valid).flatten().to(torch.int8), stable=True).indices
+        flat = [t.flatten().index_select(0, order) for t in (start, end, o["seg_embed"].long(), o["seg_label"].long(),
+                                                              o["seg_density"])]
+        offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=end.device), torch.cumsum(o["n_seg"].long(), 0)])
+        return Decoded(labels, flags, o["log_prob"], offsets, *flat, K=o["K"])
 
     # ------------------------------------------------------------------ one utterance
     def _gibbs_i_async(self, i, anneal_temp, anneal_gibbs_am):
@@ -351,6 +425,40 @@ class UnigramAcousticWordseg(object):
         for e, k in zip(segmented_embeds, assignments):
             comps.add_item(e, k)
         return log_margs
+
+
+class Decoded(object):
+    """What UnigramAcousticWordseg.decode returns.  utterance_labels: the sorted keys; boundaries bool [n_utt, N_max];
+    log_prob [n_utt]: the DP totals; segments i: the flat entries seg_offsets[i] .. seg_offsets[i + 1] - 1 of seg_start /
+    seg_end (landmark indices: the segment spans the slices [start, end)), seg_embed (row of the stacked held-out matrix,
+    utterances in sorted-key order; -1: no embedding), seg_label (the reference view's numbering; K: "would found a new
+    component"; -1: no embedding) and seg_log_marg (the held-out log density of the embedding; -inf: none); K: the active
+    components at the time of the call."""
+
+    _fields = ("boundaries", "log_prob", "seg_offsets", "seg_start", "seg_end", "seg_embed", "seg_label", "seg_log_marg", "K")
+
+    def __init__(self, utterance_labels, boundaries, log_prob, seg_offsets, seg_start, seg_end, seg_embed, seg_label,
+                 seg_log_marg, K):
+        self.utterance_labels = list(utterance_labels)
+        self.boundaries, self.log_prob, self.seg_offsets = boundaries, log_prob, seg_offsets
+        self.seg_start, self.seg_end, self.seg_embed = seg_start, seg_end, seg_embed
+        self.seg_label, self.seg_log_marg, self.K = seg_label, seg_log_marg, K
+
+    def numpy(self):
+        """The host form (waits for the device): NumPy arrays, the flat arrays cut to the segments, K an int."""
+        if isinstance(self.K, int):
+            return self
+        h = {k: getattr(self, k).cpu().numpy() for k in self._fields}
+        n = int(h["seg_offsets"][-1])
+        for k in ("seg_start", "seg_end", "seg_embed", "seg_label", "seg_log_marg"):
+            h[k] = h[k][:n]
+        h["K"] = int(h["K"])
+        return Decoded(self.utterance_labels, **h)
+
+    def transcript(self, i):
+        """The labels of utterance i's segments, in order (a list of ints; reads the device arrays back if need be)."""
+        r = self.numpy()
+        return [int(k) for k in r.seg_label[r.seg_offsets[i]:r.seg_offsets[i + 1]]]
 
 
 def _with_rng_stream(N, run):
