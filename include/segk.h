@@ -83,7 +83,9 @@ const char *segk_last_error(void);
  *  15 (no bump) segk_fbi_predict, segk_fbi_predict_diag32: labels, log densities and log responsibilities of held-out rows
  *     (FBGMM.predict / score_samples / predict_log_proba).  Two entry points added, no signature or structure changed
  *  15 (no bump) segk_fbd_decode: MAP boundaries and transcript of held-out utterances (UnigramAcousticWordseg.decode).  One
- *     entry point added, no signature or structure changed                                                                 */
+ *     entry point added, no signature or structure changed
+ *  15 (no bump) segk_kmd_decode: boundaries, objective and transcript of held-out utterances against a fitted segmental
+ *     k-means (SegmentalKMeansWordseg.decode).  One entry point added, no signature or structure changed                   */
 #define SEGK_ABI_VERSION 15
 int32_t segk_abi_version(void);
 
@@ -1043,6 +1045,37 @@ int32_t segk_fbd_decode(segk_ctx *ctx, const segk_corpus *cq, int32_t n_slices_m
                         double time_power_term, const double *density, const int32_t *label, uint8_t *boundaries,
                         int32_t *seg_embed, int32_t *seg_label, double *seg_density, int32_t *n_seg, double *log_prob,
                         void *stream);
+/* Held-out UTTERANCES against a fitted segmental k-means (added at ABI 15 without a bump; SegmentalKMeansWordseg.decode;
+ * specification tests/kmeans_decode.py): segment_i (kmeans_acoustic_wordseg.py:225-332) of every utterance of `cq` up to and
+ * without its update (:314-320) -- the reference scores an utterance's spans against the current means without removing its
+ * own items and takes boundaries and labels (:288, :313) before it updates, so nothing differs from it.  `cq` is a corpus that
+ * is in no model: its rows are the M candidate embeddings of the held-out utterances, its span tables index them.  The caller
+ * has scored the rows with segk_kmeans_score(cq, m) into `cand`, a segk_cand of n_emb = M entries of its own: cand->k[row] =
+ * argmax_neg_sqrd_norm_i (first maximum), cand->s[row] = max_neg_sqrd_norm_i over all K_max rows of m->means, inactive rows
+ * included (kmeans_components.py:225-232).  Per utterance i of N landmarks:
+ *   vec[j] = cand->s[id_j] * dur_j + wip, -inf where id_j == -1 or dur_j is NaN (get_vec_embed_neg_len_sqrd_norms, :334-351);
+ *   boundaries [dev] uint8 [n_utt, N_max], objective [dev] double [n_utt]: forward_backward_kmeans_viterbi(vec, N,
+ *            n_slices_min, n_slices_max) (:449-555) from cleared flags -- among equal maxima the shortest span, the reference's
+ *            stepping back from a dead end (:521-533); the objective is summed in the backward walk's order; the flags beyond N
+ *            are written 0;
+ *   seg_embed / seg_row / seg_label [dev] int32, seg_score [dev] double, each [n_utt, N_max]: per chosen segment, in landmark
+ *            order, its embedding row id, cand->k[id], min(cand->k[id], *m->K) -- the component add_item would give it
+ *            (kmeans_components.py:103-106), K for "would found a new component" -- and cand->s[id], the unscaled
+ *            max_neg_sqrd_norm; a chosen segment whose span has no embedding (only after stepping back from a dead end) is
+ *            kept as (-1, -1, -1, -inf) so that segment j ends at the j-th set flag; the entries beyond the count are written
+ *            (-1, -1, -1, -inf);
+ *   n_seg [dev] int32 [n_utt]: the number of chosen segments.
+ * The call reads cq, cand->k, cand->s and m->K and writes its seven outputs: no old boundaries, no token lists, no flag counts,
+ * no status word, nothing of the model.  One launch, one wave per utterance, no atomics: for N_max <= 64 and windows 1..8 the
+ * register DP of segk_kmeans_segment's fast path, otherwise its generic walk (any N_max, n_slices_max == 0, windows above 8).
+ * The layout is chosen from cq->N_max, whatever corpus the model was trained on.
+ * SEGK_ERR_ARG before any launch: n_slices_min outside {0, 1}; n_slices_max < 0; a corpus without span tables; a NULL
+ * argument.  SEGK_ERR_UNSUPPORTED before any launch: a band of N_max x W spans (W = n_slices_max, or N_max without a window)
+ * beyond the 160 KiB of LDS of a workgroup (generic: 12 N_max W + 9 N_max + 8 bytes rounded up to 16).  n_utt == 0 returns
+ * SEGK_OK and launches nothing.                                                                                             */
+int32_t segk_kmd_decode(segk_ctx *ctx, const segk_corpus *cq, const segk_kmeans *m, const segk_cand *cand, int32_t n_slices_min,
+                        int32_t n_slices_max, double wip, uint8_t *boundaries, int32_t *seg_embed, int32_t *seg_row,
+                        int32_t *seg_label, double *seg_score, int32_t *n_seg, double *objective, void *stream);
 /* Acoustic-model batch sweeps of the unigram segmenter (added at ABI 15 without a bump; the inner sweeps of
  * UnigramAcousticWordseg.gibbs_sample(n, am_n_iter=m), unigram_acoustic_wordseg.py:440-443 -- FBGMM.gibbs_sample(m,
  * consider_unassigned=False) over the currently assigned tokens -- as a blocked sampler on the segmenter's batch state;

@@ -160,6 +160,7 @@ SIGNATURES = {
     "segk_fbi_predict": (_i32, [_P, _CP, _FP, _BP, _P, _i64, _i64, _P, _P, _P, _P, _i64, _P, _i64, _P]),
     "segk_fbi_predict_diag32": (_i32, [_P, _CP, _FP, _BP, _P, _i64, _i64, _P, _P, _P, _P, _i64, _P, _i64, _P]),
     "segk_fbd_decode": (_i32, [_P, _CP, _i32, _i32, _f64, _f64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "segk_kmd_decode": (_i32, [_P, _CP, _KP, _DP, _i32, _i32, _f64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "segk_fbi_assign_orphans": (_i32, [_P, _CP, _FP, _BP, _i32, _i32, _i32, _P, _u64, _P, _P, _P, _P, _i64, _P]),
     "segk_fbt_assign": (_i32, [_P, _CP, _FP, _BP, _i32, _i32, _i32, _P, _P, _u64, _f64, _P, _P, _P, _i64, _P]),
     "segk_fbt_assign_diag32": (_i32, [_P, _CP, _FP, _BP, _i32, _i32, _i32, _P, _P, _u64, _f64, _P, _P, _P, _i64, _P]),

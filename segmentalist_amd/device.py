@@ -209,6 +209,7 @@ class DeviceKMeans(object):
         self.bounds_stale = None
         self._L = _abi.lib()
         self._ctx = _abi.ctx()
+        self._ctx_q = None           # the context held-out rows are scored on (_heldout_ctx), created at the first such call
         if init is None:
             check(self._L.segk_kmeans_init_stats(self._ctx, C.byref(c.c), C.byref(self.m), _abi.stream()))
         else:
@@ -328,6 +329,109 @@ class DeviceKMeans(object):
             return
         check(self._L.segk_kmeans_score(self._ctx, self._cp(), C.byref(self.m), p, int(row0), int(n),
                                         C.byref(self.cand), ptr(self.status), _abi.stream()))
+
+    # ------------------------------------------------------------------ held-out rows
+    def check_heldout(self, D, what):
+        """What scoring rows that are not in the model refuses, from host values alone (nothing is launched)."""
+        if self.batch_comm.world > 1:
+            raise SegkError("%s runs in one process only (%d ranks): held-out rows are not sharded" % (what, self.batch_comm.world))
+        if self.shard is not None:
+            raise SegkError("%s needs a model whose corpus is not sharded (this device holds rows %d..%d of %d)"
+                            % (what, self.shard[0], self.shard[1], self.n_rows_global))
+        if D != self.corpus.D:
+            raise SegkError("%s: the held-out embeddings have D = %d, the model's have D = %d" % (what, D, self.corpus.D))
+
+    def _heldout_ctx(self):
+        """A second segk_ctx, this model's own: the score path's workspaces, the per-XCD shares, the hint feedback and the
+        delta pass's base state belong to a context (include/segk.h, segk_kmeans_score_hinted), and every un-hinted score
+        call drops the delta state of the context it runs on.  Held-out rows are scored here, so the context the sweeps run
+        on never sees them."""
+        if self._ctx_q is None:
+            h = C.c_void_p()
+            check(self._L.segk_create(int(_torch().cuda.current_device()), C.byref(h)))
+            self._ctx_q = h
+        return self._ctx_q
+
+    def __del__(self):
+        try:
+            if self._ctx_q is not None:
+                self._L.segk_destroy(self._ctx_q)
+                self._ctx_q = None
+        except Exception:
+            pass
+
+    def score_heldout(self, cq):
+        """segk_kmeans_score, un-hinted, over all rows of `cq` -- a DeviceCorpus that is in no model, of the model's D and
+        dtype -- against the means as they stand, on the model's second context and into candidate buffers of the call's
+        own: returns (CandDev, its tensors k int32 [M], f, s float64 [M], queue, count, status): k / s = np.argmax / np.max
+        of neg_sqrd_norm over all K_max rows.  Reads means, tiles and mnorm_max; writes nothing of the model: not cand_k
+        (the next sweep's hints), not `status`.  Enqueued on the current stream, nothing read back."""
+        torch = _torch()
+        dev = _dev()
+        self.check_heldout(cq.D, "scoring held-out rows")
+        if cq.x_dtype != self.corpus.x_dtype:
+            raise SegkError("scoring held-out rows: the held-out embeddings must have the dtype of the model's")
+        if self.tiles_b3 is not None:
+            cq.ensure_b3()
+        M = cq.n_emb
+        t = (torch.zeros(M, dtype=torch.int32, device=dev), torch.zeros((M, 2), dtype=torch.float32, device=dev),
+             torch.zeros(M, dtype=torch.float64, device=dev), torch.zeros(M, dtype=torch.int32, device=dev),
+             torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(8, dtype=torch.int32, device=dev))
+        cand = _abi.CandDev(k=t[0].data_ptr(), f=t[1].data_ptr(), s=t[2].data_ptr(), queue=t[3].data_ptr(), count=t[4].data_ptr())
+        check(self._L.segk_kmeans_score(self._heldout_ctx(), C.byref(cq.c), C.byref(self.m), None, 0, int(M), C.byref(cand),
+                                        ptr(t[5]), _abi.stream()))
+        return cand, t
+
+    @staticmethod
+    def decode_lds_bytes(N_max, n_slices_max):
+        """The LDS of one wave of k_kmd_decode (segk_kmdecode.hip kmd_lds)."""
+        Wc = n_slices_max if 0 < n_slices_max < N_max else N_max
+        cells = N_max * Wc
+        if 1 <= n_slices_max <= 8 and N_max <= 64:
+            b = (9 * N_max + 12) * 8 + (2 * cells + 2 * N_max + 8) * 4
+        else:
+            b = (cells + N_max + 1) * 8 + cells * 4 + N_max
+        return (b + 15) // 16 * 16
+
+    def check_decode(self, D, N_max, n_slices_min, n_slices_max):
+        """What decode() refuses, from host values alone (nothing is launched): the limits of segk_kmd_decode, each named."""
+        self.check_heldout(D, "decode")
+        if n_slices_min not in (0, 1):
+            raise SegkError("decode: n_slices_min must be 0 or 1, got %r" % (n_slices_min,))
+        if n_slices_max < 0:
+            raise SegkError("decode: n_slices_max must be >= 0, got %r" % (n_slices_max,))
+        lds = self.decode_lds_bytes(N_max, n_slices_max)
+        if lds > 160 * 1024:
+            raise SegkError("decode: the band of spans of the longest held-out utterance does not fit in the LDS of a workgroup: "
+                            "N_max = %d landmarks, n_slices_max = %d: %d bytes needed, %d available"
+                            % (N_max, n_slices_max, lds, 160 * 1024))
+
+    def decode(self, cq, n_slices_min, n_slices_max, wip):
+        """Boundaries, objective and transcript of the HELD-OUT utterances of `cq` against the means as they stand --
+        SegmentalKMeansWordseg.decode; specification tests/kmeans_decode.py; DESIGN.md 4.24: score_heldout, then
+        segk_kmd_decode.  Returns a dict of device tensors, enqueued on the current stream, nothing read back: boundaries
+        uint8 [n_utt, N_max], objective [n_utt], n_seg int32 [n_utt], seg_embed / seg_row / seg_label int32 and seg_score
+        float64 [n_utt, N_max], row int32 / score float64 [M] (every candidate row), K (a copy of the model's).  Read-only:
+        whatever ensure_state() has pending stays pending."""
+        torch = _torch()
+        dev = _dev()
+        self.check_decode(cq.D, cq.N_max, int(n_slices_min), int(n_slices_max))
+        n_utt, NM = cq.n_utt, cq.N_max
+        cand, t = self.score_heldout(cq)
+        i32 = torch.int32
+        out = dict(boundaries=torch.zeros((n_utt, NM), dtype=torch.uint8, device=dev),
+                   objective=torch.zeros(n_utt, dtype=torch.float64, device=dev), n_seg=torch.zeros(n_utt, dtype=i32, device=dev),
+                   seg_embed=torch.full((n_utt, NM), -1, dtype=i32, device=dev),
+                   seg_row=torch.full((n_utt, NM), -1, dtype=i32, device=dev),
+                   seg_label=torch.full((n_utt, NM), -1, dtype=i32, device=dev),
+                   seg_score=torch.full((n_utt, NM), -np.inf, dtype=torch.float64, device=dev), row=t[0], score=t[2])
+        # (the model's own context: the kernel uses none of a context's state)
+        check(self._L.segk_kmd_decode(self._ctx, C.byref(cq.c), C.byref(self.m), C.byref(cand), int(n_slices_min), int(n_slices_max),
+                                      float(wip), ptr(out["boundaries"]), ptr(out["seg_embed"]), ptr(out["seg_row"]),
+                                      ptr(out["seg_label"]), ptr(out["seg_score"]), ptr(out["n_seg"]), ptr(out["objective"]),
+                                      _abi.stream()))
+        out["K"] = self.K.clone()
+        return out
 
     def delta_stats(self):
         """What the delta score pass did in the latest hinted call whose figures have arrived (segk_kmeans_delta_stats, no

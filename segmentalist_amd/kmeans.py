@@ -104,6 +104,27 @@ class KMeans(object):
                 break
         return record_dict
 
+    def predict(self, Xq, return_score=False):
+        """Rows that are NOT in the model against the means as they stand, read-only: per row of Xq
+        [M, D] the raw argmax row of `means` over all K_max rows, inactive ones included (argmax_neg_sqrd_norm_i of the row
+        appended to X, kmeans_components.py:231-232, first maximum; min(row, K) is the component add_item would give it),
+        and with return_score=True also max_neg_sqrd_norm (:228-229) in the dtype of X -> int64 [M] or (int64 [M], [M]).
+        Xq is converted to the dtype of X.  One segk_kmeans_score on a context of the model's own, into candidate buffers
+        of the call's own: no statistic, no hint of the next sweep and no random state changes.
+        Raises SegkError before any launch for more than one rank, a sharded corpus and a D other than the model's."""
+        from .device import DeviceCorpus
+        dk = self.components.dev
+        Xq = np.asarray(Xq)
+        if Xq.ndim != 2:
+            raise ValueError("predict takes a matrix [M, D], got shape %r" % (Xq.shape,))
+        dk.check_heldout(Xq.shape[1], "KMeans.predict")
+        dtype = dk.corpus.x_np_dtype
+        if Xq.shape[0] == 0:
+            return (np.zeros(0, np.int64), np.zeros(0, dtype)) if return_score else np.zeros(0, np.int64)
+        _, t = dk.score_heldout(DeviceCorpus(Xq.astype(dtype, copy=False)))
+        rows = t[0].cpu().numpy().astype(np.int64)
+        return (rows, t[2].cpu().numpy().astype(dtype)) if return_score else rows
+
     def get_n_assigned(self):
         """Number of assigned items (the reference counts `assignments != -1`): the sum of the component counts, read
         from the device without copying the assignment vector to the host."""

@@ -50,6 +50,7 @@ class SegmentalKMeansWordseg(object):
         self.n_batches = int(n_batches)      # batch mode: statistics refreshed n_batches times per sweep (mini-batches)
         self.n_slices_min = n_slices_min
         self.n_slices_max = n_slices_max
+        self.min_duration = min_duration
         self.wip = wip
         self.sync = sync
 
@@ -157,6 +158,80 @@ class SegmentalKMeansWordseg(object):
             with np.errstate(invalid="ignore"):
                 out[valid] = np.where(np.isnan(d), -np.inf, mx * d)
         return out + self.wip
+
+    # ------------------------------------------------------------------ held-out utterances
+    def decode(self, embedding_mats, vec_ids_dict, durations_dict, landmarks_dict, device_out=False):
+        """Segment and label HELD-OUT utterances, read-only (specification tests/kmeans_decode.py; segk_kmd_decode,
+        DESIGN.md 4.24).  The four dictionaries are the constructor's, for utterances that are in no model.  Per utterance,
+        with the model's n_slices_min / n_slices_max / min_duration / wip, exactly segment_i (kmeans_acoustic_wordseg.py:225-332)
+        up to and without its update (:314-320): the span scores of get_vec_embed_neg_len_sqrd_norms (:334-351) -- the
+        maximum over all K_max rows of `means`, inactive rows included --, the boundaries and objective of
+        forward_backward_kmeans_viterbi (:449-555) from cleared flags, and for every chosen segment the raw argmax row
+        (argmax_neg_sqrd_norm_i, first maximum), min(row, K) -- the component add_item would give it (kmeans_components.py:
+        103-106), K for "would found a new component" -- and the unscaled max_neg_sqrd_norm.  A chosen segment whose span
+        has no embedding (only after the DP stepped back from a dead end) is kept with embedding -1, row -1, label -1 and
+        score -inf.
+
+        The model is not changed: no statistic, no boundary, no hint of the next sweep, no `random` / `np.random` draw;
+        works on a sequential model and on a live batch state, whatever is pending after batch sweeps or refits.
+
+        Returns a `KMeansDecoded`; with device_out=True its arrays are device tensors, enqueued without a synchronisation (the
+        flat segment arrays then have n_utt * N_max entries, the first seg_offsets[-1] of them segments).
+        Raises SegkError before any launch for: more than one rank or a sharded corpus, a held-out D other than the model's,
+        a span id beyond the held-out rows, n_slices_min outside {0, 1}, and a band of spans beyond the LDS of a workgroup."""
+        labels, cq = self._heldout_corpus(embedding_mats, vec_ids_dict, durations_dict, landmarks_dict)
+        out = self._decode_corpus(labels, cq)
+        return out if device_out else out.numpy()
+
+    def _heldout_corpus(self, embedding_mats, vec_ids_dict, durations_dict, landmarks_dict):
+        """The checks of decode() and the device image of the held-out utterances: (sorted keys, DeviceCorpus or None for an
+        empty set).  Host work and one upload; nothing of the model is read on the device."""
+        from ._abi import SegkError
+        dk = self._dk
+        if get_comm(self._batch_args[2]).world > 1:
+            raise SegkError("decode runs in one process only (%d ranks): held-out utterances are not sharded"
+                            % get_comm(self._batch_args[2]).world)
+        if not embedding_mats:
+            dk.check_decode(self._corpus.D, 1, self.n_slices_min, self.n_slices_max)
+            return [], None
+        embeddings, vec_ids, labels = process_embeddings(embedding_mats, vec_ids_dict)
+        embeddings = np.asarray(embeddings)
+        D = embeddings.shape[1] if embeddings.ndim == 2 else -1
+        lengths = [len(landmarks_dict[i]) for i in labels]
+        u = Utterances(lengths, vec_ids, [durations_dict[i] for i in labels], [landmarks_dict[i] for i in labels],
+                       p_boundary_init=0, n_slices_min=self.n_slices_min, n_slices_max=self.n_slices_max,
+                       min_duration=self.min_duration)
+        dk.check_decode(D, u.N_max, self.n_slices_min, self.n_slices_max)
+        if u.vec_ids.max(initial=-1) >= len(embeddings):
+            raise SegkError("decode: a span id names row %d of %d held-out embeddings" % (u.vec_ids.max(), len(embeddings)))
+        if len(embeddings) == 0:
+            raise SegkError("decode: the held-out utterances have no embedding at all")
+        # the banded span tables of the kernel's window (the constructor builds them for the fast path's shapes)
+        band = u.band_tables(self.n_slices_max) if 1 <= self.n_slices_max <= 8 else None
+        return labels, DeviceCorpus(embeddings.astype(self._corpus.x_np_dtype, copy=False), u.vec_ids, u.durations, u.lengths,
+                                    band=band)
+
+    def _decode_corpus(self, labels, cq):
+        """decode() on the device image of the held-out utterances: a `KMeansDecoded` of device tensors, nothing read back."""
+        import torch
+        dk = self._dk
+        if cq is None:
+            e_i, e_f = np.zeros(0, np.int64), np.zeros(0)
+            return KMeansDecoded([], np.zeros((0, 0), bool), e_f, np.zeros(1, np.int64), e_i, e_i, e_i, e_i, e_i, e_f,
+                                 int(self.acoustic_model.components.K))
+        o = dk.decode(cq, self.n_slices_min, self.n_slices_max, self.wip)
+        # segment j of utterance i ends behind its j-th set flag and starts where segment j - 1 ends; the flat arrays are the
+        # rows' first n_seg entries in utterance order (stable sorts: nothing is read back)
+        n_utt, NM = o["boundaries"].shape
+        flags = o["boundaries"] != 0
+        end = torch.sort((~flags).to(torch.int8), dim=1, stable=True).indices + 1
+        start = torch.cat([torch.zeros_like(end[:, :1]), end[:, :-1]], dim=1)
+        valid = torch.arange(NM, device=end.device)[None, :] < o["n_seg"][:, None]
+        order = torch.sort((~valid).flatten().to(torch.int8), stable=True).indices
+        flat = [t.flatten().index_select(0, order) for t in (start, end, o["seg_embed"].long(), o["seg_row"].long(),
+                                                              o["seg_label"].long(), o["seg_score"])]
+        offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=end.device), torch.cumsum(o["n_seg"].long(), 0)])
+        return KMeansDecoded(labels, flags, o["objective"], offsets, *flat, K=o["K"])
 
     # ------------------------------------------------------------------ checkpoint / resume (SURVEY 8(f).3)
     def state_dict(self):
@@ -318,6 +393,42 @@ class SegmentalKMeansWordseg(object):
     def get_max_unsup_transcript_i(self, i):
         return self.acoustic_model.components.get_max_assignments(
             self.utterances.get_segmented_embeds_i(i))
+
+
+class KMeansDecoded(object):
+    """What SegmentalKMeansWordseg.decode returns (the k-means sibling of unigram_acoustic_wordseg.Decoded).
+    utterance_labels: the sorted keys; boundaries bool [n_utt, N_max]; objective [n_utt]: the length-weighted objective
+    segment_i returns; segments of utterance i: the flat entries seg_offsets[i] .. seg_offsets[i + 1] - 1 of seg_start / seg_end
+    (landmark indices: the segment spans the slices [start, end)), seg_embed (row of the stacked held-out matrix, utterances in
+    sorted-key order; -1: no embedding), seg_row (the raw argmax row of `means`; -1: no embedding), seg_label (min(row, K):
+    K stands for "would found a new component"; -1: no embedding) and seg_score (max_neg_sqrd_norm of the embedding, unscaled,
+    as a double; -inf: none); K: the active components at the time of the call."""
+
+    _fields = ("boundaries", "objective", "seg_offsets", "seg_start", "seg_end", "seg_embed", "seg_row", "seg_label", "seg_score",
+               "K")
+
+    def __init__(self, utterance_labels, boundaries, objective, seg_offsets, seg_start, seg_end, seg_embed, seg_row, seg_label,
+                 seg_score, K):
+        self.utterance_labels = list(utterance_labels)
+        self.boundaries, self.objective, self.seg_offsets = boundaries, objective, seg_offsets
+        self.seg_start, self.seg_end, self.seg_embed, self.seg_row = seg_start, seg_end, seg_embed, seg_row
+        self.seg_label, self.seg_score, self.K = seg_label, seg_score, K
+
+    def numpy(self):
+        """The host form (waits for the device): NumPy arrays, the flat arrays cut to the segments, K an int."""
+        if isinstance(self.K, int):
+            return self
+        h = {k: getattr(self, k).cpu().numpy() for k in self._fields}
+        n = int(h["seg_offsets"][-1])
+        for k in ("seg_start", "seg_end", "seg_embed", "seg_row", "seg_label", "seg_score"):
+            h[k] = h[k][:n]
+        h["K"] = int(h["K"].reshape(-1)[0])
+        return KMeansDecoded(self.utterance_labels, **h)
+
+    def transcript(self, i):
+        """The labels of utterance i's segments, in order (a list of ints; reads the device arrays back if need be)."""
+        r = self.numpy()
+        return [int(k) for k in r.seg_label[r.seg_offsets[i]:r.seg_offsets[i + 1]]]
 
 
 def _dp_tri(kind, vec, N, n_slices_min, n_slices_max, log_p_continue=0.0, anneal_temp=1.0, uniforms=None):
