@@ -82,10 +82,43 @@ static __device__ __forceinline__ void fbb_sum_slices(const segk_fbatch &bt, int
 // the sum by ln 2): m = float(mean - centre), q = float(q), x = float(x - centre), the differences formed in fp64.  The one
 // copy behind fbb_accumulate_rows32 (segk_fbbatch.hip: the segmenter's `score_precision="f32"` token likelihoods) and
 // k_fbi_assign_diag32 (segk_fbitems.hip: the stand-alone model's), so the two routes cannot drift apart.
+//
+// log2(1 + e), e = delta^2 q, COMPENSATED: inside a slot of n_k items e is of the order of 1 / n_k, the sum
+// u = 1 + e rounds away up to 2^-24 of it, and the slot's factor (v_N + 1) / 2 ~ n_k / 2 multiplies that back up -- an error of
+// the likelihood that grows with the count whatever the data's scale.  c = e - (u - 1) is the part the addition dropped (both
+// differences are exact for u < 2) and log2(1 + e) = log2(u) + c / (u ln 2) + O(c^2).  The factor 1 / u is left out, and the
+// correction with it from u = 2 on: there c / u is at most 2^-24, below the last bit of a logarithm that is 1 or more, while c
+// alone would grow with u.  For u < 2 the missing factor costs at most 2^-25 / ln 2 per term.  (The comparison against 2 and a
+// select, both on inline constants: a clamp of c to +-2^-24 by v_med3_f32 wants two registers for its bounds, which the
+// token kernels at their register limit do not have.)  The library is built without fast-math and with -ffp-contract=off
+// (Makefile): nothing re-associates e - (u - 1) away.
+#define FBB_LOG2E_F 1.4426950408889634f
+static __device__ __forceinline__ float fbb_log2_1p32(float e)
+{
+    const float u = 1.f + e;
+    const float c = u < 2.f ? e - (u - 1.f) : 0.f;
+    return __builtin_fmaf(c, FBB_LOG2E_F, __builtin_amdgcn_logf(u));
+}
+
+// The same term on a PAIR of rows, for the packed float32 loops of k_fbb_score_diag32 and k_fbb_step_diag32 (segk_fbbatch.hip):
+// d2 = delta^2 of the two rows, q2 = (q, q).  u = fma(d2, q2, 1) as those loops always formed it, and c = fma(d2, q2, 1 - u):
+// the product unrounded less u - 1 (1 - u is exact) -- again what the addition dropped.  Three packed instructions and a
+// compare and select per row more than log2(u) alone.
+typedef float fbb_f32x2 __attribute__((ext_vector_type(2)));
+static __device__ __forceinline__ fbb_f32x2 fbb_log2_1p32x2(fbb_f32x2 d2, fbb_f32x2 q2)
+{
+    const fbb_f32x2 one2 = {1.f, 1.f}, log2e2 = {FBB_LOG2E_F, FBB_LOG2E_F};
+    const fbb_f32x2 u = __builtin_elementwise_fma(d2, q2, one2);
+    const fbb_f32x2 c = __builtin_elementwise_fma(d2, q2, one2 - u);
+    const fbb_f32x2 cc = {u.x < 2.f ? c.x : 0.f, u.y < 2.f ? c.y : 0.f};
+    const fbb_f32x2 lg = {__builtin_amdgcn_logf(u.x), __builtin_amdgcn_logf(u.y)};                     // v_log_f32: log2
+    return __builtin_elementwise_fma(cc, log2e2, lg);
+}
+
 static __device__ __forceinline__ float fbb_term32(float m, float q, float x)
 {
     const float delta = m - x;
-    return __builtin_amdgcn_logf(1.f + (delta * delta) * q);
+    return fbb_log2_1p32((delta * delta) * q);
 }
 
 // THE draw of one token's slot without a language model, by one wave (k_fbb_slots of segk_fbbatch.hip: a wave per token of an

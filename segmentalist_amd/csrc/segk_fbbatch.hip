@@ -493,8 +493,12 @@ static __device__ __forceinline__ void fbb_accumulate_rows32(const segk_fbatch &
 {
     int d = 0;
     // sixteen dimensions' parameters in flight (four at a time were ten dependent round trips for D = 39), then four; the terms
-    // in the same order
-    for (; d + 16 <= D; d += 16) fbb_terms32<NR, 16>(bt, KM, k, D, d, xs, acc);
+    // in the same order.  With eight rows a thread (k_fbb_slots and k_fbb_assign_lm, at 252 registers with the plain term)
+    // eight dimensions: sixteen, with the compensated term's temporaries, spilled 39 registers there.
+    if (NR <= 4)
+        for (; d + 16 <= D; d += 16) fbb_terms32<NR, 16>(bt, KM, k, D, d, xs, acc);
+    else
+        for (; d + 8 <= D; d += 8) fbb_terms32<NR, 8>(bt, KM, k, D, d, xs, acc);
     for (; d + 4 <= D; d += 4) fbb_terms32<NR, 4>(bt, KM, k, D, d, xs, acc);
     for (; d < D; d++) {
         const double cd = fbb_centre(bt, d);
@@ -635,7 +639,8 @@ __global__ __launch_bounds__(256) void k_fbb_score(segk_corpus c, segk_fbgmm f, 
 // ---------------------------------------------------------------------------------------
 // The diagonal (Student-t) span score in float32 (`score_precision="f32"`, opt-in): the kernel above spends its life in
 // the fp64 software logarithm of every (row, slot, dimension) term -- one log per term, K_max * D terms per row.  Here
-// the term log(1 + delta^2 q) is four float32 instructions, the logarithm the hardware's v_log_f32 (base 2; ln 2 is
+// the term log(1 + delta^2 q) is a handful of float32 instructions (fbb_log2_1p32x2 of segk_fbb_dev.h: compensated for what
+// 1 + delta^2 q rounds away, which a slot's count multiplies back up), the logarithm the hardware's v_log_f32 (base 2; ln 2 is
 // folded into the slot's factor), the terms of a (row, slot) accumulate in float32, z = zc - h ln2 acc is formed in
 // fp64 and the online log-sum-exp over the slots runs in float32 in base 2 (v_exp_f32) relative to the running
 // maximum.  Error budget against the fp64 kernel (tests/test_gpu_fbgmm_batch.py measures it): |log2(1 + t)| carries
@@ -718,9 +723,9 @@ __global__ __launch_bounds__(256) void k_fbb_score_diag32(segk_corpus c, segk_fb
     // (v_log_f32 for the two constants as for the terms: ~1e-7 relative, two fp64 library logarithms were 2 us of every workgroup)
     const double zc_empty = f.lms * fb_log_fast(prior_alpha / (double)KM);
     const double norm = f.lms * fb_log_fast(total + prior_alpha);
-    // The term log2(1 + (m - x)^2 q) on PAIRS of rows: subtract, multiply, multiply-add and the accumulation as packed float32
-    // operations (v_pk_*_f32: two rows per instruction), the logarithm per row -- three vector instructions per term instead of
-    // five, and one 16-byte LDS read for four rows
+    // The term log2(1 + (m - x)^2 q) on PAIRS of rows: subtract, multiply, the multiply-adds and the accumulation as packed
+    // float32 operations (v_pk_*_f32: two rows per instruction), the logarithm and the guard of the compensation per row
+    // (fbb_log2_1p32x2), and one 16-byte LDS read for four rows
     typedef float f32x2_t __attribute__((ext_vector_type(2)));
     typedef float f32x4_t __attribute__((ext_vector_type(4)));
     static_assert(RPG % 4 == 0, "rows per thread in fours");
@@ -734,16 +739,14 @@ __global__ __launch_bounds__(256) void k_fbb_score_diag32(segk_corpus c, segk_fb
             f32x2_t acc2[RPG / 2];
 #pragma unroll
             for (int r = 0; r < RPG / 2; r++) acc2[r] = (f32x2_t){0.f, 0.f};
-            const f32x2_t one2 = {1.f, 1.f};
             auto term = [&](int d, float m, float q) {
                 const f32x2_t m2 = {m, m}, q2 = {q, q};
 #pragma unroll
                 for (int r4 = 0; r4 < RPG / 4; r4++) {
                     const f32x4_t xv = *reinterpret_cast<const f32x4_t *>(xg + d * FBB_R32 + 4 * r4);
                     const f32x2_t d0 = m2 - xv.xy, d1 = m2 - xv.zw;
-                    const f32x2_t u0 = __builtin_elementwise_fma(d0 * d0, q2, one2), u1 = __builtin_elementwise_fma(d1 * d1, q2, one2);
-                    acc2[2 * r4] += (f32x2_t){__builtin_amdgcn_logf(u0.x), __builtin_amdgcn_logf(u0.y)};       // v_log_f32: log2
-                    acc2[2 * r4 + 1] += (f32x2_t){__builtin_amdgcn_logf(u1.x), __builtin_amdgcn_logf(u1.y)};
+                    acc2[2 * r4] += fbb_log2_1p32x2(d0 * d0, q2);           // (compensated: segk_fbb_dev.h)
+                    acc2[2 * r4 + 1] += fbb_log2_1p32x2(d1 * d1, q2);
                 }
             };
             int d = (dbg & 2) ? D : 0;
@@ -980,7 +983,6 @@ __global__ __launch_bounds__(512) void k_fbb_step_diag32(segk_corpus c, segk_fbg
                 f32x2_t acc2[4];
 #pragma unroll
                 for (int r = 0; r < 4; r++) acc2[r] = (f32x2_t){0.f, 0.f};
-                const f32x2_t one2 = {1.f, 1.f};
                 for (int d = 0; d < D; d++) {
                     const float m = tm[d * KM + k], q = tq[d * KM + k];
                     const f32x2_t m2 = {m, m}, q2 = {q, q};
@@ -988,9 +990,8 @@ __global__ __launch_bounds__(512) void k_fbb_step_diag32(segk_corpus c, segk_fbg
                     for (int r4 = 0; r4 < 2; r4++) {
                         const f32x4_t xv = *reinterpret_cast<const f32x4_t *>(xg + d * RC + 4 * r4);
                         const f32x2_t d0 = m2 - xv.xy, d1 = m2 - xv.zw;
-                        const f32x2_t u0 = __builtin_elementwise_fma(d0 * d0, q2, one2), u1 = __builtin_elementwise_fma(d1 * d1, q2, one2);
-                        acc2[2 * r4] += (f32x2_t){__builtin_amdgcn_logf(u0.x), __builtin_amdgcn_logf(u0.y)};
-                        acc2[2 * r4 + 1] += (f32x2_t){__builtin_amdgcn_logf(u1.x), __builtin_amdgcn_logf(u1.y)};
+                        acc2[2 * r4] += fbb_log2_1p32x2(d0 * d0, q2);       // (compensated: segk_fbb_dev.h)
+                        acc2[2 * r4 + 1] += fbb_log2_1p32x2(d1 * d1, q2);
                     }
                 }
                 const double zc = bt.zconst[k], hl = bt.half[k] * 0.6931471805599453;
@@ -1137,9 +1138,10 @@ __global__ __launch_bounds__(512) void k_fbb_step_diag32(segk_corpus c, segk_fbg
     }
 }
 
-// calibration of the roofline of k_fbb_score_diag32: the same four float32 instructions per term (subtract, multiply,
-// multiply-add, v_log_f32) and the accumulate, operands in registers, eight independent chains per thread -- what the
-// vector ALUs deliver on this chip for the kernel's inner term with nothing else in the way
+// calibration of the roofline of k_fbb_score_diag32: the float32 instructions of one term (fbb_term32 itself: the difference,
+// delta^2 q, 1 + e, the compensation and its guard, v_log_f32, the multiply-add) and the accumulate, operands in registers,
+// eight independent chains per thread -- what the vector ALUs deliver on this chip for the kernel's inner term with nothing
+// else in the way
 __global__ __launch_bounds__(256) void k_vlog_calibrate(int iters, float seed, float *out)
 {
     float acc[8], m[8];
@@ -1149,8 +1151,7 @@ __global__ __launch_bounds__(256) void k_vlog_calibrate(int iters, float seed, f
     for (int i = 0; i < iters; i++) {
 #pragma unroll
         for (int j = 0; j < 8; j++) {
-            const float delta = m[j] - x;
-            acc[j] += __builtin_amdgcn_logf(1.f + (delta * delta) * q);
+            acc[j] += fbb_term32(m[j], q, x);
         }
         x += 1e-6f;
     }

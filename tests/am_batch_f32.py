@@ -62,6 +62,11 @@ RUNS = [(name, t) for name in CASES for t in TRANSFORMS[name]]
 BOTH_PRECISIONS = ["dg_D39_K65_tiles", "dg_band_N80", "dg_D3_K7_8x8"]
 BOTH_ROUTES = ["dg_D39_K65_tiles", "dg_band_N80", "dg_D39_K300_tiles"]
 TILES, SLOTS = "0", str(1 << 30)               # SEGK_AM32_TILE_MIN: always the tile kernel / never
+# slots of thousands of tokens, where a float32 term's rounding is multiplied by the slot's count: the
+# settled case of tests/fbgmm_items_f32.py as utterances of one landmark (f32.segmenter_of; its specification f32.spec_of --
+# tests/test_fbgmm_items_cpu.py holds the item sweep to be FbgmmBatch.sweep on such utterances, draw for draw).  The cases
+# above hold about five tokens a slot and cannot show it.
+SETTLED = "st_D39_K8_n4096"
 
 
 def temps_of(case):
@@ -199,3 +204,86 @@ def run(name, transform="identity"):
         out.changed_by_T.append(changed)
         out.history.append(spec.slot.copy())
     return out
+
+
+# ---- a settled MULTI-LANDMARK corpus: SETTLED above reaches every float32 kernel at large counts, but with one token and one span
+# an utterance.  Here 800 utterances of eight landmarks and a window of three (21 spans each: rows of three durations in one
+# score tile, three to eight tokens an utterance in the token kernels), the rows from TWO cluster centres, every token in the slot of its row's centre: two slots of about 2 000 tokens.
+# cov, dtype, D, K_max, B, S, tokens of every utterance, landmarks N, window, corpus seed, temperatures (the layout of CASES)
+SETTLED_SEG = ("diag", "float32", 39, 6, 4, 2, [8, 4, 5, 3, 6] * 160, 8, 3, 377, (1.0,))
+N_CENTRES = 2
+# rows: unit vectors times ROW_SCALE sqrt(D).  The contract's measure is relative to max(|want|, 1): at ab.SCALE = 1.5 the span
+# scores lie near -18 and the plain term's error (the same absolute size) is 4e-5 of them, inside the contract -- such a corpus
+# could not show the defect; at 0.8 they lie near -3 and the plain term misses by 3.3e-4 or more on every block's probes
+# (tests/test_am_batch_f32_cpu.py holds that)
+ROW_SCALE = 0.8
+
+
+def settled_seg_corpus(case=SETTLED_SEG):
+    """ab.case_corpus with N_CENTRES cluster centres, at ROW_SCALE"""
+    cov, dtype, D, K, B, S, tokens, N, nmax, cseed = case[:10]
+    corpus = ab.fl.corpus_of(dict(n_utt=len(tokens), D=D, K=2 * N_CENTRES, cseed=cseed, N=N, nmax=nmax))
+    mats = {k: (ROW_SCALE * np.sqrt(D) * np.asarray(v, np.float64)).astype(dtype) for k, v in corpus[0].items()}
+    return (mats,) + tuple(corpus[1:])
+
+
+def settled_seg_spec(case=SETTLED_SEG):
+    """(corpus, boundaries, AmBatch) of the settled start: a32.spec_of's construction with every token labelled by the centre
+    its row lies nearest to (the centres: the first draw of synth.make_corpus' generator, as directions)"""
+    cov, dtype, D, K, B, S, tokens, N, nmax, cseed = case[:10]
+    corpus = settled_seg_corpus(case)
+    bounds = ab.case_boundaries(case, corpus)
+    np.random.seed(1)
+    prior = no.NIW(*fi.prior_params("diag", D))
+    seg = no.UnigramAcousticWordseg(no.FBGMM, ab.ALPHA, K, prior, *corpus, seed_boundaries_dict=bounds, **ab.seg_kwargs(case))
+    u = seg.utterances
+    X = seg.acoustic_model.components.X
+    mu = np.random.RandomState(cseed).randn(N_CENTRES, D)
+    rows = np.array([e for i in range(u.D) for e in u.get_segmented_embeds_i(i)], np.int64)
+    assert -1 not in rows
+    a = -np.ones(len(X), np.int64)
+    a[rows] = np.argmax(X[rows].astype(np.float64) @ mu.T, axis=1)
+    seg.acoustic_model = no.FBGMM(X, prior, ab.ALPHA, K, a, covariance_type=cov, lms=ab.LMS)
+    spec = ab.AmBatch(seg, n_gibbs_blocks=B, n_stat_blocks=S, seed=ab.BATCH_SEED)
+    assert [len(spec._tokens(i)) for i in range(u.D)] == list(tokens)
+    return corpus, bounds, spec
+
+
+def settled_seg_product(case, corpus, bounds, spec, **kw):
+    """the device segmenter of the same start (score_precision="f32", sync="batch" unless `kw` says otherwise)"""
+    from segmentalist_amd.fbgmm import FBGMM
+    from segmentalist_amd.niw import NIW
+    from segmentalist_amd.unigram_acoustic_wordseg import UnigramAcousticWordseg
+    D, K, B, S = case[2], case[3], case[4], case[5]
+    args = dict(ab.seg_kwargs(case), sync="batch", n_gibbs_blocks=B, n_stat_blocks=S, batch_seed=ab.BATCH_SEED, score_precision="f32")
+    args.update(kw)
+    np.random.seed(1)
+    return UnigramAcousticWordseg(FBGMM, ab.ALPHA, K, NIW(*fi.prior_params("diag", D)), *corpus, seed_boundaries_dict=bounds,
+                                  seed_assignments_dict=ab.seeds_from(spec, spec.slot), **args)
+
+
+def block_span_rows(spec, b):
+    """the embedding rows of every span of the utterances of block b (slice order), with the span's duration"""
+    u = spec.seg.utterances
+    out = []
+    for s in range(spec.S):
+        for i in range(*spec.ranges[s][b]):
+            n = u.lengths[i]
+            for j in range(n * (n + 1) // 2):
+                if u.vec_ids[i, j] != -1 and not np.isnan(u.durations[i, j]):
+                    out.append((int(u.vec_ids[i, j]), float(u.durations[i, j])))
+    return out
+
+
+def settled_seg_figures(spec, b, centre, rows=None):
+    """block b of the settled start: the probed span rows, the fp64 span scores (log marginals) and likelihoods of those rows on
+    the statistics without the block, and the error of the emulation / of the emulation without the compensation on the span
+    scores, by the contract's measure: (d, rows, want_ll, want_score, emulated, plain)"""
+    d = spec.derive(*spec.stats_excluding(b))
+    if rows is None:
+        rows = f32.probe_rows(np.array([e for e, _ in block_span_rows(spec, b)], np.int64))
+    want, _, _, _ = f32.compare(spec, d, spec.X[rows], None, centre)
+    want_score = np.array([spec.log_marg(d, spec.X[e]) for e in rows])
+    view = f32._Rows(spec, spec.X[rows])
+    new, old = (rel(f32.marginals(spec, d, emulate(view, d, range(len(rows)), centre, c)), want_score) for c in (True, False))
+    return d, rows, want, want_score, new, old

@@ -6,9 +6,13 @@ adds
 
   CASES        the shapes that walk every place the kernel can go wrong, and the affine transforms (tests/affine.py) each runs
                under
+  SETTLED      shapes with slots of thousands of items, where the rounding of a float32 term shows in the likelihood; compared
+               on PROBES rows (`compare`, `settled_figures`), also as utterances of one landmark through the segmenter
+               (`segmenter_of`)
   emulate      a NumPy emulation of the kernel's float32 terms on the specification's `derive` output: float32 subtract /
-               multiply / add / log2, a sequential float32 sum over the dimensions, fp64 constants -- what the contract can
-               be checked against before a device is asked anything
+               multiply / add / log2 with the compensation of what 1 + e rounds away, a sequential float32 sum over the
+               dimensions, fp64 constants -- what the contract can be checked against before a device is asked anything;
+               `emulate_uncompensated`: the term as it stood before
   step / run   the specification walked one Gibbs step at a time with a hook per step (the device test keeps the specification
                on the device's own slots; the CPU test measures the emulation and the draws' margins)
 
@@ -16,6 +20,7 @@ The contract is the project's tolerance contract (tests/test_gpu_tolerance_modes
 within 1e-4 max(|want|, 1) of the fp64 specification on the same statistics; statistics and draws stay fp64.
 """
 import numpy as np
+from scipy.special import logsumexp as _sp_logsumexp
 
 from oracle import np_fbgmm_batch as nb
 from oracle import np_oracle as no
@@ -85,10 +90,57 @@ TRANSFORMS["dg_D3_K7_n40"] = ["identity", "scale1_64"]
 RUNS = [(name, t) for name in CASES for t in TRANSFORMS[name]]
 
 
+# SETTLED cases: few clusters, every item in the slot of the cluster that generated it, so that a slot holds THOUSANDS of items
+# -- where a float32 term's rounding, multiplied by the slot's factor (v_N + 1) / 2 ~ n_k / 2, shows in the likelihood (DESIGN.md
+# 4.16.1).  fi.case_assignments mixes the clusters, and CASES holds 700 items over 300 slots at the most: neither reaches it.
+# The layout of CASES with the number of clusters appended; the smallest shapes at which the term without its compensation
+# (emulate_uncompensated) misses the contract by more than 3 x over all rows; eight Gibbs blocks, so that a step's statistics
+# keep seven eighths of the items.  Their specification is evaluated on PROBES rows a step, never walked item by item, and they
+# are held to the contract only: CASES keeps the draws' margins and the census of founded / emptied slots.
+# Under `mfcc` the log-densities are larger (|ll| >= 11 against >= 0.1), the same absolute error is a smaller relative one, and
+# N = 4 096 gives 3.7e-5 without the compensation -- inside the contract, so that shape could not tell the two terms apart
+# there; `mfcc` runs at N = 65 536 (4.2e-4 or more on every step's probes).
+SETTLED = {
+    "st_D39_K8_n4096": ("diag", "float32", 39, 8, 8, 2, 4096, 7, (1.0,), 0.0, 2),
+    "st_D39_K8_n65536": ("diag", "float32", 39, 8, 8, 2, 65536, 7, (1.0,), 0.0, 2),
+    "st_D100_K8_n16384": ("diag", "float64", 100, 8, 8, 2, 16384, 7, (1.0,), 0.0, 3),                # float64 rows
+}
+SETTLED_RUNS = [("st_D39_K8_n4096", "identity"), ("st_D39_K8_n4096", "shift16"), ("st_D39_K8_n65536", "mfcc"),
+                ("st_D100_K8_n16384", "identity")]
+SETTLED_IDS = ["%s-%s" % r for r in SETTLED_RUNS]
+PROBES = 256                     # rows a settled case is compared on
+DISCRIMINATES = 2.0              # the term without its compensation misses the contract by at least this factor there
+
+
+def settled_data(case, M=None, query_seed=0):
+    """(rows, generating cluster) of a SETTLED case: the recipe of fi.case_data (centres 1.5 randn, noise 0.3) with the number
+    of clusters the case names.  M, query_seed: M held-out rows of the same centres, z and noise from RandomState(seed +
+    query_seed)."""
+    cov, dtype, D, K, B, S, N, seed = case[:8]
+    rs = np.random.RandomState(seed)
+    mu = 1.5 * rs.randn(case[10], D)
+    if M is not None:
+        rs, N = np.random.RandomState(seed + query_seed), M
+    z = rs.randint(0, len(mu), N)
+    return (mu[z] + 0.3 * rs.randn(N, D)).astype(dtype), z.astype(np.int64)
+
+
+def settled_queries(case, transform="identity", M=PROBES, query_seed=5000):
+    """M held-out rows of the case's own clusters, under the transform"""
+    Xq = settled_data(case, M, query_seed)[0]
+    return Xq if transform == "identity" else affine.rows(Xq, *affine.params(transform, case[2]))
+
+
+def probe_rows(items, m=PROBES):
+    """m of the items (a number: of range(items)), evenly"""
+    items = np.arange(items) if np.isscalar(items) else np.asarray(items, np.int64)
+    return items[::max(1, len(items) // m)][:m]
+
+
 def inputs(case, transform="identity"):
     """(X, assignments, NIW parameters) of a case under a transform: prior and data are moved together"""
     D = case[2]
-    X, a = fi.make_inputs(case)
+    X, a = settled_data(case) if len(case) > 10 else fi.make_inputs(case)
     s, c = affine.params(transform, D)
     if transform == "identity":
         return X, a, fi.prior_params("diag", D)
@@ -116,6 +168,40 @@ def product_of(case, transform="identity", assignments=None, **kw):
     return FBGMM(X, NIW(*pp), fi.ALPHA, K, a if assignments is None else assignments, **args)
 
 
+def one_landmark_corpus(X):
+    """the rows as utterances of one landmark, one span of duration 1 each, in row order: (corpus, keys)"""
+    keys = ["u%07d" % i for i in range(len(X))]
+    return ({k: X[i:i + 1] for i, k in enumerate(keys)}, {k: np.array([0]) for k in keys}, {k: [1] for k in keys},
+            {k: [1] for k in keys}), keys
+
+
+def segmenter_of(case, transform="identity", **kw):
+    """The device's UNIGRAM SEGMENTER over the case's rows as utterances of one landmark (score_precision="f32", sync="batch"
+    unless `kw` says otherwise), in the case's initial state: the span score of utterance i is the log marginal of row i, its
+    one token row i, and the blocks are the stand-alone model's -- spec_of(case) is its specification."""
+    from segmentalist_amd.fbgmm import FBGMM
+    from segmentalist_amd.niw import NIW
+    from segmentalist_amd.unigram_acoustic_wordseg import UnigramAcousticWordseg
+    K, B, S = case[3], case[4], case[5]
+    X, a, pp = inputs(case, transform)
+    corpus, keys = one_landmark_corpus(X)
+    args = dict(covariance_type="diag", n_slices_min=0, n_slices_max=1, beta_sent_boundary=-1, lms=fi.LMS, sync="batch",
+                n_gibbs_blocks=B, n_stat_blocks=S, batch_seed=fi.BATCH_SEED, score_precision="f32")
+    args.update(kw)
+    np.random.seed(1)
+    seg = UnigramAcousticWordseg(FBGMM, fi.ALPHA, K, NIW(*pp), *corpus, seed_boundaries_dict={k: [1] for k in keys},
+                                 seed_assignments_dict={k: [int(a[i])] for i, k in enumerate(keys)}, **args)
+    assert np.array_equal(seg.acoustic_model.components.assignments, a)
+    return seg
+
+
+def marginals(spec, d, ll):
+    """log marginals [n] of likelihood rows ll [n, K_max] on the parameters d: nb.FbgmmBatch.log_marg without a language model
+    (fbgmm.py:256-285), which is also the held-out log density of tests/fbgmm_predict.py"""
+    z = spec.lms * (np.log(float(spec.alpha) / spec.K_max + d["cnt"]) - np.log(int(np.sum(d["cnt"])) + spec.alpha))
+    return _sp_logsumexp(z[None, :] + np.asarray(ll, np.float64), axis=1)
+
+
 def rel(got, want):
     """the contract's measure: max |got - want| / max(|want|, 1)"""
     got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
@@ -127,10 +213,26 @@ def centre_of(X):
     return np.add.reduce(X, axis=0, dtype=np.float64) / max(len(X), 1)
 
 
-def emulate(spec, d, rows, centre):
+LOG2E_F = np.float32(1.4426950408889634)
+
+
+def _term(e, compensated):
+    """log2(1 + e) of the float32 route on float32 e >= 0 (fbb_term32 of segk_fbb_dev.h): u = 1 + e; c = e - (u - 1), the
+    part of e the addition dropped (exact), taken where u < 2 and 0 beyond (there c / u is below the logarithm's own last bit
+    and c alone would overstate it); term = c * LOG2E_F + log2(u), rounded once (an fma: formed in fp64 here).
+    compensated=False: log2(u) alone, the arithmetic before the compensation."""
+    f32 = np.float32
+    u = f32(1.0) + e
+    if not compensated:
+        return np.log2(u)
+    c = np.where(u < f32(2.0), e - (u - f32(1.0)), f32(0.0))
+    return (c.astype(np.float64) * np.float64(LOG2E_F) + np.log2(u).astype(np.float64)).astype(f32)
+
+
+def emulate(spec, d, rows, centre, compensated=True):
     """The likelihoods [len(rows), K_max] of the float32 route on the parameters `d` (spec.derive): per (item, slot)
     m = float32(mean - centre), q = float32(q), x = float32(X[i] - centre) (the differences in fp64), delta = m - x,
-    acc += log2(1 + (delta * delta) * q) in float32, dimensions ascending, then const - half * (ln 2 * acc) in fp64; an
+    acc += _term((delta * delta) * q) in float32, dimensions ascending, then const - half * (ln 2 * acc) in fp64; an
     empty slot: the prior predictive (fp64)."""
     f32 = np.float32
     with np.errstate(all="ignore"):
@@ -140,10 +242,79 @@ def emulate(spec, d, rows, centre):
         acc = np.zeros((len(rows), spec.K_max), f32)
         for j in range(spec.D):
             delta = m[None, :, j] - x[:, None, j]
-            acc = acc + np.log2(f32(1.0) + (delta * delta) * q[None, :, j])
+            acc = acc + _term((delta * delta) * q[None, :, j], compensated)
         ll = d["const"][None, :] - d["half"][None, :] * (0.6931471805599453 * acc.astype(np.float64))
     prior = np.array([spec.log_prior_pred(spec.X[i]) for i in rows])
     return np.where(d["active"][None, :], ll, prior[:, None])
+
+
+def emulate_uncompensated(spec, d, rows, centre):
+    """`emulate` with the term as it stood before the compensation, log2(1 + e): its error grows with a slot's count (1 + e
+    rounds away up to 6e-8 of an e of the order of 1 / n_k, and half = (v_N + 1) / 2 multiplies that back up).  Kept to show
+    that a case's inputs can tell the two apart: a condition on the inputs of the SETTLED cases."""
+    return emulate(spec, d, rows, centre, compensated=False)
+
+
+def set_slots(spec, slots):
+    """the specification on these slots (the device's own), its partial sums rebuilt"""
+    spec.slot[:] = np.asarray(slots, np.int64)
+    for s in range(spec.S):
+        for b in range(spec.B):
+            spec.P[s][b] = spec._partial(s, b)
+    return spec
+
+
+def compare(spec, d, X, got=None, centre=None):
+    """The fp64 specification's likelihoods [len(X), K_max] of the rows X on the parameters d, and, by the contract's measure
+    over the occupied slots: (want, error of `got` or None, error of the emulation, error of the emulation without the
+    compensation).  The last is the condition on the inputs of a SETTLED test: at or beyond DISCRIMINATES x CONTRACT, or the
+    rows could not tell the two terms apart."""
+    occ = d["active"]
+    centre = centre_of(spec.X) if centre is None else centre
+    want = np.array([spec.loglik(d, x) for x in X]).reshape(len(X), spec.K_max)
+    rows = _Rows(spec, X)
+    new, old = (rel(emulate(rows, d, range(len(X)), centre, c)[:, occ], want[:, occ]) for c in (True, False))
+    return want, None if got is None else rel(np.asarray(got)[:, occ], want[:, occ]), new, old
+
+
+def settled_figures(name, transform="identity"):
+    """A SETTLED case at its start, before a device is asked anything: {"steps": over the probes of every Gibbs step, on the
+    statistics without the step's block; "queries": the held-out rows on all statistics} -> (the emulation's error, the
+    emulation's without the compensation), and the largest count"""
+    case = SETTLED[name]
+    spec = spec_of(case, transform)
+    centre = centre_of(spec.X)
+    new = old = 0.0
+    for b in range(spec.B):
+        d = spec.derive(*spec.stats_excluding(b))
+        rows = probe_rows(considered(spec, b, True))
+        _, _, e_new, e_old = compare(spec, d, spec.X[rows], centre=centre)
+        new, old = max(new, e_new), max(old, e_old)
+    d = spec.derive(*spec.stats_excluding(-1))
+    _, _, q_new, q_old = compare(spec, d, settled_queries(case, transform), centre=centre)
+    return {"steps": (new, old), "queries": (q_new, q_old)}, int(d["cnt"].max())
+
+
+def discriminates(spec, what, queries=None):
+    """The FIRST thing a device test of a SETTLED case does, before the device is asked anything: on the state `spec` holds,
+    the emulation without the compensation over the rows the test will sample -- the probes of every Gibbs step on the
+    statistics without the step's block, or `queries` on all statistics -- must miss the contract by DISCRIMINATES x or more;
+    otherwise the rows could not show the defect and the case has to be chosen again.  Returns that figure."""
+    centre = centre_of(spec.X)
+    if queries is not None:
+        plain = compare(spec, spec.derive(*spec.stats_excluding(-1)), queries, centre=centre)[3]
+    else:
+        plain = max(compare(spec, spec.derive(*spec.stats_excluding(b)), spec.X[probe_rows(considered(spec, b, True))],
+                            centre=centre)[3] for b in range(spec.B))
+    assert plain >= DISCRIMINATES * CONTRACT, "%s: the plain term gives %.3g on the sampled rows: they prove nothing" % (what, plain)
+    return plain
+
+
+class _Rows(object):
+    """what `emulate` asks of a specification, on rows that need not be the model's"""
+
+    def __init__(self, spec, X):
+        self.X, self.K_max, self.D, self.log_prior_pred = X, spec.K_max, spec.D, spec.log_prior_pred
 
 
 def considered(spec, b, consider_unassigned):

@@ -14,6 +14,7 @@ import inspect
 import os
 import re
 
+import numpy as np
 import pytest
 
 from tests import am_batch as ab
@@ -40,6 +41,39 @@ def test_emulation_within_half_the_contract(runs, name, transform):
     r = _run(runs, name, transform)
     print("%s %s: emulation worst %.3g over %d draws" % (name, transform, r.worst, r.draws))
     assert r.draws >= 1 and r.worst <= a32.EMULATION
+
+
+def test_settled_case_tells_the_compensated_term_from_the_plain_one():
+    """a32.SETTLED, slots of thousands of tokens: the emulation stays within half the contract and the emulation WITHOUT the
+    compensation misses the contract by 2 x or more on the probes of every Gibbs step -- a condition on the inputs of the
+    device test; about five tokens a slot (every case of CASES) cannot tell the two apart"""
+    figures, n_k = a32.f32.settled_figures(a32.SETTLED)
+    new, old = figures["steps"]
+    print("%s, largest slot %d tokens: emulation %.3g, without the compensation %.3g" % (a32.SETTLED, n_k, new, old))
+    assert n_k >= 2000 and new <= a32.EMULATION and old >= a32.f32.DISCRIMINATES * a32.CONTRACT
+    case = a32.CASES["dg_D39_K65_tiles"]
+    _, spec = a32.spec_of(case)
+    d = spec.derive(*spec.stats_excluding(-1))
+    rows = [e for i in range(spec.seg.utterances.D) for e in spec._tokens(i)]
+    _, _, new, old = a32.f32.compare(spec, d, spec.X[rows])
+    print("dg_D39_K65_tiles, largest slot %d tokens: emulation %.3g, without the compensation %.3g" % (d["cnt"].max(), new, old))
+    assert new <= a32.EMULATION and old <= a32.EMULATION
+
+
+def test_settled_multi_landmark_corpus_tells_the_compensated_term_from_the_plain_one():
+    """a32.SETTLED_SEG: two slots of about 2 000 tokens, utterances of three to eight tokens, span rows of every duration in a
+    block.  On the probes of every block the span scores of the emulation stay within half the contract and those of the
+    emulation WITHOUT the compensation miss the contract by 2 x or more: a condition on the inputs of the device test."""
+    corpus, bounds, spec = a32.settled_seg_spec()
+    cnt = spec.stats_excluding(-1)[0]
+    assert sorted(cnt[cnt > 0].tolist())[0] >= 2000 and np.count_nonzero(cnt) == a32.N_CENTRES
+    assert {len(spec._tokens(i)) for i in range(spec.seg.utterances.D)} == {3, 4, 5, 6, 8}
+    centre = a32.centre_of(spec.X)
+    for b in range(spec.B):
+        assert len({dur for _, dur in a32.block_span_rows(spec, b)}) >= 3
+        d, rows, want, want_score, new, old = a32.settled_seg_figures(spec, b, centre)
+        print("settled multi-landmark corpus, block %d: span scores of the emulation %.3g, without the compensation %.3g" % (b, new, old))
+        assert new <= a32.EMULATION and old >= a32.f32.DISCRIMINATES * a32.CONTRACT
 
 
 @pytest.mark.parametrize("name,transform", a32.RUNS, ids=IDS)

@@ -7,7 +7,9 @@ the device is asked anything (as tests/test_anneal_batch_cpu.py does for the ann
    distribution (a uniform puts about K_max * 2e-6 of them nearer);
 3. every case with more than one slot founds and empties a slot over its sweeps, every annealed sweep changes draws against
    T = 1;
-4. header, binding and library carry segk_fbi_assign_diag32 at ABI 15.
+4. header, binding and library carry segk_fbi_assign_diag32 at ABI 15;
+5. on the SETTLED cases (slots of thousands of items) the emulation stays within 5e-5 while the emulation of the term WITHOUT
+   its compensation (`emulate_uncompensated`) misses the contract by 2 x or more: the inputs can show the defect.
 """
 import ctypes
 import os
@@ -39,6 +41,31 @@ def test_emulation_within_half_the_contract(runs, name, transform):
     r = _run(runs, name, transform)
     print("%s %s: emulation worst %.3g over %d draws" % (name, transform, r.worst, r.draws))
     assert r.draws >= 1 and r.worst <= f32.EMULATION
+
+
+@pytest.mark.parametrize("name,transform", f32.SETTLED_RUNS, ids=f32.SETTLED_IDS)
+def test_settled_cases_tell_the_compensated_term_from_the_plain_one(name, transform):
+    """slots of thousands of items (f32.SETTLED): the emulation stays within half the contract, and the emulation WITHOUT the
+    compensation misses the contract by 2 x or more -- on the probes of the Gibbs steps and on the held-out rows alike.  The
+    second is a condition on the inputs: a case that does not meet it could not show the defect and must be chosen again."""
+    figures, n_k = f32.settled_figures(name, transform)
+    for what, (new, old) in sorted(figures.items()):
+        print("%s %s, largest slot %d items, %s: emulation %.3g, without the compensation %.3g" % (name, transform, n_k, what, new, old))
+    assert n_k >= 2000
+    for new, old in figures.values():
+        assert new <= f32.EMULATION
+        assert old >= f32.DISCRIMINATES * f32.CONTRACT
+
+
+def test_the_plain_term_misses_nothing_on_the_small_cases():
+    """why CASES alone never saw it: with a handful of items a slot the term without the compensation is as good"""
+    case = f32.CASES["dg_D39_K300_8x8"]
+    spec = f32.spec_of(case)
+    d = spec.derive(*spec.stats_excluding(-1))
+    rows = f32.probe_rows(case[6])
+    _, _, new, old = f32.compare(spec, d, spec.X[rows])
+    print("dg_D39_K300_8x8, largest slot %d items: emulation %.3g, without the compensation %.3g" % (d["cnt"].max(), new, old))
+    assert new <= f32.EMULATION and old <= f32.EMULATION
 
 
 @pytest.mark.parametrize("name,transform", f32.RUNS, ids=["%s-%s" % r for r in f32.RUNS])

@@ -402,3 +402,67 @@ def test_refusals(gpu):
     gpu.cuda.synchronize()
     assert gpu.equal(sws.slot, slots)                          # nothing was launched
     seg._df.check_status()
+
+
+def test_replay_on_settled_slots_of_thousands_of_tokens(gpu, monkeypatch):
+    """segk_fbt_assign_diag32 where a float32 term's rounding is multiplied by a slot's count: a32.SETTLED as
+    utterances of one landmark, one float32 inner sweep on the device, replayed on the specification block by block on
+    f32.PROBES tokens a block: the contract on the occupied slots, the prior predictive at 1e-9 on the empty ones, every probed
+    token's slot the draw on the device's OWN row, the device's slots taken over, the partial sums at 1e-13.  First the
+    tokens must show that they can tell the compensated term from the plain one: the emulation without the compensation
+    misses the contract by 2 x or more on them."""
+    f32 = a32.f32
+    monkeypatch.setenv("SEGK_AM32_TILE_MIN", a32.TILES)
+    case = f32.SETTLED[a32.SETTLED]
+    N, K = case[6], case[3]
+    spec = f32.spec_of(case)
+    f32.discriminates(spec, a32.SETTLED)           # (first, on the settled start; once more below on the replayed state)
+    seg = f32.segmenter_of(case, sync="sequential", score_precision="f64")
+    sw = seg._get_sweeper()
+    assert sw.score_precision == "f64" and seg._df.corpus.N_max == 1
+    sw.probe_ll = gpu.full((N, K), float("nan"), dtype=gpu.float64, device="cuda")
+    seg._df._L = Spy(seg._df._L)
+    sw.enter(seg._dev_bounds)
+    before = frozen(seg)
+    seg.am_batch_sweep_async(1.0, score_precision="f32")
+    gpu.cuda.synchronize()
+    seg._df.check_status()
+    assert sw.sweep_index == 1
+    for x, y, nm in zip(before, frozen(seg), ("boundaries", "new_tok", "n_new", "out_logprob")):
+        assert x.tobytes() == y.tobytes(), nm
+    assert taken(seg) == {"segk_fbt_assign_diag32": sw.B, "segk_fbb_assign_diag32": 0, "segk_fbt_assign": 0}
+    got, slots = sw.probe_ll.cpu().numpy()[:, :K], sw.slot.cpu().numpy()
+    assert np.isfinite(got).all()                            # every utterance holds its one token
+    centre = f32.centre_of(spec.X)
+    assert np.array_equal(sw._centre32.cpu().numpy(), centre)
+    worst = worst_empty = emulated = plain = 0.0
+    draws = skipped = 0
+    for b in range(spec.B):
+        d = spec.derive(*spec.stats_excluding(b))
+        occ = d["active"]
+        items = np.array(f32.considered(spec, b, True))
+        rows = f32.probe_rows(items)
+        want, e, e_new, e_old = f32.compare(spec, d, spec.X[rows], got[rows], centre)
+        worst, emulated, plain = max(worst, e), max(emulated, e_new), max(plain, e_old)
+        worst_empty = max(worst_empty, rel(got[rows][:, ~occ], want[:, ~occ]))
+        pz = spec.prior_z(d, None, None, None)
+        for i in rows:
+            p, u = spec._probabilities(pz + got[i], 1.0), nb.u01(spec.seed, 0, int(i), 1 + 0)      # (N_max + t: one landmark, token 0)
+            draws += 1
+            if a32.margin(p, u) < a32.DRAW_MARGIN:
+                skipped += 1
+            else:
+                assert slots[i] == nb.draw_chunked(p, u), (b, i)
+        f32.apply_slots(spec, b, items, slots[items])          # the specification goes on from the device's slots
+    print("%s as one-landmark utterances: worst likelihood error %.3g (occupied), %.3g (empty) on %d probes a block; the "
+          "emulation %.3g, without the compensation %.3g; %d draws, %d skipped near an edge"
+          % (a32.SETTLED, worst, worst_empty, f32.PROBES, emulated, plain, draws, skipped))
+    assert plain >= f32.DISCRIMINATES * a32.CONTRACT               # (the inputs: or the tokens prove nothing)
+    assert worst <= a32.CONTRACT and worst_empty <= 1e-9
+    assert skipped <= a32.NEAR_EDGE * draws
+    assert np.array_equal(slots, spec.slot)
+    for b in range(spec.B):
+        for s in range(spec.S):
+            cnt, sx, sxx = sw.cell_partials(b, s)
+            rc, rx, rxx = spec.P[s][b]
+            assert np.array_equal(cnt, rc) and rel(sx, rx) <= 1e-13 and rel(sxx, rxx) <= 1e-13, (b, s)

@@ -15,6 +15,10 @@ device's slots and recomputes its partial sums of block b.  Per step:
     may not exceed 1 % of the draws;
   * the cell's partial sums equal the specification's from the same slots at 1e-13.
 
+The SETTLED cases of tests/fbgmm_items_f32.py -- slots of thousands of items, where the rounding of a float32 term is multiplied
+by the slot's count -- are walked in the same way on f32.PROBES rows a step (`walk_settled`), after those rows have shown that
+the term without its compensation would miss the contract on them by 2 x or more.
+
 Measured worst likelihood error per case (MI355X; printed by every run): see the table of DESIGN.md 4.16.1.
 """
 import ctypes as C
@@ -100,6 +104,102 @@ def walk(gpu, case, transform="identity", consider_unassigned=True, what=""):
     assert worst_partials <= 1e-13, what
     assert skipped <= f32.NEAR_EDGE * draws, what
     return spec, m
+
+
+def walk_settled(gpu, name, transform="identity", map_assign=False):
+    """A case of f32.SETTLED (slots of thousands of items) one Gibbs step at a time, sampled (segk_fbi_assign_diag32) or MAP
+    (segk_fbi_assign_map_diag32; tests/test_gpu_fbgmm_items_map.py): the specification is evaluated on f32.PROBES rows of
+    every step, on the device's own slots; the rest of the walk's checks on those rows.  First of all the rows must be able to
+    tell the compensated term from the plain one: the emulation without the compensation misses the contract by 2 x or more
+    on them.  Returns the worst likelihood error over the occupied slots."""
+    from segmentalist_amd import _abi
+    case = f32.SETTLED[name]
+    what = "%s %s%s" % (name, transform, " MAP" if map_assign else "")
+    spec = f32.spec_of(case, transform)
+    f32.discriminates(spec, what)                  # (first, on the settled start; once more below on the state the walk saw)
+    m = f32.product_of(case, transform)
+    sw = m._get_sweeper()
+    assert sw.score_diag32 and np.array_equal(sw.centre.cpu().numpy(), f32.centre_of(spec.X))
+    centre = f32.centre_of(spec.X)
+    N, K = len(spec.slot), spec.K_max
+    probe = gpu.empty((N, K), dtype=gpu.float64, device="cuda")
+    sw.enter()
+    L, ctx, cp, fp, bp, st = sw._args()
+    worst = worst_empty = worst_partials = emulated = plain = 0.0
+    draws = skipped = 0
+    for sweep_index, temp in enumerate(case[8]):
+        sw.n_moved.zero_()
+        moved = 0
+        for b in range(spec.B):
+            probe.fill_(float("nan"))
+            _abi.check(L.segk_fbb_prepare(ctx, cp, fp, bp, b, st))
+            if map_assign:
+                _abi.check(L.segk_fbi_assign_map_diag32(ctx, cp, fp, bp, 0, sw.S, b, sw._n_items[b], sweep_index, 1, _abi.ptr(sw.new_tok),
+                                                        _abi.ptr(sw.n_new), _abi.ptr(probe), K, _abi.ptr(sw.n_moved), st))
+            else:
+                _abi.check(L.segk_fbi_assign_diag32(ctx, cp, fp, bp, 0, sw.S, b, sw._n_items[b], sweep_index, float(temp), 1,
+                                                    _abi.ptr(sw.new_tok), _abi.ptr(sw.n_new), _abi.ptr(probe), K, st))
+            _abi.check(L.segk_fbb_partials(ctx, cp, fp, bp, 0, sw.S, b, _abi.ptr(sw.new_tok), _abi.ptr(sw.n_new), st))
+            gpu.cuda.synchronize()
+            m.components.dev.check_status()
+            where = "%s sweep %d step %d" % (what, sweep_index, b)
+            items = np.array(f32.considered(spec, b, True))
+            rows = f32.probe_rows(items)
+            got, slots = probe[gpu.from_numpy(rows).cuda()].cpu().numpy(), sw.slot.cpu().numpy()
+            assert np.isfinite(got).all(), where
+            d = spec.derive(*spec.stats_excluding(b))
+            occ = d["active"]
+            want, e, e_new, e_old = f32.compare(spec, d, spec.X[rows], got, centre)
+            worst, emulated, plain = max(worst, e), max(emulated, e_new), max(plain, e_old)
+            worst_empty = max(worst_empty, f32.rel(got[:, ~occ], want[:, ~occ]))
+            # the slots of the probed items: the fp64 functions of the device's OWN likelihoods
+            if map_assign:
+                pz = np.log(float(spec.alpha) / K + d["cnt"])
+                for j, i in enumerate(rows):
+                    z = pz + got[j]
+                    k = int(np.argmax(z))
+                    below = z[z < z[k]]
+                    draws += 1
+                    if len(below) and z[k] - below.max() < 1e-9 * max(1.0, abs(z[k])):
+                        skipped += 1
+                    else:
+                        assert slots[i] == k, (where, i)
+            else:
+                pz = spec.prior_z(d, None, None, None)
+                for j, i in enumerate(rows):
+                    p, u = spec._probabilities(pz + got[j], temp), f32.nb.u01(spec.seed, sweep_index, int(i), 1)
+                    draws += 1
+                    if f32.margin(p, u) < fi.DRAW_MARGIN:
+                        skipped += 1
+                    else:
+                        assert slots[i] == f32.nb.draw_chunked(p, u), (where, i)
+            others = np.setdiff1d(np.arange(N), items)
+            assert np.array_equal(slots[others], spec.slot[others]), where
+            assert np.all((slots >= 0) & (slots < K)), where
+            moved += int(np.count_nonzero(slots[items] != spec.slot[items]))
+            f32.apply_slots(spec, b, items, slots[items])           # the specification goes on from the device's slots
+            for s in range(spec.S):
+                cnt, sx, sxx = sw.cell_partials(b, s)
+                rc, rx, rxx = spec.P[s][b]
+                assert np.array_equal(cnt, rc), where
+                worst_partials = max(worst_partials, f32.rel(sx, rx), f32.rel(sxx, rxx))
+        assert not map_assign or sw.moved() == moved, what
+    n_k = int(spec.stats_excluding(-1)[0].max())
+    print("%s: largest slot %d items; worst likelihood error %.3g (occupied), %.3g (empty) on %d probes a step; the emulation %.3g, "
+          "without the compensation %.3g; partials %.3g; %d slots compared, %d skipped near an edge"
+          % (what, n_k, worst, worst_empty, f32.PROBES, emulated, plain, worst_partials, draws, skipped))
+    assert plain >= f32.DISCRIMINATES * f32.CONTRACT, what             # (the inputs: or the rows prove nothing)
+    assert worst <= f32.CONTRACT, what
+    assert worst_empty <= 1e-9, what
+    assert worst_partials <= 1e-13, what
+    assert skipped <= f32.NEAR_EDGE * draws, what
+    return worst
+
+
+@pytest.mark.parametrize("name,transform", f32.SETTLED_RUNS, ids=f32.SETTLED_IDS)
+def test_steps_on_settled_slots_of_thousands_of_items(gpu, name, transform):
+    """the contract where a float32 term's rounding is multiplied by a slot's count: DESIGN.md 4.16.1 holds the figures"""
+    walk_settled(gpu, name, transform)
 
 
 @pytest.fixture(scope="module")

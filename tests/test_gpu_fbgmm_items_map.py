@@ -179,6 +179,15 @@ def test_float32_map_steps(gpu, monkeypatch, name):
     assert np.array_equal(other._get_sweeper().slot.cpu().numpy(), spec.slot)
 
 
+@pytest.mark.parametrize("name,transform", f32.SETTLED_RUNS, ids=f32.SETTLED_IDS)
+def test_float32_map_steps_on_settled_slots_of_thousands_of_items(gpu, name, transform):
+    """segk_fbi_assign_map_diag32 where a float32 term's rounding is multiplied by a slot's count (f32.SETTLED): the contract on
+    f32.PROBES rows of every step, the slots of those rows the fp64 first argmax on the device's own likelihoods, the counter
+    the slots that changed -- after the rows have shown that they can tell the compensated term from the plain one"""
+    from tests.test_gpu_fbgmm_items_f32 import walk_settled
+    walk_settled(gpu, name, transform, map_assign=True)
+
+
 @pytest.mark.parametrize("name,cu", fm.SERIAL_FORM + [(n, True) for n in fm.SERIAL],
                          ids=_ids(fm.SERIAL_FORM + [(n, True) for n in fm.SERIAL]))
 def test_serial_map_sweeps(gpu, name, cu):

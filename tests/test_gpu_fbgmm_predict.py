@@ -271,6 +271,45 @@ def test_float32_likelihoods(gpu, monkeypatch, name):
         assert rel(dens, own.density) <= RTOL and rel(resp, own.resp) <= RTOL
 
 
+@pytest.mark.parametrize("name,transform", f32.SETTLED_RUNS, ids=f32.SETTLED_IDS)
+def test_float32_likelihoods_on_settled_slots_of_thousands_of_items(gpu, name, transform):
+    """segk_fbi_predict_diag32 where a float32 term's rounding is multiplied by a slot's count (f32.SETTLED): held-out rows of
+    the case's own clusters against the settled start and against the state after a sweep, the specification on the device's
+    own slots.  The rows must first show that they can tell the compensated term from the plain one: the emulation without the
+    compensation misses the contract by 2 x or more on them."""
+    case = f32.SETTLED[name]
+    Xq = f32.settled_queries(case, transform)
+    spec = f32.spec_of(case, transform)
+    f32.discriminates(spec, "%s %s" % (name, transform), Xq)          # (first; once more below on each state's own slots)
+    m = f32.product_of(case, transform)
+    sw = m._get_sweeper()
+    assert sw.score_diag32
+    K = case[3]
+    for state in ("settled", "swept"):
+        if state == "swept":
+            m.batch_sweep_async(1.0)
+        probe = gpu.full((len(Xq), K), float("nan"), dtype=gpu.float64, device="cuda")
+        label, dens, resp = sw.predict(Xq, True, True, True, probe_ll=probe)
+        gpu.cuda.synchronize()
+        m.components.dev.check_status()
+        ll = probe.cpu().numpy()
+        assert np.isfinite(ll).all()
+        f32.set_slots(spec, device_slots(m))
+        d = spec.derive(*spec.stats_excluding(-1))
+        occ = d["active"]
+        want, worst, emulated, plain = f32.compare(spec, d, Xq, ll)
+        worst_empty = f32.rel(ll[:, ~occ], want[:, ~occ])
+        own = fp.functions_of(ll, d["cnt"], fi.ALPHA, fi.LMS)
+        print("%s %s %s: largest slot %d items; likelihoods %.3g (occupied), %.3g (empty) on %d held-out rows; the emulation "
+              "%.3g, without the compensation %.3g; density %.3g, responsibilities %.3g on the device's own"
+              % (name, transform, state, d["cnt"].max(), worst, worst_empty, len(Xq), emulated, plain, rel(dens, own.density),
+                 rel(resp, own.resp)))
+        assert plain >= f32.DISCRIMINATES * f32.CONTRACT                # (the inputs: or the rows prove nothing)
+        assert worst <= f32.CONTRACT and worst_empty <= RTOL
+        assert np.array_equal(label, own.label)
+        assert rel(dens, own.density) <= RTOL and rel(resp, own.resp) <= RTOL
+
+
 def test_refusals(gpu, monkeypatch):
     from segmentalist_amd import _abi, device
     from segmentalist_amd._abi import SegkError

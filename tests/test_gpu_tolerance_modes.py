@@ -307,3 +307,167 @@ def _fused_against_three_launches(transform, anneal_temp=1.0, **kw):
     both = (a[2] >= 0) | (b_[2] >= 0)
     assert np.mean(a[2][both] == b_[2][both]) > 0.98, np.mean(a[2][both] == b_[2][both])
     return a
+
+
+@pytest.mark.parametrize("fused", [False, True], ids=["three_launches", "fused"])
+def test_span_scores_and_token_likelihoods_on_settled_slots_of_thousands_of_items(gpu, fused):
+    """The float32 Student-t term where its rounding is multiplied by a slot's count: the rows of the settled
+    case st_D39_K8_n4096 of tests/fbgmm_items_f32.py -- two slots of 2 000 items each -- as utterances of one landmark through
+    the unigram segmenter with score_precision="f32".  The span score of an utterance is then the log marginal of its row
+    (segk_fbb_score_diag32, or the fused segk_fbb_step_diag32: the packed form of the term), its one token's likelihoods the
+    row's (segk_fbb_assign_diag32 / the fused step).  Every Gibbs step on the settled start, f32.PROBES rows a step against
+    the specification (tests/fbgmm_items.py: FbgmmItems.log_marg, loglik) on the statistics without the step's block.
+    First the rows must show that they can tell the compensated term from the plain one: the emulation without the
+    compensation misses the contract by 2 x or more on them, on the span scores and on the likelihoods."""
+    from segmentalist_amd import _abi
+    from segmentalist_amd._abi import check, ptr
+    from tests import fbgmm_items_f32 as f32
+    torch = gpu
+    name = "st_D39_K8_n4096"
+    case = f32.SETTLED[name]
+    K, N = case[3], case[6]
+    spec = f32.spec_of(case)
+    centre = f32.centre_of(spec.X)
+    # first, before the device is asked anything: the specification on the rows every step will sample, and the inputs' condition
+    steps = []
+    plain_ll = plain_score = 0.0
+    for b in range(spec.B):
+        d = spec.derive(*spec.stats_excluding(b))
+        rows = f32.probe_rows(f32.considered(spec, b, True))
+        want, _, _, e_plain = f32.compare(spec, d, spec.X[rows], None, centre)
+        want_score = np.array([spec.log_marg(d, spec.X[i]) for i in rows])
+        assert f32.rel(f32.marginals(spec, d, want), want_score) <= 1e-12
+        plain = f32.emulate_uncompensated(f32._Rows(spec, spec.X[rows]), d, range(len(rows)), centre)
+        plain_ll = max(plain_ll, e_plain)
+        plain_score = max(plain_score, f32.rel(f32.marginals(spec, d, plain), want_score))
+        steps.append((d, rows, want, want_score))
+    assert plain_score >= f32.DISCRIMINATES * f32.CONTRACT and plain_ll >= f32.DISCRIMINATES * f32.CONTRACT, (plain_score, plain_ll)
+    seg = f32.segmenter_of(case)
+    sw = seg._get_sweeper()
+    assert sw.score_diag32 and seg._corpus.N_max == 1
+    sw.enter(seg._dev_bounds)
+    alpha = torch.full((N, 1), float("nan"), dtype=torch.float64, device="cuda")
+    ll = torch.full((N, K), float("nan"), dtype=torch.float64, device="cuda")
+    L, ctx = _abi.lib(), _abi.ctx()
+    check(L.segk_fbb_set_probe(ctx, ptr(alpha), ptr(ll), K))
+    try:
+        for b in range(sw.B):
+            _one_step(sw, seg, b, fused=fused)          # (no partial-sum refresh: every step on the settled start)
+    finally:
+        check(L.segk_fbb_set_probe(ctx, None, None, 0))
+    ll, score, slots = ll.cpu().numpy(), seg._df.score.cpu().numpy(), sw.slot.cpu().numpy()
+    assert np.array_equal(seg._df.new_tok.cpu().numpy().reshape(-1), np.arange(N))      # utterance i: row i, its one token
+    worst_ll = worst_score = worst_empty = worst_draw = 0.0
+    draws = skipped = 0
+    for d, rows, want, want_score in steps:
+        occ = d["active"]
+        worst_ll = max(worst_ll, f32.rel(ll[rows][:, occ], want[:, occ]))
+        worst_empty = max(worst_empty, f32.rel(ll[rows][:, ~occ], want[:, ~occ]))
+        worst_score = max(worst_score, f32.rel(score[rows], want_score))
+        # the slots: the fp64 function of the device's OWN likelihoods.  segk_fbb_assign_diag32 draws in fp64 (fbb_draw_row): the
+        # slot is draw_chunked's wherever the uniform lies 1e-6 clear of an edge; the fused step forms its probabilities with
+        # v_exp_f32 / v_log_f32: the uniform within 1e-4 of its slot's interval, as for the cases above
+        pz = spec.prior_z(d, None, None, None)
+        for i in rows:
+            p, u = spec._probabilities(pz + ll[i], 1.0), nb.u01(spec.seed, 0, int(i), 1 + 0)
+            k = int(slots[i])
+            assert 0 <= k < K
+            draws += 1
+            if fused:
+                cum = np.cumsum(p)
+                worst_draw = max(worst_draw, (cum[k - 1] if k > 0 else 0.0) - u, u - cum[k])
+            elif f32.margin(p, u) < f32.fi.DRAW_MARGIN:
+                skipped += 1
+            else:
+                assert k == nb.draw_chunked(p, u), i
+    print("%s as one-landmark utterances%s: span scores worst %.3g, token likelihoods %.3g (occupied), %.3g (empty) on %d "
+          "probes a step; the emulation without the compensation: %.3g, %.3g; %d draws, %d skipped near an edge, worst distance "
+          "from the slot's interval %.3g"
+          % (name, " fused" if fused else "", worst_score, worst_ll, worst_empty, f32.PROBES, plain_score, plain_ll, draws, skipped,
+             worst_draw))
+    assert worst_score <= f32.CONTRACT and worst_ll <= f32.CONTRACT
+    # (an empty slot: the row's prior predictive, fp64 in segk_fbb_assign_diag32; the fused step keeps every logit of a token as
+    # a float32 in base 2 and its probe gives that back -- the contract there, as for the cases above)
+    assert worst_empty <= (f32.CONTRACT if fused else 1e-9)
+    assert skipped <= f32.NEAR_EDGE * draws and worst_draw < 1e-4
+
+
+@pytest.mark.parametrize("fused", [False, True], ids=["three_launches", "fused"])
+def test_span_scores_and_token_likelihoods_on_a_settled_multi_landmark_corpus(gpu, fused):
+    """The same term at large counts on UTTERANCES OF EIGHT LANDMARKS (tests/am_batch_f32.py SETTLED_SEG: 800 utterances, a
+    window of three, two slots of about 2 000 tokens): span rows of every duration in one score tile, three to eight tokens an
+    utterance in the token kernels.  Every Gibbs step on the settled start (no partial-sum refresh), with
+    segk_fbb_score_diag32 + segk_fbb_segment + segk_fbb_assign_diag32 or the fused segk_fbb_step_diag32:
+      * first, before the device is asked anything, the probed span rows must tell the compensated term from the plain one;
+      * the span scores of f32.PROBES span rows a block within the contract of nb.FbgmmBatch.log_marg;
+      * the likelihoods of EVERY new token within the contract of loglik (empty slots at 1e-9; the fused step's float32
+        logits: the contract), on tokens that can tell the two terms apart too;
+      * every new token's slot the fp64 function of the device's own likelihoods: draw_chunked's wherever the uniform lies
+        1e-6 clear of an edge (fbb_draw_row), the uniform within 1e-4 of the slot's interval for the fused step."""
+    from segmentalist_amd import _abi
+    from segmentalist_amd._abi import check, ptr
+    from tests import am_batch_f32 as a32
+    f32 = a32.f32
+    torch = gpu
+    case = a32.SETTLED_SEG
+    K = case[3]
+    corpus, bounds, spec = a32.settled_seg_spec(case)
+    centre = f32.centre_of(spec.X)
+    steps = [a32.settled_seg_figures(spec, b, centre) for b in range(spec.B)]
+    plain_score = min(st[5] for st in steps)
+    assert plain_score >= f32.DISCRIMINATES * f32.CONTRACT, plain_score             # (the inputs: or the rows prove nothing)
+    seg = a32.settled_seg_product(case, corpus, bounds, spec)
+    assert np.array_equal(seg.acoustic_model.components.assignments, spec.slot)
+    assert np.array_equal(seg.utterances.boundaries, spec.seg.utterances.boundaries)
+    sw = seg._get_sweeper()
+    n_utt, N_max = seg._corpus.n_utt, seg._corpus.N_max
+    assert sw.score_diag32 and N_max == case[7]
+    sw.enter(seg._dev_bounds)
+    alpha = torch.full((n_utt, N_max), float("nan"), dtype=torch.float64, device="cuda")
+    ll = torch.full((n_utt * N_max, K), float("nan"), dtype=torch.float64, device="cuda")
+    L, ctx = _abi.lib(), _abi.ctx()
+    check(L.segk_fbb_set_probe(ctx, ptr(alpha), ptr(ll), K))
+    try:
+        for b in range(sw.B):
+            _one_step(sw, seg, b, fused=fused)
+    finally:
+        check(L.segk_fbb_set_probe(ctx, None, None, 0))
+    ll, score, slots = ll.cpu().numpy().reshape(n_utt, N_max, K), seg._df.score.cpu().numpy(), sw.slot.cpu().numpy()
+    new_tok, n_new = seg._df.new_tok.cpu().numpy(), seg._df.n_new.cpu().numpy()
+    worst_score = worst_ll = worst_empty = worst_draw = plain_ll = 0.0
+    n_tok = skipped = 0
+    per_utt = set()
+    for b, (d, rows, want, want_score, _, _) in enumerate(steps):
+        occ = d["active"]
+        worst_score = max(worst_score, f32.rel(score[rows], want_score))
+        pz = spec.prior_z(d, None, None, None)
+        toks = [(i, t) for s in range(spec.S) for i in range(*spec.ranges[s][b]) for t in range(n_new[i])]
+        got = np.array([ll[i, t] for i, t in toks])
+        assert np.isfinite(got).all()
+        tok_rows = np.array([new_tok[i, t] for i, t in toks], np.int64)
+        want_tok, e, _, e_plain = f32.compare(spec, d, spec.X[tok_rows], got, centre)
+        worst_ll, plain_ll = max(worst_ll, e), max(plain_ll, e_plain)
+        worst_empty = max(worst_empty, f32.rel(got[:, ~occ], want_tok[:, ~occ]))
+        per_utt |= {int(n_new[i]) for s in range(spec.S) for i in range(*spec.ranges[s][b])}
+        for j, (i, t) in enumerate(toks):
+            p, u = spec._probabilities(pz + got[j], 1.0), nb.u01(spec.seed, 0, i, N_max + t)
+            k = int(slots[tok_rows[j]])
+            assert 0 <= k < K
+            n_tok += 1
+            if fused:
+                cum = np.cumsum(p)
+                worst_draw = max(worst_draw, (cum[k - 1] if k > 0 else 0.0) - u, u - cum[k])
+            elif f32.margin(p, u) < f32.fi.DRAW_MARGIN:
+                skipped += 1
+            else:
+                assert k == nb.draw_chunked(p, u), (b, i, t)
+    print("settled multi-landmark corpus%s: span scores worst %.3g on %d probes a block (without the compensation %.3g); token "
+          "likelihoods %.3g (occupied), %.3g (empty) over %d tokens, %s an utterance (without the compensation %.3g); %d draws "
+          "skipped near an edge, worst distance from the slot's interval %.3g"
+          % (" fused" if fused else "", worst_score, f32.PROBES, plain_score, worst_ll, worst_empty, n_tok, sorted(per_utt), plain_ll,
+             skipped, worst_draw))
+    assert plain_ll >= f32.DISCRIMINATES * f32.CONTRACT
+    assert len(per_utt) >= 3 and max(per_utt) >= 4
+    assert worst_score <= f32.CONTRACT and worst_ll <= f32.CONTRACT
+    assert worst_empty <= (f32.CONTRACT if fused else 1e-9)
+    assert skipped <= f32.NEAR_EDGE * n_tok and worst_draw < 1e-4

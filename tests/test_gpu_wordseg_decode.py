@@ -263,6 +263,49 @@ def test_float32_scores_decide_optimally_on_their_own_numbers(gpu, name):
     print("%s f32: likelihoods %.3g, densities %.3g from fp64, worst shortfall of the path total %.3g" % (name, worst_ll, worst_dens, worst_path))
 
 
+def test_float32_decode_on_settled_slots_of_thousands_of_items(gpu):
+    """decode with score_precision="f32" where a float32 term's rounding is multiplied by a slot's count: the
+    settled case st_D39_K8_n4096 of tests/fbgmm_items_f32.py -- two slots of 2 000 items each -- as a segmenter over
+    utterances of one landmark, and held-out rows of the same clusters as held-out utterances of one landmark.  The one
+    segment of such an utterance carries the row's held-out log density, and the utterance's log probability is that number:
+    within the 1e-4 contract of the fp64 definition on the same statistics.  First the rows must show that they can tell the
+    compensated term from the plain one: the emulation without the compensation misses the contract by 2 x or more on them."""
+    from tests import fbgmm_items_f32 as f32
+    name = "st_D39_K8_n4096"
+    case = f32.SETTLED[name]
+    Xq = f32.settled_queries(case)
+    f32.discriminates(f32.spec_of(case), name, Xq)                      # (first: likelihoods; the densities below)
+    seg = f32.segmenter_of(case)
+    assert seg._get_sweeper().score_diag32
+    held, keys = f32.one_landmark_corpus(Xq)
+    res = seg.decode(*held)
+    assert res.utterance_labels == keys and np.array_equal(res.seg_offsets, np.arange(len(Xq) + 1))
+    assert np.array_equal(res.seg_embed, np.arange(len(Xq))) and res.boundaries.all()
+    spec = f32.spec_of(case)
+    d = spec.derive(*spec.stats_excluding(-1))
+    want_ll, _, _, _ = f32.compare(spec, d, Xq)
+    want = f32.marginals(spec, d, want_ll)
+    centre = f32.centre_of(spec.X)
+    rows = f32._Rows(spec, Xq)
+    emulated, plain = (wd.rel(f32.marginals(spec, d, f32.emulate(rows, d, range(len(Xq)), centre, c)), want) for c in (True, False))
+    worst = wd.rel(res.seg_log_marg, want)
+    print("%s decode f32: log densities of %d held-out rows worst %.3g; the emulation %.3g, without the compensation %.3g"
+          % (name, len(Xq), worst, emulated, plain))
+    assert plain >= f32.DISCRIMINATES * f32.CONTRACT                    # (the inputs: or the rows prove nothing)
+    assert worst <= f32.CONTRACT
+    assert np.array_equal(res.log_prob, res.seg_log_marg)               # (one span of duration 1, no insertion penalty)
+    # the labels: the first maximum of the fp64 logits wherever the specification's decision is clear of the contract
+    pz = np.log(float(spec.alpha) / spec.K_max + d["cnt"])
+    z = pz[None, :] + want_ll
+    top = np.sort(z, axis=1)
+    clear = top[:, -1] - top[:, -2] > 2 * f32.CONTRACT * np.maximum(1.0, np.abs(top[:, -1]))
+    occ = d["cnt"] > 0
+    rank = np.cumsum(occ) - occ
+    k = np.argmax(z, axis=1)
+    assert clear.sum() >= 0.9 * len(Xq)
+    assert np.array_equal(res.seg_label[clear], np.where(occ[k], rank[k], res.K)[clear])
+
+
 def test_fixed_variance_tolerance_sweepers_decode_in_fp64(gpu):
     """a fixed-variance sweeper of float32 span scores has no float32 item form: decode takes the fp64 likelihoods"""
     name = "fixed_small"
